@@ -6,11 +6,17 @@ ads, 10 s windows), HBM-resident before timing starts, as batches of 16.67M even
 line offsets cap a batch at 4 GiB) scanned by ONE kernel launch
 (ysb_submit_device_segments; --per-batch: one launch per batch).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
---gpus 1 (default): configs[1], 100M events.  Then, after the headline line's numbers
-are taken, the same process times configs[2] (1M campaigns / 10M ads) and the fork's
-.tbl rows as extra keys (--no-extras skips them).
+A plain run sets up, warms up, times the K steps, writes the timed path's outputs if
+--dump-outputs is given and prints the result line.  --full adds everything else after the
+headline's numbers are taken: the generator-truth check, the CPU baseline, the rocprofv3
+traffic passes and the extras below (cpu_baseline and check are null in a plain line, and
+roofline.traffic comes from profiles/pmc_traffic.json).
+
+--gpus 1 (default): configs[1], 100M events.  With --full the same process then times
+configs[2] (1M campaigns / 10M ads) and the fork's .tbl rows as extra keys (--no-extras
+skips them).
 
 --gpus N > 1: one process per GPU.  Started without torchrun (WORLD_SIZE unset), this
 process is only a launcher: it starts N rank processes (RANK / LOCAL_RANK / WORLD_SIZE /
@@ -18,10 +24,10 @@ MASTER_* set, 127.0.0.1) before anything touches a GPU and exits with their stat
 under torchrun each rank runs directly.  Events are sharded by ad_id hash (rank r draws
 from its own ad shard; per-GPU work fixed: weak scaling; 1B / N events per GPU at N >= 8,
 so N = 8 is configs[3]'s 1B events), every step ends with the RCCL reduce-scatter of the
-(campaign, window) tables over xGMI, and after timing the owners' rows are checked
-against the generator truth summed over ranks (check.exchange).
+(campaign, window) tables over xGMI, and with --full the owners' rows are checked after
+timing against the generator truth summed over ranks (check.exchange).
 
-Rank 0 prints one JSON line (metric/value/unit/... + roofline + cpu_baseline).
+Rank 0 prints one JSON line (metric/value/unit/... + roofline; --full: + cpu_baseline, check).
 """
 from __future__ import annotations
 
@@ -105,7 +111,18 @@ def parse_args(argv=None):
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="N = 1: take roofline.traffic from --traffic instead of two rocprofv3 --pmc child passes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the generator-truth check, the CPU baseline, the rocprofv3 "
+                         "traffic passes and the extras (each still has its --no-* switch); without it the run is "
+                         "set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they left in the context as DIR/<name>.npy (float64): "
+                         "counts = the drained rows (campaign, window_ms, count) sorted by campaign and window, "
+                         "stats = the context's counters in ysb_stats order; N > 1: rank r's owned rows as "
+                         "counts_rank<r> / stats_rank<r>")
     a = ap.parse_args(argv)
+    if not a.full:
+        a.no_cpu = a.no_check = a.no_extras = a.no_live_traffic = True
     if a.events is None:
         a.events = TOTAL_EVENTS_8 // a.gpus if a.gpus >= 8 else 100_000_000
     return a
@@ -374,6 +391,23 @@ def cpu_baseline(ctx, d_b, d_o, nb_seg, n_seg, ads, camp, sample, seconds):
             "sample": "first %d events (%.2f GB) of the GPU workload, oracle/ysb_oracle.c with %d threads, "
                       "%.1f s of repeats; 1 thread: %.0f events/s; counts identical to the GPU path on "
                       "that sample: %s" % (n, end / 1e9, threads, el, res[1][0], same)}
+
+
+def dump_outputs(ctx, d, path):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the rows
+    ysb_drain returns (the counts of the warm-up and timed steps together: the steps never
+    reset the table) and the context's counters -- as float64 .npy files (window_ms < 2^53 and
+    the counts are exact in float64).  The generator is seeded and its event times start at a
+    fixed t0, so the same arguments give the same files."""
+    os.makedirs(path, exist_ok=True)
+    rows = ctx.drain()
+    counts = np.array(sorted((c, w, v) for (c, w), v in rows.items()), dtype=np.float64).reshape(-1, 3)
+    st = ctx.stats()
+    stats = np.array(list(st.values()), dtype=np.float64)
+    suffix = "_rank%d" % d.rank if d.world > 1 else ""
+    np.save(os.path.join(path, "counts%s.npy" % suffix), counts)
+    np.save(os.path.join(path, "stats%s.npy" % suffix), stats)
+    log("rank %d: wrote %d rows and %d counters to %s" % (d.rank, len(counts), len(stats), path))
 
 
 def gen_segments(ctx, g, events, segment):
@@ -1040,6 +1074,8 @@ def main():
     kms, launches = ctx.kernel_time()
     xinfo = ctx.exchange_info(reset=True) if d.world > 1 else None
     layout_run = ctx.launch_info()["layout"]
+    if args.dump_outputs:
+        dump_outputs(ctx, d, args.dump_outputs)
 
     events_all = args.events * d.world * args.steps
     value = events_all / el

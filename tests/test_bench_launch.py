@@ -42,6 +42,19 @@ def test_bench_eight_gpus_is_one_billion_events():
     assert bench.parse_args(["--gpus", "8", "--events", "7"]).events == 7
 
 
+def test_bench_plain_run_skips_what_full_adds():
+    """Without --full nothing runs after the timed steps (check, CPU baseline, rocprofv3
+    passes, extras); --full leaves each leg to its own --no-* switch."""
+    import bench
+    legs = ("no_cpu", "no_check", "no_extras", "no_live_traffic")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not plain.full and plain.dump_outputs is None and all(getattr(plain, k) for k in legs)
+    full = bench.parse_args(["--full"])
+    assert full.full and not any(getattr(full, k) for k in legs)
+    some = bench.parse_args(["--full", "--no-cpu", "--dump-outputs", "out"])
+    assert some.no_cpu and not some.no_check and not some.no_extras and some.dump_outputs == "out"
+
+
 def test_bench_launcher_stops_the_ranks_when_one_fails():
     env = clean_env()
     env["YSB_BENCH_FAIL_RANK"] = "1"
@@ -63,9 +76,15 @@ def test_rank_device_mapping():
 
 
 def test_device_count_without_a_gpu_is_zero():
-    """ysb_device_count on this CPU-only container: 0, no exception, no framework needed."""
-    from ysb_amd import device_count
-    assert device_count() == 0
+    """ysb_device_count in a process that sees no GPU: 0, no exception, no framework needed.
+    The count is taken in a child whose HIP_VISIBLE_DEVICES names no device, so the same holds
+    on a machine that has GPUs."""
+    code = ("import sys; sys.path.insert(0, %r); from ysb_amd import device_count; print(device_count())"
+            % os.path.join(ROOT, "streaming-benchmarks_amd"))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120,
+                       env=dict(clean_env(), HIP_VISIBLE_DEVICES="-1"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert r.stdout.split() == ["0"] and "Traceback" not in r.stderr
 
 
 def test_live_traffic_reads_the_two_pmc_passes(monkeypatch, tmp_path):

@@ -21,10 +21,11 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     extras = str(tmp_path / "extras.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-host-collectives",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2",
+                        "--rehearse-host-collectives",
                         "--events", "4000000", "--steps", "2", "--warmup", "1", "--c3-events", "2000000",
                         "--extra-steps", "1", "--stream-seconds", "2", "--stream-target", "40e6",
-                        "--stream-host-gb", "4", "--extras-out", extras],
+                        "--stream-host-gb", "4", "--extras-out", extras, "--dump-outputs", str(tmp_path / "dump")],
                        capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     last = r.stdout.strip().splitlines()[-1]
@@ -36,6 +37,13 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     x = c["exchange"]
     assert x["post_exchange_mismatched_cells"] == 0 and x["owned_views"] == x["truth_views_summed"]
     assert x["owned_blocks"] == [[0, 50], [50, 100]]
+    # --dump-outputs: each rank's owned rows after the timed region's last (complete) exchange,
+    # the counts of the warm-up step and the two timed steps together
+    import numpy as np
+    dumped = [np.load(tmp_path / "dump" / ("counts_rank%d.npy" % rk)) for rk in (0, 1)]
+    for (lo, hi), rows in zip(x["owned_blocks"], dumped):
+        assert rows.dtype == np.float64 and len(rows) and lo <= rows[:, 0].min() and rows[:, 0].max() < hi
+    assert sum(rows[:, 2].sum() for rows in dumped) == 3 * x["owned_views"]
     s = line["extras_summary"]
     assert s["config3"]["exact"] is True, s
     assert s["stream_native"]["exact"] is True, s

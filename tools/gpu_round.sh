@@ -19,7 +19,7 @@ for s in $STAGES; do
     smoke)
       timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 ;;
     bench)
-      timeout -k 10 400 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+      timeout -k 10 400 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
     trace)
       (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
          -d "$OUT/trace" -o run -- python3 "$REPO/bench.py" --steps 20 --warmup 10 --no-cpu --no-check \
