@@ -311,35 +311,62 @@ class YsbContext:
     def group_init(self, rank, nranks, uid: bytes):
         self._c(lib().ysb_group_init(self._h, rank, nranks, C.create_string_buffer(uid, _lib.UNIQUE_ID_BYTES)))
 
+    callback_error = None   # the last exception a group_init_host_fns callable raised
+
+    def group_init_host_fns(self, rank, nranks, allreduce_max, reduce_scatter_sum):
+        """ysb_group_init_host over two Python callables on numpy views of the library's host
+        buffers (a transport of the caller's; a test that plays the other ranks itself):
+          allreduce_max(buf: uint64[n])  -- elementwise max over the ranks, in place;
+          reduce_scatter_sum(send, count, width) -> count cells -- send is the read-only uint8
+            view of this rank's nranks * count cells of `width` bytes (every owner's block);
+            the return value is this rank's block summed over the ranks, as unsigned cells.
+        An exception in a callable never crosses the C frame: it is kept in
+        self.callback_error and the library call fails (YSB_ERR_RCCL)."""
+        cell = {1: np.uint8, 4: np.uint32, 8: np.uint64}
+
+        def amax(_user, buf, n):
+            try:
+                allreduce_max(np.ctypeslib.as_array(buf, shape=(n,)))
+                return 0
+            except BaseException as e:   # noqa: BLE001 (a failing callback fails the call)
+                self.callback_error = e
+                return 1
+
+        def rsum(_user, send, recv, count, width):
+            try:
+                nb = count * width
+                s_ = np.frombuffer((C.c_char * (nb * nranks)).from_address(send), dtype=np.uint8)
+                s_.flags.writeable = False
+                out = np.ascontiguousarray(reduce_scatter_sum(s_, count, width), dtype=cell[width])
+                if out.size != count:
+                    raise ValueError("reduce_scatter_sum returned %d cells, not %d" % (out.size, count))
+                C.memmove(recv, out.ctypes.data, nb)
+                return 0
+            except BaseException as e:   # noqa: BLE001
+                self.callback_error = e
+                return 1
+        self.callback_error = None
+        self._coll = _lib.YsbCollectives(_lib.ALLREDUCE_MAX_FN(amax), _lib.REDUCE_SCATTER_FN(rsum), None)
+        self._c(lib().ysb_group_init_host(self._h, rank, nranks, C.byref(self._coll)))
+
     def group_init_host(self, rank, nranks, dist):
         """ysb_group_init_host over torch.distributed (e.g. gloo) as the transport: the
         library's exchange with the process group's collectives on host memory (N ranks on
         one GPU, where RCCL refuses two ranks per device)."""
         import torch
 
-        def amax(_user, buf, n):
-            try:
-                a = np.ctypeslib.as_array(buf, shape=(n,))
-                t = torch.from_numpy((a ^ np.uint64(1 << 63)).view(np.int64).copy())
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-                a[:] = t.numpy().view(np.uint64) ^ np.uint64(1 << 63)
-                return 0
-            except Exception:   # noqa: BLE001 (a failing callback fails the call)
-                return 1
+        def amax(a):
+            t = torch.from_numpy((a ^ np.uint64(1 << 63)).view(np.int64).copy())
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            a[:] = t.numpy().view(np.uint64) ^ np.uint64(1 << 63)
 
-        def rsum(_user, send, recv, count, width):
-            try:
-                cell = {1: np.uint8, 4: np.int32, 8: np.int64}[width]
-                nb = count * width
-                s_ = np.frombuffer((C.c_char * (nb * nranks)).from_address(send), dtype=cell).copy()
-                out = torch.zeros(count, dtype={1: torch.uint8, 4: torch.int32, 8: torch.int64}[width])
-                dist.reduce_scatter_tensor(out, torch.from_numpy(s_))
-                C.memmove(recv, out.numpy().ctypes.data, nb)
-                return 0
-            except Exception:   # noqa: BLE001
-                return 1
-        self._coll = _lib.YsbCollectives(_lib.ALLREDUCE_MAX_FN(amax), _lib.REDUCE_SCATTER_FN(rsum), None)
-        self._c(lib().ysb_group_init_host(self._h, rank, nranks, C.byref(self._coll)))
+        def rsum(send, count, width):
+            # (torch has no unsigned 32 / 64-bit sums: two's complement adds the same bits)
+            s_ = send.view({1: np.uint8, 4: np.int32, 8: np.int64}[width]).copy()
+            out = torch.zeros(count, dtype={1: torch.uint8, 4: torch.int32, 8: torch.int64}[width])
+            dist.reduce_scatter_tensor(out, torch.from_numpy(s_))
+            return out.numpy().view({1: np.uint8, 4: np.uint32, 8: np.uint64}[width])
+        self.group_init_host_fns(rank, nranks, amax, rsum)
 
     def group_reduce_scatter(self):
         """The complete exchange: every pending count reaches its owner."""
