@@ -401,6 +401,65 @@ int         ysb_ring_range(ysb_ctx* ctx, int64_t* lo, uint32_t* width);
  * differ). */
 int         ysb_ring_advance(ysb_ctx* ctx, int64_t new_lo);
 
+/* ---- columnar decode -------------------------------------------------------------------
+ * The fork's second use of the parsed events: WindowedArrowFormatBolter
+ * (AdvertisingTopologyNative.java:278-356, wired commented at :106-109) turns a count window
+ * of tuples into a fixed-stride, page-aligned columnar batch in a shared mapping, its hand-off
+ * format for an accelerator.  These calls give DeserializeBolt's Tuple7 (:263-272) /
+ * split("\\|")'s items (:197-226) in that layout, in HBM, for other GPU operators.  Additive:
+ * nothing of the counting path is touched (the ABI version stays 5). */
+
+/* The layout of a batch of batch_rows rows (host function, no context): seven columns
+ * user_id, page_id, ad_id, ad_type, event_type, event_time, stamp of width[] =
+ * {36,36,36,4,4,8,8} bytes per row (:284).  As the reference's constructor does (:291-302),
+ * column j starts at the running offset start[j], which then grows by width[j] * batch_rows
+ * rounded up to 4096-byte pages; the offset after column 6 is the reference's buffer_size =
+ * image_bytes, so the first image_bytes bytes are the reference's file image.  One more buffer
+ * follows at start[7] = image_bytes, an Arrow-style validity bitmap: row i is bit i % 64 of the
+ * little-endian 64-bit word i / 64, ceil(batch_rows / 64) words rounded up to a page;
+ * start[8] is the whole size.  YSB_ERR_ARG for batch_rows 0 or above 2^31 - 1. */
+typedef struct ysb_columns_layout {
+    uint64_t rows;          /* batch_rows the layout was computed for                */
+    uint64_t start[9];      /* byte offset of column j; [7] validity, [8] = total    */
+    uint32_t width[7];      /* 36,36,36,4,4,8,8 (AdvertisingTopologyNative.java:284) */
+    uint32_t reserved;
+    uint64_t image_bytes;   /* the reference's buffer_size = start[7]                */
+} ysb_columns_layout;
+int         ysb_columns_layout_of(uint64_t batch_rows, ysb_columns_layout* out);
+
+#define YSB_COL_JAVA_ORDER 0x1u  /* columns 5 and 6 big-endian, as MappedByteBuffer.putLong writes them */
+typedef struct ysb_decode_info {
+    uint64_t rows;          /* n_events                                              */
+    uint64_t valid;         /* rows the reference would not have thrown on           */
+    uint64_t fast_rows;     /* rows the kernel's fast tier took                      */
+    double   kernel_ms;     /* device time of the decode kernel (a HIP event pair)   */
+} ysb_decode_info;
+/* Replaces WindowedArrowFormatBolter.flatMap's per-tuple puts (:323-334) for one device batch
+ * (as for ysb_submit_device: d_bytes 16-byte aligned, < 4 GiB, n_events u32 line offsets).
+ * d_out is a 16-byte aligned HBM buffer of ysb_columns_layout_of(batch_rows).start[8] bytes;
+ * n_events > batch_rows is YSB_ERR_CAPACITY.  Row i is line i.  The input format is the
+ * context's: JSON lines with org.json's semantics, or .tbl rows under YSB_F_FORMAT_TBL;
+ * YSB_F_REQUIRE_IP also requires a string ip_address (which gets no column).
+ *   A row is valid iff the reference would not throw on it: the line parses (new JSONObject +
+ * getString of the six keys, :263-272; .tbl: at least 6 items, :197-226), each of the five
+ * String values has at least its column's width in UTF-8 bytes (put(bytes, 0, entry_len[j])
+ * throws on a shorter array, :325-331), and Long.parseLong(event_time) succeeds.  A valid row
+ * holds the first width[j] bytes of each String value (longer ones are cut, as the reference
+ * cuts them: "banner" -> "bann"; a multi-byte character may be cut), the parsed long in column
+ * 5 and `stamp` in column 6 (the reference writes 10L, :333) -- little-endian, or with
+ * YSB_COL_JAVA_ORDER the file image's big-endian.  An invalid row holds zero bytes in every
+ * column and a zero validity bit.
+ *   Only rows [0, n_events) of each column and validity words [0, ceil(n_events / 64)) are
+ * written (the bits of rows >= n_events in the last word zero); page padding and rows
+ * [n_events, batch_rows) keep whatever d_out held.
+ *   Runs on the compute stream behind everything submitted, then waits.  It reads no join
+ * table (no ad map needs to be loaded) and changes neither the ring, the side list, the stats
+ * nor the layout sampling's state.  info may be NULL. */
+int         ysb_decode_columns_device(ysb_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes,
+                                      const uint32_t* d_line_off, uint64_t n_events,
+                                      uint8_t* d_out, uint64_t batch_rows, int64_t stamp,
+                                      uint32_t flags, ysb_decode_info* info);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* With YSB_F_TIMING: total device time of the scan kernel launches (HIP events on
  * the compute stream) and the number of launches since the last call (resets). */

@@ -119,6 +119,9 @@ static void destroy(ysb_ctx* c) {
     hipFree(c->d_defer);
     hipFree(c->d_defer_ctr);
     hipFree(c->d_dbg);
+    hipFree(c->d_colinfo);
+    for (hipEvent_t e : c->ev_col)
+        if (e) hipEventDestroy(e);
     for (int s = 0; s < 2; ++s) {
         hipHostFree(c->h_bytes[s]);
         hipHostFree(c->h_off[s]);

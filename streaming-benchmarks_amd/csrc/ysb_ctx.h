@@ -257,6 +257,9 @@ struct ysb_ctx {
     u32 dyn_chunk = 16;                    // tiles per claim (YSB_DYN_CHUNK)
     unsigned long long* d_dbg = nullptr;   // YSB_STAMPS diagnostic build
     u64 dbg_words = 0;
+    // columnar decode (ysb_columns.cpp): {valid rows, fast-tier rows} of a call, its event pair
+    unsigned long long* d_colinfo = nullptr;
+    hipEvent_t ev_col[2] = {nullptr, nullptr};
 };
 
 #define YSB_INTERNAL __attribute__((visibility("hidden")))

@@ -259,6 +259,25 @@ void launch_ring_autobase(const ScanParams& p, hipStream_t s);
 // The pipe-delimited .tbl input format (YSB_F_FORMAT_TBL): scan + ring auto-base.
 void launch_tbl_ring_autobase(const ScanParams& p, hipStream_t s);
 
+// Columnar decode (ysb_scan_columns.h, ysb_decode_columns_device): lines [0, n) of one device
+// batch into rows [0, n) of the seven columns and the validity words [0, ceil(n / 64)) of out;
+// nothing else of out is written.  info[0] += valid rows, info[1] += rows the fast tier took.
+struct ColParams {
+    const u8* bytes;            // batch bytes (16-byte aligned)
+    u64 nbytes;
+    const u32* off;             // n line offsets
+    u64 n;
+    u64 n_tiles;                // ceil(n / TILE_LINES)
+    u8* out;                    // 16-byte aligned
+    u64 start[8];               // byte offsets of the columns, [7] the validity bitmap (page multiples)
+    i64 stamp;                  // column 6 of every valid row
+    u32 java_order;             // 1: columns 5 and 6 big-endian (YSB_COL_JAVA_ORDER)
+    u32 tbl;                    // 1: the fork's .tbl rows instead of JSON lines
+    u32 require_mask;           // required-key bit mask (JSON)
+    unsigned long long* info;   // [2]
+};
+void launch_columns(const ColParams& p, int cus, hipStream_t s);
+
 // Generator kernels (ysb_gen.hip).
 hipError_t gen_events_device(const GenSpec& spec, u64 first, u64 n, u8* d_out, u64 cap,
                              u32* d_off, u64* nbytes, hipStream_t s);

@@ -1297,3 +1297,5 @@ void launch_ring_autobase(const ScanParams& p, hipStream_t s) {
 int scan_lds_bytes() { return LDS_BYTES; }
 
 }  // namespace ysb
+
+#include "ysb_scan_columns.h"

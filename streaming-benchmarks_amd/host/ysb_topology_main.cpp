@@ -4,6 +4,7 @@
 // one GPU, and writes the (campaign, window) counts to Redis in the reference's schema
 // (or to a CSV file).
 //
+//   ysb_topology --confPath PATH --columns [--device N] [--format json|tbl] [--require-ip]
 //   ysb_topology --confPath PATH [--device N] [--sink none|csv:FILE|redis[:HOST[:PORT]]]
 //                [--format json|tbl] [--flush-ms MS] [--batch-mb MB | --batch-bytes B] [--batch-events N]
 //                [--window-ring W] [--require-ip] [--dry-run] [--print-config]
@@ -39,6 +40,7 @@ struct Args {
     long long batch_bytes = 256ll << 20, batch_events = 1 << 20;
     unsigned window_ring = 1024;
     bool require_ip = false, dry = false, print_config = false, host_split = false;
+    bool columns = false;                       // --columns: the columnar chain (:106-109)
     long long repeat = 1;
     unsigned io_threads = 0;
     bool io_mmap = true;
@@ -65,6 +67,8 @@ void usage() {
                  "       [--window-ring W] [--require-ip] [--dry-run] [--print-config] [--replay-rows CSV]\n"
                  "       [--host-split] [--repeat K] [--io-threads T] [--io auto|mapped|mmap|pread]\n"
                  "       [--h2d-sdma]\n"
+                 "   or: ysb_topology --confPath PATH --columns [--device N] [--format json|tbl] [--require-ip]\n"
+                 "       [--batch-mb MB | --batch-bytes B]   (window.size rows per <shared_file>_<k>)\n"
                  "   or: ysb_topology --stream [--sink none|csv:FILE|redis[:HOST[:PORT]]] [--shards N] [--device D]\n"
                  "       [--seed S] [--campaigns C] [--ads-per-campaign A] [--event-rate E] [--speedup F]\n"
                  "       [--cycle-ms MS] [--flush-ms MS] [--batch-ms MS] [--ooo-ms MS] [--seconds S]\n"
@@ -105,6 +109,7 @@ Args parse(int argc, char** argv) {
             a.io = m;
         }
         else if (k == "--h2d-sdma") a.h2d_sdma = true;
+        else if (k == "--columns") a.columns = true;
         else if (k == "--stream") a.stream = true;
         else if (k == "--stream-self-check") { a.stream = true; a.self_check = true; }
         else if (k == "--shards") a.so.shards = std::atoi(val().c_str());
@@ -132,6 +137,10 @@ Args parse(int argc, char** argv) {
                                                                                     : StreamOptions::COPY;
         }
         else { usage(); std::exit(2); }
+    }
+    if (a.stream && a.columns) {
+        std::fprintf(stderr, "--columns reads events_path in batch mode: not with --stream\n");
+        std::exit(2);
     }
     if (a.stream) {   // the generator's ids and events: no config file needed
         a.so.device = a.device;
@@ -335,6 +344,111 @@ int run(const Args& a) {
     return s.overflow_dropped ? 3 : 0;
 }
 
+// --columns: the reference's commented chain (AdvertisingTopologyNative.java:106-109) instead
+// of the counting chain -- countWindowAll(window.size) over the events file's rows, each
+// window decoded on the GPU into WindowedArrowFormatBolter's columnar image (:278-356) and
+// written to <shared_file>_<k> (:317) as the reference's mapping would hold it: image_bytes
+// long, longs big-endian (MappedByteBuffer.putLong), stamp 10 (:333), padding zero.  A trailing
+// partial window is never written (the count window does not fire).  A row the reference
+// would have thrown on fails the job.
+int run_columns(const Args& a) {
+    const Config conf = Config::findAndReadConfigFile(a.conf, true);
+    const std::string events = conf.get("events_path");
+    const std::string shared = conf.get("shared_file");
+    const long long window = conf.getLong("window.size");
+    if (window <= 0 || window > 0x7FFFFFFFll) throw std::runtime_error("window.size must be in [1, 2^31 - 1]");
+    if (!a.format.empty() && a.format != "json" && a.format != "tbl") { usage(); return 2; }
+    const bool tbl = a.format.empty() ? (events.size() > 4 && events.compare(events.size() - 4, 4, ".tbl") == 0)
+                                      : a.format == "tbl";
+    ysb_columns_layout lay;
+    if (ysb_columns_layout_of((uint64_t)window, &lay)) throw std::runtime_error("ysb_columns_layout_of failed");
+
+    ysb_config cfg;
+    ysb_config_default(&cfg);
+    cfg.n_campaigns = 1;   // the decode uses no join table and no ring
+    cfg.window_ring = 16;
+    cfg.max_ads = 1;
+    cfg.max_batch_events = 64;
+    cfg.max_batch_bytes = 1 << 16;
+    cfg.overflow_capacity = 16;
+    cfg.flags = YSB_F_LAYOUT_FIXED | (tbl ? YSB_F_FORMAT_TBL : 0u) | (a.require_ip ? YSB_F_REQUIRE_IP : 0u);
+    ysb_ctx* ctx = nullptr;
+    if (ysb_open(&ctx, a.device, &cfg)) throw std::runtime_error(std::string("ysb_open: ") + ysb_last_error(nullptr));
+    auto chk = [&](int rc, const char* what) {
+        if (rc) {
+            const std::string msg = std::string(what) + ": " + ysb_last_error(ctx);
+            ysb_close(ctx);
+            throw std::runtime_error(msg);
+        }
+    };
+    const uint64_t cap = (uint64_t)a.batch_bytes;
+    void *d_bytes = nullptr, *d_off = nullptr, *d_out = nullptr;
+    chk(ysb_device_alloc(ctx, cap, &d_bytes), "ysb_device_alloc");
+    chk(ysb_device_alloc(ctx, 4 * (uint64_t)window, &d_off), "ysb_device_alloc");
+    chk(ysb_device_alloc(ctx, lay.start[8], &d_out), "ysb_device_alloc");
+    std::vector<uint8_t> image(lay.start[8], 0);   // a fresh mapping is zero
+    chk(ysb_memcpy_h2d(ctx, d_out, image.data(), image.size()), "ysb_memcpy_h2d");
+
+    FileBasedDataSource src(events, a.io_threads, a.io_mmap);
+    std::vector<uint8_t> wbytes(cap), buf(cap);
+    std::vector<uint32_t> woff((size_t)window), off((size_t)window);
+    uint64_t have = 0, used = 0, files = 0, rows = 0;
+    double kernel_ms = 0;
+    const double t0 = now_s();
+    for (;;) {
+        uint64_t nb = 0;
+        const uint64_t n = src.fill(buf.data(), cap - used, off.data(), (uint64_t)window - have, &nb);
+        if (n == 0) break;
+        std::memcpy(wbytes.data() + used, buf.data(), nb);
+        for (uint64_t i = 0; i < n; ++i) woff[have + i] = (uint32_t)(used + off[i]);
+        have += n;
+        used += nb;
+        if (have < (uint64_t)window) {
+            if (used >= cap) {
+                ysb_close(ctx);
+                throw std::runtime_error("a window of " + std::to_string(window) + " rows exceeds --batch-bytes");
+            }
+            continue;
+        }
+        chk(ysb_memcpy_h2d(ctx, d_bytes, wbytes.data(), used), "ysb_memcpy_h2d");
+        chk(ysb_memcpy_h2d(ctx, d_off, woff.data(), 4 * have), "ysb_memcpy_h2d");
+        ysb_decode_info info;
+        chk(ysb_decode_columns_device(ctx, (const uint8_t*)d_bytes, used, (const uint32_t*)d_off, have, (uint8_t*)d_out,
+                                      (uint64_t)window, 10, YSB_COL_JAVA_ORDER, &info),
+            "ysb_decode_columns_device");
+        kernel_ms += info.kernel_ms;
+        chk(ysb_memcpy_d2h(ctx, image.data(), d_out, image.size()), "ysb_memcpy_d2h");
+        if (info.valid != info.rows) {   // the reference's flatMap throws: the job fails
+            uint64_t bad = 0;
+            while (bad < have && ((image[lay.start[7] + bad / 8] >> (bad % 8)) & 1)) ++bad;
+            ysb_close(ctx);
+            throw std::runtime_error("--columns: " + shared + "_" + std::to_string(files) + " (file index " +
+                                     std::to_string(files) + "), row " + std::to_string(bad) + " (line " +
+                                     std::to_string(rows + bad + 1) + " of " + events +
+                                     "): a row the reference throws on (" +
+                                     std::to_string(info.rows - info.valid) + " in this window)");
+        }
+        const std::string path = shared + "_" + std::to_string(files);
+        std::FILE* f = std::fopen(path.c_str(), "wb");
+        if (!f || std::fwrite(image.data(), 1, lay.image_bytes, f) != lay.image_bytes || std::fclose(f) != 0) {
+            ysb_close(ctx);
+            throw std::runtime_error("cannot write " + path);
+        }
+        ++files;
+        rows += have;
+        have = used = 0;
+    }
+    for (void* p : {d_bytes, d_off, d_out}) ysb_device_free(ctx, p);
+    ysb_close(ctx);
+    const double el = now_s() - t0;
+    std::printf("{\"mode\": \"columns\", \"files\": %llu, \"rows\": %llu, \"dropped_tail_rows\": %llu, "
+                "\"window_size\": %lld, \"image_bytes\": %llu, \"kernel_ms\": %.3f, \"seconds\": %.3f, "
+                "\"format\": \"%s\", \"shared_file\": %s}\n",
+                (unsigned long long)files, (unsigned long long)rows, (unsigned long long)have, window,
+                (unsigned long long)lay.image_bytes, kernel_ms, el, tbl ? "tbl" : "json", json_str(shared).c_str());
+    return 0;
+}
+
 double pct(std::vector<double> v, double q) {
     if (v.empty()) return 0;
     std::sort(v.begin(), v.end());
@@ -451,6 +565,7 @@ int main(int argc, char** argv) {
             return r.find("\"ok\": true") != std::string::npos ? 0 : 1;
         }
         if (a.stream) return run_stream(a);
+        if (a.columns) return run_columns(a);
         return run(a);
     } catch (const std::exception& e) {   // the job fails, as the reference's uncaught exceptions do
         std::fprintf(stderr, "ysb_topology: %s\n", e.what());

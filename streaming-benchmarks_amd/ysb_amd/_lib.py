@@ -85,6 +85,19 @@ class YsbSegment(C.Structure):
                 ("n_events", C.c_uint64)]
 
 
+YSB_COL_JAVA_ORDER = 0x1
+
+
+class YsbColumnsLayout(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("start", C.c_uint64 * 9), ("width", C.c_uint32 * 7),
+                ("reserved", C.c_uint32), ("image_bytes", C.c_uint64)]
+
+
+class YsbDecodeInfo(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("valid", C.c_uint64), ("fast_rows", C.c_uint64),
+                ("kernel_ms", C.c_double)]
+
+
 class YsbGenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_campaigns", C.c_uint32), ("ads_per_campaign", C.c_uint32),
                 ("t0_ms", C.c_int64), ("events_per_sec", C.c_uint64), ("with_skew", C.c_uint32),
@@ -129,6 +142,9 @@ SIGNATURES = {
     "ysb_copy_time": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_U64), C.POINTER(_U64)]),
     "ysb_submit_device": (_I, [_P, _PU8, _U64, _PU32, _U64]),
     "ysb_submit_device_segments": (_I, [_P, C.c_void_p, _U32]),
+    "ysb_columns_layout_of": (_I, [_U64, C.POINTER(YsbColumnsLayout)]),
+    "ysb_decode_columns_device": (_I, [_P, _PU8, _U64, _PU32, _U64, _PU8, _U64, _I64, _U32,
+                                       C.POINTER(YsbDecodeInfo)]),
     "ysb_sync": (_I, [_P]),
     "ysb_drain": (_I, [_P, _I64, _I64, _I, C.POINTER(YsbCount), _U64, C.POINTER(_U64)]),
     "ysb_stats_get": (_I, [_P, C.POINTER(YsbStats)]),

@@ -33,6 +33,17 @@ def device_sync(device):
     check(lib().ysb_device_sync(int(device)), None)
 
 
+def columns_layout(rows):
+    """ysb_columns_layout_of: the fork's seven-column layout (WindowedArrowFormatBolter,
+    AdvertisingTopologyNative.java:278-356) for a batch of `rows` rows, as a dict: rows,
+    start (9 byte offsets: the columns, [7] the validity bitmap, [8] the total), width (7),
+    image_bytes (the reference's file image = start[7])."""
+    lay = _lib.YsbColumnsLayout()
+    check(lib().ysb_columns_layout_of(int(rows), C.byref(lay)), None)
+    return {"rows": lay.rows, "start": [int(v) for v in lay.start], "width": [int(v) for v in lay.width],
+            "image_bytes": lay.image_bytes}
+
+
 def rank_device(local_rank, n_visible):
     """The device a rank uses (one context per GPU): its LOCAL_RANK, unless the launcher left
     each process fewer visible devices (e.g. one per rank through HIP_VISIBLE_DEVICES): then
@@ -208,6 +219,44 @@ class YsbContext:
 
     def sync(self):
         self._c(lib().ysb_sync(self._h))
+
+    # -- columnar decode ---------------------------------------------------------------
+    def decode_columns_device(self, d_bytes, nbytes, d_off, n, d_out, batch_rows, stamp=10, flags=0):
+        """ysb_decode_columns_device: lines [0, n) of a device batch into rows [0, n) of the
+        seven columns and the validity bitmap of d_out (columns_layout(batch_rows)["start"][8]
+        bytes of HBM).  Returns the info as a dict: rows, valid, fast_rows, kernel_ms."""
+        info = _lib.YsbDecodeInfo()
+        self._c(lib().ysb_decode_columns_device(self._h, C.c_void_p(d_bytes), nbytes, C.c_void_p(d_off), n,
+                                                C.c_void_p(d_out), batch_rows, int(stamp), int(flags),
+                                                C.byref(info)))
+        return {k: getattr(info, k) for k, _ in _lib.YsbDecodeInfo._fields_}
+
+    def decode_columns(self, data, offsets, batch_rows=None, **kw):
+        """Host batch (bytes / uint8 array + uint32 line offsets) decoded on the device:
+        allocates, copies, decodes and returns (image: uint8[start[8]], valid: bool[n], info).
+        The image is zero wherever the decode writes nothing (padding, rows past n).
+        batch_rows defaults to the number of lines; kw: stamp, flags."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        n = off.size
+        rows = max(n, 1) if batch_rows is None else int(batch_rows)
+        total = columns_layout(rows)["start"][8]
+        image = np.zeros(total, dtype=np.uint8)
+        d_b, d_o, d_out = self.device_alloc(buf.size), self.device_alloc(4 * n), self.device_alloc(total)
+        try:
+            if buf.size:
+                self.h2d(d_b, buf)
+            if n:
+                self.h2d(d_o, off)
+            self.h2d(d_out, image)
+            info = self.decode_columns_device(d_b, buf.size, d_o, n, d_out, rows, **kw)
+            self.d2h(image, d_out)
+        finally:
+            for p in (d_b, d_o, d_out):
+                self.device_free(p)
+        words = image[columns_layout(rows)["start"][7]:][:8 * ((n + 63) // 64)].view("<u8")
+        valid = ((words[np.arange(n) // 64] >> (np.arange(n) % 64).astype(np.uint64)) & np.uint64(1)).astype(np.bool_)
+        return image, valid, info
 
     # -- results -----------------------------------------------------------------------
     def drain(self, bucket_lo=INT64_MIN, bucket_hi=(1 << 63) - 1, clear=False):
