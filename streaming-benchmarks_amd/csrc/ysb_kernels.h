@@ -254,10 +254,8 @@ constexpr int N_STAMPS = 8;     // phases timed by the YSB_STAMPS diagnostic bui
 void launch_scan(const ScanParams& p, hipStream_t s);
 // The general-path lines the scan deferred (same stream, right after launch_scan).
 void launch_defer(const ScanParams& p, int blocks, hipStream_t s);
-// Sets ring[0..1] from the first lines of a batch if ring[1] == 0.
+// Sets ring[0..1] from the first lines of a batch (JSON, or .tbl rows with p.tbl) if ring[1] == 0.
 void launch_ring_autobase(const ScanParams& p, hipStream_t s);
-// The pipe-delimited .tbl input format (YSB_F_FORMAT_TBL): scan + ring auto-base.
-void launch_tbl_ring_autobase(const ScanParams& p, hipStream_t s);
 
 // Columnar decode (ysb_scan_columns.h, ysb_decode_columns_device): lines [0, n) of one device
 // batch into rows [0, n) of the seven columns and the validity words [0, ceil(n / 64)) of out;

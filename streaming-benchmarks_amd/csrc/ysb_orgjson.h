@@ -2,8 +2,9 @@
 // `new JSONObject(line)` + `getString` as DeserializeBolt calls them
 // (flink-benchmarks/.../AdvertisingTopologyNative.java:263-272; org.json is the
 // third-party dependency pom.xml:24 pins).  Included by ysb_scan.hip after the byte
-// sources, Span and the key matchers; used by the deferred-line kernel and the ring
-// auto-base probe only (the canonical fast path never calls it).
+// sources, Span and the key matchers; used by the deferred-line kernel, the ring
+// auto-base probe and the columnar decode's general tier (the canonical fast paths never
+// call it).
 //
 // The grammar (same rules as oracle/orgjson.py and oracle/ysb_oracle.c; DESIGN.md
 // section 3 lists them and the documented limits):
@@ -517,11 +518,31 @@ __device__ __forceinline__ bool oj_value(OjTok<S>& t, OjVal& v) {
 enum : u8 { OJR_TOP = 0, OJR_KEY, OJR_VALUE, OJR_ELEM };
 enum : int { OJS_KEY = 0, OJS_COLON, OJS_VALUE, OJS_OSEP, OJS_AFIRST, OJS_AELEM, OJS_ASEP };
 
+// What parse_line keeps of a line: put(kid, v) receives the String value v of the top-level
+// key with id kid (one of K_USER .. K_IP).  The counting path keeps the three values the
+// bolts after DeserializeBolt read, the columnar decode all seven (sp[k]: key bit k).
+struct KeepCount {
+    Span ad{0, 0, 0}, et{0, 0, 0}, tm{0, 0, 0};
+    __device__ __forceinline__ void put(u32 kid, const Span& v) {
+        if (kid == K_AD) ad = v;
+        else if (kid == K_ETYPE) et = v;
+        else if (kid == K_ETIME) tm = v;
+    }
+};
+struct KeepAll {
+    Span sp[7] = {};
+    __device__ __forceinline__ void put(u32 kid, const Span& v) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k)
+            if (kid == (1u << k)) sp[k] = v;
+    }
+};
+
 // new JSONObject(line [s, e)) then getString of the fields in `require`: false where
-// DeserializeBolt would throw.  ad / et / tm receive the String values of the
-// top-level ad_id / event_type / event_time.
-template <class S>
-__device__ __noinline__ bool parse_line(const S& src, int s, int e, u32 require, Span& ad, Span& et, Span& tm) {
+// DeserializeBolt would throw.  keep receives the String values of the top-level keys
+// DeserializeBolt reads.
+template <class S, class K>
+__device__ __noinline__ bool parse_line(const S& src, int s, int e, u32 require, K& keep) {
     int end = e;                                                           // NUL: end of input
     for (int q = s & ~3; q < e; q += 4) {                                  // word at a time
         const u32 w = src.load4(q);
@@ -594,10 +615,7 @@ __device__ __noinline__ bool parse_line(const S& src, int s, int e, u32 require,
             if (!oj_value(t, v)) return false;
             if (v.kind == OJV_OBJ || v.kind == OJV_ARR) { kid = 0; nested = OJR_VALUE; break; }
             if (kid && (v.kind == OJV_STR || oj_token_kind(src, v.a, v.b) == OJ_STR)) {   // getString
-                const Span sp{v.a, v.b, v.kind == OJV_STR ? v.esc : 0};
-                if (kid == K_AD) ad = sp;
-                else if (kid == K_ETYPE) et = sp;
-                else if (kid == K_ETIME) tm = sp;
+                keep.put(kid, Span{v.a, v.b, v.kind == OJV_STR ? v.esc : 0});
                 seen |= kid;
             }
             kid = 0;

@@ -76,26 +76,21 @@ constexpr u32 VIEW_W = w4('v', 'i', 'e', 'w');
 // ---------------------------------------------------------------------------
 // Byte sources.  Positions are ints relative to the source base.
 // ---------------------------------------------------------------------------
-struct LdsSrc {
-    const u32* d;   // tile bytes as dwords
+template <class W>
+struct WordSrc {
+    W d;   // tile bytes as dwords
     __device__ __forceinline__ u32 b(int p) const { return (d[p >> 2] >> ((p & 3) << 3)) & 0xFFu; }
     __device__ __forceinline__ u32 load4(int p) const {
         const u32 lo = d[p >> 2], hi = d[(p >> 2) + 1];
         return __builtin_amdgcn_alignbyte(hi, lo, (u32)(p & 3));
     }
 };
+using LdsSrc = WordSrc<const u32*>;
 
 // The same through an explicitly LDS-qualified pointer, for code that is not inlined into
 // the kernel (the general parser): ds_read instead of flat loads.
 typedef __attribute__((address_space(3))) const u32 lds_u32;
-struct LdsSrc3 {
-    lds_u32* d;
-    __device__ __forceinline__ u32 b(int p) const { return (d[p >> 2] >> ((p & 3) << 3)) & 0xFFu; }
-    __device__ __forceinline__ u32 load4(int p) const {
-        const u32 lo = d[p >> 2], hi = d[(p >> 2) + 1];
-        return __builtin_amdgcn_alignbyte(hi, lo, (u32)(p & 3));
-    }
-};
+using LdsSrc3 = WordSrc<lds_u32*>;
 
 struct GlbSrc {  // slow path for tiles that do not fit the LDS tile
     const u8* base;
@@ -341,10 +336,10 @@ __device__ __forceinline__ bool finish_line(const S& src, const Span& ad, const 
 template <class S>
 __device__ __forceinline__ bool process_line(const S& src, int s, int e, const ScanParams& P,
                                              Tally& t, u32& campaign, i64& bucket) {
-    Span ad{0, 0, 0}, et{0, 0, 0}, tm{0, 0, 0};
+    KeepCount k;
     t.ev++;
-    if (!parse_line(src, s, e, P.require_mask, ad, et, tm)) { t.perr++; return false; }
-    return finish_line(src, ad, et, tm, P, t, campaign, bucket);
+    if (!parse_line(src, s, e, P.require_mask, k)) { t.perr++; return false; }
+    return finish_line(src, k.ad, k.et, k.tm, P, t, campaign, bucket);
 }
 
 }  // namespace ysb
@@ -373,10 +368,11 @@ struct TileInfo {
     bool oversize; // does not fit TILE_CAP (or offsets are not monotone)
 };
 
-// Tile bounds come from the LDS copy tb[] (loaded once per workgroup), so no HBM
-// round trip sits between two tiles.
-template <int CAP>
-__device__ __forceinline__ TileInfo tile_info(const ScanParams& P, u64 t, u64 t_begin, const u32* tb) {
+// Tile t of P's batch (ScanParams, ColParams) from its bounds tb[t - t_begin],
+// tb[t - t_begin + 1].  The scan's come from the LDS copy tb[] (loaded once per workgroup),
+// so no HBM round trip sits between two tiles.
+template <int CAP, class PP>
+__device__ __forceinline__ TileInfo tile_info(const PP& P, u64 t, u64 t_begin, const u32* tb) {
     TileInfo ti;
     ti.first = t * TILE_LINES;
     const u64 rem = P.n - ti.first;
@@ -438,12 +434,13 @@ __device__ __forceinline__ u32 lane_line(int tid) {
 // loads through per-tile descriptors (base = the tile, num_records = its length, so
 // chunks past the tile read zeros and never fault); per-lane offsets are
 // loop-invariant, so issuing costs no VALU.  Always the same number of loads per lane,
-// so later waits can count them (vmcnt) instead of draining everything.
+// so later waits can count them (vmcnt) instead of draining everything.  li: the tile
+// line whose offsets this lane receives.
 template <int CPT>
-__device__ __forceinline__ void issue_tile_loads(const ScanParams& P, const TileInfo& ti, uint4 (&pre)[CPT],
-                                                 u32& my_off, u32& my_end) {
+__device__ __forceinline__ void issue_tile_loads(const u8* bytes, const u32* off, u64 n, u32 li, const TileInfo& ti,
+                                                 uint4 (&pre)[CPT], u32& my_off, u32& my_end) {
     const int tid = threadIdx.x;
-    const u8* tbase = P.bytes + (ti.s0 - ti.delta);
+    const u8* tbase = bytes + (ti.s0 - ti.delta);
     // A 16-byte access that straddles num_records reads as all zeros, so the range is the
     // tile rounded up to 16 bytes: with a 16-byte aligned base, a chunk holding any batch
     // byte never leaves the batch's last page.
@@ -454,11 +451,10 @@ __device__ __forceinline__ void issue_tile_loads(const ScanParams& P, const Tile
         const auto v = __builtin_amdgcn_raw_buffer_load_b128(rb, 16 * (j * SCAN_TPB + tid), 0, AUX_NT);
         pre[j] = make_uint4(v[0], v[1], v[2], v[3]);
     }
-    const u64 left = P.n - min(ti.first, P.n);
+    const u64 left = n - min(ti.first, n);
     const u32 nrec = (u32)min<u64>((u64)ti.count + 1u, left) * 4u;   // my_end of the tile's last line included
     const __amdgpu_buffer_rsrc_t ro =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.off + min(ti.first, P.n)), 0, (int)nrec, 0x00020000);
-    const u32 li = lane_line(tid);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(off + min(ti.first, n)), 0, (int)nrec, 0x00020000);
     my_off = __builtin_amdgcn_raw_buffer_load_b32(ro, 4 * li, 0, 0);
     my_end = __builtin_amdgcn_raw_buffer_load_b32(ro, 4 * li + 4, 0, 0);   // 0 past the batch end
 }
@@ -664,7 +660,7 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu((Geom<
         STAMP(1);
         if constexpr (DIAG_A_ONLY) {
             inf = t + PF_DEPTH < t_end ? tile_info<G::CAP>(P, t + PF_DEPTH, t_begin, tb) : none;
-            issue_tile_loads(P, inf, pre, pre_off, pre_end);
+            issue_tile_loads(P.bytes, P.off, P.n, li, inf, pre, pre_off, pre_end);
             __syncthreads();
             return;
         }
@@ -747,7 +743,6 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu((Geom<
                 CanonA c2;
                 CanonB b2;
                 b2.view = false;
-                // both canonical layouts open with {"user_id": then ' ' or '"' (byte 11)
                 const u32 h2 = lsrc.load4(ls + 8);
                 const bool up = lsrc.load4(ls) == w4('{', '"', 'u', 's') && lsrc.load4(ls + 4) == w4('e', 'r', '_', 'i') &&
                                 (h2 & 0xFFFFFFu) == (w4('d', '"', ':', 0) & 0xFFFFFFu);
@@ -837,7 +832,7 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu((Geom<
         // loads return zeros) so every path has the same count of loads in flight and
         // the waits below stay counted.
         inf = t + PF_DEPTH < t_end ? tile_info<G::CAP>(P, t + PF_DEPTH, t_begin, tb) : none;
-        issue_tile_loads(P, inf, pre, pre_off, pre_end);
+        issue_tile_loads(P.bytes, P.off, P.n, li, inf, pre, pre_off, pre_end);
         // ---- Phase B2: join result ------------------------------------------------
         bool valid = false, dfr2 = false;
         u32 campaign = 0;
@@ -942,7 +937,7 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu((Geom<
         }
         __syncthreads();
         infA = tile_info<G::CAP>(P, t_begin, t_begin, tb);
-        issue_tile_loads(P, infA, preA, offA, endA);
+        issue_tile_loads(P.bytes, P.off, P.n, lane_line(tid), infA, preA, offA, endA);
         for (u64 t = t_begin; t < t_end; ++t) tile_step(t, infA, preA, offA, endA);
     };
     auto use_segment = [&](const ScanSeg& sg) {
@@ -1033,40 +1028,45 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu((Geom<
 // error); then the same filter / join / bucket as the JSON chain (event_time = items[5],
 // the Storm/Spark projection).  The line is the batch line minus its "\n" / "\r\n"
 // terminator (BufferedReader.readLine, :153-159).
+// scan_kernel<*, true> takes the generator's rows (ysb_scan_tbl.h): one wave per 64-line
+// tile, staged through LDS like the JSON scan, one line per lane; every other row comes here.
 // ---------------------------------------------------------------------------
+// The row [s, e) without its terminator (e moves) and its first six '|' (p[5] = e when there
+// are only five); returns how many of the six it found.  items[k] lies between p[k - 1] and p[k].
+template <class S>
+__device__ __forceinline__ int tbl_split(const S& src, int s, int& e, int (&p)[6]) {
+    if (e > s && src.b(e - 1) == '\n') --e;
+    if (e > s && src.b(e - 1) == '\r') --e;
+    int k = 0;
+    for (int q = s; q < e && k < 6; ++q)
+        if (src.b(q) == '|') p[k++] = q;
+    if (k == 5) p[5] = e;
+    return k;
+}
+
 template <class S>
 __device__ __forceinline__ bool process_tbl_line(const S& src, int s, int e, const ScanParams& P, Tally& t,
                                                  u32& campaign, i64& bucket) {
     t.ev++;
-    if (e > s && src.b(e - 1) == '\n') --e;
-    if (e > s && src.b(e - 1) == '\r') --e;
-    // the first six '|' (p[5] = e when there are only five)
     int p[6];
-    int k = 0;
-    for (int q = s; q < e && k < 6; ++q)
-        if (src.b(q) == '|') p[k++] = q;
-    if (k < 5) { t.perr++; return false; }
-    if (k == 5) p[5] = e;
+    if (tbl_split(src, s, e, p) < 5) { t.perr++; return false; }
     // items[5] exists iff something other than '|' follows the fifth '|'
     bool tail = p[5] > p[4] + 1;
     for (int q = p[5]; !tail && q < e; ++q) tail = src.b(q) != '|';
     if (!tail) { t.perr++; return false; }
-    const Span et{p[3] + 1, p[4], 0};
-    if (!(et.e - et.s == 4 && src.load4(et.s) == VIEW_W)) return false;   // EventFilterBolt
-    t.view++;
-    const Span ad{p[1] + 1, p[2], 0};
-    u32 kw[KEY_WORDS];
-    u32 klen = 0;
-    int c = -1;
-    const bool keyed = span_key(src, ad, kw, klen);
-    if (keyed) c = probe(P.table, P.table_mask, kw, klen);   // RedisJoinBolt
-    if (c < 0) { count_miss(P, kw, klen, keyed, t); return false; }
-    t.join++;
-    i64 tv;
-    if (!parse_digits(src, p[4] + 1, p[5], tv)) { t.terr++; return false; }   // Long.parseLong
-    campaign = (u32)c;
-    bucket = div_trunc(tv, P.div);
-    return true;
+    return finish_line(src, Span{p[1] + 1, p[2], 0}, Span{p[3] + 1, p[4], 0}, Span{p[4] + 1, p[5], 0}, P, t, campaign,
+                       bucket);
+}
+
+// Line `line` of the batch in P as the bytes [ls, le); false where the offsets are out of
+// order or past the batch, or the line is longer than an int can index.
+__device__ __forceinline__ bool line_sane(u64 ls, u64 le, u64 nbytes) {
+    return ls <= le && le <= nbytes && le - ls <= 0x7FFFFFFFull;
+}
+__device__ __forceinline__ bool line_bounds(const ScanParams& P, u64 line, u64& ls, u64& le) {
+    ls = P.off[line];
+    le = line + 1 < P.n ? (u64)P.off[line + 1] : P.nbytes;
+    return line_sane(ls, le, P.nbytes);
 }
 
 // Kernel 1b: the lines the fast path deferred (any layout other than the generator's,
@@ -1109,9 +1109,8 @@ __global__ __launch_bounds__(DEFER_TPB) void defer_kernel(const ScanParams P0) {
         P.n = P0.seg[sgi].n;
         P.nbytes = P0.seg[sgi].nbytes;
         li -= P0.seg[sgi].line_base;
-        const u64 ls = P.off[li];
-        const u64 le = li + 1 < P.n ? (u64)P.off[li + 1] : P.nbytes;
-        if (ls > le || le > P.nbytes || le - ls > 0x7FFFFFFFull) {
+        u64 ls, le;
+        if (!line_bounds(P, li, ls, le)) {
             tl.ev++;
             tl.perr++;
             continue;
@@ -1177,22 +1176,22 @@ __global__ __launch_bounds__(DEFER_TPB) void defer_kernel(const ScanParams P0) {
 }
 
 // Ring auto-base: the first joined view with a valid time among the first 256 lines
-// fixes the ring at min bucket - W/8 (room for out-of-order / late events).
+// fixes the ring at min bucket - W/8 (room for out-of-order / late events).  TBL: .tbl rows.
+template <bool TBL>
 __global__ __launch_bounds__(AUX_TPB) void ring_autobase_kernel(ScanParams P, i64* ring) {
     __shared__ i64 scratch[AUX_TPB / 64];
     if (ring[1] != 0) return;
     const int tid = threadIdx.x;
     i64 b = INT64_MAX;
-    if ((u64)tid < P.n) {
-        const u64 ls = P.off[tid];
-        const u64 le = ((u64)tid + 1 < P.n) ? (u64)P.off[tid + 1] : P.nbytes;
-        if (ls <= le && le <= P.nbytes && le - ls < 0x7FFFFFFFull) {
-            Tally tl{0, 0, 0, 0, 0, 0, 0, 0};
-            u32 c;
-            i64 bk;
-            const GlbSrc gsrc{P.bytes + ls, le - ls};
-            if (process_line(gsrc, 0, (int)(le - ls), P, tl, c, bk)) b = bk;
-        }
+    u64 ls, le;
+    if ((u64)tid < P.n && line_bounds(P, (u64)tid, ls, le)) {
+        Tally tl{0, 0, 0, 0, 0, 0, 0, 0};
+        u32 c;
+        i64 bk;
+        const GlbSrc gsrc{P.bytes + ls, le - ls};
+        const bool ok = TBL ? process_tbl_line(gsrc, 0, (int)(le - ls), P, tl, c, bk)
+                            : process_line(gsrc, 0, (int)(le - ls), P, tl, c, bk);
+        if (ok) b = bk;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -1211,77 +1210,33 @@ __global__ __launch_bounds__(AUX_TPB) void ring_autobase_kernel(ScanParams P, i6
     }
 }
 
-
-// One wave per 64-line tile, staged through LDS like the JSON scan; one line per lane.
-
-// Ring auto-base for .tbl batches (the JSON one is ring_autobase_kernel).
-__global__ __launch_bounds__(AUX_TPB) void tbl_ring_autobase_kernel(ScanParams P, i64* ring) {
-    __shared__ i64 scratch[AUX_TPB / 64];
-    if (ring[1] != 0) return;
-    const int tid = threadIdx.x;
-    i64 b = INT64_MAX;
-    if ((u64)tid < P.n) {
-        const u64 ls = P.off[tid];
-        const u64 le = ((u64)tid + 1 < P.n) ? (u64)P.off[tid + 1] : P.nbytes;
-        if (ls <= le && le <= P.nbytes && le - ls < 0x7FFFFFFFull) {
-            Tally tl{0, 0, 0, 0, 0, 0, 0, 0};
-            u32 c;
-            i64 bk;
-            const GlbSrc gsrc{P.bytes + ls, le - ls};
-            if (process_tbl_line(gsrc, 0, (int)(le - ls), P, tl, c, bk)) b = bk;
-        }
+// One scan launch: the instantiation of the probe / record mode for the batch's format and
+// the JSON layout tried first (layouts 2-4 carry the flat tier's key table in LDS).
+template <bool SERIAL, bool REC>
+static void launch_scan_as(const ScanParams& p, hipStream_t s) {
+    const dim3 g(p.grid), b(SCAN_TPB);
+    constexpr int LDS = Geom<false, REC>::LDS, LDS_KT = LDS + FLAT_KT_LDS;
+    if (p.tbl) {
+        hipLaunchKernelGGL((scan_kernel<SERIAL, true, REC>), g, b, (Geom<true, REC>::LDS), s, p);
+        return;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const i64 x = __shfl_xor(b, o, 64);
-        b = x < b ? x : b;
+    switch (p.layout) {
+    case 1: hipLaunchKernelGGL((scan_kernel<SERIAL, false, REC, 1>), g, b, LDS, s, p); break;
+    case 2: hipLaunchKernelGGL((scan_kernel<SERIAL, false, REC, 2>), g, b, LDS_KT, s, p); break;
+    case 3: hipLaunchKernelGGL((scan_kernel<SERIAL, false, REC, 3>), g, b, LDS_KT, s, p); break;
+    case 4: hipLaunchKernelGGL((scan_kernel<SERIAL, false, REC, 4>), g, b, LDS_KT, s, p); break;
+    default: hipLaunchKernelGGL((scan_kernel<SERIAL, false, REC>), g, b, LDS, s, p); break;
     }
-    if ((tid & 63) == 0) scratch[tid >> 6] = b;
-    __syncthreads();
-    if (tid == 0) {
-        i64 r = scratch[0];
-        for (int w = 1; w < AUX_TPB / 64; ++w) r = scratch[w] < r ? scratch[w] : r;
-        if (r != INT64_MAX) {
-            ring[0] = r - (i64)(P.ring_w / 8);
-            ring[1] = 1;
-        }
-    }
-}
-
-void launch_tbl_ring_autobase(const ScanParams& p, hipStream_t s) {
-    if (p.n == 0) return;
-    hipLaunchKernelGGL(tbl_ring_autobase_kernel, dim3(1), dim3(AUX_TPB), 0, s, p, const_cast<i64*>(p.ring));
 }
 
 void launch_scan(const ScanParams& p, hipStream_t s) {
     if (p.n == 0) return;
-    const dim3 g(p.grid), b(SCAN_TPB);
-    // record mode only with HBM-resident tables (large configurations: serial probes)
-    if (p.tbl) {
-        if (p.rec_on) hipLaunchKernelGGL((scan_kernel<true, true, true>), g, b, (Geom<true, true>::LDS), s, p);
-        else if (p.probe_serial) hipLaunchKernelGGL((scan_kernel<true, true, false>), g, b, Geom<true>::LDS, s, p);
-        else hipLaunchKernelGGL((scan_kernel<false, true, false>), g, b, Geom<true>::LDS, s, p);
-    } else {
-        // HBM-resident join table (configs[2]): record mode or serial probes, each with the
-        // layout instantiations too (round 4), so other producers' layouts keep their fast tier
-        if (p.rec_on) {
-            if (p.layout == 1) hipLaunchKernelGGL((scan_kernel<true, false, true, 1>), g, b, (Geom<false, true>::LDS), s, p);
-            else if (p.layout == 2) hipLaunchKernelGGL((scan_kernel<true, false, true, 2>), g, b, (Geom<false, true>::LDS + FLAT_KT_LDS), s, p);
-            else if (p.layout == 3) hipLaunchKernelGGL((scan_kernel<true, false, true, 3>), g, b, (Geom<false, true>::LDS + FLAT_KT_LDS), s, p);
-            else if (p.layout == 4) hipLaunchKernelGGL((scan_kernel<true, false, true, 4>), g, b, (Geom<false, true>::LDS + FLAT_KT_LDS), s, p);
-            else hipLaunchKernelGGL((scan_kernel<true, false, true>), g, b, (Geom<false, true>::LDS), s, p);
-        } else if (p.probe_serial) {
-            if (p.layout == 1) hipLaunchKernelGGL((scan_kernel<true, false, false, 1>), g, b, Geom<false>::LDS, s, p);
-            else if (p.layout == 2) hipLaunchKernelGGL((scan_kernel<true, false, false, 2>), g, b, (Geom<false>::LDS + FLAT_KT_LDS), s, p);
-            else if (p.layout == 3) hipLaunchKernelGGL((scan_kernel<true, false, false, 3>), g, b, (Geom<false>::LDS + FLAT_KT_LDS), s, p);
-            else if (p.layout == 4) hipLaunchKernelGGL((scan_kernel<true, false, false, 4>), g, b, (Geom<false>::LDS + FLAT_KT_LDS), s, p);
-            else hipLaunchKernelGGL((scan_kernel<true, false, false>), g, b, Geom<false>::LDS, s, p);
-        } else if (p.layout == 1) hipLaunchKernelGGL((scan_kernel<false, false, false, 1>), g, b, Geom<false>::LDS, s, p);
-        else if (p.layout == 2) hipLaunchKernelGGL((scan_kernel<false, false, false, 2>), g, b, (Geom<false>::LDS + FLAT_KT_LDS), s, p);
-        else if (p.layout == 3) hipLaunchKernelGGL((scan_kernel<false, false, false, 3>), g, b, (Geom<false>::LDS + FLAT_KT_LDS), s, p);
-        else if (p.layout == 4) hipLaunchKernelGGL((scan_kernel<false, false, false, 4>), g, b, (Geom<false>::LDS + FLAT_KT_LDS), s, p);
-        else hipLaunchKernelGGL((scan_kernel<false, false, false>), g, b, Geom<false>::LDS, s, p);
-    }
+    // HBM-resident join table (configs[2]): record mode (only with serial probes) or serial
+    // probes, each with the layout instantiations too (round 4), so other producers' layouts
+    // keep their fast tier
+    if (p.rec_on) launch_scan_as<true, true>(p, s);
+    else if (p.probe_serial) launch_scan_as<true, false>(p, s);
+    else launch_scan_as<false, false>(p, s);
 }
 
 void launch_defer(const ScanParams& p, int blocks, hipStream_t s) {
@@ -1291,7 +1246,9 @@ void launch_defer(const ScanParams& p, int blocks, hipStream_t s) {
 
 void launch_ring_autobase(const ScanParams& p, hipStream_t s) {
     if (p.n == 0) return;
-    hipLaunchKernelGGL(ring_autobase_kernel, dim3(1), dim3(AUX_TPB), 0, s, p, const_cast<i64*>(p.ring));
+    const dim3 g(1), b(AUX_TPB);
+    if (p.tbl) hipLaunchKernelGGL(ring_autobase_kernel<true>, g, b, 0, s, p, const_cast<i64*>(p.ring));
+    else hipLaunchKernelGGL(ring_autobase_kernel<false>, g, b, 0, s, p, const_cast<i64*>(p.ring));
 }
 
 int scan_lds_bytes() { return LDS_BYTES; }

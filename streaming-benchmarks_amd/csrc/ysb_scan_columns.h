@@ -4,9 +4,11 @@
 // {36,36,36,4,4,8,8} -- user_id, page_id, ad_id, ad_type, event_type, the parsed
 // event_time and a stamp -- each starting on a 4096-byte page (:291-302), plus an
 // Arrow-style validity bitmap behind them (include/ysb_hip.h ysb_columns_layout).
-// Part of the scan kernel's translation unit: included at the end of ysb_scan.hip, after
-// the byte sources, the canonical / vocabulary tiers, tbl_stage1/2, decode_str and the
-// org.json machine, none of which it changes.
+// Part of the scan kernel's translation unit: included at the end of ysb_scan.hip, whose
+// code it shares rather than repeats -- the byte sources, the canonical / vocabulary tiers,
+// tbl_stage1/2, decode_str, the org.json machine (parse_line, here keeping all seven
+// values: KeepAll), the .tbl row split (tbl_split), the per-line sanity test (line_sane)
+// and the tile loader (TileInfo, tile_lines / tile_bytes, issue_tile_loads).
 //
 // Shape: one-wave workgroups, one line per lane, tiles of 64 lines staged into LDS (the
 // next tile's bytes are loaded into registers while this one is parsed).  Lane i takes line
@@ -14,159 +16,13 @@
 // generator's JSON layout (vocab_stage1/2, then canon_stage1/2: both prove the line parses
 // exactly as org.json parses it and locate every value) and the generator's .tbl rows
 // (tbl_stage1/2); every other line runs through the general parser in the same lane
-// (parse_line_all below; lines outside the staged tile through GlbSrc).  The 64 rows of a
+// (parse_line or tbl_split; lines outside the staged tile through GlbSrc).  The 64 rows of a
 // tile are contiguous in every column (2304 / 256 / 512 bytes, 128-byte aligned), so each
 // column's block is assembled in LDS and written with 16-byte stores, whole lines for a
 // full tile.
 #pragma once
 
 namespace ysb {
-
-// ---------------------------------------------------------------------------
-// parse_line (ysb_orgjson.h) with the String value of every key DeserializeBolt reads:
-// sp[k] is the span of key bit k (0 user_id .. 5 event_time, 6 ip_address).  The same
-// machine, state for state; only the value capture differs.
-// ---------------------------------------------------------------------------
-template <class S>
-__device__ __noinline__ bool parse_line_all(const S& src, int s, int e, u32 require, Span (&sp)[7]) {
-    int end = e;                                                           // NUL: end of input
-    for (int q = s & ~3; q < e; q += 4) {                                  // word at a time
-        const u32 w = src.load4(q);
-        const u32 z = (w - 0x01010101u) & ~w & 0x80808080u;                // a zero byte (exact for the lowest)
-        if (z == 0u) continue;
-        int k = 0;
-        for (; k < 4; ++k) {
-            const int pos = q + k;
-            if (pos >= s && pos < e && ((w >> (8 * k)) & 0xFFu) == 0u) break;
-        }
-        if (k < 4) { end = q + k; break; }
-    }
-    OjTok<S> t{src, s, end, false, -1, 0u};
-    if (t.clean() != '{') return false;                                    // must begin with '{'
-    int open[OJ_MAX_DEPTH + 1];                                            // each open container's bracket
-    u8 role[OJ_MAX_DEPTH + 1];
-    int depth = 1;
-    open[1] = t.p - 1;
-    role[1] = OJR_TOP;
-    int state = OJS_KEY, kpos = 0;
-    OjKey key{OJK_RAW, 0, 0};
-    u32 kid = 0, seen = 0;
-    u32 khash[OJ_TOP_KEYS];   // the top-level object's key hashes so far
-    int ntop = 0;
-    for (;;) {
-        OjVal v;
-        u8 nested = 0;          // != 0: v opened a container in this role
-        bool closed = false;    // the innermost container closed
-        int c;
-        switch (state) {
-        case OJS_KEY:                                                      // a key, or '}'
-            c = t.clean();
-            if (c < 0) return false;                                       // must end with '}'
-            if (c == '}') { closed = true; break; }
-            t.back();
-            kpos = t.p;
-            if (!oj_value(t, v)) return false;
-            if (v.kind == OJV_OBJ || v.kind == OJV_ARR) { nested = OJR_KEY; break; }
-            kid = 0;
-            if (v.kind == OJV_STR) {
-                key = OjKey{OJK_STR, v.a, v.b};
-                if (depth == 1) kid = v.esc ? match_key_esc(src, v.a, v.b) : match_key_raw(src, v.a, v.b - v.a);
-            } else {
-                const int k = oj_token_kind(src, v.a, v.b);
-                key = OjKey{k == OJ_TRUE ? OJK_TRUE : k == OJ_FALSE ? OJK_FALSE : k == OJ_NULL ? OJK_NULL : OJK_RAW,
-                            v.a, v.b};
-                if (depth == 1 && key.kind == OJK_RAW) kid = match_key_raw(src, v.a, v.b - v.a);
-            }
-            state = OJS_COLON;
-            continue;
-        case OJS_COLON:
-            if (t.clean() != ':') return false;                            // Expected a ':' after a key
-            if (depth == 1 && ntop < OJ_TOP_KEYS) {
-                // top level: compare hashes with the earlier keys', re-walk only on a hit
-                const u32 h = oj_key_hash(src, key);
-                bool hit = false;
-#pragma unroll
-                for (int k = 0; k < OJ_TOP_KEYS; ++k) hit |= k < ntop && khash[k] == h;
-                if (hit && oj_dup_key(src, open[depth], kpos, end, key)) return false;   // Duplicate key
-#pragma unroll
-                for (int k = 0; k < OJ_TOP_KEYS; ++k)
-                    if (k == ntop) khash[k] = h;
-                ++ntop;
-            } else if (oj_dup_key(src, open[depth], kpos, end, key)) {
-                return false;                                                   // Duplicate key
-            }
-            state = OJS_VALUE;
-            continue;
-        case OJS_VALUE:
-            if (!oj_value(t, v)) return false;
-            if (v.kind == OJV_OBJ || v.kind == OJV_ARR) { kid = 0; nested = OJR_VALUE; break; }
-            if (kid && (v.kind == OJV_STR || oj_token_kind(src, v.a, v.b) == OJ_STR)) {   // getString
-                const Span val{v.a, v.b, v.kind == OJV_STR ? v.esc : 0};
-#pragma unroll
-                for (int k = 0; k < 7; ++k)
-                    if (kid == (1u << k)) sp[k] = val;
-                seen |= kid;
-            }
-            kid = 0;
-            state = OJS_OSEP;
-            continue;
-        case OJS_OSEP:                                                     // ',' / ';' / '}'
-            c = t.clean();
-            if (c == ',' || c == ';') {
-                if (t.clean() == '}') { closed = true; break; }
-                if (!t.back()) return false;
-                state = OJS_KEY;
-                continue;
-            }
-            if (c == '}') { closed = true; break; }
-            return false;                                                  // Expected a ',' or '}'
-        case OJS_AFIRST:
-            c = t.clean();
-            if (c == ']') { closed = true; break; }
-            if (!t.back()) return false;
-            state = OJS_AELEM;
-            continue;
-        case OJS_AELEM:
-            c = t.clean();
-            if (!t.back()) return false;
-            if (c == ',') { state = OJS_ASEP; continue; }                  // an empty slot: NULL
-            if (!oj_value(t, v)) return false;
-            if (v.kind == OJV_OBJ || v.kind == OJV_ARR) { nested = OJR_ELEM; break; }
-            state = OJS_ASEP;
-            continue;
-        default:                                                           // OJS_ASEP
-            c = t.clean();
-            if (c == ',') {
-                if (t.clean() == ']') { closed = true; break; }
-                if (!t.back()) return false;
-                state = OJS_AELEM;
-                continue;
-            }
-            if (c == ']') { closed = true; break; }
-            return false;                                                  // Expected a ',' or ']'
-        }
-        if (nested) {
-            if (++depth > OJ_MAX_DEPTH) return false;
-            open[depth] = v.a;
-            role[depth] = nested;
-            state = v.kind == OJV_OBJ ? OJS_KEY : OJS_AFIRST;
-            continue;
-        }
-        if (closed) {
-            const u8 r = role[depth];
-            const int op = open[depth];
-            if (--depth == 0) return (seen & require) == require;          // nothing after '}' is read
-            if (r == OJR_KEY) {                                            // toString() of a container
-                key = OjKey{OJK_RAW, op, t.p};
-                kpos = op;
-                kid = 0;
-                state = OJS_COLON;
-            } else {
-                state = r == OJR_VALUE ? OJS_OSEP : OJS_ASEP;
-            }
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------
 // One decoded row: what WindowedArrowFormatBolter.flatMap puts per tuple (:323-334).
@@ -222,11 +78,9 @@ __device__ __forceinline__ bool row_of_spans(const S& src, const Span* sp, ColRo
 // A line in any layout: new JSONObject(line) + getString of the required keys.
 template <class S>
 __device__ __noinline__ bool col_json_general(const S& src, int s, int e, u32 require, ColRow& r) {
-    Span sp[7];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) sp[k] = Span{0, 0, 0};
-    if (!parse_line_all(src, s, e, require, sp)) return false;
-    return row_of_spans(src, sp, r);
+    KeepAll k;
+    if (!parse_line(src, s, e, require, k)) return false;
+    return row_of_spans(src, k.sp, r);
 }
 
 // Any .tbl row: readLine's terminator stripped, items = line.split("\\|") (MockWindowedFlatMap,
@@ -235,14 +89,8 @@ __device__ __noinline__ bool col_json_general(const S& src, int s, int e, u32 re
 // way, so the row is valid iff the five values are long enough and items[5] parses.
 template <class S>
 __device__ __noinline__ bool col_tbl_general(const S& src, int s, int e, ColRow& r) {
-    if (e > s && src.b(e - 1) == '\n') --e;
-    if (e > s && src.b(e - 1) == '\r') --e;
     int p[6];
-    int k = 0;
-    for (int q = s; q < e && k < 6; ++q)
-        if (src.b(q) == '|') p[k++] = q;
-    if (k < 5) return false;
-    if (k == 5) p[5] = e;
+    if (tbl_split(src, s, e, p) < 5) return false;
     const Span sp[6] = {{s, p[0], 0},        {p[0] + 1, p[1], 0}, {p[1] + 1, p[2], 0},
                         {p[2] + 1, p[3], 0}, {p[3] + 1, p[4], 0}, {p[4] + 1, p[5], 0}};
     return row_of_spans(src, sp, r);
@@ -259,14 +107,15 @@ struct ColGeom {
 };
 static_assert(TILE_LINES == 64, "a tile's validity word is one 64-lane ballot");
 
-struct ColTile {
-    u64 first;     // first line
-    u32 count;     // lines
-    u32 s0;        // byte offset of the first line
-    u32 delta;     // s0 - 16-byte aligned base
-    u32 len;       // bytes staged from the aligned base (0: nothing)
-    u32 e;         // end of the staged bytes
-};
+// Tile t (< P.n_tiles) of the batch by the scan's tile_info, its two bounds straight from
+// P.off (one wave per workgroup: no LDS copy of them).  len == 0: nothing staged (offsets
+// out of order or past the batch), every line from HBM.
+template <int CAP>
+__device__ __forceinline__ TileInfo col_tile_info(const ColParams& P, u64 t) {
+    const u64 first = t * TILE_LINES, next = first + TILE_LINES;
+    const u32 tb[2] = {P.off[first], next < P.n ? P.off[next] : (u32)P.nbytes};   // (nbytes < 4 GiB)
+    return tile_info<CAP>(P, t, t, tb);
+}
 
 // column c's width, and the dword offset of its block of a tile in the LDS staging area
 __host__ __device__ constexpr int col_w(int c) { return c < 3 ? 36 : c < 5 ? 4 : 8; }
@@ -290,50 +139,14 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu(2))) v
     u32 n_valid = 0, n_fast = 0;
     if (tid < 16) tile32[G::CAP / 4 + tid] = 0u;   // the slack past a full tile
 
-    // the tile's bounds (wave-uniform), then its bytes and line offsets HBM -> registers by
-    // bounds-checked buffer loads, as the scan's issue_tile_loads reads them (chunks past the
-    // staged bytes and offsets past the batch read zeros; the range is the tile rounded up
-    // to 16 bytes, which never leaves the batch's last page)
-    auto issue = [&](u64 t, ColTile& ti, uint4 (&pre)[CPT], u32& p_off, u32& p_end) {
-        ti = ColTile{t * TILE_LINES, 0u, 0u, 0u, 0u, 0u};
-        if (ti.first < P.n) {
-            const u64 rem = P.n - ti.first;
-            ti.count = rem < (u64)TILE_LINES ? (u32)rem : (u32)TILE_LINES;
-            const u32 s0 = (u32)__builtin_amdgcn_readfirstlane((int)P.off[ti.first]);
-            const u64 e = ti.first + ti.count < P.n
-                              ? (u64)(u32)__builtin_amdgcn_readfirstlane((int)P.off[ti.first + ti.count])
-                              : P.nbytes;
-            ti.s0 = s0;
-            ti.delta = s0 & 15u;   // P.bytes is 16-byte aligned
-            if ((u64)s0 <= e && e <= P.nbytes) {
-                const u64 len = e - s0 + ti.delta;
-                ti.len = (u32)(len < (u64)G::CAP ? len : (u64)G::CAP);
-            }
-            ti.e = s0 - ti.delta + ti.len;
-        }
-        const u8* tbase = P.bytes + ((u64)ti.s0 - ti.delta);   // (len 0: nothing is read)
-        const __amdgpu_buffer_rsrc_t rb =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<u8*>(tbase), 0, (int)((ti.len + 15u) & ~15u), 0x00020000);
-#pragma unroll
-        for (int j = 0; j < CPT; ++j) {
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(rb, 16 * (j * SCAN_TPB + tid), 0, AUX_NT);
-            pre[j] = make_uint4(v[0], v[1], v[2], v[3]);
-        }
-        const u64 f = ti.first < P.n ? ti.first : P.n;
-        const u64 left = P.n - f;
-        const u32 nrec = (u32)((u64)ti.count + 1u < left ? (u64)ti.count + 1u : left) * 4u;   // the last line's end included
-        const __amdgpu_buffer_rsrc_t ro =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.off + f), 0, (int)nrec, 0x00020000);
-        p_off = __builtin_amdgcn_raw_buffer_load_b32(ro, 4 * tid, 0, 0);
-        p_end = __builtin_amdgcn_raw_buffer_load_b32(ro, 4 * tid + 4, 0, 0);   // 0 past the batch end
-    };
-
-    ColTile cur;
+    // a tile's bytes and line offsets HBM -> registers by the scan's loader; lane i receives
+    // line i's offsets
     uint4 pre[CPT];
     u32 pre_off = 0, pre_end = 0;
     u64 t = blockIdx.x;
     if (t >= P.n_tiles) return;
-    issue(t, cur, pre, pre_off, pre_end);
+    TileInfo cur = col_tile_info<G::CAP>(P, t);
+    issue_tile_loads(P.bytes, P.off, P.n, (u32)tid, cur, pre, pre_off, pre_end);
     for (; t < P.n_tiles; t += gridDim.x) {
         // ---- registers -> LDS (chunks past the staged bytes hold zeros) ----------------
 #pragma unroll
@@ -341,7 +154,7 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu(2))) v
             const u32 k = (u32)(j * SCAN_TPB + tid);
             if (j * SCAN_TPB + SCAN_TPB <= G::CHUNKS || k < (u32)G::CHUNKS) reinterpret_cast<uint4*>(tile32)[k] = pre[j];
         }
-        const ColTile ti = cur;
+        const TileInfo ti = cur;
         __syncthreads();
         // ---- this lane's line ------------------------------------------------------------
         const u64 line = ti.first + (u32)tid;
@@ -349,8 +162,11 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu(2))) v
         const u32 my_off = pre_off;
         const u32 my_end = line + 1 < P.n ? pre_end : (u32)P.nbytes;
         // the next tile's bytes land while this one is parsed
-        if (t + gridDim.x < P.n_tiles) issue(t + gridDim.x, cur, pre, pre_off, pre_end);
-        const bool sane = active && my_off <= my_end && (u64)my_end <= P.nbytes && my_end - my_off <= 0x7FFFFFFFu;
+        if (t + gridDim.x < P.n_tiles) {
+            cur = col_tile_info<G::CAP>(P, t + gridDim.x);
+            issue_tile_loads(P.bytes, P.off, P.n, (u32)tid, cur, pre, pre_off, pre_end);
+        }
+        const bool sane = active && line_sane(my_off, my_end, P.nbytes);
         const bool in_lds = sane && ti.len != 0u && my_off >= ti.s0 && my_end <= ti.e;
         const int ls = (int)(my_off - ti.s0 + ti.delta), le = (int)(my_end - ti.s0 + ti.delta);
         ColRow r;
@@ -392,7 +208,10 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu(2))) v
                 }
             }
         }
-        if (sane && !fast) {
+        // (a branch no generator line takes.  The hint keeps what the kernel spills around
+        // the general parser's call inside the branch: without it the JSON fast tier took
+        // 1.40 ms for 0.92, profiles/AB_LOG.md "Scan unit de-duplication")
+        if (__builtin_expect(sane && !fast, 0)) {
             if (in_lds) {
                 const LdsSrc3 s3{(lds_u32*)tile32};
                 valid = TBL ? col_tbl_general(s3, ls, le, r) : col_json_general(s3, ls, le, P.require_mask, r);

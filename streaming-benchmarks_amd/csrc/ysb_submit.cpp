@@ -272,10 +272,8 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin) {
     p.dbg = c->d_dbg;
 #endif
     poll_ring(c);
-    const bool tbl = (c->cfg.flags & YSB_F_FORMAT_TBL) != 0;
     if (!c->ring_known) {
-        if (tbl) launch_tbl_ring_autobase(p, c->s_comp);
-        else launch_ring_autobase(p, c->s_comp);
+        launch_ring_autobase(p, c->s_comp);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(c->h_ring, c->d_ring, 16, hipMemcpyDeviceToHost, c->s_comp));
         HIPCHK(c, hipEventRecord(c->ev_ring, c->s_comp));

@@ -134,6 +134,17 @@ def test_line_longer_than_a_tile(ctx):
     assert counts["valid"] == 150 and 64 <= info["fast_rows"] < 150
 
 
+@pytest.mark.parametrize("where", ["first_item", "seventh_item"])
+def test_tbl_row_longer_than_a_tile(ctx_tbl, where):
+    gen = fixture_lines("gen_s7", ".tbl")[:150]
+    row = gen[70].rstrip(b"\n")
+    pad = b"x" * 20000   # > 64 * 160 bytes of LDS: the row is split straight from HBM
+    long_row = (pad + row[row.index(b"|"):] if where == "first_item" else row + b"|" + pad) + b"\n"
+    lines = gen[:70] + [long_row] + gen[71:]
+    info, counts = check(ctx_tbl, lines, fmt="tbl")
+    assert counts["valid"] == 150 and 64 <= info["fast_rows"] < 150
+
+
 def test_java_order_swaps_only_the_longs(ctx, corpus):
     lines = [ln for ln, _, _ in corpus[:130]]
     check(ctx, lines, flags=_lib.YSB_COL_JAVA_ORDER)

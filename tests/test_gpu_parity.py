@@ -367,6 +367,23 @@ def test_tbl_mutations_match_oracle(seed):
     _oracle_vs_gpu(out, False, lds=False, fmt="tbl", ad_map=amap)
 
 
+def test_tbl_rows_past_the_deferred_stage_match_oracle():
+    """.tbl rows the deferred-line kernel cannot stage (longer than its 292-byte LDS region:
+    split and joined straight from HBM), next to staged rows whose items[5] is empty
+    (a time error) or missing (a parse error) -- every counter equals the C oracle's."""
+    raw, offs = gd.events("gen_s7", ".tbl")
+    bounds = list(offs) + [len(raw)]
+    rows = [raw[bounds[i]:bounds[i + 1]] for i in range(130)]
+    views = [i for i, r in enumerate(rows) if b"|view|" in r]
+    a, b, c, d = views[1], views[len(views) // 3], views[len(views) // 2], views[-1]
+    rows[a] = rows[a][:-1] + b"|" + b"x" * (292 - len(rows[a])) + b"\n"     # 293 bytes: one past the stage
+    rows[b] = rows[b][:-1] + b"|" + b"x" * (19999 - len(rows[b])) + b"\n"   # 20 000 bytes
+    rows[c] = rows[c][:rows[c].index(b"|view|")] + b"|view||x\n"
+    rows[d] = rows[d][:rows[d].index(b"|view|")] + b"|view|\n"
+    assert len(rows[a]) == 293 and len(rows[b]) == 20000 and len({a, b, c, d}) == 4
+    _oracle_vs_gpu(rows, False, fmt="tbl")
+
+
 @pytest.mark.parametrize("seed", [3, 4])
 def test_tbl_vocabulary_edges_match_oracle(seed):
     """The .tbl fast path names ad_type / event_type from the generator's sets and wants 13
