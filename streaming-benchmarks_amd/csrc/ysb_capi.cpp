@@ -23,6 +23,19 @@ int fail(ysb_ctx* c, int code, const char* fmt, ...) {
     return code;
 }
 
+int grow_device(ysb_ctx* c, void** buf, u64* have, u64 bytes, u64 floor_bytes) {
+    if (*have >= bytes) return YSB_OK;
+    for (hipStream_t s : {c->s_comp, c->s_copy, c->s_split, c->s_x})   // nothing queued may still use the old one
+        if (s) HIPCHK(c, hipStreamSynchronize(s));
+    hipFree(*buf);
+    *buf = nullptr;
+    *have = 0;
+    const u64 b = std::max(bytes, floor_bytes);
+    HIPCHK(c, hipMalloc(buf, b));
+    *have = b;
+    return YSB_OK;
+}
+
 extern "C" {
 
 int ysb_abi_version(void) { return YSB_ABI_VERSION; }
@@ -130,7 +143,7 @@ static void destroy(ysb_ctx* c) {
         if (c->ev_h2d[s]) hipEventDestroy(c->ev_h2d[s]);
         if (c->ev_kdone[s]) hipEventDestroy(c->ev_kdone[s]);
     }
-    for (auto& p : c->tev) for (hipEvent_t e : p) hipEventDestroy(e);
+    for (auto& p : c->tev.ev) for (hipEvent_t e : p) hipEventDestroy(e);
     hipFree(c->d_rec);
     hipFree(c->d_rec_n);
     hipFree(c->d_delta);
@@ -161,9 +174,8 @@ static void destroy(ysb_ctx* c) {
         if (c->ev_raw[s]) hipEventDestroy(c->ev_raw[s]);
     }
     hipFree(c->d_split_chunk);
-    hipFree(c->d_rawn);
     hipHostFree(c->h_rawn);
-    for (auto& p : c->cev) for (hipEvent_t e : p) hipEventDestroy(e);
+    for (auto& p : c->cev.ev) for (hipEvent_t e : p) hipEventDestroy(e);
     hipFree(c->d_rebase);
     for (auto& r : c->host_ranges) hipHostUnregister(reinterpret_cast<void*>(r.first));
     for (auto& f : c->fl) {
@@ -223,6 +235,11 @@ int ysb_open(ysb_ctx** out, int device, const ysb_config* cfg_in) {
         if (v > 0 && v < c->delta_limit) c->delta_limit = v;
     }
     if (const char* e = getenv("YSB_DYN_CHUNK")) c->dyn_chunk = (u32)strtoul(e, nullptr, 10);
+    // the raw path's A/B knobs
+    if (const char* e = getenv("YSB_SPLIT_STREAM")) c->split_place = std::atoi(e);
+    if (const char* e = getenv("YSB_H2D_WG")) c->h2d_wg = std::max(1, std::atoi(e));
+    if (const char* e = getenv("YSB_H2D_PRIO")) c->h2d_prio = std::atoi(e) != 0;
+    if (const char* e = getenv("YSB_H2D_GRID")) c->h2d_grid = std::max(0, std::atoi(e));
     if (hipStreamCreateWithFlags(&c->s_comp, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking) != hipSuccess) {
         fail(c, YSB_ERR_HIP, "stream creation failed");
@@ -597,13 +614,8 @@ int pull_side_list(ysb_ctx* c) {
         launch_side_compact(c->d_side, c->side_slots, c->side_cbits, true, nullptr, c->d_rows_n, 0, c->s_comp);
         HIPCHK(c, hipMemcpyAsync(&k, c->d_rows_n, 4, hipMemcpyDeviceToHost, c->s_comp));
         HIPCHK(c, hipStreamSynchronize(c->s_comp));
-        if (k > c->rows_cap) {
-            hipFree(c->d_rows);
-            c->d_rows = nullptr;
-            const u64 cap = std::max<u64>(k, 4096);
-            HIPCHK(c, hipMalloc(&c->d_rows, cap * sizeof(TableRow)));
-            c->rows_cap = cap;
-        }
+        const int rc = grow_device(c, &c->d_rows, &c->rows_bytes, k * sizeof(TableRow), 4096 * sizeof(TableRow));
+        if (rc) return rc;
         if (k) {
             std::vector<TableRow> h(k);
             HIPCHK(c, hipMemsetAsync(c->d_rows_n, 0, 4, c->s_comp));
@@ -647,13 +659,7 @@ static int ring_rows(ysb_ctx* c, i64 blo, i64 bhi, bool clear, std::map<std::pai
         HIPCHK(c, hipMemcpyAsync(&n, c->d_rows_n, 4, hipMemcpyDeviceToHost, c->s_comp));
         HIPCHK(c, hipStreamSynchronize(c->s_comp));
         if (!n) continue;
-        if (n > c->rows_cap) {
-            hipFree(c->d_rows);
-            c->d_rows = nullptr;
-            const u64 cap = std::max<u64>(n, 4096);
-            HIPCHK(c, hipMalloc(&c->d_rows, cap * sizeof(TableRow)));
-            c->rows_cap = cap;
-        }
+        if ((frc = grow_device(c, &c->d_rows, &c->rows_bytes, n * sizeof(TableRow), 4096 * sizeof(TableRow)))) return frc;
         std::vector<TableRow> h(n);
         u32 m = 0;
         HIPCHK(c, hipMemsetAsync(c->d_rows_n, 0, 4, c->s_comp));
@@ -884,22 +890,13 @@ int ysb_kernel_time(ysb_ctx* c, double* total_ms, uint64_t* launches) {
     if (!c) return YSB_ERR_ARG;
     int rc = sync_streams(c);
     if (rc) return rc;
-    double t = c->tev_ms_fold, tp = c->tev_path_fold;
-    for (size_t i = 0; i < c->tev_used; ++i) {
-        float ms = 0, mp = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->tev[i][0], c->tev[i][1]));
-        HIPCHK(c, hipEventElapsedTime(&mp, c->tev[i][0], c->tev[i][2]));
-        t += ms;
-        tp += mp;
-    }
-    const u64 n = c->tev_folded + c->tev_used;
-    if (total_ms) *total_ms = t;
+    double t[3] = {0, 0, 0};   // (-, the scans, the launches' whole path)
+    u64 n = 0;
+    HIPCHK(c, c->tev.collect(t, &n));
+    if (total_ms) *total_ms = t[1];
     if (launches) *launches = n;
-    c->path_ms_acc = tp;
+    c->path_ms_acc = t[2];
     c->path_launches_acc = n;
-    c->tev_used = 0;
-    c->tev_ms_fold = c->tev_path_fold = 0;
-    c->tev_folded = 0;
     return YSB_OK;
 }
 
@@ -961,7 +958,7 @@ int ysb_debug_defer_list(ysb_ctx* c, uint32_t* out, uint64_t cap) {
     int rc = ysb_sync(c);
     if (rc) return rc;
     if (!c->d_defer) return YSB_OK;
-    HIPCHK(c, hipMemcpy(out, c->d_defer, std::min<u64>(cap, c->defer_cap) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->d_defer, std::min<u64>(cap * 4, c->defer_bytes), hipMemcpyDeviceToHost));
     return YSB_OK;
 }
 

@@ -553,4 +553,10 @@ struct OvfEntry {
     i64 bucket;
 };
 
+// The layout sample (ysb_layout.h; device batches: ysb_kernels.h SampleSegs): at most
+// SAMPLE_MAX lines, SAMPLE_STRIDE bytes each of which <= SAMPLE_BYTES are the line's.
+constexpr u32 SAMPLE_BYTES = 288;   // a line of the scan's tile capacity
+constexpr u32 SAMPLE_STRIDE = 16 + SAMPLE_BYTES;
+constexpr int SAMPLE_MAX = 64;
+
 }  // namespace ysb

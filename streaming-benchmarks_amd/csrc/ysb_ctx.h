@@ -1,7 +1,8 @@
 // ysb_ctx.h -- the library context behind the C ABI (include/ysb_hip.h), shared by the
 // library's host translation units:
 //   ysb_capi.cpp    context lifecycle, the ad -> campaign tables, sync / drain / ring / stats
-//   ysb_submit.cpp  batches: slots, raw lines, device batches, layout sampling, the launches
+//   ysb_submit.cpp  batches: slots, raw lines, device batches, the layout samples, the launches
+//   ysb_layout.h    the layout sampling's rules (no HIP: tests/native/layout_logic.cpp)
 //   ysb_group.cpp   multi-GPU: the RCCL / host-collective group and the keyBy exchange
 //   ysb_gen_api.cpp the synthetic generator (host and device) and its truth tables
 // Internal: nothing here is part of the ABI (the shared helpers have hidden visibility).
@@ -23,6 +24,7 @@
 
 #include "../../include/ysb_hip.h"
 #include "ysb_kernels.h"
+#include "ysb_layout.h"
 
 using namespace ysb;   // (an internal header of the library's own units)
 
@@ -42,11 +44,54 @@ constexpr size_t TIMING_KEEP = 256;
 #define YSB_BUCKETS_X4 8
 #endif
 
-// A key order read off a batch's first line (layout 3, learn_layout).
-struct LearnDesc {
-    u32 order[8];
-    u32 n;
-    u32 cp;
+// YSB_F_TIMING's event log: N events per entry (a launch, a slot copy), kept until a getter
+// collects them.  total[k] sums elapsed(ev[0], ev[k]) over the entries taken in so far, k =
+// 1..N-1.  A caller that never collects (a streaming job) would grow the log without bound:
+// once TIMING_KEEP entries are pending, acquire folds the older half into the totals (those
+// are TIMING_KEEP / 2 entries old -- normally long done; else this waits for them) and their
+// events are reused.
+template <int N>
+struct EventLog {
+    std::vector<std::array<hipEvent_t, N>> ev;
+    size_t used = 0;
+    u64 folded = 0;
+    double total[N] = {};
+
+    // the oldest n entries into the totals (wait: for each entry's last event first)
+    hipError_t fold(size_t n, bool wait) {
+        for (size_t i = 0; i < n; ++i) {
+            hipError_t e = wait ? hipEventSynchronize(ev[i][N - 1]) : hipSuccess;
+            float ms[N] = {};
+            for (int k = 1; k < N && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms[k], ev[i][0], ev[i][k]);
+            if (e != hipSuccess) return e;
+            for (int k = 1; k < N; ++k) total[k] += ms[k];
+            ++folded;
+        }
+        std::rotate(ev.begin(), ev.begin() + (ptrdiff_t)n, ev.begin() + (ptrdiff_t)used);
+        used -= n;
+        return hipSuccess;
+    }
+    // the next entry's events (created on demand)
+    hipError_t acquire(hipEvent_t** out) {
+        hipError_t e = used == TIMING_KEEP ? fold(TIMING_KEEP / 2, true) : hipSuccess;
+        if (e == hipSuccess && used == ev.size()) {
+            std::array<hipEvent_t, N> a{};
+            for (int k = 0; k < N && e == hipSuccess; ++k) e = hipEventCreate(&a[k]);
+            if (e == hipSuccess) ev.push_back(a);
+        }
+        if (e == hipSuccess) *out = ev[used++].data();
+        return e;
+    }
+    // every entry so far (all complete: the caller has synchronised): totals[1..N-1] and the
+    // entry count; the log starts over
+    hipError_t collect(double* totals, u64* n) {
+        const hipError_t e = fold(used, false);
+        if (e != hipSuccess) return e;
+        for (int k = 1; k < N; ++k) { totals[k] = total[k]; total[k] = 0; }
+        *n = folded;
+        folded = 0;
+        return hipSuccess;
+    }
 };
 
 struct ysb_ctx {
@@ -61,8 +106,6 @@ struct ysb_ctx {
     u32* d_ctable = nullptr;   // 36-byte-key cuckoo table
     u64 ctable_slots = 0;      // slots, or buckets when ctable_buckets
     bool ctable_buckets = false; // HBM-resident table: 3-entry 128-B buckets (CB_*), serial probes
-    int submit_layout = -1;      // the layout a submit read off its batch's first line (-1: the flags')
-    LearnDesc submit_learn{};    // ... and, layout 3, the key order
     ysb_launch_desc last_launch{};   // the instantiation of the last launch
     // device batches' first-line samples: written by sample_kernel on the compute stream (so
     // after whatever produced the batch there) into pinned memory, two buffers alternating
@@ -84,9 +127,8 @@ struct ysb_ctx {
     u32* d_roff[2] = {nullptr, nullptr};        // raw_lines_cap starts per slot
     u64 raw_lines_cap = 0;                      // lines a raw batch may hold (raw_line_cap)
     u32* d_split_chunk = nullptr;               // per-chunk counts, then bases
-    u64 split_chunk_words = 0;
-    unsigned long long* d_rawn = nullptr;       // [2] lines of the slot's raw batch
-    unsigned long long* h_rawn = nullptr;       // pinned mirror
+    u64 split_chunk_bytes = 0;
+    unsigned long long* h_rawn = nullptr;       // pinned: [2] lines of the slot's raw batch
     hipEvent_t ev_raw[2] = {nullptr, nullptr};  // split done and its count read back
     int raw_pend = -1;                          // the slot whose raw batch awaits its launch
     int raw_fail = 0;                           // a raw batch that could not launch: sticky until ysb_reset
@@ -95,11 +137,8 @@ struct ysb_ctx {
     int raw_layout[2] = {-1, -1};               // its first line's layout (sampled on the host)
     LearnDesc raw_learn[2]{};
     // H2D timing (YSB_F_TIMING): {start, end} of each slot copy since the last ysb_copy_time
-    std::vector<std::array<hipEvent_t, 2>> cev;
-    size_t cev_used = 0;
+    EventLog<2> cev;
     u64 copy_bytes = 0;
-    double cev_ms_fold = 0;                     // pairs folded into totals (TIMING_KEEP)
-    u64 cev_folded = 0;
     // caller host ranges registered for zero-copy raw batches (ysb_host_register): base ->
     // {bytes, device address}
     struct HostRange {
@@ -113,10 +152,11 @@ struct ysb_ctx {
     i64 rebase_base = 0;
     u32 rebase_kmax = 0;                        // the largest bucket index in it
     bool raw_rebase_on[2] = {false, false};
-    int split_place = 1;                        // raw split on: 1 s_split (default), 0 the copy stream, 2 s_comp (A/B)
-    int h2d_wg = 1;                             // copy-kernel workgroups per CU (A/B)
-    bool h2d_prio = false;                      // copy kernel at raised wave priority (A/B)
-    int h2d_grid = 32;                          // copy-kernel workgroups (0: one per CU; YSB_H2D_GRID A/B)
+    // A/B knobs, read from the environment by ysb_open
+    int split_place = 1;                        // YSB_SPLIT_STREAM: raw split on 1 s_split (default), 0 the copy stream, 2 s_comp
+    int h2d_wg = 1;                             // YSB_H2D_WG: copy-kernel workgroups per CU
+    bool h2d_prio = false;                      // YSB_H2D_PRIO: copy kernel at raised wave priority
+    int h2d_grid = 32;                          // YSB_H2D_GRID: copy-kernel workgroups (0: one per CU)
     ysb_rebase raw_rebase[2]{};
     CuckooSeed cseed{};
     bool ctable_partial = false;
@@ -131,7 +171,7 @@ struct ysb_ctx {
     unsigned long long* d_rs_tmp = nullptr;
     bool ring_agreed = false;                 // ranks' ring bases checked equal
     TableRow* d_rows = nullptr;               // drain compaction output
-    u64 rows_cap = 0;
+    u64 rows_bytes = 0;
     u32* d_rows_n = nullptr;
     i64* d_ring = nullptr;                // [lo, set]
     i64* h_ring = nullptr;                // pinned mirror
@@ -158,23 +198,20 @@ struct ysb_ctx {
     u8* d_bytes[2] = {nullptr, nullptr};
     u32* d_off[2] = {nullptr, nullptr};
     hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_kdone[2] = {nullptr, nullptr};
-    bool slot_busy[2] = {false, false};
     // timing: per launch {before scan, after scan, after the last kernel of the launch}
-    std::vector<std::array<hipEvent_t, 3>> tev;
-    size_t tev_used = 0;
-    double tev_ms_fold = 0, tev_path_fold = 0;   // launches folded into totals (TIMING_KEEP)
-    u64 tev_folded = 0;
+    // (total[1]: the scan kernels' time, total[2]: the launch's whole path)
+    EventLog<3> tev;
     double path_ms_acc = 0;                // ysb_path_time's share, collected by ysb_kernel_time
     u64 path_launches_acc = 0;
     // record mode (ysb_count.hip)
     u32* d_rec = nullptr;
-    u64 rec_words = 0;
+    u64 rec_bytes = 0;
     u32* d_rec_n = nullptr;
-    u64 rec_n_words = 0;
+    u64 rec_n_bytes = 0;
     u32* d_part = nullptr;
-    u64 part_words = 0;
+    u64 part_bytes = 0;
     u32* d_runs = nullptr;
-    u64 runs_words = 0;
+    u64 runs_bytes = 0;
     u64 rec_launches = 0;
     // record mode counts into a saturating u8 delta ring with the u64 ring's layout (a cell
     // passing 255 goes to the u64 ring, ysb_count.hip add16); fold_delta adds it to the u64
@@ -251,7 +288,7 @@ struct ysb_ctx {
     u32* d_subset = nullptr;
     u32 d_subset_n = 0;
     u32* d_defer = nullptr;                // deferred (general-path) line indices
-    u64 defer_cap = 0;
+    u64 defer_bytes = 0;
     u32* d_defer_ctr = nullptr;            // [count, done, pad, pad, dynamic-claim counters[MAX_SEGS]]
     u32 dyn_pct = 0;                       // % of a large segment's tiles claimed dynamically (YSB_DYN_PCT; measured neutral, off)
     u32 dyn_chunk = 16;                    // tiles per claim (YSB_DYN_CHUNK)
@@ -266,6 +303,14 @@ struct ysb_ctx {
 
 // an error message for ysb_last_error (the context's, or the thread's when c is NULL)
 YSB_INTERNAL int fail(ysb_ctx* c, int code, const char* fmt, ...);
+// Grows the device buffer *buf (*have bytes) to at least max(bytes, floor_bytes); contents are
+// not kept.  Before the old buffer is freed every stream of the context is synchronised
+// (without launching pending work, unlike sync_streams): growth is outside steady state.
+YSB_INTERNAL int grow_device(ysb_ctx* c, void** buf, u64* have, u64 bytes, u64 floor_bytes);
+template <class T>
+int grow_device(ysb_ctx* c, T** buf, u64* have, u64 bytes, u64 floor_bytes) {
+    return grow_device(c, reinterpret_cast<void**>(buf), have, bytes, floor_bytes);
+}
 extern thread_local std::string g_open_err;
 
 #define HIPCHK(ctx, expr)                                                                         \

@@ -221,19 +221,6 @@ static int group_setup(ysb_ctx* c, int rank, int nranks) {
     return agree_ring(c);
 }
 
-static int grow_bytes(ysb_ctx* c, void** buf, u64* have, u64 bytes) {
-    if (*have >= bytes) return YSB_OK;
-    HIPCHK(c, hipStreamSynchronize(c->s_comp));
-    if (c->s_x) HIPCHK(c, hipStreamSynchronize(c->s_x));
-    hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    const u64 b = std::max<u64>(bytes, 1ull << 16);
-    HIPCHK(c, hipMalloc(buf, b));
-    *have = b;
-    return YSB_OK;
-}
-
 int ysb_exchange_plan(const uint64_t* slot_max, uint32_t W, uint32_t nranks, uint32_t* slots, uint32_t* n_slots,
                       uint32_t* width) {
     if (!slot_max || !slots || !n_slots || !width || nranks == 0 || W == 0) return YSB_ERR_ARG;
@@ -401,8 +388,8 @@ static int exchange(ysb_ctx* c, bool pipelined) {
         c->xk ^= 1;
         // set k was last used two exchanges ago: its unpack must be done before it is rewritten
         if (c->xset_used[k]) HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_xdone[k], 0));
-        int rc = grow_bytes(c, &c->d_xsend[k], &c->xsend_bytes[k], (u64)rows * R * width);
-        if (!rc) rc = grow_bytes(c, &c->d_xrecv[k], &c->xrecv_bytes[k], (u64)per * R * width);
+        int rc = grow_device(c, &c->d_xsend[k], &c->xsend_bytes[k], (u64)rows * R * width, 1u << 16);
+        if (!rc) rc = grow_device(c, &c->d_xrecv[k], &c->xrecv_bytes[k], (u64)per * R * width, 1u << 16);
         if (rc) return rc;
         u32* dslots = c->d_xslots + (u64)k * W;
         // (the slots' pinned area is rewritten two calls later, after xplan_ev of the call

@@ -236,10 +236,7 @@ void launch_rebase(u8* b, u64 nbytes, const u32* off, u64 cap, const unsigned lo
 // Layout sampling of device launches: sampled lines (spread over the launch's segments),
 // copied on the device (in stream order after the batch's producer) into pinned host memory,
 // SAMPLE_STRIDE bytes per line: u32 {line start, sampled length, valid, 0}, then
-// <= SAMPLE_BYTES line bytes.
-constexpr u32 SAMPLE_BYTES = 288;   // a line of the scan's tile capacity
-constexpr u32 SAMPLE_STRIDE = 16 + SAMPLE_BYTES;
-constexpr int SAMPLE_MAX = 64;
+// <= SAMPLE_BYTES line bytes (the constants: ysb_common.h).
 struct SampleSegs {                  // per sampled line: its batch and its index there
     const u8* bytes[SAMPLE_MAX];
     const u32* off[SAMPLE_MAX];

@@ -1,7 +1,7 @@
 // ysb_submit.cpp -- batches into launches: the pinned double-buffered slots (ysb_submit),
 // raw lines split on the GPU (ysb_submit_raw), device batches (ysb_submit_device*), the
-// layout sampling that picks the scan instantiation, record-mode planning and the launch
-// sequence itself (scan, deferred lines, record partition + count).
+// layout samples that pick the scan instantiation (their rules: ysb_layout.h), record-mode
+// planning and the launch sequence itself (scan, deferred lines, record partition + count).
 #include "ysb_ctx.h"
 
 using namespace ysb;
@@ -10,8 +10,18 @@ extern "C" {
 
 // ---- batches ---------------------------------------------------------------------------
 
+// The scan instantiation a submit chose for its batch: layout -1 is the flags'; learn the key
+// order of layouts 3 and 4.
+struct Layout {
+    int layout = -1;
+    LearnDesc learn{};
+};
+
+static u32 require_mask(const ysb_ctx* c) { return (c->cfg.flags & YSB_F_REQUIRE_IP) ? 0x7Fu : 0x3Fu; }
+static bool flat_first(const ysb_ctx* c) { return (c->cfg.flags & YSB_F_FLAT_FIRST) != 0; }
+
 // segs: 1..MAX_SEGS batches, none empty
-static ScanParams make_params(ysb_ctx* c, const ysb_segment* segs, u32 nseg) {
+static ScanParams make_params(ysb_ctx* c, const ysb_segment* segs, u32 nseg, const Layout& lay) {
     ScanParams p{};
     p.tbl = (c->cfg.flags & YSB_F_FORMAT_TBL) ? 1u : 0u;
     p.bytes = segs[0].d_bytes;
@@ -33,19 +43,19 @@ static ScanParams make_params(ysb_ctx* c, const ysb_segment* segs, u32 nseg) {
     // HBM-resident table: buckets, the second one read only after a miss in a full first
     p.probe_serial = c->ctable_buckets ? 1u : 0u;
     p.layout = (c->cfg.flags & YSB_F_FLAT_FIRST) ? 2u : (c->cfg.flags & YSB_F_COMPACT_FIRST) ? 1u : 0u;
-    if (c->submit_layout >= 0) p.layout = (u32)c->submit_layout;
+    if (lay.layout >= 0) p.layout = (u32)lay.layout;
     if (p.layout == 3 || p.layout == 4) {   // (4: learn_n 0 when the sample named no learned order)
         p.learn_code = 0;
-        for (u32 i = 0; i < c->submit_learn.n; ++i) p.learn_code |= c->submit_learn.order[i] << (3 * i);
-        p.learn_n = c->submit_learn.n;
-        p.learn_cp = c->submit_learn.cp;
+        for (u32 i = 0; i < lay.learn.n; ++i) p.learn_code |= lay.learn.order[i] << (3 * i);
+        p.learn_n = lay.learn.n;
+        p.learn_cp = lay.learn.cp;
     }
     p.n_campaigns = c->cfg.n_campaigns;
     p.counts = c->d_counts;
     p.ring_w = c->cfg.window_ring;
     p.lds_wl = c->lds_wl;
     p.lds_wl_log2 = c->lds_wl_log2;
-    p.require_mask = (c->cfg.flags & YSB_F_REQUIRE_IP) ? 0x7Fu : 0x3Fu;
+    p.require_mask = require_mask(c);
     p.ring = c->d_ring;
     p.div = c->div;
     p.side = c->d_side;
@@ -94,59 +104,12 @@ static ScanParams make_params(ysb_ctx* c, const ysb_segment* segs, u32 nseg) {
     return p;
 }
 
-// Grows a device u32 buffer to at least `words` (contents not kept).
-static int grow_u32(ysb_ctx* c, u32** buf, u64* have, u64 words) {
-    if (*have >= words) return YSB_OK;
-    HIPCHK(c, hipStreamSynchronize(c->s_comp));
-    hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    HIPCHK(c, hipMalloc(buf, words * 4));
-    *have = words;
-    return YSB_OK;
-}
-
 // s waits for e -- unless e has completed already: the slot copies' wait for the slot's last
 // scan is normally long satisfied, and a cross-queue barrier packet costs the copy queue time
 // between copies even when it has nothing to wait for.
 static hipError_t wait_unless_done(hipStream_t s, hipEvent_t e) {
     if (hipEventQuery(e) == hipSuccess) return hipSuccess;
     return hipStreamWaitEvent(s, e, 0);
-}
-
-// YSB_F_TIMING keeps HIP events per launch and per slot copy until ysb_kernel_time /
-// ysb_copy_time read them.  A caller that never does (a streaming job) would grow them without
-// bound: once TIMING_KEEP are pending, the older half is folded into running totals (those
-// launches are TIMING_KEEP / 2 launches old -- normally long done; else this waits for them)
-// and their events are reused.
-static int fold_launch_events(ysb_ctx* c) {
-    const size_t half = TIMING_KEEP / 2;
-    for (size_t i = 0; i < half; ++i) {
-        float ms = 0, mp = 0;
-        HIPCHK(c, hipEventSynchronize(c->tev[i][2]));
-        HIPCHK(c, hipEventElapsedTime(&ms, c->tev[i][0], c->tev[i][1]));
-        HIPCHK(c, hipEventElapsedTime(&mp, c->tev[i][0], c->tev[i][2]));
-        c->tev_ms_fold += ms;
-        c->tev_path_fold += mp;
-        ++c->tev_folded;
-    }
-    std::rotate(c->tev.begin(), c->tev.begin() + (ptrdiff_t)half, c->tev.begin() + (ptrdiff_t)c->tev_used);
-    c->tev_used -= half;
-    return YSB_OK;
-}
-
-static int fold_copy_events(ysb_ctx* c) {
-    const size_t half = TIMING_KEEP / 2;
-    for (size_t i = 0; i < half; ++i) {
-        float ms = 0;
-        HIPCHK(c, hipEventSynchronize(c->cev[i][1]));
-        HIPCHK(c, hipEventElapsedTime(&ms, c->cev[i][0], c->cev[i][1]));
-        c->cev_ms_fold += ms;
-        ++c->cev_folded;
-    }
-    std::rotate(c->cev.begin(), c->cev.begin() + (ptrdiff_t)half, c->cev.begin() + (ptrdiff_t)c->cev_used);
-    c->cev_used -= half;
-    return YSB_OK;
 }
 
 // Record mode (ysb_count.hip) for this launch: large count tables without LDS window
@@ -189,19 +152,15 @@ static int plan_records(ysb_ctx* c, ScanParams& p, u64 n_events, RecParams& r) {
     r.cap = (u32)cap;
     r.area = area;
     int rc;
-    if ((rc = grow_u32(c, &c->d_rec, &c->rec_words, (u64)r.grid * r.bins * cap))) return rc;
-    if ((rc = grow_u32(c, &c->d_rec_n, &c->rec_n_words, (u64)r.grid * r.bins))) return rc;
-    if ((rc = grow_u32(c, &c->d_part, &c->part_words, part))) return rc;
-    if ((rc = grow_u32(c, &c->d_runs, &c->runs_words, (u64)r.n_blocks * REC_QUARTERS * 2))) return rc;
+    if ((rc = grow_device(c, &c->d_rec, &c->rec_bytes, (u64)r.grid * r.bins * cap * 4, 0))) return rc;
+    if ((rc = grow_device(c, &c->d_rec_n, &c->rec_n_bytes, (u64)r.grid * r.bins * 4, 0))) return rc;
+    if ((rc = grow_device(c, &c->d_part, &c->part_bytes, part * 4, 0))) return rc;
+    if ((rc = grow_device(c, &c->d_runs, &c->runs_bytes, (u64)r.n_blocks * REC_QUARTERS * 2 * 4, 0))) return rc;
     if (c->delta_cells != cells) {   // the delta ring: the u64 ring's layout, one byte a cell, zeroed
         if ((rc = fold_delta(c))) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->s_comp));
-        hipFree(c->d_delta);
-        c->d_delta = nullptr;
-        c->delta_cells = 0;
-        HIPCHK(c, hipMalloc(&c->d_delta, cells));
+        c->delta_cells = 0;   // (exactly `cells` of them: not only when it has to grow)
+        if ((rc = grow_device(c, &c->d_delta, &c->delta_cells, cells, 0))) return rc;
         HIPCHK(c, hipMemset(c->d_delta, 0, cells));
-        c->delta_cells = cells;
     }
     // the delta saturates instead of wrapping, so it needs no fold between launches; the
     // test hook YSB_DELTA_FOLD_EVENTS folds anyway once the events since the last fold
@@ -224,7 +183,7 @@ static int plan_records(ysb_ctx* c, ScanParams& p, u64 n_events, RecParams& r) {
     return YSB_OK;
 }
 
-static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin) {
+static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout& lay) {
     if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
     ysb_segment segs[MAX_SEGS];
     u32 nseg = 0;
@@ -233,14 +192,9 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin) {
         if (in[i].n_events) { segs[nseg++] = in[i]; n += in[i].n_events; }
     if (n == 0) { c->batches += nin; return YSB_OK; }
     if (n >= (1ull << 31)) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 events per launch");
-    if (n > c->defer_cap) {   // the deferred-line list can hold every line of a batch
-        HIPCHK(c, hipStreamSynchronize(c->s_comp));
-        hipFree(c->d_defer);
-        c->d_defer = nullptr;
-        const u64 cap = std::max<u64>(n, 1u << 16);
-        HIPCHK(c, hipMalloc(&c->d_defer, cap * 4));
-        c->defer_cap = cap;
-    }
+    // the deferred-line list can hold every line of a batch
+    int rc = grow_device(c, &c->d_defer, &c->defer_bytes, n * 4, 4u << 16);
+    if (rc) return rc;
     if (!c->d_defer_ctr) {
         HIPCHK(c, hipMalloc(&c->d_defer_ctr, 16 + 4 * MAX_SEGS));
         HIPCHK(c, hipMemset(c->d_defer_ctr, 0, 16 + 4 * MAX_SEGS));
@@ -250,18 +204,18 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin) {
     if (c->used_pending && hipEventQuery(c->ev_used) == hipSuccess) {
         c->used_pending = false;
         if ((u64)*c->h_used * 4 > c->side_slots) {
-            int rc = sync_streams(c);
+            rc = sync_streams(c);
             if (!rc) rc = pull_side_list(c);
             if (rc) return rc;
         }
     }
-    ScanParams p = make_params(c, segs, nseg);
+    ScanParams p = make_params(c, segs, nseg, lay);
     p.used_out = c->used_pending ? nullptr : c->h_used;
     p.defer = c->d_defer;
     p.defer_count = c->d_defer_ctr;
     p.defer_done = c->d_defer_ctr + 1;
     p.dyn_ctr = c->d_defer_ctr + 4;
-    p.defer_cap = (u32)c->defer_cap;
+    p.defer_cap = (u32)(c->defer_bytes / 4);
 #if defined(YSB_STAMPS) || defined(YSB_WGTIME)
     const u64 words = (u64)c->cus * std::max(Geom<true>::WG_PER_CU, Geom<false>::WG_PER_CU) * (SCAN_TPB / 64) * N_STAMPS;
     if (!c->d_dbg) {
@@ -282,21 +236,11 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin) {
     // dynamic claims (off by default) count from zero in every launch
     if (p.dyn_chunk) HIPCHK(c, hipMemsetAsync(p.dyn_ctr, 0, 4 * MAX_SEGS, c->s_comp));
     RecParams rp{};
-    int rc = plan_records(c, p, n, rp);
-    if (rc) return rc;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    if ((rc = plan_records(c, p, n, rp))) return rc;
+    hipEvent_t* te = nullptr;   // YSB_F_TIMING: {before the scan, after it, after the launch's last kernel}
     if (c->cfg.flags & YSB_F_TIMING) {
-        if (c->tev_used == TIMING_KEEP && (rc = fold_launch_events(c))) return rc;
-        if (c->tev_used == c->tev.size()) {
-            std::array<hipEvent_t, 3> ev{};
-            for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
-            c->tev.push_back(ev);
-        }
-        e0 = c->tev[c->tev_used][0];
-        e1 = c->tev[c->tev_used][1];
-        e2 = c->tev[c->tev_used][2];
-        c->tev_used++;
-        HIPCHK(c, hipEventRecord(e0, c->s_comp));
+        HIPCHK(c, c->tev.acquire(&te));
+        HIPCHK(c, hipEventRecord(te[0], c->s_comp));
     }
     launch_scan(p, c->s_comp);
     HIPCHK(c, hipGetLastError());
@@ -306,7 +250,7 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin) {
     c->last_launch.record_mode = p.rec_on ? 1u : 0u;
     c->last_launch.hbm_table = p.probe_serial ? 1u : 0u;
     c->last_launch.tbl = p.tbl ? 1u : 0u;
-    if (e1) HIPCHK(c, hipEventRecord(e1, c->s_comp));
+    if (te) HIPCHK(c, hipEventRecord(te[1], c->s_comp));
     launch_defer(p, c->cus, c->s_comp);
     HIPCHK(c, hipGetLastError());
     if (p.rec_on) {
@@ -316,144 +260,13 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin) {
         HIPCHK(c, hipGetLastError());
         c->rec_launches++;
     }
-    if (e2) HIPCHK(c, hipEventRecord(e2, c->s_comp));
+    if (te) HIPCHK(c, hipEventRecord(te[2], c->s_comp));
     if (p.used_out) {   // defer_kernel wrote the map's fill level into h_used
         HIPCHK(c, hipEventRecord(c->ev_used, c->s_comp));
         c->used_pending = true;
     }
     c->batches += nin;   // each segment counts as the batch it is
     return YSB_OK;
-}
-
-// The JSON layout of a batch's first line l[0, len): 0 the generator's (core.clj:90-96), 1
-// the generator's keys in its order as compact JSON, 3 another key order or subset of
-// DeserializeBolt's keys with one consistent spacing (", " / ": " or "," / ":") and plain
-// string values (36 bytes for the three ids) -- d then holds the order for the scan's
-// learned-order instantiation -- and 2 anything else (the flat-object tier first).  Only a
-// choice of instantiation: every instantiation counts every line exactly.
-static int learn_layout(const u8* l, u64 len, u32 require_mask, LearnDesc* d) {
-    static const char* keys[7] = {"user_id", "page_id", "ad_id", "ad_type", "event_type", "event_time", "ip_address"};
-    if (len < 2 || l[0] != '{' || l[1] != '"') return 2;
-    auto plain_end = [&](u64 q) {   // the closing quote of a plain string from q (len: none)
-        while (q < len && l[q] != '"' && l[q] != '\\' && l[q] >= 0x20) ++q;
-        return (q < len && l[q] == '"') ? q : len;
-    };
-    u64 p = 2;
-    int cp = -1;
-    u32 seen = 0, n = 0, order[8] = {0};
-    for (;;) {
-        u64 q = plain_end(p);
-        if (q >= len) return 2;
-        int id = -1;
-        for (int i = 0; i < 7; ++i)
-            if (std::strlen(keys[i]) == q - p && std::memcmp(l + p, keys[i], q - p) == 0) id = i;
-        if (id < 0 || ((seen >> id) & 1u) || n >= 7) return 2;
-        seen |= 1u << id;
-        order[n++] = (u32)id;
-        p = q + 1;
-        int c1;
-        if (p + 2 < len && l[p] == ':' && l[p + 1] == ' ' && l[p + 2] == '"') { c1 = 0; p += 3; }
-        else if (p + 1 < len && l[p] == ':' && l[p + 1] == '"') { c1 = 1; p += 2; }
-        else return 2;
-        if (cp < 0) cp = c1;
-        else if (cp != c1) return 2;
-        q = plain_end(p);
-        if (q >= len || (id <= 2 && q - p != 36)) return 2;
-        p = q + 1;
-        if (p < len && l[p] == '}') break;
-        if (cp == 0 && p + 2 < len && l[p] == ',' && l[p + 1] == ' ' && l[p + 2] == '"') p += 3;
-        else if (cp == 1 && p + 1 < len && l[p] == ',' && l[p + 1] == '"') p += 2;
-        else return 2;
-    }
-    // key index i is bit i of the required-key mask (ysb_scan.hip K_*)
-    if ((seen & require_mask) != require_mask || !((seen >> 2) & 1u) || !((seen >> 4) & 1u) || !((seen >> 5) & 1u))
-        return 2;
-    bool gen_order = n == 7;
-    for (u32 i = 0; i < n; ++i) gen_order &= order[i] == i;
-    if (gen_order) return cp ? 1 : 0;
-    d->n = n;
-    d->cp = (u32)cp;
-    for (u32 i = 0; i < 8; ++i) d->order[i] = order[i];
-    return 3;
-}
-
-// The batch's layout from SAMPLE_LINES of its lines (round 4; until round 3 the first line
-// only): line 0 and one line at a hashed position in each of the other strata of
-// [0, n).  If at least SAMPLE_AGREE of them name the same layout (for 3 the same key order
-// and spacing), that one; otherwise several producers are interleaved and the flat-object
-// tier, which takes every layout alike, runs first (2).  Only a choice of instantiation:
-// every instantiation counts every line exactly.
-// 46 of 64 (72 %): a producer writing most of the batch keeps its instantiation (its lines at
-// full speed, the others through the tiers); a batch half of one layout (four producers, two
-// of them in the generator's layout) reaches 46 of 64 in ~0.03 % of samples (with 32 lines
-// and 23 of them: 0.4 %, which a bench seed hit)
-constexpr u32 SAMPLE_LINES = 64, SAMPLE_AGREE = 46;
-static_assert(SAMPLE_LINES <= (u32)SAMPLE_MAX, "device samples: one SampleSegs entry per line");
-#ifndef YSB_MIXED_TILE
-#define YSB_MIXED_TILE 1   // round 4: a sample without a majority layout takes the per-tile dispatch (4), not the flat tier (2)
-#endif
-
-// Sample line j: pairs of adjacent lines, one pair per stratum of [0, n) in SAMPLE_LINES / 2
-// strata (lines 0 and 1, then a hashed position in each other stratum and the line after it)
-// -- so the sample also tells producers writing in runs (adjacent lines alike) from a
-// line-by-line interleave.
-static u64 sample_index(u64 n, u32 j) {
-    if (n <= SAMPLE_LINES) return std::min<u64>(j, n ? n - 1 : 0);
-    const u64 P = SAMPLE_LINES / 2, q = j >> 1;
-    const u64 a = n * q / P, b = n * (q + 1) / P;   // stratum q
-    const u64 base = q == 0 ? 0 : a + mix64(0x51ED27u + q) % std::max<u64>(1, b - a - 1);
-    return std::min<u64>(base + (j & 1u), n - 1);
-}
-
-static int decide_layout(const ysb_ctx* c, const std::vector<std::pair<const u8*, u64>>& lines, LearnDesc* d) {
-    const u32 req = (c->cfg.flags & YSB_F_REQUIRE_IP) ? 0x7Fu : 0x3Fu;
-    std::vector<std::pair<int, LearnDesc>> got;
-    for (const auto& l : lines) {
-        LearnDesc di{};
-        const int lay = learn_layout(l.first, l.second, req, &di);
-        got.push_back({lay, lay == 3 ? di : LearnDesc{}});
-    }
-    if (got.empty()) return 0;
-    u32 best_learned = 0;
-    for (const auto& g : got) {   // the most frequent (layout, order) of the sample
-        u32 k = 0;
-        for (const auto& h : got) k += h.first == g.first && std::memcmp(&h.second, &g.second, sizeof(LearnDesc)) == 0;
-        if (k >= std::min<u32>(SAMPLE_AGREE, (u32)got.size())) {
-            *d = g.second;
-            return g.first;
-        }
-        if (g.first == 3 && k > best_learned) {   // the most frequent learned order, for layout 4
-            best_learned = k;
-            *d = g.second;
-        }
-    }
-#if YSB_MIXED_TILE
-    // several producers.  Writing in runs (3 of 4 adjacent sample pairs alike): the per-tile
-    // dispatch (4) -- tiles of one producer take its path (the learned order: the sample's
-    // most frequent one), mixed tiles the flat tier; interleaved line by line: every tile
-    // would be mixed, so the flat tier without the dispatch (2)
-    u32 pairs = 0, alike = 0;
-    for (size_t i = 0; i + 1 < got.size(); i += 2, ++pairs)
-        alike += got[i].first == got[i + 1].first &&
-                 std::memcmp(&got[i].second, &got[i + 1].second, sizeof(LearnDesc)) == 0;
-    if (4 * alike >= 3 * pairs) {
-        if (!best_learned) *d = LearnDesc{};
-        return 4;
-    }
-#endif
-    return 2;
-}
-
-// A host batch (held in the pinned slot).
-static int sniff_layout(const ysb_ctx* c, const uint8_t* bytes, u64 nbytes, const u32* off, u64 n, LearnDesc* d) {
-    std::vector<std::pair<const u8*, u64>> lines;
-    for (u32 j = 0; j < SAMPLE_LINES && j < n; ++j) {
-        const u64 i = sample_index(n, j);
-        const u64 s = off[i], e = i + 1 < n ? (u64)off[i + 1] : nbytes;
-        if (s >= e || e > nbytes) return 0;   // bad offsets: the scan defers them anyway
-        lines.push_back({bytes + s, std::min<u64>(e - s, SAMPLE_BYTES)});
-    }
-    return decide_layout(c, lines, d);
 }
 
 // Whether batches pick the scan instantiation from their first line (the default): not
@@ -464,14 +277,6 @@ static int sniff_layout(const ysb_ctx* c, const uint8_t* bytes, u64 nbytes, cons
 static bool layout_sampling(const ysb_ctx* c) {
     const u32 f = c->cfg.flags;
     return !(f & (YSB_F_LAYOUT_FIXED | YSB_F_COMPACT_FIRST | YSB_F_FORMAT_TBL));
-}
-
-// The sampled layout under the flags' hint: YSB_F_FLAT_FIRST keeps the flat-object tier
-// first unless the first line names a key order (3: the learned-order instantiation, whose
-// lines off that order go to the same flat tier).
-static int hinted_layout(const ysb_ctx* c, int sampled) {
-    if ((c->cfg.flags & YSB_F_FLAT_FIRST) && sampled >= 0 && sampled != 3 && sampled != 4) return 2;
-    return sampled;
 }
 
 // Device batches: SAMPLE_LINES lines spread over the launch's segments (as sniff_layout
@@ -490,10 +295,6 @@ static int hinted_layout(const ysb_ctx* c, int sampled) {
 //    dispatch, without a wait.
 // So a producer that changes its layout costs one launch of the wrong instantiation and then
 // dispatch launches until it settles; counts never depend on the choice.
-static bool same_decision(int a, const LearnDesc& la, int b, const LearnDesc& lb) {
-    return a == b && (a != 3 || std::memcmp(&la, &lb, sizeof(LearnDesc)) == 0);
-}
-
 static int decide_sample(ysb_ctx* c, int k) {
     if (c->sample_dec[k] >= 0) return YSB_OK;
     HIPCHK(c, hipEventSynchronize(c->ev_sample[k]));
@@ -508,13 +309,13 @@ static int decide_sample(ysb_ctx* c, int k) {
         if (!hd[2]) { lay = 0; break; }   // bad offsets: the scan defers them anyway
         lines.push_back({sp + 16, hd[1]});
     }
-    if (lay < 0) lay = decide_layout(c, lines, &d);
+    if (lay < 0) lay = decide_layout(require_mask(c), lines, &d);
     c->sample_dec[k] = lay;
     c->sample_learn[k] = lay == 3 || lay == 4 ? d : LearnDesc{};
     return YSB_OK;
 }
 
-static int sample_device_layout(ysb_ctx* c, const ysb_segment* segs, u32 nseg, LearnDesc* d) {
+static int sample_device_layout(ysb_ctx* c, const ysb_segment* segs, u32 nseg, Layout* out) {
     const u64 buf = (u64)SAMPLE_LINES * SAMPLE_STRIDE;
     if (!c->h_sample) {
         HIPCHK(c, hipHostMalloc(&c->h_sample, 2 * buf));
@@ -554,40 +355,16 @@ static int sample_device_layout(ysb_ctx* c, const ysb_segment* segs, u32 nseg, L
     int rc;
     if (idle) {   // this launch's own sample
         if ((rc = decide_sample(c, k))) return rc;
-        *d = c->sample_learn[k];
-        return c->sample_dec[k];
+        *out = {c->sample_dec[k], c->sample_learn[k]};
+        return YSB_OK;
     }
     const int p = k ^ 1;   // the previous launch's sample
     if (!c->sample_nseg[p]) {   // none: no wait, the dispatch
-        *d = LearnDesc{};
-        return 4;
+        *out = {4, LearnDesc{}};
+        return YSB_OK;
     }
     if ((rc = decide_sample(c, p))) return rc;
-    // (no older decision -- the first two launches -- trusts the previous sample alone)
-    if (older < 0 || same_decision(older, older_learn, c->sample_dec[p], c->sample_learn[p])) {
-        *d = c->sample_learn[p];
-        return c->sample_dec[p];
-    }
-    // two samples disagree: the per-tile dispatch (with the newer sample's learned order, if any)
-    *d = c->sample_dec[p] == 3 || c->sample_dec[p] == 4 ? c->sample_learn[p] : LearnDesc{};
-    return 4;
-}
-
-// With YSB_F_TIMING: an event pair around a slot's H2D copy (ysb_copy_time), else none.
-static int copy_events(ysb_ctx* c, hipEvent_t** out, u64 bytes) {
-    *out = nullptr;
-    if (!(c->cfg.flags & YSB_F_TIMING)) return YSB_OK;
-    if (c->cev_used == TIMING_KEEP) {
-        const int rc = fold_copy_events(c);
-        if (rc) return rc;
-    }
-    if (c->cev_used == c->cev.size()) {
-        std::array<hipEvent_t, 2> ev{};
-        for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
-        c->cev.push_back(ev);
-    }
-    *out = c->cev[c->cev_used++].data();
-    c->copy_bytes += bytes;
+    out->layout = settled_layout(older, older_learn, c->sample_dec[p], c->sample_learn[p], &out->learn);
     return YSB_OK;
 }
 
@@ -617,6 +394,30 @@ static hipError_t h2d(ysb_ctx* c, void* dst, const void* dsrc, const void* hsrc,
     return hipGetLastError();
 }
 
+// A slot's copies (up to two; 0 bytes: none) on the copy stream once the slot's previous
+// kernel has run -- its device buffers are free then -- with YSB_F_TIMING inside an event
+// pair (ysb_copy_time); ev_h2d[slot] marks them done.
+struct SlotCopy {
+    void* dst;
+    const void* dsrc;   // the source's device address (the copy kernel) ...
+    const void* hsrc;   // ... and its host address (YSB_F_H2D_SDMA)
+    u64 bytes;
+};
+static int copy_slot(ysb_ctx* c, int slot, const SlotCopy& a, const SlotCopy& b = {}) {
+    HIPCHK(c, wait_unless_done(c->s_copy, c->ev_kdone[slot]));
+    hipEvent_t* ce = nullptr;
+    if (c->cfg.flags & YSB_F_TIMING) {
+        HIPCHK(c, c->cev.acquire(&ce));
+        c->copy_bytes += a.bytes + b.bytes;
+        HIPCHK(c, hipEventRecord(ce[0], c->s_copy));
+    }
+    if (a.bytes) HIPCHK(c, h2d(c, a.dst, a.dsrc, a.hsrc, a.bytes));
+    if (b.bytes) HIPCHK(c, h2d(c, b.dst, b.dsrc, b.hsrc, b.bytes));
+    if (ce) HIPCHK(c, hipEventRecord(ce[1], c->s_copy));
+    HIPCHK(c, hipEventRecord(c->ev_h2d[slot], c->s_copy));
+    return YSB_OK;
+}
+
 int ysb_slot_buffers(ysb_ctx* c, int slot, uint8_t** bytes, uint32_t** line_off) {
     if (!c || slot < 0 || slot > 1) return c ? fail(c, YSB_ERR_ARG, "slot must be 0 or 1") : YSB_ERR_ARG;
     int rc = ensure_slots(c);
@@ -643,24 +444,18 @@ int ysb_submit(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, cons
     if (bytes != c->h_bytes[slot] && nbytes) std::memcpy(c->h_bytes[slot], bytes, nbytes);
     if (line_off != c->h_off[slot] && n) std::memcpy(c->h_off[slot], line_off, n * 4);
     // ... and the slot's previous kernel must be done before its device buffers are
-    HIPCHK(c, wait_unless_done(c->s_copy, c->ev_kdone[slot]));
-    hipEvent_t* ce = nullptr;
-    if ((rc = copy_events(c, &ce, nbytes + n * 4))) return rc;
-    if (ce) HIPCHK(c, hipEventRecord(ce[0], c->s_copy));
-    if (nbytes) HIPCHK(c, h2d(c, c->d_bytes[slot], c->hd_bytes[slot], c->h_bytes[slot], nbytes));
-    if (n) HIPCHK(c, h2d(c, c->d_off[slot], c->hd_off[slot], c->h_off[slot], n * 4));
-    if (ce) HIPCHK(c, hipEventRecord(ce[1], c->s_copy));
-    HIPCHK(c, hipEventRecord(c->ev_h2d[slot], c->s_copy));
+    if ((rc = copy_slot(c, slot, {c->d_bytes[slot], c->hd_bytes[slot], c->h_bytes[slot], nbytes},
+                        {c->d_off[slot], c->hd_off[slot], c->h_off[slot], n * 4})))
+        return rc;
     HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_h2d[slot], 0));
     const ysb_segment sg{c->d_bytes[slot], nbytes, c->d_off[slot], n};
     // the scan instantiation named by the batch's first line, which the host holds in the
     // pinned slot (counts are the same whichever runs)
+    Layout lay;
     if (layout_sampling(c) && n)
-        c->submit_layout =
-            hinted_layout(c, sniff_layout(c, c->h_bytes[slot], nbytes, c->h_off[slot], n, &c->submit_learn));
-    rc = enqueue_scan(c, &sg, 1);
-    c->submit_layout = -1;
-    if (rc) return rc;
+        lay.layout = hinted_layout(flat_first(c), sniff_layout(require_mask(c), c->h_bytes[slot], nbytes,
+                                                               c->h_off[slot], n, &lay.learn));
+    if ((rc = enqueue_scan(c, &sg, 1, lay))) return rc;
     HIPCHK(c, hipEventRecord(c->ev_kdone[slot], c->s_comp));
     return YSB_OK;
 }
@@ -693,18 +488,9 @@ static int ensure_raw(ysb_ctx* c) {
         if (!c->ev_raw[s]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_raw[s], hipEventDisableTiming));
     }
     if (!c->s_split) HIPCHK(c, hipStreamCreateWithFlags(&c->s_split, hipStreamNonBlocking));
-    if (const char* e = getenv("YSB_SPLIT_STREAM")) c->split_place = std::atoi(e);
-    if (const char* e = getenv("YSB_H2D_WG")) c->h2d_wg = std::max(1, std::atoi(e));
-    if (const char* e = getenv("YSB_H2D_PRIO")) c->h2d_prio = std::atoi(e) != 0;
-    if (const char* e = getenv("YSB_H2D_GRID")) c->h2d_grid = std::max(0, std::atoi(e));
-    const u64 words = split_chunks(c->cfg.max_batch_bytes) + 1;
-    if (c->split_chunk_words < words) {
-        hipFree(c->d_split_chunk);
-        c->d_split_chunk = nullptr;
-        c->split_chunk_words = 0;
-        HIPCHK(c, hipMalloc(&c->d_split_chunk, words * 4));
-        c->split_chunk_words = words;
-    }
+    const u64 chunk_bytes = (split_chunks(c->cfg.max_batch_bytes) + 1) * 4;
+    const int rc = grow_device(c, &c->d_split_chunk, &c->split_chunk_bytes, chunk_bytes, 0);
+    if (rc) return rc;
     HIPCHK(c, hipHostMalloc(&c->h_rawn, 16));
     return YSB_OK;
 }
@@ -731,10 +517,7 @@ int launch_pending_raw(ysb_ctx* c) {
                   (unsigned long long)c->raw_lines_cap);
     } else {
         const ysb_segment sg{c->d_bytes[slot], c->raw_nbytes[slot], c->d_roff[slot], c->h_rawn[slot]};
-        c->submit_layout = c->raw_layout[slot];
-        c->submit_learn = c->raw_learn[slot];
-        rc = enqueue_scan(c, &sg, 1);
-        c->submit_layout = -1;
+        rc = enqueue_scan(c, &sg, 1, {c->raw_layout[slot], c->raw_learn[slot]});
     }
     // the slot's device buffers are free again once this launch (or nothing) has run
     if (hipEventRecord(c->ev_kdone[slot], c->s_comp) != hipSuccess && !rc)
@@ -745,35 +528,6 @@ int launch_pending_raw(ysb_ctx* c) {
         c->raw_fail_msg = c->err;
     }
     return rc;
-}
-
-// The layout of a raw batch (host bytes): its first line and the first complete line after
-// each of SAMPLE_LINES - 1 spread byte positions, decided as sniff_layout decides.
-static int sniff_raw(const ysb_ctx* c, const u8* b, u64 nbytes, LearnDesc* d) {
-    auto line_at = [&](u64 p) -> std::pair<const u8*, u64> {   // the line starting at p
-        const u64 lim = std::min<u64>(nbytes, p + SAMPLE_BYTES);
-        u64 e = p;
-        while (e < lim && b[e] != '\n' && b[e] != '\r') ++e;
-        return {b + p, std::min<u64>(e + 1, nbytes) - p};
-    };
-    // pairs of adjacent lines (as sample_index): the first two, then the two after a '\n' at
-    // each other stratum's start (a lone '\r' only ends lines elsewhere)
-    auto next_start = [&](u64 p) -> u64 {   // past the '\n' at or after p (nbytes: none near)
-        const u64 lim = std::min<u64>(nbytes, p + 4096);
-        while (p < lim && b[p] != '\n') ++p;
-        return p + 1 < lim ? p + 1 : nbytes;
-    };
-    std::vector<std::pair<const u8*, u64>> lines;
-    for (u32 q = 0; q < SAMPLE_LINES / 2; ++q) {
-        const u64 s0 = q == 0 ? 0 : next_start(nbytes * q / (SAMPLE_LINES / 2));
-        if (s0 >= nbytes) continue;
-        const u64 s1 = next_start(s0);
-        if (s1 >= nbytes) continue;   // a pair or nothing
-        lines.push_back(line_at(s0));
-        lines.push_back(line_at(s1));
-    }
-    if (lines.empty()) lines.push_back(line_at(0));
-    return decide_layout(c, lines, d);
 }
 
 static int raw_args(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes) {
@@ -792,7 +546,7 @@ static int enqueue_raw(ysb_ctx* c, int slot, const u8* hsrc, const u8* dsrc, u64
     int rc;
     c->raw_layout[slot] = -1;
     if (layout_sampling(c) && nbytes)
-        c->raw_layout[slot] = hinted_layout(c, sniff_raw(c, hsrc, nbytes, &c->raw_learn[slot]));
+        c->raw_layout[slot] = hinted_layout(flat_first(c), sniff_raw(require_mask(c), hsrc, nbytes, &c->raw_learn[slot]));
     // H2D once the slot's previous kernel has run.  The split on a stream of its own behind its
     // copy, so the next slot's copy queues right behind this one.  Round 5 kept it on the copy
     // stream: beside a copy kernel of one workgroup per CU the split was starved (its 32 us
@@ -804,13 +558,7 @@ static int enqueue_raw(ysb_ctx* c, int slot, const u8* hsrc, const u8* dsrc, u64
     // stream, 2 the compute stream -- A/B only.)
     const bool sdma = (c->cfg.flags & YSB_F_H2D_SDMA) != 0u;
     hipStream_t ss = sdma || c->split_place == 1 ? c->s_split : c->split_place == 2 ? c->s_comp : c->s_copy;
-    HIPCHK(c, wait_unless_done(c->s_copy, c->ev_kdone[slot]));
-    hipEvent_t* ce = nullptr;
-    if ((rc = copy_events(c, &ce, nbytes))) return rc;
-    if (ce) HIPCHK(c, hipEventRecord(ce[0], c->s_copy));
-    if (nbytes) HIPCHK(c, h2d(c, c->d_bytes[slot], dsrc, hsrc, nbytes));
-    if (ce) HIPCHK(c, hipEventRecord(ce[1], c->s_copy));
-    HIPCHK(c, hipEventRecord(c->ev_h2d[slot], c->s_copy));
+    if ((rc = copy_slot(c, slot, {c->d_bytes[slot], dsrc, hsrc, nbytes}))) return rc;
     if (ss != c->s_copy) HIPCHK(c, hipStreamWaitEvent(ss, c->ev_h2d[slot], 0));
     c->raw_rebase_on[slot] = rb != nullptr;
     if (rb) c->raw_rebase[slot] = *rb;
@@ -921,20 +669,36 @@ static const u8* mapped_src(const ysb_ctx* c, const uint8_t* bytes, u64 nbytes) 
     return it->second.dptr + (a - it->first);
 }
 
+// ... or the error: a batch with bytes must have one.
+static int mapped_src_or_fail(ysb_ctx* c, const uint8_t* bytes, u64 nbytes, const u8** dsrc) {
+    *dsrc = mapped_src(c, bytes, nbytes);
+    if (nbytes && !*dsrc)
+        return fail(c, YSB_ERR_ARG, "the batch (widened to 16-byte boundaries) is not inside a registered range");
+    return YSB_OK;
+}
+
+// A mapped batch's rebase argument (NULL: none) against the context's table.  A raw batch
+// (n_lines NULL: its line count is not known yet, launch_pending_raw checks it) must start
+// inside the table; a batch with offsets must fit its *n_lines lines.
+static int rebase_args(ysb_ctx* c, const ysb_rebase* rb, const u64* n_lines) {
+    if (!rb) return YSB_OK;
+    if (!c->d_rebase) return fail(c, YSB_ERR_STATE, "no rebase table (ysb_rebase_table)");
+    if (!n_lines && rb->first_line >= c->rebase_n) return fail(c, YSB_ERR_ARG, "first_line beyond the rebase table");
+    if (n_lines && (rb->first_line > c->rebase_n || *n_lines > c->rebase_n - rb->first_line))
+        return fail(c, YSB_ERR_ARG, "the batch's lines run past the rebase table");
+    const i64 lo = c->rebase_base + rb->lead_shift;
+    if (lo < 0 || lo + (i64)c->rebase_kmax >= 1000000000LL)
+        return fail(c, YSB_ERR_ARG, "rebased leading digits out of [0, 10^9)");
+    return YSB_OK;
+}
+
 int ysb_submit_raw_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_rebase* rb) {
     if (!c) return YSB_ERR_ARG;
     int rc = raw_args(c, slot, bytes, nbytes);
+    const u8* dsrc = nullptr;
+    if (!rc) rc = mapped_src_or_fail(c, bytes, nbytes, &dsrc);
+    if (!rc) rc = rebase_args(c, rb, nullptr);
     if (rc) return rc;
-    const u8* dsrc = mapped_src(c, bytes, nbytes);
-    if (nbytes && !dsrc)
-        return fail(c, YSB_ERR_ARG, "the batch (widened to 16-byte boundaries) is not inside a registered range");
-    if (rb) {
-        if (!c->d_rebase) return fail(c, YSB_ERR_STATE, "no rebase table (ysb_rebase_table)");
-        if (rb->first_line >= c->rebase_n) return fail(c, YSB_ERR_ARG, "first_line beyond the rebase table");
-        const i64 lo = c->rebase_base + rb->lead_shift;
-        if (lo < 0 || lo + (i64)c->rebase_kmax >= 1000000000LL)
-            return fail(c, YSB_ERR_ARG, "rebased leading digits out of [0, 10^9)");
-    }
     rc = c->raw_pend == slot ? launch_pending_raw(c) : YSB_OK;
     if (!rc) rc = ensure_slots(c);
     if (!rc) rc = ensure_raw(c);
@@ -954,17 +718,8 @@ int ysb_submit_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbyte
     if (rc) return rc;
     if (n > 0x7FFFFFFFull) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 events per batch");
     if (n && !d_line_off) return fail(c, YSB_ERR_ARG, "NULL line offsets");
-    const u8* dsrc = mapped_src(c, bytes, nbytes);
-    if (nbytes && !dsrc)
-        return fail(c, YSB_ERR_ARG, "the batch (widened to 16-byte boundaries) is not inside a registered range");
-    if (rb) {
-        if (!c->d_rebase) return fail(c, YSB_ERR_STATE, "no rebase table (ysb_rebase_table)");
-        if (rb->first_line > c->rebase_n || n > c->rebase_n - rb->first_line)
-            return fail(c, YSB_ERR_ARG, "the batch's lines run past the rebase table");
-        const i64 lo = c->rebase_base + rb->lead_shift;
-        if (lo < 0 || lo + (i64)c->rebase_kmax >= 1000000000LL)
-            return fail(c, YSB_ERR_ARG, "rebased leading digits out of [0, 10^9)");
-    }
+    const u8* dsrc = nullptr;
+    if ((rc = mapped_src_or_fail(c, bytes, nbytes, &dsrc)) || (rc = rebase_args(c, rb, &n))) return rc;
     if (!n) return YSB_OK;
     rc = launch_pending_raw(c);   // batches launch in submission order
     if (!rc) rc = ensure_slots(c);
@@ -973,14 +728,9 @@ int ysb_submit_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbyte
     // at most two copies in flight: the slot's previous one must be done (its device buffer is
     // then only still read by its scan, which the copy waits for on the device)
     HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
-    if (layout_sampling(c)) c->submit_layout = hinted_layout(c, sniff_raw(c, bytes, nbytes, &c->submit_learn));
-    HIPCHK(c, wait_unless_done(c->s_copy, c->ev_kdone[slot]));
-    hipEvent_t* ce = nullptr;
-    if ((rc = copy_events(c, &ce, nbytes))) return rc;
-    if (ce) HIPCHK(c, hipEventRecord(ce[0], c->s_copy));
-    HIPCHK(c, h2d(c, c->d_bytes[slot], dsrc, bytes, nbytes));
-    if (ce) HIPCHK(c, hipEventRecord(ce[1], c->s_copy));
-    HIPCHK(c, hipEventRecord(c->ev_h2d[slot], c->s_copy));
+    Layout lay;
+    if (layout_sampling(c)) lay.layout = hinted_layout(flat_first(c), sniff_raw(require_mask(c), bytes, nbytes, &lay.learn));
+    if ((rc = copy_slot(c, slot, {c->d_bytes[slot], dsrc, bytes, nbytes}))) return rc;
     HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_h2d[slot], 0));
     if (rb) {
         launch_rebase(c->d_bytes[slot], nbytes, d_line_off, n, nullptr, n, c->d_rebase + rb->first_line,
@@ -988,9 +738,7 @@ int ysb_submit_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbyte
         HIPCHK(c, hipGetLastError());
     }
     const ysb_segment sg{c->d_bytes[slot], nbytes, d_line_off, n};
-    rc = enqueue_scan(c, &sg, 1);
-    c->submit_layout = -1;
-    if (rc) return rc;
+    if ((rc = enqueue_scan(c, &sg, 1, lay))) return rc;
     HIPCHK(c, hipEventRecord(c->ev_kdone[slot], c->s_comp));
     return YSB_OK;
 }
@@ -1004,16 +752,7 @@ int ysb_split_lines_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, 
     int rc = launch_pending_raw(c);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const u64 words = split_chunks(nbytes) + 1;
-    if (c->split_chunk_words < words) {
-        if (c->s_split) HIPCHK(c, hipStreamSynchronize(c->s_split));
-        HIPCHK(c, hipStreamSynchronize(c->s_comp));
-        hipFree(c->d_split_chunk);
-        c->d_split_chunk = nullptr;
-        c->split_chunk_words = 0;
-        HIPCHK(c, hipMalloc(&c->d_split_chunk, words * 4));
-        c->split_chunk_words = words;
-    }
+    if ((rc = grow_device(c, &c->d_split_chunk, &c->split_chunk_bytes, (split_chunks(nbytes) + 1) * 4, 0))) return rc;
     if (!c->d_cmp) HIPCHK(c, hipMalloc(&c->d_cmp, 32));
     unsigned long long* d_n = c->d_cmp + 3;
     HIPCHK(c, launch_split_lines(d_bytes, nbytes, c->d_split_chunk, d_off, cap, d_n, c->s_comp));
@@ -1036,34 +775,27 @@ int ysb_copy_time(ysb_ctx* c, double* total_ms, uint64_t* copies, uint64_t* byte
     if (!c) return YSB_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->s_copy));
-    double t = c->cev_ms_fold;
-    for (size_t i = 0; i < c->cev_used; ++i) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->cev[i][0], c->cev[i][1]));
-        t += ms;
-    }
-    if (total_ms) *total_ms = t;
-    if (copies) *copies = c->cev_folded + c->cev_used;
+    double t[2] = {0, 0};
+    u64 n = 0;
+    HIPCHK(c, c->cev.collect(t, &n));
+    if (total_ms) *total_ms = t[1];
+    if (copies) *copies = n;
     if (bytes) *bytes = c->copy_bytes;
-    c->cev_used = 0;
-    c->cev_ms_fold = 0;
-    c->cev_folded = 0;
     c->copy_bytes = 0;
     return YSB_OK;
 }
 
-// Device batches: the layout sampled from their first lines (unless fixed), then the launch.
+// Device batches: the layout sampled from their lines (unless fixed), then the launch.
 static int enqueue_device(ysb_ctx* c, const ysb_segment* segs, u32 nseg) {
     int prc = launch_pending_raw(c);   // batches launch in submission order
     if (prc) return prc;
+    Layout lay;
     if (c->table_loaded && layout_sampling(c)) {
-        const int lay = sample_device_layout(c, segs, nseg, &c->submit_learn);
-        if (lay < 0) return lay;
-        c->submit_layout = hinted_layout(c, lay);
+        const int rc = sample_device_layout(c, segs, nseg, &lay);
+        if (rc) return rc;
+        lay.layout = hinted_layout(flat_first(c), lay.layout);
     }
-    const int rc = enqueue_scan(c, segs, nseg);
-    c->submit_layout = -1;
-    return rc;
+    return enqueue_scan(c, segs, nseg, lay);
 }
 
 int ysb_submit_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const uint32_t* d_off, uint64_t n) {

@@ -115,12 +115,22 @@ def test_bad_config_rejected_before_device_use():
     assert b"window_ring" in L.ysb_last_error(None)
 
 
-def test_host_logic_native(tmp_path):
-    exe = tmp_path / "host_logic"
+def run_native(tmp_path, name):
+    exe = tmp_path / name
     subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "streaming-benchmarks_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "native", "host_logic.cpp"), "-o", str(exe)], check=True)
+                    os.path.join(ROOT, "tests", "native", name + ".cpp"), "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout
+
+
+def test_host_logic_native(tmp_path):
+    run_native(tmp_path, "host_logic")
+
+
+def test_layout_logic_native(tmp_path):
+    """The layout sampling's rules (csrc/ysb_layout.h, no HIP): which instantiation a line, a
+    sample and two successive samples name."""
+    run_native(tmp_path, "layout_logic")
 
 
 def test_ad_shard_is_stable_and_balanced():

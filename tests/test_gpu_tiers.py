@@ -183,7 +183,7 @@ def _batch(lines):
 @pytest.mark.parametrize("device", [False, True])
 def test_learned_key_order_layout(variant, device):
     """Another key order (the generator's GEN_REORDER lines, also compact and with other
-    values): the batch's first line names the order (ysb_capi.cpp learn_layout) and the
+    values): the batch's first line names the order (ysb_layout.h learn_layout) and the
     scan runs the learned-order instantiation (layout 3) -- host batches from the pinned
     slot, device batches from a sampled first line -- exact vs the oracle, nothing
     deferred."""
