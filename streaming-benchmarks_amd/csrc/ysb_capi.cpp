@@ -23,16 +23,25 @@ int fail(ysb_ctx* c, int code, const char* fmt, ...) {
     return code;
 }
 
-int grow_device(ysb_ctx* c, void** buf, u64* have, u64 bytes, u64 floor_bytes) {
-    if (*have >= bytes) return YSB_OK;
+int grow_device(ysb_ctx* c, DevMem& buf, u64 bytes, u64 floor_bytes) {
+    if (buf.bytes() >= bytes) return YSB_OK;
     for (hipStream_t s : {c->s_comp, c->s_copy, c->s_split, c->s_x})   // nothing queued may still use the old one
         if (s) HIPCHK(c, hipStreamSynchronize(s));
-    hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    const u64 b = std::max(bytes, floor_bytes);
-    HIPCHK(c, hipMalloc(buf, b));
-    *have = b;
+    HIPCHK(c, buf.alloc(std::max(bytes, floor_bytes)));
+    return YSB_OK;
+}
+
+int first_use(ysb_ctx* c, DevMem& buf, u64 bytes) {
+    if (!buf.h) HIPCHK(c, buf.alloc(bytes));
+    return YSB_OK;
+}
+
+int regrow_table(ysb_ctx* c, DevBuf<unsigned long long>& t, u64 old_cells, u64 cells) {
+    DevBuf<unsigned long long> grown;
+    HIPCHK(c, grown.alloc(cells * 8));
+    HIPCHK(c, hipMemset(grown, 0, cells * 8));
+    if (old_cells) HIPCHK(c, hipMemcpy(grown, t, old_cells * 8, hipMemcpyDeviceToDevice));
+    t = std::move(grown);
     return YSB_OK;
 }
 
@@ -106,96 +115,77 @@ const char* ysb_last_error(const ysb_ctx* c) { return c ? c->err.c_str() : g_ope
 static void destroy(ysb_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
-    if (c->s_comp) hipStreamSynchronize(c->s_comp);
-    if (c->s_copy) hipStreamSynchronize(c->s_copy);
-    if (c->s_split) hipStreamSynchronize(c->s_split);
-    if (c->s_x) hipStreamSynchronize(c->s_x);
+    for (hipStream_t s : {c->s_comp, c->s_copy, c->s_split, c->s_x})
+        if (s) hipStreamSynchronize(s);
     if (c->comm) ncclCommDestroy(c->comm);
-    hipFree(c->d_table);
-    hipFree(c->d_ctable);
-    hipFree(c->d_counts);
-    hipFree(c->d_owned);
-    hipFree(c->d_owned8);
-    hipFree(c->d_rs_tmp);
-    hipFree(c->d_rows);
-    hipFree(c->d_rows_n);
-    hipFree(c->d_ring);
-    hipHostFree(c->h_ring);
-    hipFree(c->d_ovf);
-    hipFree(c->d_ovf_count);
-    hipFree(c->d_side);
-    hipFree(c->d_stats);
-    hipFree(c->d_truth);
-    hipFree(c->d_truth_out);
-    hipFree(c->d_cmp);
-    hipFree(c->d_subset);
-    hipFree(c->d_defer);
-    hipFree(c->d_defer_ctr);
-    hipFree(c->d_dbg);
-    hipFree(c->d_colinfo);
-    for (hipEvent_t e : c->ev_col)
-        if (e) hipEventDestroy(e);
-    for (int s = 0; s < 2; ++s) {
-        hipHostFree(c->h_bytes[s]);
-        hipHostFree(c->h_off[s]);
-        hipFree(c->d_bytes[s]);
-        hipFree(c->d_off[s]);
-        if (c->ev_h2d[s]) hipEventDestroy(c->ev_h2d[s]);
-        if (c->ev_kdone[s]) hipEventDestroy(c->ev_kdone[s]);
-    }
-    for (auto& p : c->tev.ev) for (hipEvent_t e : p) hipEventDestroy(e);
-    hipFree(c->d_rec);
-    hipFree(c->d_rec_n);
-    hipFree(c->d_delta);
-    hipFree(c->d_dirty);
-    hipFree(c->d_xmax);
-    hipHostFree(c->h_xmax);
-    for (hipEvent_t e : c->xplan_ev)
-        if (e) hipEventDestroy(e);
-    hipFree(c->d_xslots);
-    for (int k = 0; k < 2; ++k) {
-        hipFree(c->d_xsend[k]);
-        hipFree(c->d_xrecv[k]);
-        if (c->ev_xpacked[k]) hipEventDestroy(c->ev_xpacked[k]);
-        if (c->ev_xdone[k]) hipEventDestroy(c->ev_xdone[k]);
-    }
-    if (c->s_x) hipStreamDestroy(c->s_x);
-    for (auto& p : c->xev) for (hipEvent_t e : p) hipEventDestroy(e);
-    hipFree(c->d_part);
-    hipFree(c->d_runs);
-    if (c->ev_ring) hipEventDestroy(c->ev_ring);
-    hipHostFree(c->h_sample);
-    for (hipEvent_t e : c->ev_sample)
-        if (e) hipEventDestroy(e);
-    hipHostFree(c->h_used);
-    if (c->ev_used) hipEventDestroy(c->ev_used);
-    for (int s = 0; s < 2; ++s) {
-        hipFree(c->d_roff[s]);
-        if (c->ev_raw[s]) hipEventDestroy(c->ev_raw[s]);
-    }
-    hipFree(c->d_split_chunk);
-    hipHostFree(c->h_rawn);
-    for (auto& p : c->cev.ev) for (hipEvent_t e : p) hipEventDestroy(e);
-    hipFree(c->d_rebase);
     for (auto& r : c->host_ranges) hipHostUnregister(reinterpret_cast<void*>(r.first));
-    for (auto& f : c->fl) {
-        hipHostFree(f.h_rows);
-        hipHostFree(f.h_n);
-        if (f.ev) hipEventDestroy(f.ev);
-    }
-    hipFree(c->d_fl_n);
+    if (c->s_x) hipStreamDestroy(c->s_x);
     if (c->s_split) hipStreamDestroy(c->s_split);
     if (c->s_comp) hipStreamDestroy(c->s_comp);
     if (c->s_copy) hipStreamDestroy(c->s_copy);
-    delete c;
+    delete c;   // the members release themselves, the device still current
 }
 
-static int alloc_counts(ysb_ctx* c) {
-    const u64 cells = (u64)c->c_pad * c->cfg.window_ring;
-    hipFree(c->d_counts);
-    c->d_counts = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_counts, cells * 8));
-    HIPCHK(c, hipMemset(c->d_counts, 0, cells * 8));
+// A new context's streams, events and tables on its device; the error code (its text in c->err).
+static int init(ysb_ctx* c) {
+    const ysb_config& cfg = c->cfg;
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, YSB_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) c->cus = prop.multiProcessorCount;
+    // scan schedule overrides (timing experiments): YSB_DYN_PCT=0 -> all static
+    if (const char* e = getenv("YSB_DYN_PCT")) c->dyn_pct = (u32)strtoul(e, nullptr, 10);
+    if (const char* e = getenv("YSB_DELTA_FOLD_EVENTS")) {
+        const u64 v = strtoull(e, nullptr, 10);
+        if (v > 0 && v < c->delta_limit) c->delta_limit = v;
+    }
+    if (const char* e = getenv("YSB_DYN_CHUNK")) c->dyn_chunk = (u32)strtoul(e, nullptr, 10);
+    // the raw path's A/B knobs
+    if (const char* e = getenv("YSB_SPLIT_STREAM")) c->split_place = std::atoi(e);
+    if (const char* e = getenv("YSB_H2D_WG")) c->h2d_wg = std::max(1, std::atoi(e));
+    if (const char* e = getenv("YSB_H2D_PRIO")) c->h2d_prio = std::atoi(e) != 0;
+    if (const char* e = getenv("YSB_H2D_GRID")) c->h2d_grid = std::max(0, std::atoi(e));
+    if (hipStreamCreateWithFlags(&c->s_comp, hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking) != hipSuccess)
+        return fail(c, YSB_ERR_HIP, "stream creation failed");
+    for (Event* e : {&c->ev_h2d[0], &c->ev_kdone[0], &c->ev_h2d[1], &c->ev_kdone[1], &c->ev_ring, &c->ev_used})
+        if (e->create() != hipSuccess) return fail(c, YSB_ERR_HIP, "event creation failed");
+    if (c->h_used.alloc(16) != hipSuccess) return fail(c, YSB_ERR_HIP, "event creation failed");   // (the text this pinned word has always failed with)
+    const int rc = regrow_table(c, c->d_counts, 0, (u64)c->c_pad * cfg.window_ring);
+    if (rc) return rc;
+    // out-of-ring map: load <= 1/2 at overflow_capacity distinct cells
+    c->side_slots = 64;
+    while (c->side_slots < 2 * cfg.overflow_capacity) c->side_slots <<= 1;
+    c->side_cbits = 1;
+    while (c->side_cbits < 32 && (1ull << c->side_cbits) <= cfg.n_campaigns) ++c->side_cbits;   // bit_width
+    // stats and the map's slot count share one allocation: ysb_sync reads both in one copy
+    if (c->d_side.alloc(c->side_slots * sizeof(SideSlot)) != hipSuccess ||
+        c->d_stats.alloc((ST_COUNT_ + 1) * 8) != hipSuccess ||
+        hipMemset(c->d_stats, 0, (ST_COUNT_ + 1) * 8) != hipSuccess ||
+        c->d_dirty.alloc(16) != hipSuccess || hipMemset(c->d_dirty, 0, 16) != hipSuccess)
+        return fail(c, YSB_ERR_NOMEM, "device allocation failed");
+    c->d_side_used = reinterpret_cast<u32*>(c->d_stats + ST_COUNT_);
+    launch_side_clear(c->d_side, c->side_slots, c->s_comp);
+    if (hipStreamSynchronize(c->s_comp) != hipSuccess) return fail(c, YSB_ERR_HIP, "side map initialisation failed");
+    if (c->d_ring.alloc(16) != hipSuccess || c->h_ring.alloc(16) != hipSuccess ||
+        c->d_ovf.alloc(cfg.overflow_capacity * sizeof(OvfEntry)) != hipSuccess || c->d_ovf_count.alloc(16) != hipSuccess)
+        return fail(c, YSB_ERR_NOMEM, "device allocation failed");
+    i64 ring[2] = {0, 0};
+    if (cfg.ring_base_bucket != INT64_MIN) {
+        ring[0] = cfg.ring_base_bucket;
+        ring[1] = 1;
+        c->ring_known = true;
+        c->ring_lo = cfg.ring_base_bucket;
+    }
+    if (hipMemcpy(c->d_ring, ring, 16, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(c->d_ovf_count, 0, 16) != hipSuccess)
+        return fail(c, YSB_ERR_HIP, "initialisation copy failed");
+    // LDS window counters: WL = largest power of two with n_campaigns * WL <= LCNT_CAP
+    if (!(cfg.flags & YSB_F_NO_LDS_COUNT)) {
+        u32 wl = 0;
+        for (u32 w = 2; (u64)w * cfg.n_campaigns <= (u64)LCNT_CAP && w <= cfg.window_ring; w <<= 1) wl = w;
+        c->lds_wl = wl;
+        c->lds_wl_log2 = wl ? log2u(wl) : 0;
+    }
     return YSB_OK;
 }
 
@@ -223,85 +213,11 @@ int ysb_open(ysb_ctx** out, int device, const ysb_config* cfg_in) {
     c->cfg = cfg;
     c->c_pad = cfg.n_campaigns;
     c->div = div_magic(cfg.time_divisor_ms);
-    int rc = YSB_OK;
-    auto bad = [&](int code) { g_open_err = c->err; destroy(c); return code; };
-    if (hipSetDevice(device) != hipSuccess) { fail(c, YSB_ERR_HIP, "hipSetDevice(%d) failed", device); return bad(YSB_ERR_HIP); }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->cus = prop.multiProcessorCount;
-    // scan schedule overrides (timing experiments): YSB_DYN_PCT=0 -> all static
-    if (const char* e = getenv("YSB_DYN_PCT")) c->dyn_pct = (u32)strtoul(e, nullptr, 10);
-    if (const char* e = getenv("YSB_DELTA_FOLD_EVENTS")) {
-        const u64 v = strtoull(e, nullptr, 10);
-        if (v > 0 && v < c->delta_limit) c->delta_limit = v;
-    }
-    if (const char* e = getenv("YSB_DYN_CHUNK")) c->dyn_chunk = (u32)strtoul(e, nullptr, 10);
-    // the raw path's A/B knobs
-    if (const char* e = getenv("YSB_SPLIT_STREAM")) c->split_place = std::atoi(e);
-    if (const char* e = getenv("YSB_H2D_WG")) c->h2d_wg = std::max(1, std::atoi(e));
-    if (const char* e = getenv("YSB_H2D_PRIO")) c->h2d_prio = std::atoi(e) != 0;
-    if (const char* e = getenv("YSB_H2D_GRID")) c->h2d_grid = std::max(0, std::atoi(e));
-    if (hipStreamCreateWithFlags(&c->s_comp, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking) != hipSuccess) {
-        fail(c, YSB_ERR_HIP, "stream creation failed");
-        return bad(YSB_ERR_HIP);
-    }
-    for (int s = 0; s < 2; ++s) {
-        if (hipEventCreateWithFlags(&c->ev_h2d[s], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_kdone[s], hipEventDisableTiming) != hipSuccess) {
-            fail(c, YSB_ERR_HIP, "event creation failed");
-            return bad(YSB_ERR_HIP);
-        }
-    }
-    if (hipEventCreateWithFlags(&c->ev_ring, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_used, hipEventDisableTiming) != hipSuccess ||
-        hipHostMalloc(&c->h_used, 16) != hipSuccess) {
-        fail(c, YSB_ERR_HIP, "event creation failed");
-        return bad(YSB_ERR_HIP);
-    }
-    if ((rc = alloc_counts(c)) != YSB_OK) return bad(rc);
-    // out-of-ring map: load <= 1/2 at overflow_capacity distinct cells
-    c->side_slots = 64;
-    while (c->side_slots < 2 * cfg.overflow_capacity) c->side_slots <<= 1;
-    c->side_cbits = 1;
-    while (c->side_cbits < 32 && (1ull << c->side_cbits) <= cfg.n_campaigns) ++c->side_cbits;   // bit_width
-    // stats and the map's slot count share one allocation: ysb_sync reads both in one copy
-    if (hipMalloc(&c->d_side, c->side_slots * sizeof(SideSlot)) != hipSuccess ||
-        hipMalloc(&c->d_stats, (ST_COUNT_ + 1) * 8) != hipSuccess ||
-        hipMemset(c->d_stats, 0, (ST_COUNT_ + 1) * 8) != hipSuccess ||
-        hipMalloc(&c->d_dirty, 16) != hipSuccess || hipMemset(c->d_dirty, 0, 16) != hipSuccess) {
-        fail(c, YSB_ERR_NOMEM, "device allocation failed");
-        return bad(YSB_ERR_NOMEM);
-    }
-    c->d_side_used = reinterpret_cast<u32*>(c->d_stats + ST_COUNT_);
-    launch_side_clear(c->d_side, c->side_slots, c->s_comp);
-    if (hipStreamSynchronize(c->s_comp) != hipSuccess) {
-        fail(c, YSB_ERR_HIP, "side map initialisation failed");
-        return bad(YSB_ERR_HIP);
-    }
-    if (hipMalloc(&c->d_ring, 16) != hipSuccess || hipHostMalloc(&c->h_ring, 16) != hipSuccess ||
-        hipMalloc(&c->d_ovf, cfg.overflow_capacity * sizeof(OvfEntry)) != hipSuccess ||
-        hipMalloc(&c->d_ovf_count, 16) != hipSuccess) {
-        fail(c, YSB_ERR_NOMEM, "device allocation failed");
-        return bad(YSB_ERR_NOMEM);
-    }
-    i64 ring[2] = {0, 0};
-    if (cfg.ring_base_bucket != INT64_MIN) {
-        ring[0] = cfg.ring_base_bucket;
-        ring[1] = 1;
-        c->ring_known = true;
-        c->ring_lo = cfg.ring_base_bucket;
-    }
-    if (hipMemcpy(c->d_ring, ring, 16, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(c->d_ovf_count, 0, 16) != hipSuccess) {
-        fail(c, YSB_ERR_HIP, "initialisation copy failed");
-        return bad(YSB_ERR_HIP);
-    }
-    // LDS window counters: WL = largest power of two with n_campaigns * WL <= LCNT_CAP
-    if (!(cfg.flags & YSB_F_NO_LDS_COUNT)) {
-        u32 wl = 0;
-        for (u32 w = 2; (u64)w * cfg.n_campaigns <= (u64)LCNT_CAP && w <= cfg.window_ring; w <<= 1) wl = w;
-        c->lds_wl = wl;
-        c->lds_wl_log2 = wl ? log2u(wl) : 0;
+    const int rc = init(c);
+    if (rc) {
+        g_open_err = c->err;
+        destroy(c);
+        return rc;
     }
     *out = c;
     return YSB_OK;
@@ -354,7 +270,7 @@ int ysb_load_ad_map_shard(ysb_ctx* c, const char* const* ad_ids, const uint32_t*
         std::vector<u32> l, cm;
         for (u64 i = 0; i < n; ++i) {
             const u32 len = lens ? lens[i] : 36u;
-            if (ad_ids[i] && ysb_ad_shard(ad_ids[i], len, nranks) != rank) continue;
+            if (ad_ids[i] && ad_shard(ad_ids[i], len, nranks) != rank) continue;
             p.push_back(ad_ids[i]);
             l.push_back(len);
             cm.push_back(campaign_idx[i]);
@@ -367,152 +283,39 @@ int ysb_load_ad_map_shard(ysb_ctx* c, const char* const* ad_ids, const uint32_t*
     return YSB_OK;
 }
 
+// Build (ysb_admap.h: host data only), upload, commit.  A table whose size changes gets its
+// new buffer before the old one is released (peak device memory during such a reload: the old
+// tables plus the new ones), and the context takes nothing before both copies are done: a
+// failed allocation leaves the old map whole and in use.  Only a failed copy into a buffer
+// that is reused (same size) has damaged the map in use: submits then fail as before a load.
 static int load_map(ysb_ctx* c, const char* const* ad_ids, const uint32_t* lens, const uint32_t* campaign_idx,
                     uint64_t n) {
     // the tables live on this context's GPU, whichever device the calling thread last set
     // (one process may drive several contexts, e.g. one per GPU of a node)
     HIPCHK(c, hipSetDevice(c->device));
-    u64 slots = 64;
-    while (slots < 2 * n) slots <<= 1;   // load factor <= 0.5
-    if (slots > (1ull << 31)) return fail(c, YSB_ERR_CAPACITY, "ad map too large (%llu)", (unsigned long long)n);
-    std::vector<u32> tab(slots * SLOT_WORDS, 0);
-    for (u64 s = 0; s < slots; ++s) tab[s * SLOT_WORDS + 1] = EMPTY_SLOT;
-    const u32 mask = (u32)(slots - 1);
-    for (u64 i = 0; i < n; ++i) {
-        const u32 len = lens ? lens[i] : 36u;
-        if (len > MAX_KEY_BYTES) return fail(c, YSB_ERR_FORMAT, "ad id %llu longer than %u bytes", (unsigned long long)i, MAX_KEY_BYTES);
-        if (campaign_idx[i] >= c->cfg.n_campaigns)
-            return fail(c, YSB_ERR_FORMAT, "campaign index %u >= n_campaigns %u", campaign_idx[i], c->cfg.n_campaigns);
-        if (!ad_ids[i] && len) return fail(c, YSB_ERR_ARG, "ad id %llu is NULL", (unsigned long long)i);
-        u32 kw[KEY_WORDS] = {0};
-        if (len) std::memcpy(kw, ad_ids[i], len);
-        const u32 h = key_hash(kw, len);
-        for (u64 pr = 0;; ++pr) {
-            u32* sl = &tab[(u64)((h + pr) & mask) * SLOT_WORDS];
-            if (sl[1] == EMPTY_SLOT) {
-                sl[0] = len;
-                sl[1] = campaign_idx[i];
-                std::memcpy(sl + 2, kw, sizeof kw);
-                break;
-            }
-            if (sl[0] == len && std::memcmp(sl + 2, kw, sizeof kw) == 0) {   // HashMap.put: later wins
-                sl[1] = campaign_idx[i];
-                break;
-            }
-        }
-    }
-    HIPCHK(c, hipSetDevice(c->device));
+    JoinTables jt;
+    std::string err;
+    const int rc = build_join_tables(ad_ids, lens, campaign_idx, n, c->cfg.n_campaigns,
+                                     (c->cfg.flags & YSB_F_SPARSE_FAST_JOIN) != 0, &jt, &err);
+    if (rc) return fail(c, rc, "%s", err.c_str());
     HIPCHK(c, hipStreamSynchronize(c->s_comp));
-    if (slots != c->table_slots) {
-        hipFree(c->d_table);
-        c->d_table = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_table, tab.size() * 4));
-        c->table_slots = slots;
+    const u64 tbytes = jt.table.size() * 4, cbytes = jt.ctable.size() * 4;
+    DevBuf<u32> table, ctable;   // the new buffers of the tables that change size
+    if (tbytes != c->d_table.bytes()) HIPCHK(c, table.alloc(tbytes));
+    if (cbytes != c->d_ctable.bytes()) HIPCHK(c, ctable.alloc(cbytes));
+    hipError_t e = hipMemcpy(table.h ? table : c->d_table, jt.table.data(), tbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ctable.h ? ctable : c->d_ctable, jt.ctable.data(), cbytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (!table.h || !ctable.h) c->table_loaded = false;   // a buffer of the map in use may be half written
+        return fail(c, YSB_ERR_HIP, "ad map upload: %s", hipGetErrorString(e));
     }
-    HIPCHK(c, hipMemcpy(c->d_table, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-    // every 36-byte key also goes into the two-choice cuckoo table (load <= 1/4)
-    typedef std::array<u32, CKEY_WORDS> Key36;
-    // the distinct 36-byte keys with their final (later-wins) campaign: the general
-    // table already holds exactly that set
-    std::vector<std::pair<Key36, u32>> keys36;
-    for (u64 sl = 0; sl < slots; ++sl) {
-        const u32* e = &tab[sl * SLOT_WORDS];
-        if (e[1] == EMPTY_SLOT || e[0] != 36) continue;
-        Key36 k;
-        std::memcpy(k.data(), e + 2, 36);
-        keys36.push_back({k, e[1]});
-    }
-    bool partial = false;
-    if (c->cfg.flags & YSB_F_SPARSE_FAST_JOIN) {
-        for (size_t i = 0; 2 * i + 1 < keys36.size(); ++i) keys36[i] = keys36[2 * i + 1];
-        keys36.resize(keys36.size() / 2);
-        partial = true;
-    }
-    u64 cslots = 64;
-    while (cslots < 4 * keys36.size()) cslots <<= 1;
-    // tables far beyond the L2s (32 MiB) go to HBM per probe: bucket layout
-    const bool buckets = cslots * CSLOT_WORDS * 4 > (64ull << 20);
-    if (buckets) {
-        // buckets >= YSB_BUCKETS_X4 / 4 per key (3 entries each)
-        cslots = 64;
-        while (cslots * 4 < (u64)YSB_BUCKETS_X4 * keys36.size()) cslots <<= 1;
-    }
-    const u32 unit = buckets ? CB_WORDS : CSLOT_WORDS;
-    std::vector<u32> kw, cv;   // bucket layout: the keys as words, their campaigns
-    if (buckets) {
-        kw.resize(keys36.size() * CKEY_WORDS);
-        cv.resize(keys36.size());
-        for (size_t i = 0; i < keys36.size(); ++i) {
-            std::memcpy(&kw[i * CKEY_WORDS], keys36[i].first.data(), 36);
-            cv[i] = keys36[i].second;
-        }
-    }
-    std::vector<u32> ct;
-    CuckooSeed cs{};
-    u64 seed = 0x5EEDC0FFEEULL;
-    for (int attempt = 0;; ++attempt) {
-        if (attempt == 16) { cslots <<= 1; attempt = 0; }
-        if (cslots > (1ull << 26)) {
-            // No placement found (a key family the hash cannot separate): keep the
-            // table without the keys that did not fit; the scan defers its misses to
-            // the general path, so the join stays exact.
-            cslots = 1ull << 26;
-            partial = true;
-        }
-        seed = mix64(seed + (u64)attempt + cslots);
-        cs = cuckoo_seed(seed);
-        ct.assign(cslots * unit, 0);
-        const u32 cm = (u32)(cslots - 1);
-        bool ok = true;
-        if (buckets) {
-            const u64 homeless = cuckoo_build_buckets(kw.data(), cv.data(), keys36.size(), cs, cslots, seed, partial,
-                                                      ct.data());
-            ok = homeless == 0;
-            if (ok || partial) break;
-            continue;
-        }
-        for (u64 s = 0; s < cslots; ++s) ct[s * CSLOT_WORDS + CSLOT_CAMP] = EMPTY_SLOT;
-        for (const auto& kv : keys36) {
-            Key36 k = kv.first;
-            u32 camp = kv.second;
-            u32 a, b;
-            cuckoo_slots36(k.data(), cs, cm, &a, &b);
-            u32 pos = a;
-            int kicks = 0;
-            while (true) {
-                u32* sl = &ct[(u64)pos * CSLOT_WORDS];
-                if (sl[CSLOT_CAMP] == EMPTY_SLOT) {
-                    std::memcpy(sl, k.data(), 36);
-                    sl[CSLOT_CAMP] = camp;
-                    break;
-                }
-                // evict the occupant to its other slot
-                Key36 ok_;
-                std::memcpy(ok_.data(), sl, 36);
-                const u32 oc = sl[CSLOT_CAMP];
-                std::memcpy(sl, k.data(), 36);
-                sl[CSLOT_CAMP] = camp;
-                k = ok_;
-                camp = oc;
-                u32 oa, ob;
-                cuckoo_slots36(k.data(), cs, cm, &oa, &ob);
-                pos = (pos == oa) ? ob : oa;
-                if (++kicks > 500) { ok = false; break; }
-            }
-            if (!ok && !partial) break;   // partial: the homeless key is simply left out
-        }
-        if (ok || partial) break;
-    }
-    if (cslots != c->ctable_slots) {
-        hipFree(c->d_ctable);
-        c->d_ctable = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_ctable, ct.size() * 4));
-        c->ctable_slots = cslots;
-    }
-    HIPCHK(c, hipMemcpy(c->d_ctable, ct.data(), ct.size() * 4, hipMemcpyHostToDevice));
-    c->cseed = cs;
-    c->ctable_buckets = buckets;
-    c->ctable_partial = partial;
+    if (table.h) c->d_table = std::move(table);
+    if (ctable.h) c->d_ctable = std::move(ctable);
+    c->table_slots = jt.slots;
+    c->ctable_slots = jt.cslots;
+    c->cseed = jt.cseed;
+    c->ctable_buckets = jt.buckets;
+    c->ctable_partial = jt.partial;
     c->table_loaded = true;
     return YSB_OK;
 }
@@ -608,14 +411,14 @@ int pull_side_list(ysb_ctx* c) {
     u32 used = 0;
     HIPCHK(c, hipMemcpy(&used, c->d_side_used, 4, hipMemcpyDeviceToHost));
     if (used) {
-        if (!c->d_rows_n) HIPCHK(c, hipMalloc(&c->d_rows_n, 8));
+        int rc = first_use(c, c->d_rows_n, 8);
+        if (rc) return rc;
         u32 k = 0;
         HIPCHK(c, hipMemsetAsync(c->d_rows_n, 0, 4, c->s_comp));
         launch_side_compact(c->d_side, c->side_slots, c->side_cbits, true, nullptr, c->d_rows_n, 0, c->s_comp);
         HIPCHK(c, hipMemcpyAsync(&k, c->d_rows_n, 4, hipMemcpyDeviceToHost, c->s_comp));
         HIPCHK(c, hipStreamSynchronize(c->s_comp));
-        const int rc = grow_device(c, &c->d_rows, &c->rows_bytes, k * sizeof(TableRow), 4096 * sizeof(TableRow));
-        if (rc) return rc;
+        if ((rc = grow_device(c, c->d_rows, k * sizeof(TableRow), 4096 * sizeof(TableRow)))) return rc;
         if (k) {
             std::vector<TableRow> h(k);
             HIPCHK(c, hipMemsetAsync(c->d_rows_n, 0, 4, c->s_comp));
@@ -651,7 +454,7 @@ static int ring_rows(ysb_ctx* c, i64 blo, i64 bhi, bool clear, std::map<std::pai
         ysb_group_block(c->cfg.n_campaigns, c->rank, c->nranks, &olo, &ohi);
         if (ohi > olo) tabs.push_back({c->d_owned, ohi - olo, olo});
     }
-    if (!c->d_rows_n) HIPCHK(c, hipMalloc(&c->d_rows_n, 8));
+    if ((frc = first_use(c, c->d_rows_n, 8))) return frc;
     for (const Tab& t : tabs) {
         u32 n = 0;
         HIPCHK(c, hipMemsetAsync(c->d_rows_n, 0, 4, c->s_comp));
@@ -659,7 +462,7 @@ static int ring_rows(ysb_ctx* c, i64 blo, i64 bhi, bool clear, std::map<std::pai
         HIPCHK(c, hipMemcpyAsync(&n, c->d_rows_n, 4, hipMemcpyDeviceToHost, c->s_comp));
         HIPCHK(c, hipStreamSynchronize(c->s_comp));
         if (!n) continue;
-        if ((frc = grow_device(c, &c->d_rows, &c->rows_bytes, n * sizeof(TableRow), 4096 * sizeof(TableRow)))) return frc;
+        if ((frc = grow_device(c, c->d_rows, n * sizeof(TableRow), 4096 * sizeof(TableRow)))) return frc;
         std::vector<TableRow> h(n);
         u32 m = 0;
         HIPCHK(c, hipMemsetAsync(c->d_rows_n, 0, 4, c->s_comp));
@@ -689,15 +492,15 @@ int ysb_flush_begin(ysb_ctx* c, int64_t blo, int64_t bhi) {
     const int k = (c->fl_head + c->fl_n) % ysb_ctx::FLUSH_SLOTS;
     auto& f = c->fl[k];
     if (!c->d_fl_n) {
-        HIPCHK(c, hipMalloc(&c->d_fl_n, 4 * ysb_ctx::FLUSH_SLOTS));
+        HIPCHK(c, c->d_fl_n.alloc(4 * ysb_ctx::FLUSH_SLOTS));
         HIPCHK(c, hipMemset(c->d_fl_n, 0, 4 * ysb_ctx::FLUSH_SLOTS));
     }
     if (!f.h_rows) {   // every nonzero cell of the ring fits (up to FLUSH_MAX_ROWS)
         f.cap = std::min<u64>((u64)c->cfg.n_campaigns * W, FLUSH_MAX_ROWS);
-        HIPCHK(c, hipHostMalloc(&f.h_rows, f.cap * sizeof(TableRow)));
+        HIPCHK(c, f.h_rows.alloc(f.cap * sizeof(TableRow)));
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&f.hd_rows), f.h_rows, 0));
-        HIPCHK(c, hipHostMalloc(&f.h_n, 16));
-        HIPCHK(c, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
+        HIPCHK(c, f.h_n.alloc(16));
+        HIPCHK(c, f.ev.create());
     }
     // the ring's base: known once the first launch's auto-base is back (a copy of 16 bytes)
     poll_ring(c);
@@ -738,7 +541,7 @@ int ysb_flush_end(ysb_ctx* c, int wait, ysb_count* out, uint64_t cap, uint64_t* 
     if (!out) return YSB_OK;   // (the rows stay: call again with a buffer)
     if (cap < n) return fail(c, YSB_ERR_CAPACITY, "flush needs %llu rows, cap %llu", (unsigned long long)n,
                              (unsigned long long)cap);
-    std::vector<TableRow> rows(f.h_rows, f.h_rows + n);
+    std::vector<TableRow> rows(f.h_rows.get(), f.h_rows.get() + n);
     std::sort(rows.begin(), rows.end(), [](const TableRow& x, const TableRow& y) {
         return x.campaign != y.campaign ? x.campaign < y.campaign : x.bucket < y.bucket;
     });
@@ -958,7 +761,7 @@ int ysb_debug_defer_list(ysb_ctx* c, uint32_t* out, uint64_t cap) {
     int rc = ysb_sync(c);
     if (rc) return rc;
     if (!c->d_defer) return YSB_OK;
-    HIPCHK(c, hipMemcpy(out, c->d_defer, std::min<u64>(cap * 4, c->defer_bytes), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->d_defer, std::min<u64>(cap * 4, c->d_defer.bytes()), hipMemcpyDeviceToHost));
     return YSB_OK;
 }
 

@@ -49,8 +49,8 @@ int ysb_decode_columns_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
     const int prc = launch_pending_raw(c);   // behind everything submitted
     if (prc) return prc;
     if (!c->d_colinfo) {
-        HIPCHK(c, hipMalloc(&c->d_colinfo, 2 * sizeof(unsigned long long)));
-        for (hipEvent_t& e : c->ev_col) HIPCHK(c, hipEventCreate(&e));
+        for (Event& e : c->ev_col) HIPCHK(c, e.create(hipEventDefault));
+        HIPCHK(c, c->d_colinfo.alloc(2 * sizeof(unsigned long long)));   // (last: it marks the events present)
     }
     ColParams p{};
     p.bytes = d_bytes;

@@ -3,6 +3,7 @@
 //   ysb_capi.cpp    context lifecycle, the ad -> campaign tables, sync / drain / ring / stats
 //   ysb_submit.cpp  batches: slots, raw lines, device batches, the layout samples, the launches
 //   ysb_layout.h    the layout sampling's rules (no HIP: tests/native/layout_logic.cpp)
+//   ysb_admap.h     the join tables as host data (no HIP: tests/native/admap_logic.cpp)
 //   ysb_group.cpp   multi-GPU: the RCCL / host-collective group and the keyBy exchange
 //   ysb_gen_api.cpp the synthetic generator (host and device) and its truth tables
 // Internal: nothing here is part of the ABI (the shared helpers have hidden visibility).
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "../../include/ysb_hip.h"
+#include "ysb_admap.h"
 #include "ysb_kernels.h"
 #include "ysb_layout.h"
 
@@ -38,11 +40,42 @@ constexpr size_t XEV_KEEP = 64;   // exchange timing pairs pending before they a
 // running totals (a streaming caller may never call ysb_kernel_time / ysb_copy_time)
 constexpr size_t TIMING_KEEP = 256;
 
-// HBM-resident join table (bucket layout): buckets per key, x4 (8: 2 per key, a 4 GiB
-// table at 10M ads; fewer buckets -> a smaller table, more keys in their second bucket)
-#ifndef YSB_BUCKETS_X4
-#define YSB_BUCKETS_X4 8
-#endif
+// One owner per GPU resource: move-only, released when the owner goes (the context's members
+// in ysb_close, with its device current) or takes another, and converting to the raw handle
+// that the kernels' parameter structs and the launch functions take.
+template <class H, hipError_t (*Free)(H)>
+struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned& operator=(Owned&& o) noexcept {
+        if (this != &o) { reset(); h = o.h; o.h = nullptr; }
+        return *this;
+    }
+    ~Owned() { reset(); }
+    void reset() { if (h) Free(h); h = nullptr; }
+};
+struct DevMem : Owned<void*, hipFree> {   // device memory (alloc releases what it held first)
+    u64 n = 0;
+    hipError_t alloc(u64 bytes) { reset(); n = bytes; return hipMalloc(&h, bytes); }
+    u64 bytes() const { return h ? n : 0; }
+};
+template <class T>
+struct DevBuf : DevMem {
+    T* get() const { return static_cast<T*>(h); }
+    operator T*() const { return get(); }
+};
+template <class T>
+struct PinBuf : Owned<void*, hipHostFree> {   // pinned host memory
+    hipError_t alloc(u64 bytes) { reset(); return hipHostMalloc(&h, bytes); }
+    T* get() const { return static_cast<T*>(h); }
+    operator T*() const { return get(); }
+};
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+    hipError_t create(unsigned flags = hipEventDisableTiming) { reset(); return hipEventCreateWithFlags(&h, flags); }
+    hipEvent_t get() const { return h; }
+    operator hipEvent_t() const { return h; }
+};
 
 // YSB_F_TIMING's event log: N events per entry (a launch, a slot copy), kept until a getter
 // collects them.  total[k] sums elapsed(ev[0], ev[k]) over the entries taken in so far, k =
@@ -52,7 +85,7 @@ constexpr size_t TIMING_KEEP = 256;
 // events are reused.
 template <int N>
 struct EventLog {
-    std::vector<std::array<hipEvent_t, N>> ev;
+    std::vector<std::array<Event, N>> ev;
     size_t used = 0;
     u64 folded = 0;
     double total[N] = {};
@@ -72,12 +105,12 @@ struct EventLog {
         return hipSuccess;
     }
     // the next entry's events (created on demand)
-    hipError_t acquire(hipEvent_t** out) {
+    hipError_t acquire(Event** out) {
         hipError_t e = used == TIMING_KEEP ? fold(TIMING_KEEP / 2, true) : hipSuccess;
         if (e == hipSuccess && used == ev.size()) {
-            std::array<hipEvent_t, N> a{};
-            for (int k = 0; k < N && e == hipSuccess; ++k) e = hipEventCreate(&a[k]);
-            if (e == hipSuccess) ev.push_back(a);
+            std::array<Event, N> a;
+            for (int k = 0; k < N && e == hipSuccess; ++k) e = a[k].create(hipEventDefault);
+            if (e == hipSuccess) ev.push_back(std::move(a));
         }
         if (e == hipSuccess) *out = ev[used++].data();
         return e;
@@ -101,35 +134,34 @@ struct ysb_ctx {
     int cus = 256;
     hipStream_t s_comp = nullptr, s_copy = nullptr;
     // ad table
-    u32* d_table = nullptr;
+    DevBuf<u32> d_table;
     u64 table_slots = 0;
-    u32* d_ctable = nullptr;   // 36-byte-key cuckoo table
+    DevBuf<u32> d_ctable;      // 36-byte-key cuckoo table
     u64 ctable_slots = 0;      // slots, or buckets when ctable_buckets
     bool ctable_buckets = false; // HBM-resident table: 3-entry 128-B buckets (CB_*), serial probes
     ysb_launch_desc last_launch{};   // the instantiation of the last launch
     // device batches' first-line samples: written by sample_kernel on the compute stream (so
     // after whatever produced the batch there) into pinned memory, two buffers alternating
     // by launch; ev_sample[k] marks buffer k complete, sample_nseg[k] its segments (0: none)
-    u8* h_sample = nullptr;
-    hipEvent_t ev_sample[2] = {nullptr, nullptr};
+    PinBuf<u8> h_sample;
+    Event ev_sample[2];
     u32 sample_nseg[2] = {0, 0};
     int sample_cur = 0;
     // the layout decided from buffer k's sample (-1: not decided yet) and its key order
     int sample_dec[2] = {-1, -1};
     LearnDesc sample_learn[2]{};
-    u32* h_used = nullptr;       // pinned: the out-of-ring map's fill level after a launch ...
-    hipEvent_t ev_used = nullptr; // ... readable once this has completed
+    PinBuf<u32> h_used;          // pinned: the out-of-ring map's fill level after a launch ...
+    Event ev_used;                // ... readable once this has completed
     bool used_pending = false;
     // raw batches (ysb_submit_raw): the line starts are found on the GPU (ysb_split.hip) on
     // s_split after the slot's H2D, into d_roff[slot]; the scan is launched once the line
     // count is back (launch_pending_raw, at the next call), so the next H2D queues first
     hipStream_t s_split = nullptr;
-    u32* d_roff[2] = {nullptr, nullptr};        // raw_lines_cap starts per slot
+    DevBuf<u32> d_roff[2];                      // raw_lines_cap starts per slot
     u64 raw_lines_cap = 0;                      // lines a raw batch may hold (raw_line_cap)
-    u32* d_split_chunk = nullptr;               // per-chunk counts, then bases
-    u64 split_chunk_bytes = 0;
-    unsigned long long* h_rawn = nullptr;       // pinned: [2] lines of the slot's raw batch
-    hipEvent_t ev_raw[2] = {nullptr, nullptr};  // split done and its count read back
+    DevBuf<u32> d_split_chunk;                  // per-chunk counts, then bases
+    PinBuf<unsigned long long> h_rawn;          // pinned: [2] lines of the slot's raw batch
+    Event ev_raw[2];                            // split done and its count read back
     int raw_pend = -1;                          // the slot whose raw batch awaits its launch
     int raw_fail = 0;                           // a raw batch that could not launch: sticky until ysb_reset
     std::string raw_fail_msg;
@@ -147,7 +179,7 @@ struct ysb_ctx {
     };
     std::map<uintptr_t, HostRange> host_ranges;
     // the replay's rebase table (ysb_rebase_table) and each slot's pending rebase
-    u32* d_rebase = nullptr;
+    DevBuf<u32> d_rebase;
     u64 rebase_n = 0;
     i64 rebase_base = 0;
     u32 rebase_kmax = 0;                        // the largest bucket index in it
@@ -164,60 +196,51 @@ struct ysb_ctx {
     u32 shard_rank = 0, shard_n = 1;      // the join table's shard (ysb_load_ad_map_shard)
     // counts
     u32 c_pad = 0;                        // campaigns padded to the group size
-    unsigned long long* d_counts = nullptr;   // [c_pad][W]
-    unsigned long long* d_owned = nullptr;    // [c_pad / nranks][W] after reduce-scatter
-    u8* d_owned8 = nullptr;                   // ... its saturating u8 accumulator (xunpack), folded before reads
+    DevBuf<unsigned long long> d_counts;      // [c_pad][W]
+    DevBuf<unsigned long long> d_owned;       // [c_pad / nranks][W] after reduce-scatter
+    DevBuf<u8> d_owned8;                      // ... its saturating u8 accumulator (xunpack), folded before reads
     bool owned8_dirty = false;
-    unsigned long long* d_rs_tmp = nullptr;
     bool ring_agreed = false;                 // ranks' ring bases checked equal
-    TableRow* d_rows = nullptr;               // drain compaction output
-    u64 rows_bytes = 0;
-    u32* d_rows_n = nullptr;
-    i64* d_ring = nullptr;                // [lo, set]
-    i64* h_ring = nullptr;                // pinned mirror
-    hipEvent_t ev_ring = nullptr;
+    DevBuf<TableRow> d_rows;                  // drain compaction output
+    DevBuf<u32> d_rows_n;
+    DevBuf<i64> d_ring;                   // [lo, set]
+    PinBuf<i64> h_ring;                   // pinned mirror
+    Event ev_ring;
     bool ring_query_pending = false;
     bool ring_known = false;
     i64 ring_lo = 0;
-    OvfEntry* d_ovf = nullptr;
-    u32* d_ovf_count = nullptr;
-    SideSlot* d_side = nullptr;               // out-of-ring cells (device hash map)
+    DevBuf<OvfEntry> d_ovf;
+    DevBuf<u32> d_ovf_count;
+    DevBuf<SideSlot> d_side;                  // out-of-ring cells (device hash map)
     u64 side_slots = 0;
     u32 side_cbits = 1;
     u32* d_side_used = nullptr;               // = (u32*)(d_stats + ST_COUNT_)
-    unsigned long long* d_stats = nullptr;    // ST_COUNT_ u64, then the map's slot count
+    DevBuf<unsigned long long> d_stats;       // ST_COUNT_ u64, then the map's slot count
     u64 batches = 0;
     std::map<std::pair<u32, i64>, u64> side;   // drained side-list deltas
     DivMagic div{};
     u32 lds_wl = 0, lds_wl_log2 = 0;
     // slots
-    u8* h_bytes[2] = {nullptr, nullptr};
-    u32* h_off[2] = {nullptr, nullptr};
+    PinBuf<u8> h_bytes[2];
+    PinBuf<u32> h_off[2];
     u8* hd_bytes[2] = {nullptr, nullptr};      // the pinned slots' device-visible addresses (the CU copy)
     u32* hd_off[2] = {nullptr, nullptr};
-    u8* d_bytes[2] = {nullptr, nullptr};
-    u32* d_off[2] = {nullptr, nullptr};
-    hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_kdone[2] = {nullptr, nullptr};
+    DevBuf<u8> d_bytes[2];
+    DevBuf<u32> d_off[2];
+    Event ev_h2d[2], ev_kdone[2];
     // timing: per launch {before scan, after scan, after the last kernel of the launch}
     // (total[1]: the scan kernels' time, total[2]: the launch's whole path)
     EventLog<3> tev;
     double path_ms_acc = 0;                // ysb_path_time's share, collected by ysb_kernel_time
     u64 path_launches_acc = 0;
     // record mode (ysb_count.hip)
-    u32* d_rec = nullptr;
-    u64 rec_bytes = 0;
-    u32* d_rec_n = nullptr;
-    u64 rec_n_bytes = 0;
-    u32* d_part = nullptr;
-    u64 part_bytes = 0;
-    u32* d_runs = nullptr;
-    u64 runs_bytes = 0;
+    DevBuf<u32> d_rec, d_rec_n, d_part, d_runs;
     u64 rec_launches = 0;
     // record mode counts into a saturating u8 delta ring with the u64 ring's layout (a cell
     // passing 255 goes to the u64 ring, ysb_count.hip add16); fold_delta adds it to the u64
     // ring before anything reads that.  delta_bound: events counted into it since the last
     // fold; YSB_DELTA_FOLD_EVENTS (test hook) folds before a launch once it would pass that
-    u8* d_delta = nullptr;
+    DevBuf<u8> d_delta;
     u64 delta_cells = 0;
     u64 delta_bound = 0;
     u64 delta_limit = ~0ull;
@@ -225,7 +248,7 @@ struct ysb_ctx {
     // record mode ran or a fold moved the delta there (pend_u64), or a record-mode path
     // wrote it (*d_dirty, set on the device)
     bool pend_u64 = true;
-    u32* d_dirty = nullptr;
+    DevBuf<u32> d_dirty;
     // group: an RCCL communicator, or the caller's host collectives (ysb_group_init_host)
     ncclComm_t comm = nullptr;
     bool host_coll = false;
@@ -236,9 +259,9 @@ struct ysb_ctx {
     // Two plan buffers (device maxima; pinned host maxima + slots): a pipelined exchange
     // packs with the previous call's plan (buffer xb, ready at xplan_ev[xb]) while its own
     // plan is reduced into the other one.
-    unsigned long long* d_xmax = nullptr;   // [2][W]
-    unsigned long long* h_xmax = nullptr;   // [2][W] maxima, then [2][W] u32 slots
-    hipEvent_t xplan_ev[2] = {nullptr, nullptr};
+    DevBuf<unsigned long long> d_xmax;      // [2][W]
+    PinBuf<unsigned long long> h_xmax;      // [2][W] maxima, then [2][W] u32 slots
+    Event xplan_ev[2];
     int xb = 0;
     bool x_have_plan = false;
     // plan -> pack run on the compute stream (in order with the scans that add to the rings);
@@ -249,11 +272,9 @@ struct ysb_ctx {
     // reduce-scatter that last used it (ev_xdone[k]), the exchange stream for the pack
     // (ev_xpacked[k]).
     hipStream_t s_x = nullptr;
-    u32* d_xslots = nullptr;                // [2][W]
-    void* d_xsend[2] = {nullptr, nullptr};
-    void* d_xrecv[2] = {nullptr, nullptr};
-    u64 xsend_bytes[2] = {0, 0}, xrecv_bytes[2] = {0, 0};
-    hipEvent_t ev_xpacked[2] = {nullptr, nullptr}, ev_xdone[2] = {nullptr, nullptr};
+    DevBuf<u32> d_xslots;                   // [2][W]
+    DevBuf<void> d_xsend[2], d_xrecv[2];
+    Event ev_xpacked[2], ev_xdone[2];
     bool xset_used[2] = {false, false};
     int xk = 0;
     // the pipelined exchange whose unpack is still to run: its set, slots, width, timing entry
@@ -265,52 +286,51 @@ struct ysb_ctx {
     double x_ms = 0, x_crit_ms = 0, x_rs_ms = 0, x_exposed_ms = 0;
     // per exchange {start, packed (compute stream), reduce-scatter done (exchange stream),
     // unpack start, unpack end (compute stream)}
-    std::vector<std::array<hipEvent_t, 6>> xev;
+    std::vector<std::array<Event, 6>> xev;
     size_t xev_used = 0;
     // asynchronous flushes (ysb_flush_begin / ysb_flush_end): a ring of FLUSH_SLOTS pinned row
     // buffers the compaction kernel writes straight into, each with its device-side count
     // copied back and an event; fl_head the oldest outstanding, fl_n how many
     struct FlushSlot {
-        TableRow* h_rows = nullptr;   // pinned (device-visible: written by the kernel)
+        PinBuf<TableRow> h_rows;      // pinned (device-visible: written by the kernel)
         TableRow* hd_rows = nullptr;  // ... its device address
-        u32* h_n = nullptr;           // pinned: the rows the kernel wrote
+        PinBuf<u32> h_n;              // pinned: the rows the kernel wrote
         u64 cap = 0;
-        hipEvent_t ev = nullptr;
+        Event ev;
     };
     static constexpr int FLUSH_SLOTS = 4;
     FlushSlot fl[FLUSH_SLOTS];
     int fl_head = 0, fl_n = 0;
-    u32* d_fl_n = nullptr;                 // [FLUSH_SLOTS] device counters
+    DevBuf<u32> d_fl_n;                    // [FLUSH_SLOTS] device counters
     // truth
-    unsigned long long* d_truth = nullptr;
-    unsigned long long* d_truth_out = nullptr;
-    unsigned long long* d_cmp = nullptr;
-    u32* d_subset = nullptr;
+    DevBuf<unsigned long long> d_truth, d_truth_out, d_cmp;
+    DevBuf<u32> d_subset;
     u32 d_subset_n = 0;
-    u32* d_defer = nullptr;                // deferred (general-path) line indices
-    u64 defer_bytes = 0;
-    u32* d_defer_ctr = nullptr;            // [count, done, pad, pad, dynamic-claim counters[MAX_SEGS]]
+    DevBuf<u32> d_defer;                   // deferred (general-path) line indices
+    DevBuf<u32> d_defer_ctr;               // [count, done, pad, pad, dynamic-claim counters[MAX_SEGS]]
     u32 dyn_pct = 0;                       // % of a large segment's tiles claimed dynamically (YSB_DYN_PCT; measured neutral, off)
     u32 dyn_chunk = 16;                    // tiles per claim (YSB_DYN_CHUNK)
-    unsigned long long* d_dbg = nullptr;   // YSB_STAMPS diagnostic build
+    DevBuf<unsigned long long> d_dbg;      // YSB_STAMPS diagnostic build
     u64 dbg_words = 0;
     // columnar decode (ysb_columns.cpp): {valid rows, fast-tier rows} of a call, its event pair
-    unsigned long long* d_colinfo = nullptr;
-    hipEvent_t ev_col[2] = {nullptr, nullptr};
+    DevBuf<unsigned long long> d_colinfo;
+    Event ev_col[2];
 };
 
 #define YSB_INTERNAL __attribute__((visibility("hidden")))
 
 // an error message for ysb_last_error (the context's, or the thread's when c is NULL)
 YSB_INTERNAL int fail(ysb_ctx* c, int code, const char* fmt, ...);
-// Grows the device buffer *buf (*have bytes) to at least max(bytes, floor_bytes); contents are
-// not kept.  Before the old buffer is freed every stream of the context is synchronised
-// (without launching pending work, unlike sync_streams): growth is outside steady state.
-YSB_INTERNAL int grow_device(ysb_ctx* c, void** buf, u64* have, u64 bytes, u64 floor_bytes);
-template <class T>
-int grow_device(ysb_ctx* c, T** buf, u64* have, u64 bytes, u64 floor_bytes) {
-    return grow_device(c, reinterpret_cast<void**>(buf), have, bytes, floor_bytes);
-}
+// Grows the device buffer to at least max(bytes, floor_bytes); contents are not kept.  Before
+// the old buffer is freed every stream of the context is synchronised (without launching
+// pending work, unlike sync_streams): growth is outside steady state.
+YSB_INTERNAL int grow_device(ysb_ctx* c, DevMem& buf, u64 bytes, u64 floor_bytes);
+// A small device buffer that is allocated (bytes, not cleared) at its first use.
+YSB_INTERNAL int first_use(ysb_ctx* c, DevMem& buf, u64 bytes);
+// A campaign-major u64 table (the ring's layout) regrown from old_cells to cells: the first
+// old_cells kept, the rest zero.  The new table is allocated before the old one goes, so a
+// failed call leaves the old table in place and the context usable.
+YSB_INTERNAL int regrow_table(ysb_ctx* c, DevBuf<unsigned long long>& t, u64 old_cells, u64 cells);
 extern thread_local std::string g_open_err;
 
 #define HIPCHK(ctx, expr)                                                                         \

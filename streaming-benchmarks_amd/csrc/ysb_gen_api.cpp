@@ -130,9 +130,8 @@ static int upload_subset(ysb_ctx* c, const ysb_gen_params* p, const u32** dptr) 
     *dptr = nullptr;
     if (!p->ad_subset) return YSB_OK;
     if (c->d_subset_n < p->n_ad_subset) {
-        hipFree(c->d_subset);
-        c->d_subset = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_subset, (u64)p->n_ad_subset * 4));
+        c->d_subset_n = 0;
+        HIPCHK(c, c->d_subset.alloc((u64)p->n_ad_subset * 4));
         c->d_subset_n = p->n_ad_subset;
     }
     HIPCHK(c, hipMemcpy(c->d_subset, p->ad_subset, (u64)p->n_ad_subset * 4, hipMemcpyHostToDevice));
@@ -169,11 +168,11 @@ int ysb_truth_accumulate(ysb_ctx* c, const ysb_gen_params* p, uint64_t first, ui
     HIPCHK(c, hipSetDevice(c->device));
     const u64 cells = (u64)c->c_pad * c->cfg.window_ring;
     if (!c->d_truth) {
-        HIPCHK(c, hipMalloc(&c->d_truth, cells * 8));
-        HIPCHK(c, hipMemset(c->d_truth, 0, cells * 8));
-        HIPCHK(c, hipMalloc(&c->d_truth_out, 8));
+        HIPCHK(c, c->d_truth_out.alloc(8));
         HIPCHK(c, hipMemset(c->d_truth_out, 0, 8));
-        if (!c->d_cmp) HIPCHK(c, hipMalloc(&c->d_cmp, 32));
+        int arc = first_use(c, c->d_cmp, 32);
+        if (!arc) arc = regrow_table(c, c->d_truth, 0, cells);   // (last: d_truth marks all three present)
+        if (arc) return arc;
     }
     HIPCHK(c, hipStreamSynchronize(c->s_comp));
     int rc = read_ring(c);

@@ -59,15 +59,14 @@ static int coll_reduce_scatter(ysb_ctx* c, const void* d_send, void* d_recv, u64
 
 // h[0..n) <- elementwise max over the ranks (signed: mapped to unsigned by the sign bit).
 int allreduce_max(ysb_ctx* c, i64* h, int n) {
-    unsigned long long* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, 8 * (u64)n));
+    DevBuf<unsigned long long> d;
+    HIPCHK(c, d.alloc(8 * (u64)n));
     std::vector<u64> u(n);
     for (int i = 0; i < n; ++i) u[i] = (u64)h[i] ^ (1ull << 63);
     hipError_t e = hipMemcpy(d, u.data(), 8 * (u64)n, hipMemcpyHostToDevice);
     int rc = e == hipSuccess ? coll_max_u64(c, d, (u64)n) : YSB_OK;
     if (e == hipSuccess && !rc) e = hipMemcpyAsync(u.data(), d, 8 * (u64)n, hipMemcpyDeviceToHost, c->s_comp);
     if (e == hipSuccess && !rc) e = hipStreamSynchronize(c->s_comp);
-    hipFree(d);
     if (rc) return rc;
     if (e != hipSuccess) return fail(c, YSB_ERR_HIP, "%s", hipGetErrorString(e));
     for (int i = 0; i < n; ++i) h[i] = (i64)(u[i] ^ (1ull << 63));
@@ -140,25 +139,16 @@ static void ungroup(ysb_ctx* c) {
     c->comm = nullptr;
     c->host_coll = false;
     c->hops = ysb_collectives{};
-    hipFree(c->d_owned);
-    c->d_owned = nullptr;
-    hipFree(c->d_owned8);
-    c->d_owned8 = nullptr;
+    c->d_owned.reset();
+    c->d_owned8.reset();
     c->owned8_dirty = false;
-    hipFree(c->d_xmax);
-    c->d_xmax = nullptr;
-    hipHostFree(c->h_xmax);
-    c->h_xmax = nullptr;
-    hipFree(c->d_xslots);
-    c->d_xslots = nullptr;
-    for (hipEvent_t& e : c->xplan_ev) {
-        if (e) hipEventDestroy(e);
-        e = nullptr;
-    }
+    c->d_xmax.reset();
+    c->h_xmax.reset();
+    c->d_xslots.reset();
     for (int k = 0; k < 2; ++k) {
-        if (c->ev_xpacked[k]) hipEventDestroy(c->ev_xpacked[k]);
-        if (c->ev_xdone[k]) hipEventDestroy(c->ev_xdone[k]);
-        c->ev_xpacked[k] = c->ev_xdone[k] = nullptr;
+        c->xplan_ev[k].reset();
+        c->ev_xpacked[k].reset();
+        c->ev_xdone[k].reset();
         c->xset_used[k] = false;
     }
     c->unpack_set = -1;
@@ -179,39 +169,28 @@ static int group_setup(ysb_ctx* c, int rank, int nranks) {
         int frc = fold_delta(c);   // the delta ring has the old layout: fold it, drop it
         if (frc) return frc;
         HIPCHK(c, hipStreamSynchronize(c->s_comp));
-        hipFree(c->d_delta);
-        c->d_delta = nullptr;
+        c->d_delta.reset();
         c->delta_cells = 0;
-        unsigned long long* old = c->d_counts;
         const u64 W = c->cfg.window_ring;
-        c->d_counts = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_counts, (u64)cp * W * 8));
-        HIPCHK(c, hipMemset(c->d_counts, 0, (u64)cp * W * 8));
-        HIPCHK(c, hipMemcpy(c->d_counts, old, (u64)c->c_pad * W * 8, hipMemcpyDeviceToDevice));
-        hipFree(old);
-        if (c->d_truth) {   // the generator-truth table has the ring's layout: grow it too
-            unsigned long long* ot = c->d_truth;
-            c->d_truth = nullptr;
-            HIPCHK(c, hipMalloc(&c->d_truth, (u64)cp * W * 8));
-            HIPCHK(c, hipMemset(c->d_truth, 0, (u64)cp * W * 8));
-            HIPCHK(c, hipMemcpy(c->d_truth, ot, (u64)c->c_pad * W * 8, hipMemcpyDeviceToDevice));
-            hipFree(ot);
-        }
+        // (after a failure either table has c_pad rows or more, the rest zero: still usable)
+        if ((frc = regrow_table(c, c->d_counts, (u64)c->c_pad * W, (u64)cp * W))) return frc;
+        // the generator-truth table has the ring's layout: grow it too
+        if (c->d_truth && (frc = regrow_table(c, c->d_truth, (u64)c->c_pad * W, (u64)cp * W))) return frc;
         c->c_pad = cp;
     }
     const u64 per = (u64)c->c_pad / nranks * c->cfg.window_ring;
-    HIPCHK(c, hipMalloc(&c->d_owned, per * 8));
+    HIPCHK(c, c->d_owned.alloc(per * 8));
     HIPCHK(c, hipMemset(c->d_owned, 0, per * 8));
-    HIPCHK(c, hipMalloc(&c->d_owned8, per));
+    HIPCHK(c, c->d_owned8.alloc(per));
     HIPCHK(c, hipMemset(c->d_owned8, 0, per));
     const u32 W = c->cfg.window_ring;
-    HIPCHK(c, hipMalloc(&c->d_xmax, 2 * (u64)W * 8));
-    HIPCHK(c, hipHostMalloc(&c->h_xmax, 2 * ((u64)W * 8 + (u64)W * 4)));   // maxima, then the plans' slots
-    HIPCHK(c, hipMalloc(&c->d_xslots, 2 * (u64)W * 4));
-    for (hipEvent_t& e : c->xplan_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK(c, c->d_xmax.alloc(2 * (u64)W * 8));
+    HIPCHK(c, c->h_xmax.alloc(2 * ((u64)W * 8 + (u64)W * 4)));   // maxima, then the plans' slots
+    HIPCHK(c, c->d_xslots.alloc(2 * (u64)W * 4));
     for (int k = 0; k < 2; ++k) {
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_xpacked[k], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_xdone[k], hipEventDisableTiming));
+        HIPCHK(c, c->xplan_ev[k].create());
+        HIPCHK(c, c->ev_xpacked[k].create());
+        HIPCHK(c, c->ev_xdone[k].create());
         c->xset_used[k] = false;
     }
     if (!c->s_x) HIPCHK(c, hipStreamCreateWithFlags(&c->s_x, hipStreamNonBlocking));
@@ -352,11 +331,11 @@ static int exchange(ysb_ctx* c, bool pipelined) {
         if (rc) return rc;
     }
     if (c->xev_used == c->xev.size()) {
-        std::array<hipEvent_t, 6> ev{};
-        for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
-        c->xev.push_back(ev);
+        std::array<Event, 6> ev;
+        for (auto& e : ev) HIPCHK(c, e.create(hipEventDefault));
+        c->xev.push_back(std::move(ev));
     }
-    const auto ev = c->xev[c->xev_used];
+    const auto& ev = c->xev[c->xev_used];
     HIPCHK(c, hipEventRecord(ev[0], c->s_comp));
     // this call's plan into buffer nb
     const int nb = c->xb ^ 1;
@@ -388,8 +367,8 @@ static int exchange(ysb_ctx* c, bool pipelined) {
         c->xk ^= 1;
         // set k was last used two exchanges ago: its unpack must be done before it is rewritten
         if (c->xset_used[k]) HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_xdone[k], 0));
-        int rc = grow_device(c, &c->d_xsend[k], &c->xsend_bytes[k], (u64)rows * R * width, 1u << 16);
-        if (!rc) rc = grow_device(c, &c->d_xrecv[k], &c->xrecv_bytes[k], (u64)per * R * width, 1u << 16);
+        int rc = grow_device(c, c->d_xsend[k], (u64)rows * R * width, 1u << 16);
+        if (!rc) rc = grow_device(c, c->d_xrecv[k], (u64)per * R * width, 1u << 16);
         if (rc) return rc;
         u32* dslots = c->d_xslots + (u64)k * W;
         // (the slots' pinned area is rewritten two calls later, after xplan_ev of the call
@@ -475,7 +454,7 @@ int ysb_group_checksum(ysb_ctx* c, int what, uint32_t nranks, uint64_t* out) {
     if (rc) return rc;
     if (!c->ring_known) return fail(c, YSB_ERR_STATE, "ring base not set yet");
     const u32 W = c->cfg.window_ring, C = c->cfg.n_campaigns;
-    if (!c->d_cmp) HIPCHK(c, hipMalloc(&c->d_cmp, 32));
+    if ((rc = first_use(c, c->d_cmp, 32))) return rc;
     unsigned long long* acc = c->d_cmp;
     auto sum = [&](const unsigned long long* t, u32 rows, u32 c_off, u32 lo, u32 hi, uint64_t* o) -> int {
         HIPCHK(c, hipMemsetAsync(acc, 0, 8, c->s_comp));
@@ -532,12 +511,6 @@ int ysb_group_owned(ysb_ctx* c, uint32_t* lo, uint32_t* hi) {
     return YSB_OK;
 }
 
-uint32_t ysb_ad_shard(const char* ad_id, uint32_t len, uint32_t nranks) {
-    if (nranks <= 1) return 0;
-    u32 kw[KEY_WORDS] = {0};
-    std::memcpy(kw, ad_id, std::min<u32>(len, MAX_KEY_BYTES));
-    const u32 h = key_hash(kw, std::min<u32>(len, MAX_KEY_BYTES));
-    return (u32)(((u64)mix64(h) >> 32) * nranks >> 32);
-}
+uint32_t ysb_ad_shard(const char* ad_id, uint32_t len, uint32_t nranks) { return ad_shard(ad_id, len, nranks); }
 
 }  // extern "C"

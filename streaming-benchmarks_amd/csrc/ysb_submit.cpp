@@ -152,15 +152,16 @@ static int plan_records(ysb_ctx* c, ScanParams& p, u64 n_events, RecParams& r) {
     r.cap = (u32)cap;
     r.area = area;
     int rc;
-    if ((rc = grow_device(c, &c->d_rec, &c->rec_bytes, (u64)r.grid * r.bins * cap * 4, 0))) return rc;
-    if ((rc = grow_device(c, &c->d_rec_n, &c->rec_n_bytes, (u64)r.grid * r.bins * 4, 0))) return rc;
-    if ((rc = grow_device(c, &c->d_part, &c->part_bytes, part * 4, 0))) return rc;
-    if ((rc = grow_device(c, &c->d_runs, &c->runs_bytes, (u64)r.n_blocks * REC_QUARTERS * 2 * 4, 0))) return rc;
+    if ((rc = grow_device(c, c->d_rec, (u64)r.grid * r.bins * cap * 4, 0))) return rc;
+    if ((rc = grow_device(c, c->d_rec_n, (u64)r.grid * r.bins * 4, 0))) return rc;
+    if ((rc = grow_device(c, c->d_part, part * 4, 0))) return rc;
+    if ((rc = grow_device(c, c->d_runs, (u64)r.n_blocks * REC_QUARTERS * 2 * 4, 0))) return rc;
     if (c->delta_cells != cells) {   // the delta ring: the u64 ring's layout, one byte a cell, zeroed
         if ((rc = fold_delta(c))) return rc;
-        c->delta_cells = 0;   // (exactly `cells` of them: not only when it has to grow)
-        if ((rc = grow_device(c, &c->d_delta, &c->delta_cells, cells, 0))) return rc;
+        c->delta_cells = 0;   // (c_pad only grows, and ysb_group_init drops the ring it outgrows)
+        if ((rc = grow_device(c, c->d_delta, cells, 0))) return rc;
         HIPCHK(c, hipMemset(c->d_delta, 0, cells));
+        c->delta_cells = cells;
     }
     // the delta saturates instead of wrapping, so it needs no fold between launches; the
     // test hook YSB_DELTA_FOLD_EVENTS folds anyway once the events since the last fold
@@ -193,10 +194,10 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout
     if (n == 0) { c->batches += nin; return YSB_OK; }
     if (n >= (1ull << 31)) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 events per launch");
     // the deferred-line list can hold every line of a batch
-    int rc = grow_device(c, &c->d_defer, &c->defer_bytes, n * 4, 4u << 16);
+    int rc = grow_device(c, c->d_defer, n * 4, 4u << 16);
     if (rc) return rc;
     if (!c->d_defer_ctr) {
-        HIPCHK(c, hipMalloc(&c->d_defer_ctr, 16 + 4 * MAX_SEGS));
+        HIPCHK(c, c->d_defer_ctr.alloc(16 + 4 * MAX_SEGS));
         HIPCHK(c, hipMemset(c->d_defer_ctr, 0, 16 + 4 * MAX_SEGS));
     }
     // the out-of-ring map's fill level after an earlier launch (read without waiting): a
@@ -215,11 +216,11 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout
     p.defer_count = c->d_defer_ctr;
     p.defer_done = c->d_defer_ctr + 1;
     p.dyn_ctr = c->d_defer_ctr + 4;
-    p.defer_cap = (u32)(c->defer_bytes / 4);
+    p.defer_cap = (u32)(c->d_defer.bytes() / 4);
 #if defined(YSB_STAMPS) || defined(YSB_WGTIME)
     const u64 words = (u64)c->cus * std::max(Geom<true>::WG_PER_CU, Geom<false>::WG_PER_CU) * (SCAN_TPB / 64) * N_STAMPS;
     if (!c->d_dbg) {
-        HIPCHK(c, hipMalloc(&c->d_dbg, words * 8));
+        HIPCHK(c, c->d_dbg.alloc(words * 8));
         HIPCHK(c, hipMemset(c->d_dbg, 0, words * 8));
         c->dbg_words = words;
     }
@@ -237,7 +238,7 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout
     if (p.dyn_chunk) HIPCHK(c, hipMemsetAsync(p.dyn_ctr, 0, 4 * MAX_SEGS, c->s_comp));
     RecParams rp{};
     if ((rc = plan_records(c, p, n, rp))) return rc;
-    hipEvent_t* te = nullptr;   // YSB_F_TIMING: {before the scan, after it, after the launch's last kernel}
+    Event* te = nullptr;   // YSB_F_TIMING: {before the scan, after it, after the launch's last kernel}
     if (c->cfg.flags & YSB_F_TIMING) {
         HIPCHK(c, c->tev.acquire(&te));
         HIPCHK(c, hipEventRecord(te[0], c->s_comp));
@@ -318,8 +319,8 @@ static int decide_sample(ysb_ctx* c, int k) {
 static int sample_device_layout(ysb_ctx* c, const ysb_segment* segs, u32 nseg, Layout* out) {
     const u64 buf = (u64)SAMPLE_LINES * SAMPLE_STRIDE;
     if (!c->h_sample) {
-        HIPCHK(c, hipHostMalloc(&c->h_sample, 2 * buf));
-        for (hipEvent_t& e : c->ev_sample) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIPCHK(c, c->h_sample.alloc(2 * buf));
+        for (Event& e : c->ev_sample) HIPCHK(c, e.create());
     }
     const bool idle = hipStreamQuery(c->s_comp) == hipSuccess;
     const int k = c->sample_cur;
@@ -372,10 +373,10 @@ static int ensure_slots(ysb_ctx* c) {
     if (c->h_bytes[0]) return YSB_OK;
     HIPCHK(c, hipSetDevice(c->device));
     for (int s = 0; s < 2; ++s) {
-        HIPCHK(c, hipHostMalloc(&c->h_bytes[s], c->cfg.max_batch_bytes + 64));
-        HIPCHK(c, hipHostMalloc(&c->h_off[s], c->cfg.max_batch_events * 4 + 64));
-        HIPCHK(c, hipMalloc(&c->d_bytes[s], c->cfg.max_batch_bytes + 64));
-        HIPCHK(c, hipMalloc(&c->d_off[s], c->cfg.max_batch_events * 4 + 64));
+        HIPCHK(c, c->h_bytes[s].alloc(c->cfg.max_batch_bytes + 64));
+        HIPCHK(c, c->h_off[s].alloc(c->cfg.max_batch_events * 4 + 64));
+        HIPCHK(c, c->d_bytes[s].alloc(c->cfg.max_batch_bytes + 64));
+        HIPCHK(c, c->d_off[s].alloc(c->cfg.max_batch_events * 4 + 64));
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hd_bytes[s]), c->h_bytes[s], 0));
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hd_off[s]), c->h_off[s], 0));
     }
@@ -405,7 +406,7 @@ struct SlotCopy {
 };
 static int copy_slot(ysb_ctx* c, int slot, const SlotCopy& a, const SlotCopy& b = {}) {
     HIPCHK(c, wait_unless_done(c->s_copy, c->ev_kdone[slot]));
-    hipEvent_t* ce = nullptr;
+    Event* ce = nullptr;
     if (c->cfg.flags & YSB_F_TIMING) {
         HIPCHK(c, c->cev.acquire(&ce));
         c->copy_bytes += a.bytes + b.bytes;
@@ -482,16 +483,14 @@ static int ensure_raw(ysb_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     c->raw_lines_cap = raw_line_cap(c->cfg);
     for (int s = 0; s < 2; ++s) {   // (a failed earlier attempt may have left some of these)
-        hipFree(c->d_roff[s]);
-        c->d_roff[s] = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_roff[s], c->raw_lines_cap * 4));
-        if (!c->ev_raw[s]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_raw[s], hipEventDisableTiming));
+        HIPCHK(c, c->d_roff[s].alloc(c->raw_lines_cap * 4));
+        if (!c->ev_raw[s]) HIPCHK(c, c->ev_raw[s].create());
     }
     if (!c->s_split) HIPCHK(c, hipStreamCreateWithFlags(&c->s_split, hipStreamNonBlocking));
     const u64 chunk_bytes = (split_chunks(c->cfg.max_batch_bytes) + 1) * 4;
-    const int rc = grow_device(c, &c->d_split_chunk, &c->split_chunk_bytes, chunk_bytes, 0);
+    const int rc = grow_device(c, c->d_split_chunk, chunk_bytes, 0);
     if (rc) return rc;
-    HIPCHK(c, hipHostMalloc(&c->h_rawn, 16));
+    HIPCHK(c, c->h_rawn.alloc(16));
     return YSB_OK;
 }
 
@@ -641,14 +640,13 @@ int ysb_rebase_table(ysb_ctx* c, const uint32_t* time_at, uint64_t n_lines, int6
     // batches queued with the old table must be done with it
     HIPCHK(c, hipStreamSynchronize(c->s_copy));
     if (c->s_split) HIPCHK(c, hipStreamSynchronize(c->s_split));
-    hipFree(c->d_rebase);
-    c->d_rebase = nullptr;
+    c->d_rebase.reset();
     c->rebase_n = 0;
     if (!n_lines) return YSB_OK;
     u32 kmax = 0;
     for (u64 i = 0; i < n_lines; ++i) kmax = std::max(kmax, time_at[i] >> 16);
     if (lead_base < 0 || lead_base + kmax >= 1000000000LL) return fail(c, YSB_ERR_ARG, "leading digits out of [0, 10^9)");
-    HIPCHK(c, hipMalloc(&c->d_rebase, n_lines * 4));
+    HIPCHK(c, c->d_rebase.alloc(n_lines * 4));
     HIPCHK(c, hipMemcpy(c->d_rebase, time_at, n_lines * 4, hipMemcpyHostToDevice));
     c->rebase_n = n_lines;
     c->rebase_base = lead_base;
@@ -752,8 +750,8 @@ int ysb_split_lines_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, 
     int rc = launch_pending_raw(c);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = grow_device(c, &c->d_split_chunk, &c->split_chunk_bytes, (split_chunks(nbytes) + 1) * 4, 0))) return rc;
-    if (!c->d_cmp) HIPCHK(c, hipMalloc(&c->d_cmp, 32));
+    if ((rc = grow_device(c, c->d_split_chunk, (split_chunks(nbytes) + 1) * 4, 0))) return rc;
+    if ((rc = first_use(c, c->d_cmp, 32))) return rc;
     unsigned long long* d_n = c->d_cmp + 3;
     HIPCHK(c, launch_split_lines(d_bytes, nbytes, c->d_split_chunk, d_off, cap, d_n, c->s_comp));
     unsigned long long got = 0;

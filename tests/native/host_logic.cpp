@@ -1,12 +1,13 @@
 // Host-side checks of the arithmetic shared with the device (ysb_common.h):
-// exact Java long division by a runtime divisor, and the ad-table hash.
+// exact Java long division by a runtime divisor, and the ad-table hash; the bucket-layout
+// cuckoo table (ysb_admap.h).
 // Built and run by tests/test_capi.py with g++ (no GPU).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <random>
 #include <vector>
-#include "ysb_common.h"
+#include "ysb_admap.h"
 
 using namespace ysb;
 

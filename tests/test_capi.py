@@ -133,6 +133,13 @@ def test_layout_logic_native(tmp_path):
     run_native(tmp_path, "layout_logic")
 
 
+def test_admap_logic_native(tmp_path):
+    """The join tables as host data (csrc/ysb_admap.h, no HIP): the cuckoo builders against the
+    host restatements of the scan's probes, later-wins, the rejections, the sparse thinning, the
+    switch to buckets, and whole-table fingerprints recorded before the builders moved."""
+    run_native(tmp_path, "admap_logic")
+
+
 def test_ad_shard_is_stable_and_balanced():
     from ysb_amd import GenParams, ad_shard
     _, aids = GenParams().ids()

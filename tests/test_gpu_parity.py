@@ -1,10 +1,12 @@
 """GPU parity: the HIP path (through the C ABI) against the golden fixtures and the
 CPU oracle, bit-exact on every (campaign, window) count and every counter."""
+import functools
+
 import numpy as np
 import pytest
 
 import golden_data as gd
-from oracle import oracle
+from oracle import dostats, oracle
 from ysb_amd import GenParams, YsbContext, YsbError
 
 pytestmark = pytest.mark.gpu
@@ -205,6 +207,47 @@ def test_drain_clear_and_ranges():
         assert {(c, t // 10000): v for (c, t), v in first.items()} == {k: v for k, v in exp.items() if k[1] < mid}
         rest = ctx.drain_buckets()
         assert rest == {k: v for k, v in exp.items() if k[1] >= mid}
+
+
+@functools.lru_cache(maxsize=None)
+def _reload_case():
+    """2,000 generator events (32 tiles, the last one ragged) and three maps with what
+    oracle/dostats.py counts under each: A all 1000 ads; B the first 300 with their campaigns
+    permuted (both device tables shrink); C the same 300 keys permuted again (same sizes)."""
+    g = GenParams(n_campaigns=100, ads_per_campaign=10)
+    aids, camp = g.ids()[1], g.ad_campaign_index()
+    raw, offs = g.events_host(0, 2000)
+    lines = dostats.split_lines(raw.tobytes())[0]
+    maps = [(aids, camp), (aids[:300], [(c * 7 + 3) % 100 for c in camp[:300]]),
+            (aids[:300], [(c * 11 + 5) % 100 for c in camp[:300]])]
+    absent = set(aids[300:])
+    absent_views = dostats.run(lines, {a: 0 for a in absent}).joined   # views of the 700 ads B and C leave out
+    return raw, offs, [(m, dostats.run(lines, dict(zip(*m)))) for m in maps], absent_views
+
+
+@pytest.mark.parametrize("first", ["offsets", "raw"])
+def test_reloading_the_ad_map_between_batches(first):
+    """The ad map replaced between batches: into new device buffers when the tables change
+    size (A -> B), in place when they do not (B -> C); every drain equals the oracle under the
+    map of its step.  A raw batch still pending when the next map arrives joins the old one."""
+    raw, offs, steps, absent_views = _reload_case()
+    total = {}
+    with YsbContext(n_campaigns=100, window_ring=64, max_batch_bytes=1 << 20, max_batch_events=1 << 12) as ctx:
+        for k, ((ads, camp), exp) in enumerate(steps):
+            ctx.load_ad_map(ads, camp)
+            if k == 0 and first == "raw":
+                ctx.submit_raw(raw)
+            else:
+                ctx.submit(raw, offs, slot=k & 1)
+            assert exp.join_misses == (0 if k == 0 else absent_views) and exp.joined > 0
+            total = {s: total.get(s, 0) + v for s, v in exp.stats().items()}   # (the counters run on)
+            check_against(ctx, exp.counts, total)
+            ctx.drain(clear=True)
+        # ... and a raw batch that is still pending when the next map is loaded
+        ctx.submit_raw(raw, slot=1)
+        ctx.load_ad_map(*steps[0][0])
+        total = {s: total[s] + v for s, v in steps[2][1].stats().items()}
+        check_against(ctx, steps[2][1].counts, total)
 
 
 def test_misaligned_device_pointer_rejected():
