@@ -142,7 +142,17 @@ extern "C" {
 typedef struct ysb_ctx ysb_ctx;
 
 typedef struct ysb_config {
-    int64_t  time_divisor_ms;    /* 10000: CampaignProcessorCommon.java:28           */
+    int64_t  time_divisor_ms;    /* 10000: CampaignProcessorCommon.java:28.  Any value
+                                    >= 1: bucket = Long.parseLong(event_time) / divisor,
+                                    Java long division (truncating toward zero, so bucket 0
+                                    is the one window 2 * divisor - 1 ms wide), for negative
+                                    times too.  Every bucket must lie in
+                                    (INT64_MIN + W, INT64_MAX - W): the ring's bounds
+                                    (ring base + W, first bucket - W / 8) are computed in
+                                    int64_t.  Only a divisor of 1 with |event_time| >
+                                    2^63 - W can leave that range; with a divisor of 1 the
+                                    bucket INT64_MAX also has no half-open [lo, hi) range
+                                    that ysb_drain could name.                           */
     uint32_t n_campaigns;        /* campaign index space [0, n_campaigns)            */
     uint32_t window_ring;        /* W: live (campaign, bucket) slots per campaign,
                                     power of two >= 16 (the reference keeps <= 9 live
@@ -151,7 +161,12 @@ typedef struct ysb_config {
     uint64_t max_batch_events;   /* per ysb_submit                                   */
     uint64_t max_batch_bytes;    /* per ysb_submit, <= 4 GiB (u32 line offsets)      */
     int64_t  ring_base_bucket;   /* first bucket of the ring; INT64_MIN = take it from
-                                    the first event of the first batch              */
+                                    the first event of the first batch (the smallest bucket
+                                    among the joined views of its first 256 lines, minus
+                                    W / 8).  May be negative or zero: the ring
+                                    [base, base + W) may straddle bucket 0 or lie below it.
+                                    base + W must not overflow: base in
+                                    (INT64_MIN + W, INT64_MAX - W), as every bucket        */
     uint64_t overflow_capacity;  /* (campaign, bucket) deltas outside the ring that
                                     are kept exactly in a side list                  */
     uint32_t flags;              /* YSB_F_*                                          */

@@ -12,9 +12,9 @@ from ysb_amd.stream import SlotContext, StreamingOperator
 pytestmark = pytest.mark.gpu
 
 
-def oracle_rows(g, raw, offs):
+def oracle_rows(g, raw, offs, divisor=10000):
     _, aids = g.ids()
-    return oracle.run(oracle.AdMap(aids, g.ad_campaign_index()), raw, offs)
+    return oracle.run(oracle.AdMap(aids, g.ad_campaign_index()), raw, offs, divisor=divisor)
 
 
 def test_drain_compaction_and_ring_advance_exact():
@@ -47,15 +47,18 @@ def test_drain_compaction_and_ring_advance_exact():
         assert ctx.ring_range() == (lo - 20, W)
 
 
-def test_streaming_operator_end_to_end_exact():
+@pytest.mark.parametrize("divisor", [10000, 1000])
+def test_streaming_operator_end_to_end_exact(divisor):
     g = GenParams(seed=5, n_campaigns=100, ads_per_campaign=10, events_per_sec=20_000, with_skew=True,
                   n_users=100, t0_ms=1_700_000_000_000)
     n = 600_000                                          # 30 s of event time
     _, aids = g.ids()
     clock = {"t": 1_700_000_000_000.0}
-    with YsbContext(n_campaigns=100, window_ring=16, max_batch_bytes=2 << 20, max_batch_events=4096) as ctx:
+    with YsbContext(n_campaigns=100, window_ring=16, max_batch_bytes=2 << 20, max_batch_events=4096,
+                    time_divisor_ms=divisor) as ctx:
         ctx.load_ad_map(aids, g.ad_campaign_index())
         sctx = SlotContext(ctx)
+        assert sctx.divisor == divisor
         written = []
         op = StreamingOperator(sctx, sink=written.extend, clock_ms=lambda: clock["t"],
                                lateness_horizon_ms=20_000)
@@ -75,7 +78,7 @@ def test_streaming_operator_end_to_end_exact():
             op.submit()
         op.close()
         raw, offs = g.events_host(0, n)
-        rows, st = oracle_rows(g, raw, offs)
+        rows, st = oracle_rows(g, raw, offs, divisor)
         assert op.totals == rows
         s = ctx.stats()
         assert s["events"] == n and s["parse_errors"] == 0 and s["joined"] == st["joined"]
@@ -85,7 +88,8 @@ def test_streaming_operator_end_to_end_exact():
         assert lo > min(b for _, b in rows)              # the ring followed the watermark
         tot = {}
         for c, w, k in written:
-            tot[(c, w // 10000)] = tot.get((c, w // 10000), 0) + k
+            assert w % divisor == 0
+            tot[(c, w // divisor)] = tot.get((c, w // divisor), 0) + k
         assert tot == rows
 
 

@@ -70,6 +70,31 @@ def test_bucket_known_answers(t, bucket):
     assert dostats.java_div(dostats.parse_long(t), 10000) == bucket
 
 
+# The same arithmetic at other divisors (time_divisor_ms is a runtime value): Java's `/` on
+# longs truncates toward zero, so bucket 0 spans (-d, d) and the negative edges are at -k*d.
+@pytest.mark.parametrize("t,d,bucket", [
+    ("-1", 1, -1), ("0", 1, 0), ("-0", 1, 0),
+    ("6", 7, 0), ("-6", 7, 0), ("-7", 7, -1), ("-8", 7, -1), ("-14", 7, -2),
+    ("999", 1000, 0), ("-999", 1000, 0), ("-1000", 1000, -1), ("-1001", 1000, -1), ("1999", 1000, 1),
+    ("20001", 10001, 1), ("-10000", 10001, 0), ("-10001", 10001, -1),
+    ("1700000000000", 60000, 28333333), ("-1700000000000", 60000, -28333333),
+    ("86399999", 86400000, 0), ("-86400000", 86400000, -1),
+    ("9223372036854775807", 2, 4611686018427387903), ("-9223372036854775808", 2, -4611686018427387904),
+    ("-9223372036854775808", 3, -3074457345618258602), ("9223372036854775807", 3, 3074457345618258602),
+    ("9223372036854775807", 9223372036854775807, 1), ("9223372036854775806", 9223372036854775807, 0),
+    ("-9223372036854775807", 9223372036854775807, -1), ("-9223372036854775808", 9223372036854775807, -1),
+])
+def test_bucket_known_answers_other_divisors(t, d, bucket):
+    m = oracle.AdMap(["ad"], [0])
+    line = ('{"user_id": "u", "page_id": "p", "ad_id": "ad", "ad_type": "t", "event_type": "view", '
+            '"event_time": "%s"}' % t).encode()
+    rows, st = oracle.run(m, line, [0], divisor=d)
+    assert st["joined"] == 1 and st["time_errors"] == 0
+    assert rows == {(0, bucket): 1}
+    assert dostats.java_div(dostats.parse_long(t), d) == bucket
+    assert dostats.run([line], {"ad": 0}, divisor=d).counts == {(0, bucket): 1}
+
+
 @pytest.mark.parametrize("t", ["", "-", "+", "1.5", "17e3", " 1", "1 ", "9223372036854775808",
                                "-9223372036854775809", "0x10", "١٢"])
 def test_time_errors(t):
