@@ -42,8 +42,10 @@ extern "C" {
  *    ysb_submit_mapped) with the replay's event-time rebasing on the device
  *    (ysb_rebase_table); ysb_exchange_info_size (the struct grew in ABI 4: a caller
  *    checks the size it was built with); YSB_F_TIMING's event records are folded into running
- *    totals, so a caller that never reads them keeps a bounded number */
-#define YSB_ABI_VERSION 5
+ *    totals, so a caller that never reads them keeps a bounded number
+ * 6: ysb_record_info / ysb_record_desc_size (the last record-mode launch's plan, sub-buffer
+ *    fill and partition runs, read-only) */
+#define YSB_ABI_VERSION 6
 
 /* status codes */
 #define YSB_OK            0
@@ -497,6 +499,38 @@ typedef struct ysb_launch_desc {
     uint32_t tbl;
 } ysb_launch_desc;
 int         ysb_launch_info(ysb_ctx* ctx, ysb_launch_desc* out);
+/* A read-only view of the last record-mode launch (ABI 6; the tests' evidence of which device
+ * paths ran): its plan -- level-2 blocks of 1 << blk_shift campaigns, level-1 bins of
+ * 1 << sub_log2 blocks, `cap` records per (scan workgroup, bin) sub-buffer, `area` u32 words per
+ * (bin, slice) partition output, `part` words in all -- the launch's scan workgroups (grid) and
+ * partition slices per bin (slices), whether anything was added to the u64 ring past the u8
+ * delta ring (dirty: a delta cell passed 255, a full sub-buffer's views or a general-path view
+ * went to the atomics; sticky until ysb_reset or an exchange) and the events counted into the
+ * delta ring since it was last folded (delta_bound).  rec_n (may be NULL) receives the records
+ * stored per sub-buffer as [grid][bins], runs (may be NULL) each block's run per slice as
+ * [n_blocks][slices][2] = {offset, length} in words of the partition output; a capacity
+ * (in elements) too small for either fails with YSB_ERR_CAPACITY, the descriptor filled in.
+ * Waits for every queued launch; changes nothing (no fold).  YSB_ERR_STATE before the first
+ * record-mode launch. */
+typedef struct ysb_record_desc {
+    uint32_t w_log2;
+    uint32_t blk_shift;
+    uint32_t n_blocks;
+    uint32_t sub_log2;
+    uint32_t bins;
+    uint32_t cap;
+    uint32_t grid;
+    uint32_t slices;
+    uint64_t area;
+    uint64_t part;
+    uint64_t delta_bound;
+    uint32_t dirty;
+    uint32_t reserved;
+} ysb_record_desc;
+int         ysb_record_info(ysb_ctx* ctx, ysb_record_desc* out, uint32_t* rec_n, uint64_t rec_n_cap,
+                            uint32_t* runs, uint64_t runs_cap);
+/* sizeof(ysb_record_desc) as this library writes it (ABI 6). */
+uint64_t    ysb_record_desc_size(void);
 /* The layout sampling's decision for one line (host function; what every submit applies
  * to its batch's first line): 0 the generator's layout (core.clj:90-96), 1 its keys in its
  * order as compact JSON, 3 another order or subset of DeserializeBolt's keys with one

@@ -719,6 +719,38 @@ int ysb_launch_info(ysb_ctx* c, ysb_launch_desc* out) {
     return YSB_OK;
 }
 
+uint64_t ysb_record_desc_size(void) { return sizeof(ysb_record_desc); }
+
+int ysb_record_info(ysb_ctx* c, ysb_record_desc* out, uint32_t* rec_n, uint64_t rec_n_cap, uint32_t* runs,
+                    uint64_t runs_cap) {
+    if (!c || !out) return c ? fail(c, YSB_ERR_ARG, "NULL output") : YSB_ERR_ARG;
+    int rc = sync_streams(c);
+    if (rc) return rc;
+    if (!c->rec_launches) return fail(c, YSB_ERR_STATE, "no record-mode launch has run");
+    const RecPlan& pl = c->rec_last;
+    *out = ysb_record_desc{};
+    out->w_log2 = pl.w_log2;
+    out->blk_shift = pl.blk_shift;
+    out->n_blocks = pl.n_blocks;
+    out->sub_log2 = pl.sub_log2;
+    out->bins = pl.bins;
+    out->cap = pl.cap;
+    out->grid = c->rec_last_grid;
+    out->slices = REC_QUARTERS;
+    out->area = pl.area;
+    out->part = pl.part;
+    out->delta_bound = c->delta_bound;
+    HIPCHK(c, hipMemcpy(&out->dirty, c->d_dirty, 4, hipMemcpyDeviceToHost));
+    const u64 n_rec = (u64)c->rec_last_grid * pl.bins, n_runs = (u64)pl.n_blocks * REC_QUARTERS * 2;
+    if ((rec_n && rec_n_cap < n_rec) || (runs && runs_cap < n_runs))
+        return fail(c, YSB_ERR_CAPACITY, "ysb_record_info: rec_n holds %llu of %llu, runs %llu of %llu",
+                    (unsigned long long)rec_n_cap, (unsigned long long)n_rec, (unsigned long long)runs_cap,
+                    (unsigned long long)n_runs);
+    if (rec_n) HIPCHK(c, hipMemcpy(rec_n, c->d_rec_n, n_rec * 4, hipMemcpyDeviceToHost));
+    if (runs) HIPCHK(c, hipMemcpy(runs, c->d_runs, n_runs * 4, hipMemcpyDeviceToHost));
+    return YSB_OK;
+}
+
 void* ysb_stream(ysb_ctx* c) {
     if (!c) return nullptr;
     // work the caller orders after it follows every submitted batch; NULL if one could not

@@ -46,9 +46,9 @@ constexpr u32 REC_NONE = 0xFFFFFFFFu;
 // [w_lo, w_hi) (one of REC_QUARTERS slices).  Each wave walks its own sub-buffers (wave,
 // wave + 16, ...) 512 records per round, 8 loads in flight per lane.  Sweep 1 counts
 // the records per level-2 block; each block's run starts 32-record aligned in this
-// workgroup's output area.  Sweep 2 stages every record in its block's 64-record LDS ring
-// (a record arriving when its ring is full goes straight to its final slot) and after
-// every round each block's full 128-B lines are written out by one thread.
+// workgroup's output area.  Sweep 2 stages every record in its block's PART_RING-record (32)
+// LDS ring (a record arriving when its ring is full goes straight to its final slot) and
+// after every round each block's full 128-B lines are written out by one thread.
 // (a 32-record ring keeps the workgroup under 80 KiB of LDS: two per CU, so 8 waves per
 // SIMD, which the register budget must allow)
 __global__ __launch_bounds__(REC_TPB) __attribute__((amdgpu_waves_per_eu(PART_RING == 32 ? 8 : 4)))
@@ -161,7 +161,7 @@ void rec_partition_kernel(const RecParams R) {
         __syncthreads();
         for (u32 k = tid; k < S; k += REC_TPB) {
             const u32 f0 = fl[k], c = cur[k];
-            // staged this round: positions [f0, f0 + 64); beyond that they went direct
+            // staged this round: positions [f0, f0 + PART_RING); beyond that they went direct
             const u32 lines = min(c - f0, (u32)PART_RING) / 32;
             for (u32 l = 0; l < lines; ++l) write_line(k, 32);
             if (c - f0 > (u32)PART_RING) fl[k] = c;   // direct positions are written already

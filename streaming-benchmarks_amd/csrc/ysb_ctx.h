@@ -4,6 +4,7 @@
 //   ysb_submit.cpp  batches: slots, raw lines, device batches, the layout samples, the launches
 //   ysb_layout.h    the layout sampling's rules (no HIP: tests/native/layout_logic.cpp)
 //   ysb_admap.h     the join tables as host data (no HIP: tests/native/admap_logic.cpp)
+//   ysb_recplan.h   record mode's plan of a launch (no HIP: tests/native/recplan_logic.cpp)
 //   ysb_group.cpp   multi-GPU: the RCCL / host-collective group and the keyBy exchange
 //   ysb_gen_api.cpp the synthetic generator (host and device) and its truth tables
 // Internal: nothing here is part of the ABI (the shared helpers have hidden visibility).
@@ -236,6 +237,8 @@ struct ysb_ctx {
     // record mode (ysb_count.hip)
     DevBuf<u32> d_rec, d_rec_n, d_part, d_runs;
     u64 rec_launches = 0;
+    RecPlan rec_last{};                    // the last record launch's plan and grid (ysb_record_info)
+    u32 rec_last_grid = 0;
     // record mode counts into a saturating u8 delta ring with the u64 ring's layout (a cell
     // passing 255 goes to the u64 ring, ysb_count.hip add16); fold_delta adds it to the u64
     // ring before anything reads that.  delta_bound: events counted into it since the last
@@ -341,8 +344,7 @@ extern thread_local std::string g_open_err;
                         __LINE__);                                                                \
     } while (0)
 
-inline bool is_pow2(u64 x) { return x && !(x & (x - 1)); }
-inline u32 log2u(u64 x) { u32 l = 0; while (((u64)1 << l) < x) ++l; return l; }
+inline bool is_pow2(u64 x) { return x && !(x & (x - 1)); }   // (log2u: ysb_recplan.h)
 
 extern "C" {
 // ysb_capi.cpp

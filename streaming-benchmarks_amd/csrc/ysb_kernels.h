@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ysb_common.h"
+#include "ysb_recplan.h"   // TILE_LINES, MAX_TILES_PER_BLOCK and record mode's REC_* constants
 
 namespace ysb {
 
@@ -11,18 +12,10 @@ namespace ysb {
 // and the two waves of a SIMD drift into different phases (one classifying while the
 // other parses), which hides each other's LDS latency.
 constexpr int SCAN_TPB = 64;                  // threads per scan workgroup (one wave)
-#ifndef YSB_TILE_LINES
-#define YSB_TILE_LINES 64
-#endif
-// lines per tile: one per lane (fewer than 64 leaves lanes idle but shrinks the LDS tile,
-// so more workgroups fit a CU)
-constexpr int TILE_LINES = YSB_TILE_LINES;
+// (TILE_LINES, the lines per tile: ysb_recplan.h)
 static_assert(TILE_LINES >= 1 && TILE_LINES <= SCAN_TPB, "one line per lane at most");
 #ifndef YSB_WG_PER_CU
 #define YSB_WG_PER_CU 8
-#endif
-#ifndef YSB_MAX_TILES
-#define YSB_MAX_TILES 128
 #endif
 constexpr int SCAN_WG_PER_CU = YSB_WG_PER_CU; // resident scan workgroups per CU (LDS-bound)
 #ifndef YSB_TILE_LINE_BYTES
@@ -32,7 +25,6 @@ constexpr int TILE_CAP = TILE_LINES * YSB_TILE_LINE_BYTES;   // LDS bytes of one
 constexpr int TILE_CHUNKS = TILE_CAP / 16;    // 16-byte chunks per tile
 constexpr int CHUNKS_PER_THREAD = (TILE_CHUNKS + SCAN_TPB - 1) / SCAN_TPB;  // 17
 constexpr int LCNT_CAP = 256;                 // u32 per-workgroup (campaign, window) counters
-constexpr int MAX_TILES_PER_BLOCK = YSB_MAX_TILES;   // tile bounds preloaded into LDS
 // .tbl rows are ~140 B (JSON lines ~254 B): smaller tiles, so more workgroups fit a CU's
 // LDS and the bytes in flight per CU stay comparable.
 #ifndef YSB_TBL_LINE_BYTES
@@ -45,9 +37,8 @@ constexpr int MAX_TILES_PER_BLOCK = YSB_MAX_TILES;   // tile bounds preloaded in
 // Per-input-format geometry of the scan kernel: tile capacity, prefetch registers and
 // the LDS carve (tile | slack | window counters | misc | tile bounds).
 // Record mode (REC): the window-counter area holds the record staging lines instead --
-// REC_BINS_MAX level-1 bins x a 64-record ring each (2 KiB).
-constexpr int REC_BINS_MAX = 8;       // level-1 bins of the scan's record staging
-constexpr int REC_RING = 64;          // staged records per bin (two 128-B lines)
+// REC_BINS_MAX level-1 bins (ysb_recplan.h) x a 64-record ring each (2 KiB).
+constexpr int REC_RING = 64;         // staged records per bin (two 128-B lines)
 template <bool TBL, bool REC = false>
 struct Geom {
     static constexpr int WG_PER_CU = TBL ? YSB_TBL_WG_PER_CU : SCAN_WG_PER_CU;
@@ -169,12 +160,7 @@ struct ScanParams {
 // Every stage writes whole 128-B lines from LDS staging: a partial-line store costs a
 // memory write of its own (the XCD L2s are write-through for stores), which made scattered
 // 4-B record stores as slow as the atomics they replace (tools/mb_scatter.hip).
-constexpr int REC_BLOCK_CELLS = 32768;  // u32 LDS counters per count workgroup (128 KiB)
-#ifndef YSB_REC_QUARTERS
-#define YSB_REC_QUARTERS 64
-#endif
-constexpr int REC_QUARTERS = YSB_REC_QUARTERS;   // partition workgroups per level-1 bin (each a slice of the scan workgroups)
-constexpr int REC_SUB_MAX = 512;      // level-2 blocks per level-1 bin (the partition's staging rings)
+// REC_BLOCK_CELLS, REC_QUARTERS, REC_SUB_MAX and the launch's geometry: ysb_recplan.h.
 struct RecParams {
     const u32* rec;             // the scan's sub-buffers
     const u32* rec_n;

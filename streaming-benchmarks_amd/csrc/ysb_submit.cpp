@@ -122,39 +122,27 @@ static int plan_records(ysb_ctx* c, ScanParams& p, u64 n_events, RecParams& r) {
     const u64 cells = (u64)c->c_pad * W;
     const bool force = (c->cfg.flags & YSB_F_RECORD_COUNT) != 0;
     // (the record-mode kernels are the HBM-table instantiations: bucket-layout join table)
-    if ((c->cfg.flags & YSB_F_NO_RECORD_COUNT) || c->lds_wl || p.dyn_chunk || cells >= (1ull << 32) ||
-        W > (u32)REC_BLOCK_CELLS || !c->ctable_buckets)
-        return YSB_OK;
+    if ((c->cfg.flags & YSB_F_NO_RECORD_COUNT) || c->lds_wl || p.dyn_chunk || !c->ctable_buckets) return YSB_OK;
     if (!force && (cells < (1ull << 20) || n_events < (1ull << 20))) return YSB_OK;
-    r.ring_w = W;
-    r.w_log2 = log2u(W);
-    r.blk_shift = log2u(REC_BLOCK_CELLS / W);
-    r.c_pad = c->c_pad;
-    r.n_blocks = (u32)((c->c_pad + (1u << r.blk_shift) - 1) >> r.blk_shift);
-    const u32 sub = (r.n_blocks + REC_BINS_MAX - 1) / REC_BINS_MAX;
-    r.sub_log2 = log2u(sub);
-    if ((1u << r.sub_log2) > (u32)REC_SUB_MAX) return YSB_OK;   // beyond 8 x 512 blocks: atomics
-    r.bins = (r.n_blocks + (1u << r.sub_log2) - 1) >> r.sub_log2;
-    r.grid = p.grid;
-    if ((r.grid + REC_QUARTERS - 1) / REC_QUARTERS > 128) return YSB_OK;   // REC_SLICE_MAX
-    // lines one workgroup scans at most in this launch; ~1/3 are joined views on generator
-    // data; 3/4 of the lines spread over the bins leaves room for skew (a full sub-buffer
-    // sends the rest of its views to the atomics: slower, still exact)
+    // tiles one workgroup scans at most in this launch, then the geometry (ysb_recplan.h)
     u64 tiles = 0;
     for (u32 i = 0; i < p.n_segs; ++i) tiles += p.seg[i].tiles_per_block + (p.seg[i].static_rem ? 1 : 0);
-    const u64 lines = tiles * TILE_LINES;
-    u64 cap = (lines * 3 / 4 + r.bins - 1) / r.bins;
-    cap = std::max<u64>(32, (cap + 31) / 32 * 32);
-    // one (bin, slice) output area: the slice's sub-buffers plus a 32-record alignment pad per block
-    const u64 area = ((u64)((r.grid + REC_QUARTERS - 1) / REC_QUARTERS) * cap + 32ull * (1u << r.sub_log2) + 31) / 32 * 32;
-    const u64 part = (u64)r.bins * REC_QUARTERS * area;
-    if (cap > 0xFFFFFFFFull || part >= (1ull << 32)) return YSB_OK;
-    r.cap = (u32)cap;
-    r.area = area;
+    RecPlan pl;
+    if (!rec_plan(c->c_pad, W, p.grid, tiles, &pl)) return YSB_OK;
+    r.ring_w = W;
+    r.w_log2 = pl.w_log2;
+    r.blk_shift = pl.blk_shift;
+    r.c_pad = c->c_pad;
+    r.n_blocks = pl.n_blocks;
+    r.sub_log2 = pl.sub_log2;
+    r.bins = pl.bins;
+    r.grid = p.grid;
+    r.cap = pl.cap;
+    r.area = pl.area;
     int rc;
-    if ((rc = grow_device(c, c->d_rec, (u64)r.grid * r.bins * cap * 4, 0))) return rc;
+    if ((rc = grow_device(c, c->d_rec, (u64)r.grid * r.bins * pl.cap * 4, 0))) return rc;
     if ((rc = grow_device(c, c->d_rec_n, (u64)r.grid * r.bins * 4, 0))) return rc;
-    if ((rc = grow_device(c, c->d_part, part * 4, 0))) return rc;
+    if ((rc = grow_device(c, c->d_part, pl.part * 4, 0))) return rc;
     if ((rc = grow_device(c, c->d_runs, (u64)r.n_blocks * REC_QUARTERS * 2 * 4, 0))) return rc;
     if (c->delta_cells != cells) {   // the delta ring: the u64 ring's layout, one byte a cell, zeroed
         if ((rc = fold_delta(c))) return rc;
@@ -181,6 +169,8 @@ static int plan_records(ysb_ctx* c, ScanParams& p, u64 n_events, RecParams& r) {
     p.rec_cap = r.cap;
     p.rec = c->d_rec;
     p.rec_n = c->d_rec_n;
+    c->rec_last = pl;   // (ysb_record_info)
+    c->rec_last_grid = p.grid;
     return YSB_OK;
 }
 

@@ -71,7 +71,14 @@ class YsbLaunchDesc(C.Structure):
     _fields_ = [("layout", C.c_uint32), ("record_mode", C.c_uint32), ("hbm_table", C.c_uint32), ("tbl", C.c_uint32)]
 
 
-ALLREDUCE_MAX_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64)
+class YsbRecordDesc(C.Structure):
+    _fields_ = [("w_log2", C.c_uint32), ("blk_shift", C.c_uint32), ("n_blocks", C.c_uint32), ("sub_log2", C.c_uint32),
+                ("bins", C.c_uint32), ("cap", C.c_uint32), ("grid", C.c_uint32), ("slices", C.c_uint32),
+                ("area", C.c_uint64), ("part", C.c_uint64), ("delta_bound", C.c_uint64), ("dirty", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+ALLREDUCE_MAX_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64)
 REDUCE_SCATTER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32)
 
 
@@ -157,6 +164,8 @@ SIGNATURES = {
     "ysb_path_time": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_U64), C.POINTER(_U64)]),
     "ysb_stream": (_P, [_P]),
     "ysb_launch_info": (_I, [_P, C.POINTER(YsbLaunchDesc)]),
+    "ysb_record_info": (_I, [_P, C.POINTER(YsbRecordDesc), _PU32, _U64, _PU32, _U64]),
+    "ysb_record_desc_size": (_U64, []),
     "ysb_layout_of_line": (_I, [C.c_char_p, _U64, _I, C.c_void_p, C.POINTER(_U32), C.POINTER(_U32)]),
     "ysb_device_alloc": (_I, [_P, _U64, C.POINTER(_P)]),
     "ysb_device_free": (_I, [_P, _P]),
@@ -190,7 +199,7 @@ SIGNATURES = {
     "ysb_gen_dump_shards": (_I, [C.POINTER(YsbGenParams), _U64, C.c_char_p, _U32]),
 }
 
-ABI_VERSION = 5   # include/ysb_hip.h YSB_ABI_VERSION this binding is written against
+ABI_VERSION = 6   # include/ysb_hip.h YSB_ABI_VERSION this binding is written against
 
 _lib = None
 
@@ -221,6 +230,9 @@ def lib():
         if L.ysb_exchange_info_size() != C.sizeof(YsbExchangeInfo):
             raise ImportError("ysb_exchange_info is %d bytes in the library, %d in this binding"
                               % (L.ysb_exchange_info_size(), C.sizeof(YsbExchangeInfo)))
+        if L.ysb_record_desc_size() != C.sizeof(YsbRecordDesc):
+            raise ImportError("ysb_record_desc is %d bytes in the library, %d in this binding"
+                              % (L.ysb_record_desc_size(), C.sizeof(YsbRecordDesc)))
         _lib = L
     return _lib
 

@@ -327,6 +327,23 @@ class YsbContext:
         self._c(lib().ysb_launch_info(self._h, C.byref(d)))
         return {n: getattr(d, n) for n, _ in YsbLaunchDesc._fields_}
 
+    def record_info(self, arrays=True):
+        """(descriptor, rec_n, runs) of the last record-mode launch (ysb_record_info): the plan
+        as a dict (w_log2, blk_shift, n_blocks, sub_log2, bins, cap, grid, slices, area, part,
+        delta_bound, dirty), rec_n uint32 [grid][bins] (records stored per sub-buffer) and runs
+        uint32 [n_blocks][slices][2] ({offset, length} of each block's run per partition slice).
+        A sync, not a fold.  arrays=False: the descriptor only, (dict, None, None).  Raises
+        YSB_ERR_STATE before the first record-mode launch."""
+        d = _lib.YsbRecordDesc()
+        self._c(lib().ysb_record_info(self._h, C.byref(d), None, 0, None, 0))
+        desc = {n: getattr(d, n) for n, _ in _lib.YsbRecordDesc._fields_ if n != "reserved"}
+        if not arrays:
+            return desc, None, None
+        rec_n = np.zeros((d.grid, d.bins), dtype=np.uint32)
+        runs = np.zeros((d.n_blocks, d.slices, 2), dtype=np.uint32)
+        self._c(lib().ysb_record_info(self._h, C.byref(d), _ptr(rec_n), rec_n.size, _ptr(runs), runs.size))
+        return desc, rec_n, runs
+
     def stream(self):
         s = lib().ysb_stream(self._h)
         if not s:   # a pending raw batch could not launch (sticky until reset)

@@ -84,9 +84,37 @@ def test_struct_layouts_match_ctypes(tmp_path):
         assert int(got["ysb_exchange_info." + f]) == getattr(_lib.YsbExchangeInfo, f).offset
 
 
+RECORD_PROBE = r"""
+#include <stddef.h>
+#include <stdio.h>
+#include "ysb_hip.h"
+#define P(F) printf(#F " %zu\n", offsetof(ysb_record_desc, F));
+int main(void) {
+  printf("size %zu\n", sizeof(ysb_record_desc));
+  P(w_log2) P(blk_shift) P(n_blocks) P(sub_log2) P(bins) P(cap) P(grid) P(slices) P(area) P(part)
+  P(delta_bound) P(dirty)
+  return 0;
+}
+"""
+
+
+def test_record_desc_layout_matches_ctypes(tmp_path):
+    """ysb_record_desc (ABI 6) as the header lays it out, field by field, against the binding
+    and against the size the library reports."""
+    src = tmp_path / "rprobe.c"
+    src.write_text(RECORD_PROBE)
+    exe = tmp_path / "rprobe"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = dict(ln.split() for ln in subprocess.run([str(exe)], capture_output=True, text=True).stdout.splitlines())
+    assert int(got.pop("size")) == C.sizeof(_lib.YsbRecordDesc) == _lib.lib().ysb_record_desc_size() == 64
+    assert len(got) == 12
+    for f, off in got.items():
+        assert int(off) == getattr(_lib.YsbRecordDesc, f).offset, f
+
+
 def test_abi_version_and_defaults():
     L = _lib.lib()
-    assert L.ysb_abi_version() == 5 == _lib.ABI_VERSION
+    assert L.ysb_abi_version() == 6 == _lib.ABI_VERSION
     # the struct the caller lays out is the library's (ysb_exchange_info grew in ABI 4)
     assert L.ysb_exchange_info_size() == C.sizeof(_lib.YsbExchangeInfo) == 64
     assert C.sizeof(_lib.YsbRebase) == 16
@@ -138,6 +166,14 @@ def test_admap_logic_native(tmp_path):
     host restatements of the scan's probes, later-wins, the rejections, the sparse thinning, the
     switch to buckets, and whole-table fingerprints recorded before the builders moved."""
     run_native(tmp_path, "admap_logic")
+
+
+def test_recplan_logic_native(tmp_path):
+    """Record mode's plan of a launch (csrc/ysb_recplan.h, no HIP) over every ring width, the
+    campaign counts around every block and bin boundary, grids around the slice limits and the
+    tile counts a workgroup can hold: the invariants the kernels rely on for every accepted
+    plan, and rejection exactly at each limit."""
+    run_native(tmp_path, "recplan_logic")
 
 
 def test_ad_shard_is_stable_and_balanced():
