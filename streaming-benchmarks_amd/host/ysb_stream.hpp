@@ -44,10 +44,12 @@
 #pragma once
 
 #include <cstdint>
-#include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "ysb_flush_merge.hpp"
+#include "ysb_replay.hpp"
 #include "ysb_topology.hpp"
 
 namespace ysb {
@@ -77,14 +79,6 @@ struct StreamOptions {
     enum Replay { MAPPED = 0, MAPPED_RAW = 1, COPY = 2 };
     int replay = MAPPED;
     bool pinNuma = true;              // feeder threads (and the cycle's pages) on the GPU's NUMA node
-};
-
-// One flush as the sink sees it: every shard's deltas, the watermark at its begin and the
-// replay-clock time it is written at (the writer's "now", CampaignProcessorCommon.java:84).
-struct FlushRows {
-    int64_t index = 0;
-    int64_t watermarkMs = 0;
-    std::vector<WindowDelta> rows;
 };
 
 struct ShardReport {
@@ -122,9 +116,6 @@ struct StreamReport {
     uint64_t overflowDropped = 0, parseErrors = 0, joinMisses = 0;
 };
 
-// sink(flush, nowMs): writes one flush's rows with the replay clock's now (ms).
-using FlushSink = std::function<void(const FlushRows&, int64_t nowMs)>;
-
 class StreamingJob {
 public:
     explicit StreamingJob(const StreamOptions& o);
@@ -134,35 +125,35 @@ public:
     void prepare();
     StreamReport run(const FlushSink& sink);
     const std::vector<std::string>& campaignIds() const { return campaigns_; }
-    // CPU check of the replay (no GPU): a cycle from the host generator, each batch of each of
-    // `cycles` rebased into a buffer (the host restatement of the device rebase) and compared
-    // byte for byte with the host generator's own lines of that cycle (t0 moved by cycle *
-    // cycleMs).  A JSON summary.
-    static std::string replaySelfCheck(const StreamOptions& o, const std::vector<uint64_t>& cycles);
-    // CPU measurement of the copy feeders (no GPU): `shards` host cycles, each shard's feeder on
-    // a thread of its own filling its slot buffer as fast as it can for `seconds` (round 5's fill:
-    // memcpy + digit patch).  A JSON summary with the aggregate events/s.  (The mapped feeder has
-    // no per-byte host work: its cost per batch is the submit call, measured by the GPU run.)
-    static std::string feedCheck(const StreamOptions& o, double seconds);
-    // CPU check of the shards' flush merge (no GPU): `shards` threads deliver `flushes` flushes
-    // each, at random moments, with jittered watermarks and one delta row per flush, through the
-    // runner's own merger and sink thread.  Checks: the sink sees every index once, in order,
-    // with every shard's rows and the minimum of the shards' watermarks; the windows it closes
-    // are exactly those the merged watermarks pass.  A JSON summary ("ok": true|false).
-    static std::string mergeCheck(int shards, int flushes, uint64_t seed);
     ~StreamingJob();
 
 private:
     struct Shard;
+    class Feeder;
     StreamOptions o_;
     std::vector<std::string> campaigns_, ads_;
-    std::vector<Shard*> shards_;
+    std::vector<std::unique_ptr<Shard>> shards_;
+    void prepareShard(Shard& sh, const std::vector<const char*>& keys, const std::vector<uint32_t>& camp);
+    StreamReport report(const std::vector<std::unique_ptr<Feeder>>& feeders, const SinkThread& st) const;
 };
 
 // The NUMA node of a GPU (its PCI device's numa_node; -1 unknown) and the CPUs of a node this
 // process may run on (empty: none / unknown).
 int gpuNumaNode(int device);
 std::vector<int> nodeCpus(int node);
+
+// Shared with the CPU checks: host threads per shard, shard `stream`'s generator, and its
+// replay cycle generated in pieces -- on its GPU (ysb_gen_events_device, the data/ generator)
+// or, ctx NULL, by the host generator -- and laid out by a CycleBuilder.
+unsigned default_threads(const StreamOptions& o);
+ysb_gen_params shard_gen(const StreamOptions& o, uint32_t stream);
+void build_cycle(ysb_ctx* ctx, const ysb_gen_params& g, const StreamOptions& o, ReplayCycle& c, WorkerPool& pool);
+
+// The CPU checks behind --stream-self-check, --stream-feed-check and --stream-merge-check
+// (ysb_stream_checks.cpp; no GPU): each returns its JSON line.
+std::string replaySelfCheck(const StreamOptions& o, const std::vector<uint64_t>& cycles);
+std::string feedCheck(const StreamOptions& o, double seconds);
+std::string mergeCheck(int shards, int flushes, uint64_t seed);
 
 }  // namespace topology
 }  // namespace ysb

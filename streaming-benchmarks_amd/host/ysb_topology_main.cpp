@@ -552,15 +552,15 @@ int main(int argc, char** argv) {
     }
     try {
         if (a.self_check) {
-            std::printf("%s\n", StreamingJob::replaySelfCheck(a.so, {0, 1, 2, 7, 1000}).c_str());
+            std::printf("%s\n", replaySelfCheck(a.so, {0, 1, 2, 7, 1000}).c_str());
             return 0;
         }
         if (a.feed_check) {
-            std::printf("%s\n", StreamingJob::feedCheck(a.so, a.feed_seconds).c_str());
+            std::printf("%s\n", feedCheck(a.so, a.feed_seconds).c_str());
             return 0;
         }
         if (a.merge_check) {
-            const std::string r = StreamingJob::mergeCheck(a.so.shards, a.merge_flushes, a.so.seed);
+            const std::string r = mergeCheck(a.so.shards, a.merge_flushes, a.so.seed);
             std::printf("%s\n", r.c_str());
             return r.find("\"ok\": true") != std::string::npos ? 0 : 1;
         }

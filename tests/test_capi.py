@@ -145,8 +145,10 @@ def test_bad_config_rejected_before_device_use():
 
 def run_native(tmp_path, name):
     exe = tmp_path / name
-    subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "streaming-benchmarks_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "native", name + ".cpp"), "-o", str(exe)], check=True)
+    inc = [a for d in (("streaming-benchmarks_amd", "csrc"), ("streaming-benchmarks_amd", "host"), ("include",))
+           for a in ("-I", os.path.join(ROOT, *d))]
+    subprocess.run(["g++", "-O2", "-std=c++17", "-pthread"] + inc +
+                   [os.path.join(ROOT, "tests", "native", name + ".cpp"), "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout
 
@@ -174,6 +176,15 @@ def test_recplan_logic_native(tmp_path):
     tile counts a workgroup can hold: the invariants the kernels rely on for every accepted
     plan, and rejection exactly at each limit."""
     run_native(tmp_path, "recplan_logic")
+
+
+def test_stream_logic_native(tmp_path):
+    """The native runner's streaming mode where it needs no library (host/ysb_replay.hpp,
+    ysb_flush_merge.hpp, ysb_feed_rules.hpp): the replay cycle's layout and event_time index
+    from hand-written lines and each rejection, the host rebase with a carry through all nine
+    digits and a batch split over two threads, which flush closes which window, the flush merge,
+    the sink thread's error path, the replay clock and the ring-follow rule."""
+    run_native(tmp_path, "stream_logic")
 
 
 def test_ad_shard_is_stable_and_balanced():

@@ -94,20 +94,27 @@ def test_runner_redis_sink_check_correct(tmp_path):
         srv.close()
 
 
-@pytest.mark.parametrize("shards,skew", [(1, 2), (2, 1)])
-def test_native_stream_mode_exact(shards, skew):
+@pytest.mark.parametrize("shards,skew,how", [
+    pytest.param(1, 2, dict(event_rate=1_000_000, slot_mb=64), id="1-2"),
+    pytest.param(2, 1, dict(event_rate=1_000_000, slot_mb=64), id="2-1"),
+    pytest.param(1, 2, dict(event_rate=200_000, slot_mb=16, replay="mapped-raw", batch_ms=100), id="mapped-raw"),
+    pytest.param(1, 2, dict(event_rate=200_000, slot_mb=16, replay="copy", batch_ms=200), id="copy"),
+])
+def test_native_stream_mode_exact(shards, skew, how):
     """bin/ysb_topology --stream (host/ysb_stream.hpp): a short replay through the pinned
     slots with asynchronous flushes to the Redis writer; every (campaign, window) read back
     through Redis equals the generator truth of what the runner played (check-correct), the
     runner's own totals agree, and the windows the final watermark passed were closed with a
     get-stats sample per (campaign, window).  Two shards share the one GPU (each its own
-    context and slots, one watermark = the minimum); skew 1 adds the reference's late events."""
+    context and slots, one watermark = the minimum); skew 1 adds the reference's late events.
+    mapped-raw and copy: the feeder's other two ingest paths over a 2 M-line cycle played three
+    times (the rebase at a cycle wrap; copy's ~9.6 MB batches are filled by two threads)."""
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import bench_stream
-    r = bench_stream.stream_native(device=0, seconds=1.5, event_rate=1_000_000, speedup=20.0, shards=shards,
-                                   slot_mb=64, skew=skew, threads=8)
+    r = bench_stream.stream_native(device=0, seconds=1.5, speedup=20.0, shards=shards, skew=skew, threads=8, **how)
     c = r["check"]
+    assert r["replay"] == how.get("replay", "mapped")
     assert r["exact_vs_generator_truth"], c
     assert c["truth_mismatched_cells"] == 0 and c["counted_views"] == c["truth_views"] > 0
     assert c["parse_errors"] == 0 and c["join_misses"] == 0 and c["overflow_dropped"] == 0
