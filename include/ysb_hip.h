@@ -477,6 +477,77 @@ int         ysb_decode_columns_device(ysb_ctx* ctx, const uint8_t* d_bytes, uint
                                       uint8_t* d_out, uint64_t batch_rows, int64_t stamp,
                                       uint32_t flags, ysb_decode_info* info);
 
+/* ---- columnar count ---------------------------------------------------------------------
+ * The consumer half of the hand-off format: the filter -> join -> window-count chain
+ * (EventFilterBolt, RedisJoinBolt, CampaignProcessor, AdvertisingTopologyNative.java:115-119)
+ * on a column batch instead of on text -- what the accelerator behind
+ * WindowedArrowFormatBolter (:278-356) does with a window of tuples.  Additive (the ABI
+ * version stays 6); works in a context of either input format: columns have none.
+ *
+ * A batch is a buffer in the layout ysb_columns_layout_of(batch_rows); rows [0, n_rows)
+ * count, n_rows <= batch_rows.  Without YSB_COL_VALIDITY the buffer is the reference's file
+ * image (image_bytes) and every row is taken; with it the buffer extends to start[8] and a
+ * row whose validity bit is zero is the row the reference would have thrown on: it adds 1 to
+ * parse_errors and nothing else (YSB_ERR_DATA at ysb_sync under YSB_F_STRICT).  Per row, in
+ * order: events += 1; the row is a view iff the four bytes of column 4 equal "view"
+ * (event_type.equals("view"), :434, on the value as the layout cut it: the layout keeps four
+ * bytes of event_type, so a value such as "viewer" is a view here and not on the JSON path
+ * -- a property of the fork's layout); the key is the 36 bytes of column 2, joined as
+ * ad_campaign.get(ad_id) (:464) through the 36-byte-key table and, where that table is
+ * partial, the general one (a miss: join_misses, or foreign_shard for a key of another shard
+ * of a sharded table); event_time is column 5 as an int64, little-endian or with
+ * YSB_COL_JAVA_ORDER big-endian; bucket = event_time / time_divisor_ms in Java long division
+ * for any divisor and negative times (CampaignProcessorCommon.java:58), counted as the scan
+ * counts a joined view (LDS window counters, ring atomics, out-of-ring map).  time_errors and
+ * deferred never change.  Each submit adds 1 to batches; n_rows = 0 is a batch that counts
+ * nothing.  An unknown ring base is taken from the batch's first 256 rows by ring_base_bucket's
+ * rule.  The calls read only rows < n_rows of columns 2, 4 and 5 and, with YSB_COL_VALIDITY,
+ * validity words < ceil(n_rows / 64): never page padding, rows >= n_rows or the other four
+ * columns.  They leave the layout sampling's state alone and never run in record mode (they
+ * count into the u64 ring).  With YSB_F_TIMING they are part of ysb_kernel_time and
+ * ysb_path_time; ysb_launch_info keeps describing scan launches only. */
+#define YSB_COL_VALIDITY 0x2u    /* the buffer carries the validity bitmap at start[7] */
+
+/* The byte ranges of a batch that a columnar count reads (host function, no context): n = 3,
+ * or 4 with YSB_COL_VALIDITY, ranges [offset[i], offset[i] + bytes[i]) in ascending order --
+ * rows [0, n_rows) of columns 2, 4 and 5, then the validity words.  What a JNI caller must
+ * make visible to the device (of the MappedByteBuffer the bolter fills, :309-311), and what
+ * ysb_submit_columns copies.  n_rows = 0: every range is empty.  YSB_ERR_ARG for unknown
+ * flags or batch_rows outside [1, 2^31 - 1], YSB_ERR_CAPACITY for n_rows > batch_rows. */
+int         ysb_columns_read_ranges(uint64_t batch_rows, uint64_t n_rows, uint32_t flags,
+                                    uint64_t offset[4], uint64_t bytes[4], uint32_t* n);
+/* Replaces the chain's flatMap calls (:115-119) for one device-resident column batch (HBM, 16-
+ * byte aligned; e.g. ysb_decode_columns_device's output, with YSB_COL_VALIDITY).  Asynchronous
+ * on the compute stream, behind everything submitted, like ysb_submit_device.  YSB_ERR_STATE
+ * without an ad map; YSB_ERR_ARG for unknown flags, a NULL or misaligned buffer or batch_rows
+ * outside [1, 2^31 - 1]; YSB_ERR_CAPACITY for n_rows > batch_rows. */
+int         ysb_submit_columns_device(ysb_ctx* ctx, const uint8_t* d_cols, uint64_t batch_rows,
+                                      uint64_t n_rows, uint32_t flags);
+/* The host form, double-buffered like ysb_submit: `image` is the slot's own pinned buffer
+ * (ysb_slot_buffers) or any host memory, e.g. the bolter's mapped file <shared_file>_<k>
+ * (:303-311) read with YSB_COL_JAVA_ORDER.  Only ysb_columns_read_ranges' bytes are copied
+ * (whole 16-byte vectors): into the slot's pinned buffer if the image is elsewhere, then to
+ * the slot's device buffer at the same offsets by the context's H2D path (the copy kernel, or
+ * the DMA engine under YSB_F_H2D_SDMA); the count launches behind the copy on the compute
+ * stream.  ysb_wait(ctx, slot) before the slot's buffer is rewritten.  YSB_ERR_CAPACITY if the
+ * buffer (image_bytes, or start[8] with YSB_COL_VALIDITY) exceeds max_batch_bytes; the other
+ * errors as ysb_submit_columns_device. */
+int         ysb_submit_columns(ysb_ctx* ctx, int slot, const uint8_t* image, uint64_t batch_rows,
+                               uint64_t n_rows, uint32_t flags);
+/* The last columnar launch (n_rows > 0): its rows, whether it counted through the LDS window
+ * counters, whether it probed the HBM-resident bucket table, and its two flags -- each 0 or 1
+ * but rows.  YSB_ERR_STATE before the first one. */
+typedef struct ysb_colcount_desc {
+    uint64_t rows;
+    uint32_t lds_counters;
+    uint32_t hbm_table;
+    uint32_t java_order;
+    uint32_t validity;
+} ysb_colcount_desc;
+int         ysb_columns_launch_info(ysb_ctx* ctx, ysb_colcount_desc* out);
+/* sizeof(ysb_colcount_desc) as this library writes it. */
+uint64_t    ysb_colcount_desc_size(void);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* With YSB_F_TIMING: total device time of the scan kernel launches (HIP events on
  * the compute stream) and the number of launches since the last call (resets). */

@@ -1,6 +1,8 @@
-// ysb_columns.cpp -- the columnar decode of the C ABI (include/ysb_hip.h, "columnar decode"):
-// the fork's WindowedArrowFormatBolter layout (AdvertisingTopologyNative.java:278-356) and
-// the launch of columns_kernel (ysb_scan_columns.h) for one device batch.
+// ysb_columns.cpp -- the columnar calls of the C ABI (include/ysb_hip.h, "columnar decode" and
+// "columnar count"): the fork's WindowedArrowFormatBolter layout (AdvertisingTopologyNative.java:
+// 278-356), the launch of columns_kernel (ysb_scan_columns.h) for one device batch, and the
+// submits that count a batch in that layout (colcount_kernel, ysb_count_columns.h) from HBM or
+// through the pinned slots.
 #include "ysb_ctx.h"
 
 namespace {
@@ -83,5 +85,142 @@ int ysb_decode_columns_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
     }
     return YSB_OK;
 }
+
+// ---- columnar count (Kernel 5, ysb_count_columns.h) ------------------------------------------
+
+int ysb_columns_read_ranges(uint64_t batch_rows, uint64_t n_rows, uint32_t flags, uint64_t offset[4],
+                            uint64_t bytes[4], uint32_t* n) {
+    ysb_columns_layout lay;
+    if (!offset || !bytes || !n || (flags & ~(YSB_COL_JAVA_ORDER | YSB_COL_VALIDITY)) ||
+        ysb_columns_layout_of(batch_rows, &lay))
+        return YSB_ERR_ARG;
+    if (n_rows > batch_rows) return YSB_ERR_CAPACITY;
+    const int col[3] = {2, 4, 5};   // ad_id, event_type, event_time
+    for (int i = 0; i < 3; ++i) {
+        offset[i] = lay.start[col[i]];
+        bytes[i] = n_rows * COL_WIDTH[col[i]];
+    }
+    *n = 3;
+    if (flags & YSB_COL_VALIDITY) {
+        offset[3] = lay.start[7];
+        bytes[3] = (n_rows + 63) / 64 * 8;
+        *n = 4;
+    }
+    return YSB_OK;
+}
+
+// The arguments every columnar submit checks; *total <- the buffer's size.
+static int colcount_args(ysb_ctx* c, const uint8_t* cols, u64 batch_rows, u64 n_rows, u32 flags,
+                         ysb_columns_layout* lay, u64* total) {
+    if (ysb_columns_layout_of(batch_rows, lay)) return fail(c, YSB_ERR_ARG, "batch_rows must be in [1, 2^31 - 1]");
+    if (flags & ~(YSB_COL_JAVA_ORDER | YSB_COL_VALIDITY)) return fail(c, YSB_ERR_ARG, "unknown columnar flags 0x%x", flags);
+    if (!cols) return fail(c, YSB_ERR_ARG, "NULL column batch");
+    if (n_rows > batch_rows)
+        return fail(c, YSB_ERR_CAPACITY, "%llu rows do not fit a batch of %llu rows", (unsigned long long)n_rows,
+                    (unsigned long long)batch_rows);
+    if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
+    *total = (flags & YSB_COL_VALIDITY) ? lay->start[8] : lay->image_bytes;
+    return YSB_OK;
+}
+
+// One columnar launch on the compute stream: the ring's auto-base if it is not known yet, the
+// count kernel, the out-of-ring map's fill level for the host.
+static int enqueue_colcount(ysb_ctx* c, const u8* d_cols, const ysb_columns_layout& lay, u64 n_rows, u32 flags) {
+    if (n_rows == 0) { c->batches++; return YSB_OK; }
+    int rc = drain_side_if_due(c);
+    if (rc) return rc;
+    ColCountParams p{};
+    context_params(c, &p.sp);
+    p.sp.used_out = c->used_pending ? nullptr : c->h_used;
+    p.cols = d_cols;
+    for (int j = 0; j < 8; ++j) p.start[j] = lay.start[j];
+    p.n_rows = n_rows;
+    p.n_tiles = (n_rows + TILE_LINES - 1) / TILE_LINES;
+    p.java_order = (flags & YSB_COL_JAVA_ORDER) ? 1u : 0u;
+    p.validity = (flags & YSB_COL_VALIDITY) ? 1u : 0u;
+    poll_ring(c);
+    if (!c->ring_known) {
+        launch_colcount_autobase(p, c->s_comp);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->h_ring, c->d_ring, 16, hipMemcpyDeviceToHost, c->s_comp));
+        HIPCHK(c, hipEventRecord(c->ev_ring, c->s_comp));
+        c->ring_query_pending = true;
+    }
+    Event* te = nullptr;   // YSB_F_TIMING: {before the count, after it, after the launch's last kernel}
+    if (c->cfg.flags & YSB_F_TIMING) {
+        HIPCHK(c, c->tev.acquire(&te));
+        HIPCHK(c, hipEventRecord(te[0], c->s_comp));
+    }
+    launch_colcount(p, c->cus, c->s_comp);
+    HIPCHK(c, hipGetLastError());
+    if (te) HIPCHK(c, hipEventRecord(te[1], c->s_comp));
+    launch_colcount_level(p, c->s_comp);   // the map's fill level into h_used (sp.used_out)
+    HIPCHK(c, hipGetLastError());
+    if (te) HIPCHK(c, hipEventRecord(te[2], c->s_comp));
+    c->pend_u64 = true;   // this launch counts into the u64 ring
+    c->last_col.rows = n_rows;
+    c->last_col.lds_counters = p.sp.lds_wl ? 1u : 0u;
+    c->last_col.hbm_table = p.sp.probe_serial ? 1u : 0u;
+    c->last_col.java_order = p.java_order;
+    c->last_col.validity = p.validity;
+    c->col_launched = true;
+    if (p.sp.used_out) {   // the map's fill level is on its way into h_used
+        HIPCHK(c, hipEventRecord(c->ev_used, c->s_comp));
+        c->used_pending = true;
+    }
+    c->batches++;
+    return YSB_OK;
+}
+
+int ysb_submit_columns_device(ysb_ctx* c, const uint8_t* d_cols, uint64_t batch_rows, uint64_t n_rows, uint32_t flags) {
+    if (!c) return YSB_ERR_ARG;
+    ysb_columns_layout lay;
+    u64 total = 0;
+    if (reinterpret_cast<uintptr_t>(d_cols) & 15) return fail(c, YSB_ERR_ARG, "d_cols must be 16-byte aligned");
+    int rc = colcount_args(c, d_cols, batch_rows, n_rows, flags, &lay, &total);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = launch_pending_raw(c))) return rc;   // batches launch in submission order
+    return enqueue_colcount(c, d_cols, lay, n_rows, flags);
+}
+
+int ysb_submit_columns(ysb_ctx* c, int slot, const uint8_t* image, uint64_t batch_rows, uint64_t n_rows,
+                       uint32_t flags) {
+    if (!c) return YSB_ERR_ARG;
+    if (slot < 0 || slot > 1) return fail(c, YSB_ERR_ARG, "slot must be 0 or 1");
+    ysb_columns_layout lay;
+    u64 total = 0;
+    int rc = colcount_args(c, image, batch_rows, n_rows, flags, &lay, &total);
+    if (rc) return rc;
+    if (total > c->cfg.max_batch_bytes)
+        return fail(c, YSB_ERR_CAPACITY, "column batch of %llu B exceeds max_batch_bytes", (unsigned long long)total);
+    if ((rc = launch_pending_raw(c)) || (rc = ensure_slots(c))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the slot's previous H2D must be done before its pinned buffer is rewritten
+    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
+    u64 off[4], len[4];
+    u32 nr = 0;
+    if ((rc = ysb_columns_read_ranges(batch_rows, n_rows, flags, off, len, &nr))) return fail(c, rc, "bad column ranges");
+    SlotCopy v[4];
+    for (u32 i = 0; i < nr; ++i) {
+        if (image != c->h_bytes[slot] && len[i]) std::memcpy(c->h_bytes[slot] + off[i], image + off[i], len[i]);
+        v[i] = {c->d_bytes[slot] + off[i], c->hd_bytes[slot] + off[i], c->h_bytes[slot] + off[i], len[i]};
+    }
+    // ... and the slot's previous kernel before its device buffer is
+    if ((rc = copy_slot_ranges(c, slot, v, (int)nr))) return rc;
+    HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_h2d[slot], 0));
+    if ((rc = enqueue_colcount(c, c->d_bytes[slot], lay, n_rows, flags))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_kdone[slot], c->s_comp));
+    return YSB_OK;
+}
+
+int ysb_columns_launch_info(ysb_ctx* c, ysb_colcount_desc* out) {
+    if (!c || !out) return c ? fail(c, YSB_ERR_ARG, "NULL output") : YSB_ERR_ARG;
+    if (!c->col_launched) return fail(c, YSB_ERR_STATE, "no columnar launch yet");
+    *out = c->last_col;
+    return YSB_OK;
+}
+
+uint64_t ysb_colcount_desc_size(void) { return sizeof(ysb_colcount_desc); }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // library's host translation units:
 //   ysb_capi.cpp    context lifecycle, the ad -> campaign tables, sync / drain / ring / stats
 //   ysb_submit.cpp  batches: slots, raw lines, device batches, the layout samples, the launches
+//   ysb_columns.cpp the columnar decode and the columnar count's submits
 //   ysb_layout.h    the layout sampling's rules (no HIP: tests/native/layout_logic.cpp)
 //   ysb_admap.h     the join tables as host data (no HIP: tests/native/admap_logic.cpp)
 //   ysb_recplan.h   record mode's plan of a launch (no HIP: tests/native/recplan_logic.cpp)
@@ -318,6 +319,18 @@ struct ysb_ctx {
     // columnar decode (ysb_columns.cpp): {valid rows, fast-tier rows} of a call, its event pair
     DevBuf<unsigned long long> d_colinfo;
     Event ev_col[2];
+    // columnar count (ysb_columns.cpp): the last columnar launch (ysb_columns_launch_info)
+    ysb_colcount_desc last_col{};
+    bool col_launched = false;
+};
+
+// One host -> device copy of a slot: the source's device address (the copy kernel) and its
+// host address (YSB_F_H2D_SDMA); 0 bytes: none.
+struct SlotCopy {
+    void* dst;
+    const void* dsrc;
+    const void* hsrc;
+    u64 bytes;
 };
 
 #define YSB_INTERNAL __attribute__((visibility("hidden")))
@@ -356,6 +369,13 @@ YSB_INTERNAL int move_ring(ysb_ctx* c, i64 new_lo);
 YSB_INTERNAL int fold_delta(ysb_ctx* c);         // record mode's u8 delta ring into the u64 ring
 // ysb_submit.cpp
 YSB_INTERNAL int launch_pending_raw(ysb_ctx* c); // the raw batch awaiting its launch
+YSB_INTERNAL int ensure_slots(ysb_ctx* c);       // the pinned slots and their device buffers
+// n copies of a slot on the copy stream once its previous kernel has run; ev_h2d[slot] marks them done
+YSB_INTERNAL int copy_slot_ranges(ysb_ctx* c, int slot, const SlotCopy* v, int n);
+// the out-of-ring map emptied into the host list if an earlier launch left it a quarter full
+YSB_INTERNAL int drain_side_if_due(ysb_ctx* c);
+// the context's join tables, ring, out-of-ring map and stats as a launch's parameters (no batch)
+YSB_INTERNAL void context_params(ysb_ctx* c, ScanParams* out);
 // ysb_group.cpp
 YSB_INTERNAL bool grouped(const ysb_ctx* c);
 YSB_INTERNAL int agree_ring(ysb_ctx* c);

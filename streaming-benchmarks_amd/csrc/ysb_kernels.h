@@ -259,6 +259,28 @@ struct ColParams {
 };
 void launch_columns(const ColParams& p, int cus, hipStream_t s);
 
+// Columnar count (ysb_count_columns.h, ysb_submit_columns*): rows [0, n_rows) of a batch in the
+// seven-column layout through filter, join and window count.  Reads rows < n_rows of columns 2
+// (ad_id), 4 (event_type) and 5 (event_time) and, with validity, the bitmap words
+// [0, ceil(n_rows / 64)) -- nothing else of cols.  sp: the context's join tables, ring,
+// out-of-ring map and stats as a scan launch gets them (its batch, segment, deferred-line and
+// record fields are not used; used_out as for defer_kernel).  Two instantiations: parallel
+// probes of the cache-resident slots, serial probes of the HBM bucket table (sp.probe_serial).
+struct ColCountParams {
+    ScanParams sp;
+    const u8* cols;             // 16-byte aligned
+    u64 start[8];               // byte offsets of the columns, [7] the validity bitmap (page multiples)
+    u64 n_rows;
+    u64 n_tiles;                // ceil(n_rows / TILE_LINES)
+    u32 java_order;             // 1: column 5 big-endian (YSB_COL_JAVA_ORDER)
+    u32 validity;               // 1: rows with a zero validity bit are parse errors (YSB_COL_VALIDITY)
+};
+void launch_colcount(const ColCountParams& p, int cus, hipStream_t s);
+// Right behind it: *sp.used_out <- the out-of-ring map's fill level (nothing if used_out is null).
+void launch_colcount_level(const ColCountParams& p, hipStream_t s);
+// Sets ring[0..1] from the batch's first 256 rows if ring[1] == 0 (launch_ring_autobase's rule).
+void launch_colcount_autobase(const ColCountParams& p, hipStream_t s);
+
 // Generator kernels (ysb_gen.hip).
 hipError_t gen_events_device(const GenSpec& spec, u64 first, u64 n, u8* d_out, u64 cap,
                              u32* d_off, u64* nbytes, hipStream_t s);

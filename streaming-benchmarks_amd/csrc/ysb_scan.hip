@@ -1256,3 +1256,4 @@ int scan_lds_bytes() { return LDS_BYTES; }
 }  // namespace ysb
 
 #include "ysb_scan_columns.h"
+#include "ysb_count_columns.h"

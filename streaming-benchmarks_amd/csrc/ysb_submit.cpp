@@ -174,6 +174,25 @@ static int plan_records(ysb_ctx* c, ScanParams& p, u64 n_events, RecParams& r) {
     return YSB_OK;
 }
 
+// The out-of-ring map's fill level after an earlier launch (read without waiting): a quarter
+// full empties it into the exact host list before the next launch adds to it.
+int drain_side_if_due(ysb_ctx* c) {
+    if (c->used_pending && hipEventQuery(c->ev_used) == hipSuccess) {
+        c->used_pending = false;
+        if ((u64)*c->h_used * 4 > c->side_slots) {
+            int rc = sync_streams(c);
+            if (!rc) rc = pull_side_list(c);
+            if (rc) return rc;
+        }
+    }
+    return YSB_OK;
+}
+
+void context_params(ysb_ctx* c, ScanParams* out) {
+    const ysb_segment none{nullptr, 0, nullptr, 1};
+    *out = make_params(c, &none, 1, Layout{});
+}
+
 static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout& lay) {
     if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
     ysb_segment segs[MAX_SEGS];
@@ -190,16 +209,7 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout
         HIPCHK(c, c->d_defer_ctr.alloc(16 + 4 * MAX_SEGS));
         HIPCHK(c, hipMemset(c->d_defer_ctr, 0, 16 + 4 * MAX_SEGS));
     }
-    // the out-of-ring map's fill level after an earlier launch (read without waiting): a
-    // quarter full empties it into the exact host list before this launch adds to it
-    if (c->used_pending && hipEventQuery(c->ev_used) == hipSuccess) {
-        c->used_pending = false;
-        if ((u64)*c->h_used * 4 > c->side_slots) {
-            rc = sync_streams(c);
-            if (!rc) rc = pull_side_list(c);
-            if (rc) return rc;
-        }
-    }
+    if ((rc = drain_side_if_due(c))) return rc;
     ScanParams p = make_params(c, segs, nseg, lay);
     p.used_out = c->used_pending ? nullptr : c->h_used;
     p.defer = c->d_defer;
@@ -359,7 +369,7 @@ static int sample_device_layout(ysb_ctx* c, const ysb_segment* segs, u32 nseg, L
     return YSB_OK;
 }
 
-static int ensure_slots(ysb_ctx* c) {
+int ensure_slots(ysb_ctx* c) {
     if (c->h_bytes[0]) return YSB_OK;
     HIPCHK(c, hipSetDevice(c->device));
     for (int s = 0; s < 2; ++s) {
@@ -385,28 +395,26 @@ static hipError_t h2d(ysb_ctx* c, void* dst, const void* dsrc, const void* hsrc,
     return hipGetLastError();
 }
 
-// A slot's copies (up to two; 0 bytes: none) on the copy stream once the slot's previous
-// kernel has run -- its device buffers are free then -- with YSB_F_TIMING inside an event
-// pair (ysb_copy_time); ev_h2d[slot] marks them done.
-struct SlotCopy {
-    void* dst;
-    const void* dsrc;   // the source's device address (the copy kernel) ...
-    const void* hsrc;   // ... and its host address (YSB_F_H2D_SDMA)
-    u64 bytes;
-};
-static int copy_slot(ysb_ctx* c, int slot, const SlotCopy& a, const SlotCopy& b = {}) {
+// A slot's copies (0 bytes: none) on the copy stream once the slot's previous kernel has run
+// -- its device buffers are free then -- with YSB_F_TIMING inside an event pair
+// (ysb_copy_time); ev_h2d[slot] marks them done.  (SlotCopy: ysb_ctx.h)
+int copy_slot_ranges(ysb_ctx* c, int slot, const SlotCopy* v, int n) {
     HIPCHK(c, wait_unless_done(c->s_copy, c->ev_kdone[slot]));
     Event* ce = nullptr;
     if (c->cfg.flags & YSB_F_TIMING) {
         HIPCHK(c, c->cev.acquire(&ce));
-        c->copy_bytes += a.bytes + b.bytes;
+        for (int i = 0; i < n; ++i) c->copy_bytes += v[i].bytes;
         HIPCHK(c, hipEventRecord(ce[0], c->s_copy));
     }
-    if (a.bytes) HIPCHK(c, h2d(c, a.dst, a.dsrc, a.hsrc, a.bytes));
-    if (b.bytes) HIPCHK(c, h2d(c, b.dst, b.dsrc, b.hsrc, b.bytes));
+    for (int i = 0; i < n; ++i)
+        if (v[i].bytes) HIPCHK(c, h2d(c, v[i].dst, v[i].dsrc, v[i].hsrc, v[i].bytes));
     if (ce) HIPCHK(c, hipEventRecord(ce[1], c->s_copy));
     HIPCHK(c, hipEventRecord(c->ev_h2d[slot], c->s_copy));
     return YSB_OK;
+}
+static int copy_slot(ysb_ctx* c, int slot, const SlotCopy& a, const SlotCopy& b = {}) {
+    const SlotCopy v[2] = {a, b};
+    return copy_slot_ranges(c, slot, v, 2);
 }
 
 int ysb_slot_buffers(ysb_ctx* c, int slot, uint8_t** bytes, uint32_t** line_off) {

@@ -521,6 +521,43 @@ void GpuAdCampaignOperator::submit() {
     waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+void GpuAdCampaignOperator::submitColumnsFile(const std::string& path, uint64_t rows) {
+    ysb_columns_layout lay;
+    uint64_t off[4], len[4];
+    uint32_t nr = 0;
+    if (ysb_columns_layout_of(rows, &lay) || ysb_columns_read_ranges(rows, rows, YSB_COL_JAVA_ORDER, off, len, &nr))
+        throw std::runtime_error("window.size must be in [1, 2^31 - 1]");
+    if (lay.image_bytes > o_.batchBytes) throw std::runtime_error("a column image exceeds the slot");
+    const int fd = ::open(path.c_str(), O_RDONLY);
+    if (fd < 0) throw std::runtime_error("cannot open " + path);
+    struct stat sb;
+    if (fstat(fd, &sb) != 0 || (uint64_t)sb.st_size != lay.image_bytes) {
+        const long long got = (long long)sb.st_size;
+        ::close(fd);
+        throw std::runtime_error(path + ": " + std::to_string(got) + " bytes, not the " +
+                                 std::to_string(lay.image_bytes) + " of an image of " + std::to_string(rows) + " rows");
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t i = 0; i < nr; ++i) {
+        for (uint64_t done = 0; done < len[i];) {
+            const ssize_t k = pread(fd, bytes_[cur_] + off[i] + done, len[i] - done, (off_t)(off[i] + done));
+            if (k <= 0) {
+                ::close(fd);
+                throw std::runtime_error("cannot read " + path);
+            }
+            done += (uint64_t)k;
+        }
+    }
+    ::close(fd);
+    fillS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    check(ysb_submit_columns(ctx_, cur_, bytes_[cur_], rows, rows, YSB_COL_JAVA_ORDER), "ysb_submit_columns");
+    submitted_ += rows;
+    cur_ ^= 1;
+    const auto t1 = std::chrono::steady_clock::now();
+    check(ysb_wait(ctx_, cur_), "ysb_wait");   // the other slot's H2D is done: refill it
+    waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+}
+
 void GpuAdCampaignOperator::copyTime(double* ms, uint64_t* copies, uint64_t* bytes) {
     check(ysb_copy_time(ctx_, ms, copies, bytes), "ysb_copy_time");
 }

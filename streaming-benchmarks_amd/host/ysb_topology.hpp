@@ -159,6 +159,11 @@ public:
     void registerSource(FileBasedDataSource& src);         // pin + map the source's mapping (mappedIo)
     uint64_t submitMapped(FileBasedDataSource& src);       // the next whole lines, read in place: bytes
     void submit();                                         // hand the open slot to the GPU
+    // One file image of WindowedArrowFormatBolter (<shared_file>_<k>, :303-317) of `rows` rows
+    // counted from its columns (ysb_submit_columns, longs big-endian): only the ranges the count
+    // reads are read from the file, straight into the open slot.  Throws, naming the file, if
+    // its size is not the layout's image_bytes.
+    void submitColumnsFile(const std::string& path, uint64_t rows);
     std::vector<WindowDelta> flushWindows();               // CampaignProcessorCommon.flushWindows (:91-98)
     void close();                                          // RichFlatMapFunction.close
     ysb_stats stats();

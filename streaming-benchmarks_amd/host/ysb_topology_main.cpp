@@ -5,6 +5,7 @@
 // (or to a CSV file).
 //
 //   ysb_topology --confPath PATH --columns [--device N] [--format json|tbl] [--require-ip]
+//   ysb_topology --confPath PATH --from-columns [--device N] [--sink ...] [--window-ring W]
 //   ysb_topology --confPath PATH [--device N] [--sink none|csv:FILE|redis[:HOST[:PORT]]]
 //                [--format json|tbl] [--flush-ms MS] [--batch-mb MB | --batch-bytes B] [--batch-events N]
 //                [--window-ring W] [--require-ip] [--dry-run] [--print-config]
@@ -41,6 +42,7 @@ struct Args {
     unsigned window_ring = 1024;
     bool require_ip = false, dry = false, print_config = false, host_split = false;
     bool columns = false;                       // --columns: the columnar chain (:106-109)
+    bool from_columns = false;                  // --from-columns: count <shared_file>_<k> images
     long long repeat = 1;
     unsigned io_threads = 0;
     bool io_mmap = true;
@@ -69,6 +71,8 @@ void usage() {
                  "       [--h2d-sdma]\n"
                  "   or: ysb_topology --confPath PATH --columns [--device N] [--format json|tbl] [--require-ip]\n"
                  "       [--batch-mb MB | --batch-bytes B]   (window.size rows per <shared_file>_<k>)\n"
+                 "   or: ysb_topology --confPath PATH --from-columns [--device N] [--sink none|csv:FILE|redis[:HOST[:PORT]]]\n"
+                 "                    [--window-ring W]\n"
                  "   or: ysb_topology --stream [--sink none|csv:FILE|redis[:HOST[:PORT]]] [--shards N] [--device D]\n"
                  "       [--seed S] [--campaigns C] [--ads-per-campaign A] [--event-rate E] [--speedup F]\n"
                  "       [--cycle-ms MS] [--flush-ms MS] [--batch-ms MS] [--ooo-ms MS] [--seconds S]\n"
@@ -110,6 +114,7 @@ Args parse(int argc, char** argv) {
         }
         else if (k == "--h2d-sdma") a.h2d_sdma = true;
         else if (k == "--columns") a.columns = true;
+        else if (k == "--from-columns") a.from_columns = true;
         else if (k == "--stream") a.stream = true;
         else if (k == "--stream-self-check") { a.stream = true; a.self_check = true; }
         else if (k == "--shards") a.so.shards = std::atoi(val().c_str());
@@ -142,6 +147,10 @@ Args parse(int argc, char** argv) {
         std::fprintf(stderr, "--columns reads events_path in batch mode: not with --stream\n");
         std::exit(2);
     }
+    if (a.from_columns && (a.stream || a.columns)) {
+        std::fprintf(stderr, "--from-columns counts the images --columns wrote: not with --stream or --columns\n");
+        std::exit(2);
+    }
     if (a.stream) {   // the generator's ids and events: no config file needed
         a.so.device = a.device;
         a.so.flushMs = a.flush_ms;
@@ -169,6 +178,28 @@ std::string json_str(const std::string& s) {
 
 double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// --sink none | csv:FILE | redis[:HOST[:PORT]] (the host defaults to the config's redis.host);
+// false (after the usage text) for anything else.
+bool open_sink(const Args& a, const Config& conf, std::unique_ptr<RedisWindowWriter>& redis, std::string& csv_path) {
+    if (a.sink.rfind("redis", 0) == 0) {
+        std::string host = conf.get("redis.host", "localhost");
+        int port = 6379;
+        const std::string rest = a.sink.size() > 6 ? a.sink.substr(6) : "";
+        if (!rest.empty()) {
+            const size_t c = rest.rfind(':');
+            host = c == std::string::npos ? rest : rest.substr(0, c);
+            if (c != std::string::npos) port = std::atoi(rest.c_str() + c + 1);
+        }
+        redis.reset(new RedisWindowWriter(host, port));
+    } else if (a.sink.rfind("csv:", 0) == 0) {
+        csv_path = a.sink.substr(4);
+    } else if (a.sink != "none") {
+        usage();
+        return false;
+    }
+    return true;
 }
 
 int run(const Args& a) {
@@ -245,22 +276,7 @@ int run(const Args& a) {
     std::unique_ptr<RedisWindowWriter> redis;
     CsvWindowSink csv;
     std::string csv_path;
-    if (a.sink.rfind("redis", 0) == 0) {
-        std::string host = conf.get("redis.host", "localhost");
-        int port = 6379;
-        const std::string rest = a.sink.size() > 6 ? a.sink.substr(6) : "";
-        if (!rest.empty()) {
-            const size_t c = rest.rfind(':');
-            host = c == std::string::npos ? rest : rest.substr(0, c);
-            if (c != std::string::npos) port = std::atoi(rest.c_str() + c + 1);
-        }
-        redis.reset(new RedisWindowWriter(host, port));
-    } else if (a.sink.rfind("csv:", 0) == 0) {
-        csv_path = a.sink.substr(4);
-    } else if (a.sink != "none") {
-        usage();
-        return 2;
-    }
+    if (!open_sink(a, conf, redis, csv_path)) return 2;
 
     if (!a.replay.empty()) {   // the sink alone: rows from a CSV, one flush
         std::vector<WindowDelta> d;
@@ -449,6 +465,73 @@ int run_columns(const Args& a) {
     return 0;
 }
 
+// --from-columns: the consumer of --columns -- the accelerator behind WindowedArrowFormatBolter
+// (AdvertisingTopologyNative.java:278-356).  Loads ad_to_campaign_path, reads <shared_file>_0,
+// _1, ... up to the first missing index, each the image_bytes of window.size rows with big-endian
+// longs and no validity bitmap (the reference's mapping), counts them through the filter -> join
+// -> window-count chain (:115-119) from their columns (ysb_submit_columns, slots 0 and 1
+// alternating) and flushes to the sink as the batch mode does.  A file of another size fails
+// the job, naming it.
+int run_from_columns(const Args& a) {
+    const Config conf = Config::findAndReadConfigFile(a.conf, true);
+    const AdCampaignMap map = AdCampaignMap::fromFile(conf.get("ad_to_campaign_path"));
+    const std::string shared = conf.get("shared_file");
+    const long long window = conf.getLong("window.size");
+    if (window <= 0 || window > 0x7FFFFFFFll) throw std::runtime_error("window.size must be in [1, 2^31 - 1]");
+    ysb_columns_layout lay;
+    if (ysb_columns_layout_of((uint64_t)window, &lay)) throw std::runtime_error("ysb_columns_layout_of failed");
+    std::unique_ptr<RedisWindowWriter> redis;
+    CsvWindowSink csv;
+    std::string csv_path;
+    if (!open_sink(a, conf, redis, csv_path)) return 2;
+
+    GpuAdCampaignOperator::Options o;
+    o.device = a.device;
+    o.windowRing = a.window_ring;
+    o.batchBytes = lay.image_bytes;
+    o.batchEvents = 64;   // (the slots' line offsets are not used)
+    o.h2dSdma = a.h2d_sdma;
+    const double t0 = now_s();
+    GpuAdCampaignOperator op(map, o);
+    op.open();
+    uint64_t files = 0, rows = 0, flushes = 0;
+    auto flush = [&]() {
+        const std::vector<WindowDelta> d = op.flushWindows();
+        rows += d.size();
+        ++flushes;
+        if (redis) redis->writeWindows(d);
+        if (!csv_path.empty()) csv.add(d);
+    };
+    double last_flush = now_s();
+    for (;; ++files) {
+        const std::string path = shared + "_" + std::to_string(files);
+        std::FILE* f = std::fopen(path.c_str(), "rb");
+        if (!f) break;   // the first missing index ends the job
+        std::fclose(f);
+        op.submitColumnsFile(path, (uint64_t)window);
+        if (a.flush_ms > 0 && (now_s() - last_flush) * 1000.0 >= (double)a.flush_ms) {
+            flush();
+            last_flush = now_s();
+        }
+    }
+    op.close();
+    flush();
+    const double el = now_s() - t0;
+    if (!csv_path.empty()) csv.write(csv_path);
+    const ysb_stats s = op.stats();
+    std::printf("{\"mode\": \"from_columns\", \"files\": %llu, \"rows\": %llu, \"views\": %llu, \"joined\": %llu, "
+                "\"join_misses\": %llu, \"out_of_ring\": %llu, \"overflow_dropped\": %llu, \"batches\": %llu, "
+                "\"rows_written\": %llu, \"flushes\": %llu, \"window_size\": %lld, \"image_bytes\": %llu, "
+                "\"bytes_read_per_row\": 48, \"seconds\": %.3f, \"rows_per_s\": %.1f, \"sink\": %s, "
+                "\"shared_file\": %s}\n",
+                (unsigned long long)files, (unsigned long long)s.events, (unsigned long long)s.views,
+                (unsigned long long)s.joined, (unsigned long long)s.join_misses, (unsigned long long)s.out_of_ring,
+                (unsigned long long)s.overflow_dropped, (unsigned long long)s.batches, (unsigned long long)rows,
+                (unsigned long long)flushes, window, (unsigned long long)lay.image_bytes, el,
+                el > 0 ? (double)s.events / el : 0.0, json_str(a.sink).c_str(), json_str(shared).c_str());
+    return s.overflow_dropped ? 3 : 0;
+}
+
 double pct(std::vector<double> v, double q) {
     if (v.empty()) return 0;
     std::sort(v.begin(), v.end());
@@ -566,6 +649,7 @@ int main(int argc, char** argv) {
         }
         if (a.stream) return run_stream(a);
         if (a.columns) return run_columns(a);
+        if (a.from_columns) return run_from_columns(a);
         return run(a);
     } catch (const std::exception& e) {   // the job fails, as the reference's uncaught exceptions do
         std::fprintf(stderr, "ysb_topology: %s\n", e.what());

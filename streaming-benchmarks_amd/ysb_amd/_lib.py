@@ -93,6 +93,7 @@ class YsbSegment(C.Structure):
 
 
 YSB_COL_JAVA_ORDER = 0x1
+YSB_COL_VALIDITY = 0x2
 
 
 class YsbColumnsLayout(C.Structure):
@@ -103,6 +104,11 @@ class YsbColumnsLayout(C.Structure):
 class YsbDecodeInfo(C.Structure):
     _fields_ = [("rows", C.c_uint64), ("valid", C.c_uint64), ("fast_rows", C.c_uint64),
                 ("kernel_ms", C.c_double)]
+
+
+class YsbColcountDesc(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("lds_counters", C.c_uint32), ("hbm_table", C.c_uint32),
+                ("java_order", C.c_uint32), ("validity", C.c_uint32)]
 
 
 class YsbGenParams(C.Structure):
@@ -152,6 +158,11 @@ SIGNATURES = {
     "ysb_columns_layout_of": (_I, [_U64, C.POINTER(YsbColumnsLayout)]),
     "ysb_decode_columns_device": (_I, [_P, _PU8, _U64, _PU32, _U64, _PU8, _U64, _I64, _U32,
                                        C.POINTER(YsbDecodeInfo)]),
+    "ysb_columns_read_ranges": (_I, [_U64, _U64, _U32, C.POINTER(_U64), C.POINTER(_U64), C.POINTER(_U32)]),
+    "ysb_submit_columns_device": (_I, [_P, _PU8, _U64, _U64, _U32]),
+    "ysb_submit_columns": (_I, [_P, _I, _PU8, _U64, _U64, _U32]),
+    "ysb_columns_launch_info": (_I, [_P, C.POINTER(YsbColcountDesc)]),
+    "ysb_colcount_desc_size": (_U64, []),
     "ysb_sync": (_I, [_P]),
     "ysb_drain": (_I, [_P, _I64, _I64, _I, C.POINTER(YsbCount), _U64, C.POINTER(_U64)]),
     "ysb_stats_get": (_I, [_P, C.POINTER(YsbStats)]),
@@ -233,6 +244,9 @@ def lib():
         if L.ysb_record_desc_size() != C.sizeof(YsbRecordDesc):
             raise ImportError("ysb_record_desc is %d bytes in the library, %d in this binding"
                               % (L.ysb_record_desc_size(), C.sizeof(YsbRecordDesc)))
+        if L.ysb_colcount_desc_size() != C.sizeof(YsbColcountDesc):
+            raise ImportError("ysb_colcount_desc is %d bytes in the library, %d in this binding"
+                              % (L.ysb_colcount_desc_size(), C.sizeof(YsbColcountDesc)))
         _lib = L
     return _lib
 

@@ -44,6 +44,16 @@ def columns_layout(rows):
             "image_bytes": lay.image_bytes}
 
 
+def columns_read_ranges(rows, n_rows, flags=0):
+    """ysb_columns_read_ranges: the [(offset, bytes), ...] a columnar count of rows [0, n_rows)
+    of a batch of `rows` rows reads -- columns 2 (ad_id), 4 (event_type) and 5 (event_time),
+    then with YSB_COL_VALIDITY the bitmap words: what a caller must make visible to the device
+    and what submit_columns copies."""
+    off, nb, n = (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), C.c_uint32()
+    check(lib().ysb_columns_read_ranges(int(rows), int(n_rows), int(flags), off, nb, C.byref(n)), None)
+    return [(int(off[i]), int(nb[i])) for i in range(n.value)]
+
+
 def rank_device(local_rank, n_visible):
     """The device a rank uses (one context per GPU): its LOCAL_RANK, unless the launcher left
     each process fewer visible devices (e.g. one per rank through HIP_VISIBLE_DEVICES): then
@@ -257,6 +267,32 @@ class YsbContext:
         words = image[columns_layout(rows)["start"][7]:][:8 * ((n + 63) // 64)].view("<u8")
         valid = ((words[np.arange(n) // 64] >> (np.arange(n) % 64).astype(np.uint64)) & np.uint64(1)).astype(np.bool_)
         return image, valid, info
+
+    # -- columnar count ----------------------------------------------------------------
+    def submit_columns_device(self, d_cols, batch_rows, n_rows, flags=0):
+        """ysb_submit_columns_device: rows [0, n_rows) of a device-resident column batch
+        (columns_layout(batch_rows); with YSB_COL_VALIDITY up to start[8]) through filter, join
+        and window count.  Asynchronous on the compute stream."""
+        self._c(lib().ysb_submit_columns_device(self._h, C.c_void_p(d_cols), int(batch_rows), int(n_rows),
+                                                int(flags)))
+
+    def submit_columns(self, image, batch_rows, n_rows, slot=0, flags=0):
+        """ysb_submit_columns: the host form.  image: a uint8 array (or bytes) holding the batch,
+        or the address of the slot's own pinned buffer (slot_buffers(slot)[0]); only
+        columns_read_ranges' bytes are copied.  wait(slot) before the slot is rewritten."""
+        if isinstance(image, int):
+            ptr = C.c_void_p(image)
+        else:
+            image = np.frombuffer(image, dtype=np.uint8) if isinstance(image, (bytes, bytearray)) else np.ascontiguousarray(image, dtype=np.uint8)
+            ptr = _ptr(image)
+        self._c(lib().ysb_submit_columns(self._h, slot, ptr, int(batch_rows), int(n_rows), int(flags)))
+
+    def columns_launch_info(self):
+        """The last columnar launch (ysb_columns_launch_info): rows, lds_counters, hbm_table,
+        java_order, validity.  Raises YSB_ERR_STATE before the first one."""
+        d = _lib.YsbColcountDesc()
+        self._c(lib().ysb_columns_launch_info(self._h, C.byref(d)))
+        return {n: getattr(d, n) for n, _ in _lib.YsbColcountDesc._fields_}
 
     # -- results -----------------------------------------------------------------------
     def drain(self, bucket_lo=INT64_MIN, bucket_hi=(1 << 63) - 1, clear=False):
