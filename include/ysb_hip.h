@@ -259,6 +259,80 @@ int         ysb_load_ad_map_packed_shard(ysb_ctx* ctx, const char* keys, uint32_
                                          const uint32_t* campaign_idx, uint64_t n,
                                          uint32_t rank, uint32_t nranks);
 
+/* ---- the live map: HashMap.put while the stream runs ------------------------------
+ * RedisAdCampaignCache.execute puts an ad into its HashMap the first time it is seen
+ * (RedisAdCampaignCache.java:23-35), and getAdCampaignMap's put lets a later entry win
+ * (AdvertisingTopologyNative.java:47-56).  ysb_ad_map_upsert is that put on the context's
+ * device tables: new ad ids are added, known ones get the campaign given, by kernels on the
+ * compute stream between two launches -- no host rebuild, no upload of the tables.  (Additive
+ * within ABI 6, as the columnar calls.) */
+typedef struct ysb_upsert_info {
+    uint64_t entries;        /* n as given = foreign + duplicates + updated + inserted            */
+    uint64_t foreign;        /* skipped: ysb_ad_shard(key, shard_n) != shard_rank (as load_*_shard) */
+    uint64_t duplicates;     /* earlier entries of a key given more than once (the last one wins)  */
+    uint64_t updated;        /* keys already in the map: campaign rewritten                        */
+    uint64_t inserted;       /* new keys                                                           */
+    uint64_t cuckoo_first, cuckoo_second;  /* new 36-byte keys placed in their first / second slot or bucket */
+    uint64_t cuckoo_moved;   /* ... placed by the eviction chain                                   */
+    uint64_t cuckoo_left_out;/* ... in the general table only: the table is now partial            */
+    uint32_t rebuilt;        /* 1: the tables were rebuilt at new sizes (see below)                */
+    uint32_t partial;        /* some 36-byte key is in the general table only, after the call      */
+    double   device_ms;      /* HIP events around the call's kernels (0 when rebuilt)              */
+} ysb_upsert_info;
+/* HashMap.put of entry 0, 1, ..., n - 1 in this order (ids as ysb_load_ad_map takes them:
+ * exact byte strings of at most 56 bytes, length 0 allowed, NULL lens = 36 each): after the
+ * call the map equals a fresh ysb_load_ad_map of the old entries followed by these.
+ * Stream order: batches submitted before the call join against the old map, batches
+ * submitted after it against the new one (a raw batch still awaiting its launch is launched
+ * first).  The call returns when the change is applied and its counters are read back: it
+ * waits for the compute stream, as a load does.
+ * Every entry is checked before any device work: YSB_ERR_FORMAT for a campaign index >=
+ * n_campaigns or an id above 56 bytes, YSB_ERR_ARG for a NULL id of nonzero length,
+ * YSB_ERR_STATE before the first load (a load of n = 0 is a valid empty map); a rejected call
+ * changes nothing.  n = 0 changes nothing and fills info.  An id given more than once counts
+ * with its last campaign; on a sharded context (ysb_load_ad_map_shard) the ids of other
+ * shards are skipped (foreign).
+ * The call works in place exactly while the sizing rules of a load still hold for the grown
+ * map: distinct keys <= table_slots / 2, and 36-byte keys in the cuckoo table <= ctable_slots
+ * / 4 (slot layout) or <= ctable_slots / 2 (bucket layout; ysb_ad_map_info) -- an upserted
+ * table is never denser than a fresh load's could be.  Otherwise it rebuilds (rebuilt = 1):
+ * the general table is read back, merged with the call's entries, and built, uploaded and
+ * committed as by ysb_load_ad_map, with that call's failure guarantees for the tables (the
+ * campaigns of the call's known keys may already be rewritten when a rebuild fails); the
+ * layout may change between slots and buckets.  In place a new 36-byte key that finds both
+ * its slots or buckets full goes through the loader's eviction chain; the key in hand when
+ * the kicks run out stays in the general table only (cuckoo_left_out, partial = 1 until the
+ * next load or rebuild: the scan then defers cuckoo misses to the general table, so the join
+ * stays exact).  YSB_F_SPARSE_FAST_JOIN (test hook) leaves every other new 36-byte key of a
+ * call out of the cuckoo table.  At most 2^31 - 1 entries per call (YSB_ERR_CAPACITY).
+ * info may be NULL. */
+int         ysb_ad_map_upsert(ysb_ctx* ctx, const char* const* ad_ids, const uint32_t* ad_id_lens,
+                              const uint32_t* campaign_idx, uint64_t n, ysb_upsert_info* info);
+/* Same for n keys of key_len bytes packed back to back. */
+int         ysb_ad_map_upsert_packed(ysb_ctx* ctx, const char* keys, uint32_t key_len,
+                                     const uint32_t* campaign_idx, uint64_t n, ysb_upsert_info* info);
+uint64_t    ysb_upsert_info_size(void);
+
+/* out_campaign[i] = the campaign of key i or 0xFFFFFFFF; out_where[i] = 0 absent, 1 / 2 in
+ * the cuckoo table, in the key's first / second slot or bucket, 3 in the general table only
+ * (a key of another length than 36, or a 36-byte key the cuckoo table left out).  Either
+ * array may be NULL.  A device kernel over the live tables, on the compute stream behind
+ * everything submitted; waits for it.  YSB_ERR_STATE before the first load, YSB_ERR_FORMAT
+ * for an id above 56 bytes, YSB_ERR_ARG for a NULL id of nonzero length. */
+int         ysb_ad_map_lookup(ysb_ctx* ctx, const char* const* ad_ids, const uint32_t* ad_id_lens,
+                              uint64_t n, uint32_t* out_campaign, uint32_t* out_where);
+
+/* The map as the context holds it: keys distinct ad ids, keys36 of them in the cuckoo table
+ * (ctable_slots slots, or with buckets = 1 that many 3-entry buckets), table_slots slots of the
+ * general table, partial as in ysb_upsert_info, the shard of the last load.  No device work.
+ * YSB_ERR_STATE before the first load. */
+typedef struct ysb_admap_desc {
+    uint64_t keys, keys36, table_slots, ctable_slots;
+    uint32_t buckets, partial, shard_rank, shard_n;
+} ysb_admap_desc;
+int         ysb_ad_map_info(ysb_ctx* ctx, ysb_admap_desc* out);
+uint64_t    ysb_admap_desc_size(void);
+
 /* ---- batches --------------------------------------------------------------------
  * A batch is n_events JSON lines packed back to back in `bytes`; line i spans
  * [line_off[i], line_off[i+1]) (the last one ends at nbytes).  This replaces the

@@ -288,6 +288,8 @@ int ysb_load_ad_map_shard(ysb_ctx* c, const char* const* ad_ids, const uint32_t*
 // tables plus the new ones), and the context takes nothing before both copies are done: a
 // failed allocation leaves the old map whole and in use.  Only a failed copy into a buffer
 // that is reused (same size) has damaged the map in use: submits then fail as before a load.
+static int commit_tables(ysb_ctx* c, const JoinTables& jt);
+
 static int load_map(ysb_ctx* c, const char* const* ad_ids, const uint32_t* lens, const uint32_t* campaign_idx,
                     uint64_t n) {
     // the tables live on this context's GPU, whichever device the calling thread last set
@@ -298,6 +300,10 @@ static int load_map(ysb_ctx* c, const char* const* ad_ids, const uint32_t* lens,
     const int rc = build_join_tables(ad_ids, lens, campaign_idx, n, c->cfg.n_campaigns,
                                      (c->cfg.flags & YSB_F_SPARSE_FAST_JOIN) != 0, &jt, &err);
     if (rc) return fail(c, rc, "%s", err.c_str());
+    return commit_tables(c, jt);
+}
+
+static int commit_tables(ysb_ctx* c, const JoinTables& jt) {
     HIPCHK(c, hipStreamSynchronize(c->s_comp));
     const u64 tbytes = jt.table.size() * 4, cbytes = jt.ctable.size() * 4;
     DevBuf<u32> table, ctable;   // the new buffers of the tables that change size
@@ -316,9 +322,172 @@ static int load_map(ysb_ctx* c, const char* const* ad_ids, const uint32_t* lens,
     c->cseed = jt.cseed;
     c->ctable_buckets = jt.buckets;
     c->ctable_partial = jt.partial;
+    c->map_keys = jt.keys;
+    c->map_keys36 = jt.keys36;
     c->table_loaded = true;
     return YSB_OK;
 }
+
+// ---- the live map (ysb_ad_map_upsert, ysb_ad_map_lookup, ysb_ad_map_info) -----------------
+
+// The call's records on the device and the tables as the table kernels take them.
+static int upsert_params(ysb_ctx* c, const std::vector<u32>& rec, UpsertParams* p) {
+    const u64 n = rec.size() / SLOT_WORDS;
+    int rc = grow_device(c, c->d_up_rec, rec.size() * 4, 64u << 10);
+    if (!rc) rc = first_use(c, c->d_up_ctr, UP_COUNT_ * 4);
+    if (rc) return rc;
+    if (!c->h_up_ctr) HIPCHK(c, c->h_up_ctr.alloc(UP_COUNT_ * 4));
+    HIPCHK(c, hipMemcpyAsync(c->d_up_rec, rec.data(), rec.size() * 4, hipMemcpyHostToDevice, c->s_comp));
+    *p = UpsertParams{};
+    p->table = c->d_table;
+    p->table_mask = (u32)(c->table_slots - 1);
+    p->ctable = c->d_ctable;
+    p->ctable_mask = (u32)(c->ctable_slots - 1);
+    p->buckets = c->ctable_buckets ? 1u : 0u;
+    p->sparse = (c->cfg.flags & YSB_F_SPARSE_FAST_JOIN) ? 1u : 0u;
+    p->cseed = c->cseed;
+    p->rec = c->d_up_rec;
+    p->n = (u32)n;
+    p->ctr = c->d_up_ctr;
+    p->rng = upsert_rng(c->cseed, c->map_keys);
+    return YSB_OK;
+}
+
+// The counters after the kernels queued so far (one small pinned read; waits).
+static int upsert_counters(ysb_ctx* c) {
+    HIPCHK(c, hipMemcpyAsync(c->h_up_ctr, c->d_up_ctr, UP_COUNT_ * 4, hipMemcpyDeviceToHost, c->s_comp));
+    HIPCHK(c, hipStreamSynchronize(c->s_comp));
+    return YSB_OK;
+}
+
+// The rebuild: the general table read back, the call's records merged in, the tables of the
+// grown map built and committed as a load's.
+static int upsert_rebuild(ysb_ctx* c, const std::vector<u32>& rec) {
+    std::vector<u32> table(c->table_slots * SLOT_WORDS), merged;
+    HIPCHK(c, hipMemcpy(table.data(), c->d_table, table.size() * 4, hipMemcpyDeviceToHost));
+    upsert_merge(table.data(), c->table_slots, rec.data(), rec.size() / SLOT_WORDS, &merged);
+    std::vector<u32>().swap(table);
+    JoinTables jt;
+    std::string err;
+    const int rc = build_join_tables_rec(merged, c->cfg.n_campaigns, (c->cfg.flags & YSB_F_SPARSE_FAST_JOIN) != 0, &jt, &err);
+    if (rc) return fail(c, rc, "%s", err.c_str());
+    return commit_tables(c, jt);
+}
+
+int ysb_ad_map_upsert(ysb_ctx* c, const char* const* ad_ids, const uint32_t* lens, const uint32_t* campaign_idx,
+                      uint64_t n, ysb_upsert_info* info) {
+    if (!c) return YSB_ERR_ARG;
+    if (n && (!ad_ids || !campaign_idx)) return fail(c, YSB_ERR_ARG, "NULL ad map arrays");
+    if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
+    if (n >= (1ull << 31)) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 entries per upsert");
+    ysb_upsert_info out{};
+    std::vector<u32> rec;
+    std::string err;
+    int rc = upsert_records(ad_ids, lens, campaign_idx, n, c->cfg.n_campaigns, c->shard_rank, c->shard_n, &rec,
+                            &out.foreign, &out.duplicates, &err);
+    if (rc) return fail(c, rc, "%s", err.c_str());
+    out.entries = n;
+    out.partial = c->ctable_partial ? 1u : 0u;
+    const u64 nrec = rec.size() / SLOT_WORDS;
+    if (nrec) {
+        if ((rc = launch_pending_raw(c))) return rc;   // a batch submitted before the call joins against the old map
+        HIPCHK(c, hipSetDevice(c->device));
+        UpsertParams p;
+        if ((rc = upsert_params(c, rec, &p))) return rc;
+        if ((rc = grow_device(c, c->d_up_fresh, nrec * 4, 16u << 10))) return rc;
+        if ((rc = grow_device(c, c->d_up_homeless, nrec * 4, 16u << 10))) return rc;
+        p.fresh = c->d_up_fresh;
+        p.homeless = c->d_up_homeless;
+        for (Event& e : c->ev_up)
+            if (!e.h) HIPCHK(c, e.create(hipEventDefault));
+        HIPCHK(c, hipMemsetAsync(c->d_up_ctr, 0, UP_COUNT_ * 4, c->s_comp));
+        HIPCHK(c, hipEventRecord(c->ev_up[0], c->s_comp));
+        launch_upsert_classify(p, c->s_comp);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = upsert_counters(c))) return rc;
+        const u32* k = c->h_up_ctr;
+        out.updated = k[UP_UPDATED];
+        out.inserted = k[UP_NEW];
+        const u64 n_new = k[UP_NEW], n_new36 = k[UP_NEW36];
+        if (!upsert_fits(c->map_keys + n_new, c->map_keys36 + n_new36, c->table_slots, c->ctable_slots, c->ctable_buckets)) {
+            if ((rc = upsert_rebuild(c, rec))) return rc;
+            out.rebuilt = 1;
+        } else {
+            if (n_new) {
+                launch_upsert_insert(p, (u32)n_new, c->s_comp);
+                if (n_new36) launch_upsert_evict(p, c->s_comp);
+                HIPCHK(c, hipGetLastError());
+            }
+            HIPCHK(c, hipEventRecord(c->ev_up[1], c->s_comp));
+            if ((rc = upsert_counters(c))) return rc;
+            float ms = 0;
+            HIPCHK(c, hipEventElapsedTime(&ms, c->ev_up[0], c->ev_up[1]));
+            out.device_ms = ms;
+            out.cuckoo_first = k[UP_FIRST];
+            out.cuckoo_second = k[UP_SECOND];
+            out.cuckoo_moved = k[UP_MOVED];
+            out.cuckoo_left_out = k[UP_LEFT_OUT];
+            if (out.cuckoo_left_out) c->ctable_partial = true;   // until the next load or rebuild
+            c->map_keys += n_new;
+            c->map_keys36 += out.cuckoo_first + out.cuckoo_second + out.cuckoo_moved;
+        }
+        out.partial = c->ctable_partial ? 1u : 0u;
+    }
+    if (info) *info = out;
+    return YSB_OK;
+}
+
+int ysb_ad_map_upsert_packed(ysb_ctx* c, const char* keys, uint32_t key_len, const uint32_t* campaign_idx,
+                             uint64_t n, ysb_upsert_info* info) {
+    if (!c) return YSB_ERR_ARG;
+    if (n && (!keys || !campaign_idx)) return fail(c, YSB_ERR_ARG, "NULL ad map arrays");
+    std::vector<const char*> ptr(n);
+    std::vector<u32> len(n, key_len);
+    for (u64 i = 0; i < n; ++i) ptr[i] = keys + i * key_len;
+    return ysb_ad_map_upsert(c, ptr.data(), len.data(), campaign_idx, n, info);
+}
+
+uint64_t ysb_upsert_info_size(void) { return sizeof(ysb_upsert_info); }
+
+int ysb_ad_map_lookup(ysb_ctx* c, const char* const* ad_ids, const uint32_t* lens, uint64_t n, uint32_t* out_campaign,
+                      uint32_t* out_where) {
+    if (!c) return YSB_ERR_ARG;
+    if (n && !ad_ids) return fail(c, YSB_ERR_ARG, "NULL ad ids");
+    if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
+    if (n >= (1ull << 31)) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 ids per lookup");
+    std::vector<u32> rec(n * SLOT_WORDS, 0);
+    for (u64 i = 0; i < n; ++i) {
+        const u32 len = lens ? lens[i] : 36u;
+        if (len > MAX_KEY_BYTES) return fail(c, YSB_ERR_FORMAT, "ad id %llu longer than %u bytes", (unsigned long long)i, MAX_KEY_BYTES);
+        if (!ad_ids[i] && len) return fail(c, YSB_ERR_ARG, "ad id %llu is NULL", (unsigned long long)i);
+        rec[i * SLOT_WORDS] = len;
+        if (len) std::memcpy(&rec[i * SLOT_WORDS + 2], ad_ids[i], len);
+    }
+    if (!n) return YSB_OK;
+    int rc = launch_pending_raw(c);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    UpsertParams p;
+    if ((rc = upsert_params(c, rec, &p))) return rc;
+    if ((rc = grow_device(c, c->d_up_out, 2 * n * 4, 32u << 10))) return rc;
+    u32* d_where = c->d_up_out + n;
+    launch_admap_lookup(p, c->d_up_out, d_where, c->s_comp);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->s_comp));
+    if (out_campaign) HIPCHK(c, hipMemcpy(out_campaign, c->d_up_out, n * 4, hipMemcpyDeviceToHost));
+    if (out_where) HIPCHK(c, hipMemcpy(out_where, d_where, n * 4, hipMemcpyDeviceToHost));
+    return YSB_OK;
+}
+
+int ysb_ad_map_info(ysb_ctx* c, ysb_admap_desc* out) {
+    if (!c || !out) return YSB_ERR_ARG;
+    if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
+    *out = ysb_admap_desc{c->map_keys, c->map_keys36, c->table_slots, c->ctable_slots, c->ctable_buckets ? 1u : 0u,
+                          c->ctable_partial ? 1u : 0u, c->shard_rank, c->shard_n};
+    return YSB_OK;
+}
+
+uint64_t ysb_admap_desc_size(void) { return sizeof(ysb_admap_desc); }
 
 void poll_ring(ysb_ctx* c) {
     if (c->ring_known || !c->ring_query_pending) return;

@@ -4,7 +4,8 @@
 //   ysb_submit.cpp  batches: slots, raw lines, device batches, the layout samples, the launches
 //   ysb_columns.cpp the columnar decode and the columnar count's submits
 //   ysb_layout.h    the layout sampling's rules (no HIP: tests/native/layout_logic.cpp)
-//   ysb_admap.h     the join tables as host data (no HIP: tests/native/admap_logic.cpp)
+//   ysb_admap.h     the join tables as host data and the live map's rules (no HIP:
+//                   tests/native/admap_logic.cpp, upsert_logic.cpp)
 //   ysb_recplan.h   record mode's plan of a launch (no HIP: tests/native/recplan_logic.cpp)
 //   ysb_group.cpp   multi-GPU: the RCCL / host-collective group and the keyBy exchange
 //   ysb_gen_api.cpp the synthetic generator (host and device) and its truth tables
@@ -196,6 +197,14 @@ struct ysb_ctx {
     bool ctable_partial = false;
     bool table_loaded = false;
     u32 shard_rank = 0, shard_n = 1;      // the join table's shard (ysb_load_ad_map_shard)
+    // the live map (ysb_ad_map_upsert): the distinct keys and the 36-byte keys in the cuckoo
+    // table, from the build and from each upsert (what upsert_fits decides by); the call's
+    // records, new-key and homeless lists and counters on the device, the counters' pinned
+    // mirror, the event pair around its kernels
+    u64 map_keys = 0, map_keys36 = 0;
+    DevBuf<u32> d_up_rec, d_up_fresh, d_up_homeless, d_up_ctr, d_up_out;
+    PinBuf<u32> h_up_ctr;
+    Event ev_up[2];
     // counts
     u32 c_pad = 0;                        // campaigns padded to the group size
     DevBuf<unsigned long long> d_counts;      // [c_pad][W]

@@ -309,4 +309,35 @@ void launch_side_clear(SideSlot* t, u64 slots, hipStream_t s);
 void launch_side_compact(const SideSlot* t, u64 slots, u32 cbits, bool count_only, TableRow* out, u32* out_n,
                          u32 cap, hipStream_t s);
 
+// Join-table kernels (ysb_upsert.hip): ysb_ad_map_upsert's three passes over n records of
+// distinct keys in the general table's slot format {len, campaign, 14 key words} (the rules:
+// ysb_admap.h), and ysb_ad_map_lookup's probe of the live tables.
+enum : u32 {
+    UP_NEW = 0, UP_NEW36, UP_UPDATED,          // classify: new keys, new 36-byte keys, known keys
+    UP_FIRST, UP_SECOND, UP_HOMELESS,          // insert: first-fit placements, keys with both full
+    UP_MOVED, UP_LEFT_OUT,                     // evict (and insert: the sparse hook's keys)
+    UP_COUNT_ = 16
+};
+constexpr u32 UP_LEAVE_OUT = 0x80000000u;      // fresh[]: the sparse hook keeps this key out of the cuckoo table
+struct UpsertParams {
+    u32* table;                 // the general table
+    u32 table_mask;
+    u32* ctable;                // the 36-byte-key cuckoo table
+    u32 ctable_mask;
+    u32 buckets;                // 1: bucket layout
+    u32 sparse;                 // YSB_F_SPARSE_FAST_JOIN
+    CuckooSeed cseed;
+    const u32* rec;             // [n][SLOT_WORDS]
+    u32 n;
+    u32* fresh;                 // [n] the new keys' record indices (| UP_LEAVE_OUT), classify's output
+    u32* homeless;              // [n] records whose slots / buckets were both full, insert's output
+    u32* ctr;                   // [UP_COUNT_], zero before classify
+    u64 rng;                    // the eviction draws' first state (upsert_rng)
+};
+void launch_upsert_classify(const UpsertParams& p, hipStream_t s);
+void launch_upsert_insert(const UpsertParams& p, u32 n_new, hipStream_t s);
+void launch_upsert_evict(const UpsertParams& p, hipStream_t s);   // over ctr[UP_HOMELESS] keys, one thread
+// out_campaign[i], out_where[i] of record i's key (ysb_ad_map_lookup)
+void launch_admap_lookup(const UpsertParams& p, u32* out_campaign, u32* out_where, hipStream_t s);
+
 }  // namespace ysb

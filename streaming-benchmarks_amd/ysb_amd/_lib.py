@@ -111,6 +111,17 @@ class YsbColcountDesc(C.Structure):
                 ("java_order", C.c_uint32), ("validity", C.c_uint32)]
 
 
+class YsbUpsertInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("entries", "foreign", "duplicates", "updated", "inserted", "cuckoo_first",
+                                          "cuckoo_second", "cuckoo_moved", "cuckoo_left_out")] + [
+                ("rebuilt", C.c_uint32), ("partial", C.c_uint32), ("device_ms", C.c_double)]
+
+
+class YsbAdmapDesc(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("keys", "keys36", "table_slots", "ctable_slots")] + [
+                (n, C.c_uint32) for n in ("buckets", "partial", "shard_rank", "shard_n")]
+
+
 class YsbGenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_campaigns", C.c_uint32), ("ads_per_campaign", C.c_uint32),
                 ("t0_ms", C.c_int64), ("events_per_sec", C.c_uint64), ("with_skew", C.c_uint32),
@@ -141,6 +152,13 @@ SIGNATURES = {
     "ysb_load_ad_map_packed": (_I, [_P, C.c_void_p, _U32, C.c_void_p, _U64]),
     "ysb_load_ad_map_shard": (_I, [_P, C.POINTER(C.c_char_p), C.POINTER(_U32), C.POINTER(_U32), _U64, _U32, _U32]),
     "ysb_load_ad_map_packed_shard": (_I, [_P, C.c_void_p, _U32, C.c_void_p, _U64, _U32, _U32]),
+    "ysb_ad_map_upsert": (_I, [_P, C.POINTER(C.c_char_p), C.POINTER(_U32), C.POINTER(_U32), _U64,
+                               C.POINTER(YsbUpsertInfo)]),
+    "ysb_ad_map_upsert_packed": (_I, [_P, C.c_void_p, _U32, C.c_void_p, _U64, C.POINTER(YsbUpsertInfo)]),
+    "ysb_upsert_info_size": (_U64, []),
+    "ysb_ad_map_lookup": (_I, [_P, C.POINTER(C.c_char_p), C.POINTER(_U32), _U64, _PU32, _PU32]),
+    "ysb_ad_map_info": (_I, [_P, C.POINTER(YsbAdmapDesc)]),
+    "ysb_admap_desc_size": (_U64, []),
     "ysb_slot_buffers": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_P)]),
     "ysb_submit": (_I, [_P, _I, _PU8, _U64, _PU32, _U64]),
     "ysb_wait": (_I, [_P, _I]),
@@ -247,6 +265,10 @@ def lib():
         if L.ysb_colcount_desc_size() != C.sizeof(YsbColcountDesc):
             raise ImportError("ysb_colcount_desc is %d bytes in the library, %d in this binding"
                               % (L.ysb_colcount_desc_size(), C.sizeof(YsbColcountDesc)))
+        for fn, st in ((L.ysb_upsert_info_size, YsbUpsertInfo), (L.ysb_admap_desc_size, YsbAdmapDesc)):
+            if fn() != C.sizeof(st):
+                raise ImportError("%s is %d bytes in the library, %d in this binding"
+                                  % (st.__name__, fn(), C.sizeof(st)))
         _lib = L
     return _lib
 

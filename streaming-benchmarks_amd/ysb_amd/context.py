@@ -148,6 +148,55 @@ class YsbContext:
         rank, nranks = shard if shard is not None else (0, 1)
         self._c(lib().ysb_load_ad_map_packed_shard(self._h, _ptr(k), key_len, _ptr(cidx), cidx.size, rank, nranks))
 
+    # -- the live map ------------------------------------------------------------------
+    @staticmethod
+    def _id_arrays(ad_ids):
+        keys = [a.encode() if isinstance(a, str) else bytes(a) for a in ad_ids]
+        n = len(keys)
+        return n, (C.c_char_p * max(n, 1))(*keys), (C.c_uint32 * max(n, 1))(*[len(k) for k in keys])
+
+    @staticmethod
+    def _upsert_info(info):
+        return {n: getattr(info, n) for n, _ in _lib.YsbUpsertInfo._fields_}
+
+    def upsert_ad_map(self, ad_ids, campaign_idx):
+        """HashMap.put of each (ad id, campaign index) in order on the live device tables
+        (ysb_ad_map_upsert): new ads are added, known ones re-pointed, in stream order between
+        the batches submitted before and after.  Returns ysb_upsert_info as a dict (entries,
+        foreign, duplicates, updated, inserted, cuckoo_first / _second / _moved / _left_out,
+        rebuilt, partial, device_ms)."""
+        n, arr, lens = self._id_arrays(ad_ids)
+        camp = (C.c_uint32 * max(n, 1))(*[int(c) for c in campaign_idx])
+        info = _lib.YsbUpsertInfo()
+        self._c(lib().ysb_ad_map_upsert(self._h, arr, lens, camp, n, C.byref(info)))
+        return self._upsert_info(info)
+
+    def upsert_ad_map_packed(self, keys, campaign_idx, key_len=36):
+        """upsert_ad_map for a uint8 array of n * key_len key bytes and n uint32 campaign indices."""
+        k = np.ascontiguousarray(keys, dtype=np.uint8)
+        cidx = np.ascontiguousarray(campaign_idx, dtype=np.uint32)
+        if k.size != cidx.size * key_len:
+            raise ValueError("keys must hold n * key_len bytes")
+        info = _lib.YsbUpsertInfo()
+        self._c(lib().ysb_ad_map_upsert_packed(self._h, _ptr(k), key_len, _ptr(cidx), cidx.size, C.byref(info)))
+        return self._upsert_info(info)
+
+    def lookup_ads(self, ad_ids):
+        """(campaign, where) uint32 arrays of the ids in the live tables (ysb_ad_map_lookup):
+        campaign 0xFFFFFFFF for an absent id; where 0 absent, 1 / 2 the cuckoo table's first /
+        second slot or bucket, 3 the general table only."""
+        n, arr, lens = self._id_arrays(ad_ids)
+        camp, where = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        self._c(lib().ysb_ad_map_lookup(self._h, arr, lens, n, _ptr(camp), _ptr(where)))
+        return camp, where
+
+    def ad_map_info(self):
+        """ysb_ad_map_info as a dict: keys, keys36, table_slots, ctable_slots, buckets, partial,
+        shard_rank, shard_n."""
+        d = _lib.YsbAdmapDesc()
+        self._c(lib().ysb_ad_map_info(self._h, C.byref(d)))
+        return {n: getattr(d, n) for n, _ in _lib.YsbAdmapDesc._fields_}
+
     # -- batches -----------------------------------------------------------------------
     def slot_buffers(self, slot):
         b, o = C.c_void_p(), C.c_void_p()
