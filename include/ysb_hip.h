@@ -333,6 +333,68 @@ typedef struct ysb_admap_desc {
 int         ysb_ad_map_info(ysb_ctx* ctx, ysb_admap_desc* out);
 uint64_t    ysb_admap_desc_size(void);
 
+/* ---- parked views: jedis.get for an ad the map does not hold ------------------------
+ * RedisAdCampaignCache.execute asks Redis for an ad its HashMap misses, puts what it finds and
+ * drops only a view whose ad Redis does not know either (RedisAdCampaignCache.java:23-35);
+ * prepare() starts that HashMap empty.  With parking enabled a view whose ad is in no device
+ * table is not counted as a join miss: it is parked on the device as a self-contained record
+ * (its decoded ad_id, whether Long.parseLong(event_time) succeeded, the parsed value) until the
+ * caller has looked the ad up.  The caller's loop after a batch (or several):
+ *     ysb_parked_keys    -> the distinct ad ids parked (one lookup per ad, not per view)
+ *     its own lookup        (Redis GET, a database, ...)
+ *     ysb_ad_map_upsert  -> the ads found, into the live tables
+ *     ysb_parked_resolve -> every parked view counted as if its ad had been known from the
+ *                           start; the views of the ads still unknown become join misses
+ * Then the counts, and events, views, joined, join_misses, time_errors and out_of_ring of
+ * ysb_stats, are those of a run whose map was complete from the start -- the reference's, as
+ * long as Redis does not change during the run.  While records are parked
+ *     views == joined + join_misses + foreign_shard + parked (ysb_parked_info).
+ * A view parks where the join reaches its final verdict: in the deferred-line kernel (with
+ * parking enabled every scan launch sends its fast-tier misses there, the route a partial or
+ * sharded table already takes) and at the columnar count's miss.  An ad_id above 56 bytes
+ * cannot be a map key and stays a join miss; on a sharded context only a key of this rank's
+ * shard parks, a foreign one stays foreign_shard.  (Additive within ABI 6.)
+ * Limits: one GPU (ysb_group_init refuses a context with parking enabled, and the reverse), and
+ * a caller that flushes windows before it resolves sees the parked counts as later deltas. */
+typedef struct ysb_parked_desc {
+    uint64_t capacity;            /* records the log holds (0: parking is off)                      */
+    uint64_t parked;              /* records parked now                                             */
+    uint64_t parked_total;        /* records parked since ysb_open / ysb_reset (dropped not among them) */
+    uint64_t dropped;             /* views that found the log full: counted as join misses (sticky) */
+    uint64_t resolved_joined;     /* the last ysb_parked_resolve: records whose ad was found ...    */
+    uint64_t resolved_missed;     /* ... and was not (join misses)                                  */
+    uint64_t resolved_time_errors;/* ... found, but Long.parseLong had rejected the event_time      */
+    uint64_t distinct_keys;       /* the last ysb_parked_keys: distinct ad ids                      */
+    double   distinct_ms;         /* HIP events around the last distinct / resolve kernels          */
+    double   resolve_ms;
+} ysb_parked_desc;
+/* Allocates the log and the distinct-key table for `capacity` records (72 + ~72 bytes of HBM
+ * each) and enables parking for every later launch; 0 disables it and frees them.  Waits for
+ * everything submitted.  YSB_ERR_STATE before the first map load, after ysb_group_init, or while
+ * records are parked (resolve first); YSB_ERR_CAPACITY for a capacity of 2^30 or more. */
+int         ysb_parked_enable(ysb_ctx* ctx, uint64_t capacity);
+/* Waits for everything submitted, then: *n = the distinct ad ids among the parked records, and
+ * with keys != NULL key i's bytes at keys + 56 * i (zero-padded) and its length in lens[i], in
+ * no particular order.  keys == NULL: only the count.  YSB_ERR_CAPACITY, *n set, if cap (in
+ * keys) is short.  YSB_ERR_STATE with parking off.  Changes nothing. */
+int         ysb_parked_keys(ysb_ctx* ctx, char* keys, uint32_t* lens, uint64_t cap, uint64_t* n);
+/* Walks the log against the join tables as they are now, on the compute stream behind
+ * everything submitted (a raw batch awaiting its launch is launched first), and waits.  A
+ * record whose ad is found counts joined += 1 and then, like a view the scan joined,
+ * time_errors += 1 for a bad event_time or else one view in its (campaign, window) cell (the
+ * ring, or the out-of-ring map and out_of_ring); any other record counts join_misses += 1.  The
+ * log is then empty.  If no batch has fixed the ring's base yet it is the smallest bucket
+ * counted here minus window_ring / 8; counts do not depend on the base.  info may be NULL.
+ * YSB_ERR_STATE with parking off. */
+int         ysb_parked_resolve(ysb_ctx* ctx, ysb_parked_desc* info);
+/* The log's state after everything submitted (waits).  Valid, all zero, with parking off. */
+int         ysb_parked_info(ysb_ctx* ctx, ysb_parked_desc* info);
+uint64_t    ysb_parked_info_size(void);   /* sizeof(ysb_parked_desc) */
+/* A full log: the view is a join miss as without parking and dropped += 1; ysb_sync and the
+ * calls built on it then return YSB_ERR_CAPACITY until ysb_reset -- the counts are no longer
+ * the reference's, as after overflow_dropped (ysb_parked_keys, _resolve and _info still work).
+ * ysb_reset empties the log and zeroes these counters; parking stays enabled. */
+
 /* ---- batches --------------------------------------------------------------------
  * A batch is n_events JSON lines packed back to back in `bytes`; line i spans
  * [line_off[i], line_off[i+1]) (the last one ends at nbytes).  This replaces the

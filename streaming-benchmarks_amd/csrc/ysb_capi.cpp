@@ -539,6 +539,17 @@ static int check_capacity(ysb_ctx* c) {
                     "fallback list (overflow_capacity %llu) filled; counts are not exact "
                     "until ysb_reset (raise overflow_capacity or window_ring, or submit smaller batches)",
                     (unsigned long long)v[ST_OVF_DROPPED], (unsigned long long)c->cfg.overflow_capacity);
+    if (c->park_cap) {   // a full log of parked views (ysb_parked_enable): those views were join misses
+        const int rc = park_counters(c);
+        if (rc) return rc;
+        const u64 dropped = ((u64)c->h_park_ctr[PK_DROPPED + 1] << 32) | c->h_park_ctr[PK_DROPPED];
+        if (dropped)
+            return fail(c, YSB_ERR_CAPACITY,
+                        "%llu views of unknown ads found the log of parked views full (capacity %llu) and "
+                        "were counted as join misses; counts are not the reference's until ysb_reset "
+                        "(raise the capacity or resolve more often)",
+                        (unsigned long long)dropped, (unsigned long long)c->park_cap);
+    }
     if ((c->cfg.flags & YSB_F_STRICT) && (v[ST_PARSE_ERR] || v[ST_TIME_ERR] || v[ST_FOREIGN]))
         return fail(c, YSB_ERR_DATA,
                     "strict mode: %llu lines JSONObject/getString would throw on, %llu event_times "
@@ -842,6 +853,7 @@ int ysb_reset(ysb_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->s_comp));
     HIPCHK(c, hipMemset(c->d_side_used, 0, 4));
     HIPCHK(c, hipMemset(c->d_stats, 0, ST_COUNT_ * 8));
+    if ((rc = park_reset(c))) return rc;   // the log of parked views emptied; parking stays enabled
     c->side.clear();
     c->batches = 0;
     return YSB_OK;

@@ -151,7 +151,8 @@ static int enqueue_colcount(ysb_ctx* c, const u8* d_cols, const ysb_columns_layo
         HIPCHK(c, c->tev.acquire(&te));
         HIPCHK(c, hipEventRecord(te[0], c->s_comp));
     }
-    launch_colcount(p, c->cus, c->s_comp);
+    ParkParams park;
+    launch_colcount(p, c->cus, c->s_comp, park_params(c, &park) ? &park : nullptr);
     HIPCHK(c, hipGetLastError());
     if (te) HIPCHK(c, hipEventRecord(te[1], c->s_comp));
     launch_colcount_level(p, c->s_comp);   // the map's fill level into h_used (sp.used_out)

@@ -157,9 +157,12 @@ __device__ __forceinline__ i64 cc_time(u32 t0, u32 t1, u32 java_order) {
     return (i64)(((u64)t1 << 32) | (u64)t0);
 }
 
-template <bool SERIAL>
+// PARK (parking enabled, ysb_parked.h): a view whose ad is in no table is appended to the log K
+// at the tile's park site -- the key and the time are in registers -- instead of being counted
+// as a join miss.
+template <bool SERIAL, bool PARK>
 __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu(CC_WG_PER_CU / 4)))
-void colcount_kernel(const ColCountParams C) {
+void colcount_kernel(const ColCountParams C, const ParkParams K) {
     const ScanParams& P = C.sp;
     __shared__ __attribute__((aligned(16))) u32 keys[CC_KEY_DW];
     __shared__ u32 lcnt[LCNT_CAP];
@@ -229,9 +232,17 @@ void colcount_kernel(const ColCountParams C) {
         // ---- the next tile's blocks land while this one is probed and counted --------------
         cc_issue(C, t + (u64)CC_PF * gridDim.x, tid, pre);
         // ---- join result, bucket, count ------------------------------------------------------
+        ParkLane pl;
+        pl.want = false;
         if (view) {
             const u32 ci = cc_probe_finish<SERIAL>(P, kw, pr);
-            if (ci == EMPTY_SLOT) {
+            if (PARK && ci == EMPTY_SLOT && park_wanted(true, key_hash_dev(kw, 36u), P.shard_rank, P.shard_n)) {
+                pl.want = pl.tok = true;   // (a column time is an int64 already: no parse to fail)
+#pragma unroll
+                for (int k = 0; k < (int)KEY_WORDS; ++k) pl.kw[k] = kw[k];
+                pl.klen = 36u;
+                pl.tv = cc_time(t0, t1, C.java_order);
+            } else if (ci == EMPTY_SLOT) {
                 count_miss(P, kw, 36u, true, tl);   // a join miss, or a key of another shard
             } else {
                 tl.join++;
@@ -249,6 +260,7 @@ void colcount_kernel(const ColCountParams C) {
                 }
             }
         }
+        if constexpr (PARK) park_append(K, pl, tl);
         __syncthreads();   // the tile's keys are read and its counts are in before the next one
     };
     ColTile pre[CC_PF];
@@ -315,13 +327,18 @@ __global__ __launch_bounds__(AUX_TPB) void colcount_autobase_kernel(const ColCou
 // after a scan).
 __global__ void colcount_used_kernel(const u32* side_used, u32* used_out) { *used_out = *side_used; }
 
-void launch_colcount(const ColCountParams& p, int cus, hipStream_t s) {
+void launch_colcount(const ColCountParams& p, int cus, hipStream_t s, const ParkParams* park) {
     if (p.n_rows == 0) return;
     // whole rounds of resident workgroups over the tiles (each walks tiles blockIdx.x + k * grid)
     const u64 resident = (u64)(cus > 0 ? cus : 1) * (u64)CC_WG_PER_CU;
     const dim3 g((u32)(p.n_tiles < resident ? p.n_tiles : resident)), b(SCAN_TPB);
-    if (p.sp.probe_serial) hipLaunchKernelGGL(colcount_kernel<true>, g, b, 0, s, p);
-    else hipLaunchKernelGGL(colcount_kernel<false>, g, b, 0, s, p);
+    if (park) {
+        if (p.sp.probe_serial) hipLaunchKernelGGL((colcount_kernel<true, true>), g, b, 0, s, p, *park);
+        else hipLaunchKernelGGL((colcount_kernel<false, true>), g, b, 0, s, p, *park);
+    } else {
+        if (p.sp.probe_serial) hipLaunchKernelGGL((colcount_kernel<true, false>), g, b, 0, s, p, ParkParams{});
+        else hipLaunchKernelGGL((colcount_kernel<false, false>), g, b, 0, s, p, ParkParams{});
+    }
 }
 
 void launch_colcount_level(const ColCountParams& p, hipStream_t s) {

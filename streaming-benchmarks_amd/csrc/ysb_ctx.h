@@ -7,6 +7,8 @@
 //   ysb_admap.h     the join tables as host data and the live map's rules (no HIP:
 //                   tests/native/admap_logic.cpp, upsert_logic.cpp)
 //   ysb_recplan.h   record mode's plan of a launch (no HIP: tests/native/recplan_logic.cpp)
+//   ysb_parked_api.cpp  parked views: the log of the views of unknown ads, its keys, its resolve
+//   ysb_parked.h    their record format, rules and host model (no HIP: tests/native/parked_logic.cpp)
 //   ysb_group.cpp   multi-GPU: the RCCL / host-collective group and the keyBy exchange
 //   ysb_gen_api.cpp the synthetic generator (host and device) and its truth tables
 // Internal: nothing here is part of the ABI (the shared helpers have hidden visibility).
@@ -205,6 +207,18 @@ struct ysb_ctx {
     DevBuf<u32> d_up_rec, d_up_fresh, d_up_homeless, d_up_ctr, d_up_out;
     PinBuf<u32> h_up_ctr;
     Event ev_up[2];
+    // parked views (ysb_parked_api.cpp; ysb_parked.h): park_cap records of PARK_WORDS words (0:
+    // parking is off), the device counters and their pinned mirror, the distinct kernel's slot
+    // table (park_slots of them) and compacted output, the resolve's campaign per record, the
+    // event pair around the log's kernels; what earlier resolves took out of the log, and the
+    // last distinct / resolve call's figures
+    u64 park_cap = 0, park_slots = 0;
+    DevBuf<u32> d_park_log, d_park_ctr, d_park_slots, d_park_lens, d_park_camp;
+    DevBuf<u8> d_park_keys;
+    PinBuf<u32> h_park_ctr;
+    Event ev_park[2];
+    u64 park_resolved_total = 0;
+    ysb_parked_desc park_last{};
     // counts
     u32 c_pad = 0;                        // campaigns padded to the group size
     DevBuf<unsigned long long> d_counts;      // [c_pad][W]
@@ -385,6 +399,12 @@ YSB_INTERNAL int copy_slot_ranges(ysb_ctx* c, int slot, const SlotCopy* v, int n
 YSB_INTERNAL int drain_side_if_due(ysb_ctx* c);
 // the context's join tables, ring, out-of-ring map and stats as a launch's parameters (no batch)
 YSB_INTERNAL void context_params(ysb_ctx* c, ScanParams* out);
+// ysb_parked_api.cpp
+// the context's log as a launch's park sites take it; false: parking is off
+YSB_INTERNAL bool park_params(const ysb_ctx* c, ParkParams* out);
+// the log's device counters into h_park_ctr (a small read on the compute stream; waits for it)
+YSB_INTERNAL int park_counters(ysb_ctx* c);
+YSB_INTERNAL int park_reset(ysb_ctx* c);         // ysb_reset's part: the log emptied, the counters zero
 // ysb_group.cpp
 YSB_INTERNAL bool grouped(const ysb_ctx* c);
 YSB_INTERNAL int agree_ring(ysb_ctx* c);

@@ -107,6 +107,7 @@ int ysb_group_init(ysb_ctx* c, int rank, int nranks, const uint8_t uid[YSB_UNIQU
     if (!c || !uid) return YSB_ERR_ARG;
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(c, YSB_ERR_ARG, "bad rank %d / %d", rank, nranks);
     if (grouped(c)) return fail(c, YSB_ERR_STATE, "group already initialised");
+    if (c->park_cap) return fail(c, YSB_ERR_STATE, "parked views are enabled (ysb_parked_enable): one GPU only");
     HIPCHK(c, hipSetDevice(c->device));
     ncclUniqueId id;
     std::memcpy(&id, uid, sizeof id);
@@ -124,6 +125,7 @@ int ysb_group_init_host(ysb_ctx* c, int rank, int nranks, const ysb_collectives*
     if (!c || !ops || !ops->allreduce_max_u64 || !ops->reduce_scatter_sum) return YSB_ERR_ARG;
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(c, YSB_ERR_ARG, "bad rank %d / %d", rank, nranks);
     if (grouped(c)) return fail(c, YSB_ERR_STATE, "group already initialised");
+    if (c->park_cap) return fail(c, YSB_ERR_STATE, "parked views are enabled (ysb_parked_enable): one GPU only");
     HIPCHK(c, hipSetDevice(c->device));
     c->hops = *ops;
     c->host_coll = true;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ysb_common.h"
+#include "ysb_parked.h"    // the parked views' record format and counters
 #include "ysb_recplan.h"   // TILE_LINES, MAX_TILES_PER_BLOCK and record mode's REC_* constants
 
 namespace ysb {
@@ -234,9 +235,18 @@ void launch_sample(const SampleSegs& s, u32 nseg, u8* out, hipStream_t st);
 
 constexpr int N_STAMPS = 8;     // phases timed by the YSB_STAMPS diagnostic build
 
+// Parked views (ysb_parked.h): the context's log as the park sites (defer_kernel, the columnar
+// count) and the log's own kernels (ysb_parked.hip) take it.
+struct ParkParams {
+    u32* log;                   // [cap][PARK_WORDS]
+    u32 cap;                    // records the log holds
+    u32* ctr;                   // [PK_COUNT_] (ysb_parked.h)
+};
+
 void launch_scan(const ScanParams& p, hipStream_t s);
-// The general-path lines the scan deferred (same stream, right after launch_scan).
-void launch_defer(const ScanParams& p, int blocks, hipStream_t s);
+// The general-path lines the scan deferred (same stream, right after launch_scan).  park: the
+// log that takes the views whose ad is in no table (null: they are join misses).
+void launch_defer(const ScanParams& p, int blocks, hipStream_t s, const ParkParams* park = nullptr);
 // Sets ring[0..1] from the first lines of a batch (JSON, or .tbl rows with p.tbl) if ring[1] == 0.
 void launch_ring_autobase(const ScanParams& p, hipStream_t s);
 
@@ -275,7 +285,7 @@ struct ColCountParams {
     u32 java_order;             // 1: column 5 big-endian (YSB_COL_JAVA_ORDER)
     u32 validity;               // 1: rows with a zero validity bit are parse errors (YSB_COL_VALIDITY)
 };
-void launch_colcount(const ColCountParams& p, int cus, hipStream_t s);
+void launch_colcount(const ColCountParams& p, int cus, hipStream_t s, const ParkParams* park = nullptr);   // park: as launch_defer's
 // Right behind it: *sp.used_out <- the out-of-ring map's fill level (nothing if used_out is null).
 void launch_colcount_level(const ColCountParams& p, hipStream_t s);
 // Sets ring[0..1] from the batch's first 256 rows if ring[1] == 0 (launch_ring_autobase's rule).
@@ -339,5 +349,17 @@ void launch_upsert_insert(const UpsertParams& p, u32 n_new, hipStream_t s);
 void launch_upsert_evict(const UpsertParams& p, hipStream_t s);   // over ctr[UP_HOMELESS] keys, one thread
 // out_campaign[i], out_where[i] of record i's key (ysb_ad_map_lookup)
 void launch_admap_lookup(const UpsertParams& p, u32* out_campaign, u32* out_where, hipStream_t s);
+
+
+// The log's own kernels (ysb_parked.hip).  distinct: one representative per distinct key of
+// records [0, n) -- slots[0, mask] all EMPTY_SLOT before, ctr[PK_DISTINCT] zero -- compacted
+// into out_keys (PARK_KEY_STRIDE bytes each) and out_lens, ctr[PK_DISTINCT] of them.
+void launch_parked_distinct(const ParkParams& k, u32 n, u32* slots, u32 mask, u8* out_keys, u32* out_lens,
+                            hipStream_t s);
+// resolve: records [0, n) against the general table as it is now (sp: context_params).  Three
+// launches: probe (camp[i] <- campaign or EMPTY_SLOT; the smallest bucket to be counted into
+// ctr[PK_MINB], INT64_MAX before), base (the ring base from it if none is set), count (stats,
+// ctr[PK_JOINED / PK_MISSED / PK_TIME_ERR], the ring through global_add, *sp.pend_dirty).
+void launch_parked_resolve(const ScanParams& sp, const ParkParams& k, u32 n, u32* camp, hipStream_t s);
 
 }  // namespace ysb

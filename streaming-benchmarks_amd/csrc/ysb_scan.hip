@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "ysb_kernels.h"
+#include "ysb_ring_add.h"
 
 // ---- diagnostic builds (make diag / variant; never used for results) ----------------------
 // Each flag cuts one part of the scan so that a profile attributes time to it: the results
@@ -299,10 +300,6 @@ __device__ __forceinline__ bool parse_digits_regs(const u32 (&w)[5], int len, i6
 
 namespace ysb {
 
-// One line end to end: returns 0 not counted, 1 counted (campaign/bucket set).
-// Per-thread tallies go to st[].
-struct Tally { u32 ev, view, join, miss, perr, terr, oor, frn; };
-
 // A view whose ad_id missed the table: dropped (RedisJoinBolt, :465-467) and counted as a
 // join miss -- or, when this context holds one shard of the table (P.shard_n > 1) and the
 // key belongs to another, as a foreign-shard view (mis-routed input).
@@ -312,10 +309,49 @@ __device__ __forceinline__ void count_miss(const ScanParams& P, const u32 (&kw)[
     else t.miss++;
 }
 
-// A parsed event's filter, join and bucket (the bolts after DeserializeBolt).
+// Parked views (ysb_parked.h): what a lane hands to its kernel's park site when its view got
+// the final miss verdict and may park -- the decoded key and Long.parseLong(event_time)'s
+// outcome (parsed here, tallied only at the resolve: the reference parses after the join).
+struct ParkLane {
+    bool want, tok;
+    u32 klen;
+    i64 tv;
+    u32 kw[KEY_WORDS];
+};
+
+// The park site: the wave's wanted lanes append their records to the log, one atomic per wave
+// (ballot and prefix count; the first wanted lane claims, as not every lane of a deferred-line
+// wave is still in its loop).  A lane whose slot lies past the log's end counts its view as the
+// join miss it would be without parking, and the wave adds such lanes to PK_DROPPED.  Once the
+// log is full nothing more is claimed, so PK_CLAIMED stays below capacity + the racing waves.
+__device__ __forceinline__ void park_append(const ParkParams& K, const ParkLane& pk, Tally& t) {
+    const unsigned long long m = __ballot(pk.want);
+    if (!m) return;
+    const int lane = threadIdx.x & 63, leader = (int)__builtin_ctzll(m);
+    const u32 n = (u32)__popcll(m);
+    u32 base = 0;
+    if (lane == leader) {
+        base = K.cap;
+        if (__hip_atomic_load(&K.ctr[PK_CLAIMED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < K.cap)
+            base = atomicAdd(&K.ctr[PK_CLAIMED], n);
+        const u32 room = base < K.cap ? K.cap - base : 0u;
+        if (n > room) atomicAdd(reinterpret_cast<unsigned long long*>(&K.ctr[PK_DROPPED]), (unsigned long long)(n - room));
+    }
+    base = __shfl(base, leader, 64);
+    if (pk.want) {
+        const u32 r = __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
+        if (base < K.cap && r < K.cap - base) park_pack(K.log + (u64)(base + r) * PARK_WORDS, pk.kw, pk.klen, pk.tok, pk.tv);
+        else t.miss++;
+    }
+}
+
+// A parsed event's filter, join and bucket (the bolts after DeserializeBolt).  pk (the
+// deferred-line kernel with parking enabled): a view whose ad is in no table is handed to the
+// park site instead of being counted as a miss, unless it cannot park (park_wanted).
 template <class S>
 __device__ __forceinline__ bool finish_line(const S& src, const Span& ad, const Span& et, const Span& tm,
-                                            const ScanParams& P, Tally& t, u32& campaign, i64& bucket) {
+                                            const ScanParams& P, Tally& t, u32& campaign, i64& bucket,
+                                            ParkLane* pk = nullptr) {
     if (!span_is_view(src, et)) return false;                // EventFilterBolt
     t.view++;
     u32 kw[KEY_WORDS];
@@ -323,6 +359,15 @@ __device__ __forceinline__ bool finish_line(const S& src, const Span& ad, const 
     int c = -1;
     const bool keyed = span_key(src, ad, kw, klen);
     if (keyed) c = probe(P.table, P.table_mask, kw, klen);   // RedisJoinBolt
+    if (c < 0 && pk && park_wanted(keyed, keyed ? key_hash_dev(kw, klen) : 0u, P.shard_rank, P.shard_n)) {
+        pk->want = true;
+#pragma unroll
+        for (int k = 0; k < (int)KEY_WORDS; ++k) pk->kw[k] = kw[k];
+        pk->klen = klen;
+        pk->tv = 0;
+        pk->tok = span_long(src, tm, pk->tv);
+        return false;
+    }
     if (c < 0) { count_miss(P, kw, klen, keyed, t); return false; }
     t.join++;
     i64 tv;
@@ -335,11 +380,11 @@ __device__ __forceinline__ bool finish_line(const S& src, const Span& ad, const 
 // The general path (lines that are not in the generator's layout).
 template <class S>
 __device__ __forceinline__ bool process_line(const S& src, int s, int e, const ScanParams& P,
-                                             Tally& t, u32& campaign, i64& bucket) {
+                                             Tally& t, u32& campaign, i64& bucket, ParkLane* pk = nullptr) {
     KeepCount k;
     t.ev++;
     if (!parse_line(src, s, e, P.require_mask, k)) { t.perr++; return false; }
-    return finish_line(src, k.ad, k.et, k.tm, P, t, campaign, bucket);
+    return finish_line(src, k.ad, k.et, k.tm, P, t, campaign, bucket, pk);
 }
 
 }  // namespace ysb
@@ -1046,7 +1091,7 @@ __device__ __forceinline__ int tbl_split(const S& src, int s, int& e, int (&p)[6
 
 template <class S>
 __device__ __forceinline__ bool process_tbl_line(const S& src, int s, int e, const ScanParams& P, Tally& t,
-                                                 u32& campaign, i64& bucket) {
+                                                 u32& campaign, i64& bucket, ParkLane* pk = nullptr) {
     t.ev++;
     int p[6];
     if (tbl_split(src, s, e, p) < 5) { t.perr++; return false; }
@@ -1055,7 +1100,7 @@ __device__ __forceinline__ bool process_tbl_line(const S& src, int s, int e, con
     for (int q = p[5]; !tail && q < e; ++q) tail = src.b(q) != '|';
     if (!tail) { t.perr++; return false; }
     return finish_line(src, Span{p[1] + 1, p[2], 0}, Span{p[3] + 1, p[4], 0}, Span{p[4] + 1, p[5], 0}, P, t, campaign,
-                       bucket);
+                       bucket, pk);
 }
 
 // Line `line` of the batch in P as the bytes [ls, le); false where the offsets are out of
@@ -1088,7 +1133,10 @@ constexpr int DEFER_STAGE_MAX = 4 * DEFER_REGION_DW - 16 - 16;   // line bytes s
 constexpr int DEFER_CHUNKS = (15 + DEFER_STAGE_MAX + 15) / 16;   // 16-B chunks a staged line can span
 static_assert(4 * DEFER_CHUNKS + 1 <= DEFER_REGION_DW, "staged chunks + the slack word fit the region");
 
-__global__ __launch_bounds__(DEFER_TPB) void defer_kernel(const ScanParams P0) {
+// PARK (parking enabled, ysb_parked.h): a view whose ad is in no table is appended to the log K
+// at the loop's park site instead of being counted as a join miss.
+template <bool PARK>
+__global__ __launch_bounds__(DEFER_TPB) void defer_kernel(const ScanParams P0, const ParkParams K) {
     __shared__ u32 stage[DEFER_TPB * DEFER_REGION_DW];
     ScanParams P = P0;   // batch fields: the segment of the line being parsed
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1118,6 +1166,9 @@ __global__ __launch_bounds__(DEFER_TPB) void defer_kernel(const ScanParams P0) {
         u32 campaign;
         i64 bucket;
         bool ok;
+        ParkLane pl;
+        pl.want = false;
+        ParkLane* const pk = PARK ? &pl : nullptr;
         const u64 a16 = ls & ~15ull;
         const int sh = (int)(ls - a16), len = (int)(le - ls);
         if (len <= DEFER_STAGE_MAX) {
@@ -1150,14 +1201,15 @@ __global__ __launch_bounds__(DEFER_TPB) void defer_kernel(const ScanParams P0) {
             }
             region[4 * nch] = 0u;                           // slack for word reads past the end
             const LdsSrc3 lsrc{(lds_u32*)region};
-            if (P.tbl) ok = process_tbl_line(lsrc, sh, sh + len, P, tl, campaign, bucket);
-            else if (flat_line(lsrc, sh, sh + len, P, tl, campaign, bucket, ok)) {}
-            else ok = process_line(lsrc, sh, sh + len, P, tl, campaign, bucket);
+            if (P.tbl) ok = process_tbl_line(lsrc, sh, sh + len, P, tl, campaign, bucket, pk);
+            else if (flat_line(lsrc, sh, sh + len, P, tl, campaign, bucket, ok, pk)) {}
+            else ok = process_line(lsrc, sh, sh + len, P, tl, campaign, bucket, pk);
         } else {
             const GlbSrc gsrc{P.bytes + ls, le - ls};
-            ok = P.tbl ? process_tbl_line(gsrc, 0, len, P, tl, campaign, bucket)
-                       : process_line(gsrc, 0, len, P, tl, campaign, bucket);
+            ok = P.tbl ? process_tbl_line(gsrc, 0, len, P, tl, campaign, bucket, pk)
+                       : process_line(gsrc, 0, len, P, tl, campaign, bucket, pk);
         }
+        if constexpr (PARK) park_append(K, pl, tl);
         if (ok) {
             global_add(P, ring_lo, ring_set, campaign, bucket, 1u, tl);
             *P.pend_dirty = 1u;   // the u64 ring holds pending counts now (the exchange reads it)
@@ -1239,9 +1291,11 @@ void launch_scan(const ScanParams& p, hipStream_t s) {
     else launch_scan_as<false, false>(p, s);
 }
 
-void launch_defer(const ScanParams& p, int blocks, hipStream_t s) {
+void launch_defer(const ScanParams& p, int blocks, hipStream_t s, const ParkParams* park) {
     if (p.n == 0) return;
-    hipLaunchKernelGGL(defer_kernel, dim3(YSB_DEFER_WG_PER_CU * blocks), dim3(DEFER_TPB), 0, s, p);
+    const dim3 g(YSB_DEFER_WG_PER_CU * blocks), b(DEFER_TPB);
+    if (park) hipLaunchKernelGGL(defer_kernel<true>, g, b, 0, s, p, *park);
+    else hipLaunchKernelGGL(defer_kernel<false>, g, b, 0, s, p, ParkParams{});
 }
 
 void launch_ring_autobase(const ScanParams& p, hipStream_t s) {

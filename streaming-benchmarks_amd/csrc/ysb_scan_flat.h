@@ -727,11 +727,11 @@ __device__ __forceinline__ bool learned_parse(const LdsSrc& src, int s, int e, c
 // The deferred-line kernel's use: true = decided here (ok = counted); false = nothing
 // counted, parse it in full.
 __device__ __forceinline__ bool flat_line(const LdsSrc3& src, int s, int e, const ScanParams& P, Tally& t,
-                                          u32& campaign, i64& bucket, bool& ok) {
+                                          u32& campaign, i64& bucket, bool& ok, ParkLane* pk = nullptr) {
     Span ad{0, 0, 0}, et{0, 0, 0}, tm{0, 0, 0};
     if (!flat_parse(src, s, e, P.require_mask, ad, et, tm)) return false;
     t.ev++;
-    ok = finish_line(src, ad, et, tm, P, t, campaign, bucket);
+    ok = finish_line(src, ad, et, tm, P, t, campaign, bucket, pk);
     return true;
 }
 
@@ -769,48 +769,6 @@ __device__ __forceinline__ bool canonical_bucket(const LdsSrc& src, const CanonB
     }
     if (ok) bucket = div_trunc(tv, P.div);
     return ok;
-}
-
-// Out-of-ring cell (c, b) += v in the device hash map; false if the key cannot express
-// the bucket or 64 probes find no slot (the caller then appends to the fallback list).
-__device__ __forceinline__ bool side_add(const ScanParams& P, u32 c, i64 b, u32 v) {
-    const i64 half = (i64)1 << (63 - P.side_cbits);
-    if (b < -half || b >= half) return false;
-    const unsigned long long key = ((unsigned long long)(b + half) << P.side_cbits) | c;
-    const u32 h = (u32)(mix64(key) >> 32);
-    for (u32 i = 0; i < 64u && i <= P.side_mask; ++i) {
-        SideSlot* sl = &P.side[(h + i) & P.side_mask];
-        const unsigned long long k = atomicCAS(&sl->key, SIDE_EMPTY, key);
-        if (k == SIDE_EMPTY || k == key) {
-            if (k == SIDE_EMPTY) atomicAdd(P.side_used, 1u);
-            atomicAdd(&sl->count, (unsigned long long)v);
-            return true;
-        }
-    }
-    return false;
-}
-
-// Adds v views to (campaign, bucket): the ring cell if the bucket is live, else the
-// exact side map (or its fallback list).
-__device__ __forceinline__ void global_add(const ScanParams& P, i64 ring_lo, bool ring_set,
-                                           u32 c, i64 b, u32 v, Tally& t) {
-    if (ring_set) {
-        const i64 rel = b - ring_lo;
-        if (rel >= 0 && rel < (i64)P.ring_w) {
-            atomicAdd(&P.counts[(u64)c * P.ring_w + (u64)(b & (i64)(P.ring_w - 1))], (unsigned long long)v);
-            return;
-        }
-    }
-    t.oor += v;
-    if (side_add(P, c, b, v)) return;
-    const u32 idx = atomicAdd(P.ovf_count, 1u);
-    if (idx < P.ovf_cap) {
-        OvfEntry en;
-        en.campaign = c; en.count = v; en.bucket = b;
-        P.ovf[idx] = en;
-    } else {
-        atomicAdd(&P.stats[ST_OVF_DROPPED], (unsigned long long)v);
-    }
 }
 
 }  // namespace ysb

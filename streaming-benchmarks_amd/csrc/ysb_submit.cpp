@@ -36,7 +36,9 @@ static ScanParams make_params(ysb_ctx* c, const ysb_segment* segs, u32 nseg, con
     p.cseed = c->cseed;
     // a sharded table's misses go to the deferred-line kernel, which tells a foreign-shard
     // key from a real miss (the scan kernels themselves carry no shard logic)
-    p.ctable_partial = (c->ctable_partial || c->shard_n > 1) ? 1u : 0u;
+    // -- and so do a context's with parking enabled (ysb_parked_enable): that kernel and the
+    // columnar count hold the park sites
+    p.ctable_partial = (c->ctable_partial || c->shard_n > 1 || c->park_cap) ? 1u : 0u;
     p.shard_rank = c->shard_rank;
     p.shard_n = c->shard_n;
     p.pend_dirty = c->d_dirty;
@@ -252,7 +254,8 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout
     c->last_launch.hbm_table = p.probe_serial ? 1u : 0u;
     c->last_launch.tbl = p.tbl ? 1u : 0u;
     if (te) HIPCHK(c, hipEventRecord(te[1], c->s_comp));
-    launch_defer(p, c->cus, c->s_comp);
+    ParkParams park;
+    launch_defer(p, c->cus, c->s_comp, park_params(c, &park) ? &park : nullptr);
     HIPCHK(c, hipGetLastError());
     if (p.rec_on) {
         launch_rec_partition(rp, c->s_comp);

@@ -239,6 +239,26 @@ AdCampaignMap AdCampaignMap::fromFile(const std::string& path) {
     return (p < t.size() && t[p] == '{') ? fromJsonLines(t) : fromCsv(t);
 }
 
+AdCampaignMap AdCampaignMap::fromFileOrEmpty(const std::string& path) {
+    struct stat st;
+    if (path.empty() || ::stat(path.c_str(), &st) != 0) return AdCampaignMap();
+    return fromFile(path);   // (an empty file reads as a CSV of no lines)
+}
+
+uint32_t AdCampaignMap::addCampaign(const std::string& campaign) {
+    auto ci = campaignIndex_.find(campaign);
+    if (ci != campaignIndex_.end()) return ci->second;
+    const uint32_t c = (uint32_t)campaigns.size();
+    campaignIndex_.emplace(campaign, c);
+    campaigns.push_back(campaign);
+    return c;
+}
+
+int64_t AdCampaignMap::campaignOf(const std::string& campaign) const {
+    auto ci = campaignIndex_.find(campaign);
+    return ci == campaignIndex_.end() ? -1 : (int64_t)ci->second;
+}
+
 // ---- FileBasedDataSource -----------------------------------------------------------------------
 
 FileBasedDataSource::FileBasedDataSource(const std::string& path, unsigned threads, bool mmap) {
@@ -448,7 +468,45 @@ void GpuAdCampaignOperator::open() {
         lens[i] = (uint32_t)map_.ads[i].size();
     }
     check(ysb_load_ad_map(ctx_, keys.data(), lens.data(), map_.adCampaign.data(), map_.ads.size()), "ysb_load_ad_map");
+    if (o_.parkCapacity) check(ysb_parked_enable(ctx_, o_.parkCapacity), "ysb_parked_enable");
     for (int s = 0; s < 2; ++s) check(ysb_slot_buffers(ctx_, s, &bytes_[s], &off_[s]), "ysb_slot_buffers");
+}
+
+GpuAdCampaignOperator::Parked GpuAdCampaignOperator::resolveParked(RedisAdLookup& redis) {
+    Parked p;
+    uint64_t n = 0;
+    check(ysb_parked_keys(ctx_, nullptr, nullptr, 0, &n), "ysb_parked_keys");
+    if (!n) return p;
+    std::vector<char> keys(n * 56);
+    std::vector<uint32_t> lens(n);
+    check(ysb_parked_keys(ctx_, keys.data(), lens.data(), n, &n), "ysb_parked_keys");
+    std::vector<std::string> ids(n);
+    for (uint64_t i = 0; i < n; ++i) ids[i].assign(keys.data() + 56 * i, lens[i]);
+    const std::vector<std::pair<bool, std::string>> got = redis.get(ids);
+    std::vector<const char*> ptr;
+    std::vector<uint32_t> len, camp;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!got[i].first) continue;   // null from jedis.get: dropped, nothing cached
+        const int64_t c = map_.campaignOf(got[i].second);
+        if (c < 0)
+            throw std::runtime_error("redis: ad " + ids[i] + " names campaign " + got[i].second +
+                                     ", which is neither in the ad map file nor in the `campaigns` set read at start-up");
+        ptr.push_back(ids[i].data());
+        len.push_back((uint32_t)ids[i].size());
+        camp.push_back((uint32_t)c);
+    }
+    if (!ptr.empty()) check(ysb_ad_map_upsert(ctx_, ptr.data(), len.data(), camp.data(), ptr.size(), nullptr), "ysb_ad_map_upsert");
+    ysb_parked_desc d;
+    check(ysb_parked_resolve(ctx_, &d), "ysb_parked_resolve");
+    p.keys = n;
+    p.found = ptr.size();
+    p.joined = d.resolved_joined;
+    p.missed = d.resolved_missed;
+    parked_.keys += p.keys;
+    parked_.found += p.found;
+    parked_.joined += p.joined;
+    parked_.missed += p.missed;
+    return p;
 }
 
 void GpuAdCampaignOperator::flatMap(const char* line, uint64_t len) {
@@ -608,6 +666,7 @@ public:
         bool nil = false;
         std::string str;
         long long num = 0;
+        std::vector<std::string> items;   // an array's bulk strings (SMEMBERS)
     };
     // Sends every command, then reads every reply in order.
     std::vector<Reply> pipeline(const std::vector<std::vector<std::string>>& cmds) {
@@ -665,7 +724,7 @@ private:
         }
         case '*': {
             const long long n = std::stoll(rest);
-            for (long long i = 0; i < n; ++i) reply();   // not used by the writer
+            for (long long i = 0; i < n; ++i) r.items.push_back(reply().str);
             break;
         }
         default: throw std::runtime_error("redis: bad reply " + ln);
@@ -673,6 +732,25 @@ private:
         return r;
     }
 };
+
+RedisAdLookup::RedisAdLookup(const std::string& host, int port) : r_(new RespClient(host, port)) {}
+RedisAdLookup::~RedisAdLookup() = default;
+
+std::vector<std::string> RedisAdLookup::campaigns() {
+    ++trips_;
+    return r_->pipeline({{"SMEMBERS", "campaigns"}})[0].items;
+}
+
+std::vector<std::pair<bool, std::string>> RedisAdLookup::get(const std::vector<std::string>& adIds) {
+    std::vector<std::vector<std::string>> cmds;
+    cmds.reserve(adIds.size());
+    for (const std::string& a : adIds) cmds.push_back({"GET", a});
+    std::vector<std::pair<bool, std::string>> out;
+    if (cmds.empty()) return out;
+    ++trips_;
+    for (RespClient::Reply& r : r_->pipeline(cmds)) out.emplace_back(!r.nil, std::move(r.str));
+    return out;
+}
 
 std::string randomUuid() {
     static thread_local std::mt19937_64 rng(std::random_device{}());

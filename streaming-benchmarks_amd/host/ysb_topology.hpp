@@ -69,6 +69,13 @@ struct AdCampaignMap {
     static AdCampaignMap fromFile(const std::string& path);
     static AdCampaignMap fromCsv(const std::string& text);
     static AdCampaignMap fromJsonLines(const std::string& text);
+    // --join-redis: the file may be absent or empty -- the cold cache of
+    // RedisAdCampaignCache.prepare() (RedisAdCampaignCache.java:19-21)
+    static AdCampaignMap fromFileOrEmpty(const std::string& path);
+    // A campaign without an ad yet (the `campaigns` set, core.clj:213): its index, added if new.
+    uint32_t addCampaign(const std::string& campaign);
+    // The index of a campaign UUID, -1 if it is not in the index space.
+    int64_t campaignOf(const std::string& campaign) const;
 
 private:
     std::unordered_map<std::string, uint32_t> campaignIndex_, adIndex_;
@@ -125,6 +132,25 @@ private:
     uint64_t completeEnd(const uint8_t* buf, uint64_t have, bool anyCr) const;
 };
 
+// ---- the join's Redis (--join-redis) ----------------------------------------------------------
+// What RedisAdCampaignCache asks Redis (RedisAdCampaignCache.java:23-35): jedis.get(ad_id), the
+// `<ad_id> -> campaign_id` strings the generator SET (core.clj:160), and the `campaigns` set it
+// SADDed (core.clj:213), which is the campaign index space.
+class RespClient;   // RESP2 over a TCP socket
+class RedisAdLookup {
+public:
+    RedisAdLookup(const std::string& host, int port);
+    ~RedisAdLookup();
+    std::vector<std::string> campaigns();                                  // SMEMBERS campaigns
+    // one pipelined GET per key: {found, campaign_id}
+    std::vector<std::pair<bool, std::string>> get(const std::vector<std::string>& adIds);
+    uint64_t roundTrips() const { return trips_; }
+
+private:
+    std::unique_ptr<RespClient> r_;
+    uint64_t trips_ = 0;
+};
+
 // One (campaign, window) delta: what writeWindow HINCRBYs into seen_count.
 struct WindowDelta {
     std::string campaign;
@@ -146,6 +172,7 @@ public:
         bool gpuSplit = true;               // fillFromRaw + ysb_submit_raw: line starts found on the GPU
         bool h2dSdma = false;               // YSB_F_H2D_SDMA: the slot's H2D by the DMA engine (default: a copy kernel)
         bool mappedIo = false;              // the source's mapping registered, batches read in place (--io mapped)
+        uint64_t parkCapacity = 0;          // --join-redis: views of unknown ads parked (ysb_parked_enable), 0 = off
     };
     GpuAdCampaignOperator(const AdCampaignMap& map, const Options& o);
     ~GpuAdCampaignOperator();
@@ -164,6 +191,15 @@ public:
     // reads are read from the file, straight into the open slot.  Throws, naming the file, if
     // its size is not the layout's image_bytes.
     void submitColumnsFile(const std::string& path, uint64_t rows);
+    // --join-redis, after a batch: everything submitted is waited for, the distinct ads of the
+    // parked views are asked of Redis (pipelined GETs), the ads found are put into the live map
+    // (ysb_ad_map_upsert) and the parked views resolved.  A GET that names a campaign outside the
+    // index space (the map file's campaigns and the `campaigns` set at start-up) throws, naming it.
+    struct Parked {
+        uint64_t keys = 0, found = 0, joined = 0, missed = 0;
+    };
+    Parked resolveParked(RedisAdLookup& redis);
+    const Parked& parkedTotals() const { return parked_; }
     std::vector<WindowDelta> flushWindows();               // CampaignProcessorCommon.flushWindows (:91-98)
     void close();                                          // RichFlatMapFunction.close
     ysb_stats stats();
@@ -183,11 +219,11 @@ private:
     uint32_t* off_[2] = {nullptr, nullptr};
     int cur_ = 0;
     uint64_t fillBytes_ = 0, fillEvents_ = 0, submitted_ = 0, rawBytes_ = 0;
+    Parked parked_;
     void check(int rc, const char* what);
 };
 
 // ---- output -------------------------------------------------------------------------------------------
-class RespClient;   // RESP2 over a TCP socket
 
 class RedisWindowWriter {
 public:

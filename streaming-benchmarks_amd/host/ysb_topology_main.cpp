@@ -51,6 +51,10 @@ struct Args {
     // slot copies out of the mapping if the registration is refused
     std::string io = "auto";
     bool h2d_sdma = false;
+    // --join-redis: the join as a cache in front of Redis (RedisAdCampaignCache): views of ads the
+    // map does not hold are parked, looked up with GET after each batch, upserted and resolved
+    bool join_redis = false;
+    long long park_capacity = 1 << 20;
     // streaming mode (configs[4]): --stream plus its options (ysb_stream.hpp)
     bool stream = false;
     StreamOptions so;
@@ -68,7 +72,7 @@ void usage() {
                  "       [--format json|tbl] [--flush-ms MS] [--batch-mb MB | --batch-bytes B] [--batch-events N]\n"
                  "       [--window-ring W] [--require-ip] [--dry-run] [--print-config] [--replay-rows CSV]\n"
                  "       [--host-split] [--repeat K] [--io-threads T] [--io auto|mapped|mmap|pread]\n"
-                 "       [--h2d-sdma]\n"
+                 "       [--h2d-sdma] [--join-redis [--park-capacity N]]\n"
                  "   or: ysb_topology --confPath PATH --columns [--device N] [--format json|tbl] [--require-ip]\n"
                  "       [--batch-mb MB | --batch-bytes B]   (window.size rows per <shared_file>_<k>)\n"
                  "   or: ysb_topology --confPath PATH --from-columns [--device N] [--sink none|csv:FILE|redis[:HOST[:PORT]]]\n"
@@ -113,6 +117,8 @@ Args parse(int argc, char** argv) {
             a.io = m;
         }
         else if (k == "--h2d-sdma") a.h2d_sdma = true;
+        else if (k == "--join-redis") a.join_redis = true;
+        else if (k == "--park-capacity") a.park_capacity = std::max(1ll, std::atoll(val().c_str()));
         else if (k == "--columns") a.columns = true;
         else if (k == "--from-columns") a.from_columns = true;
         else if (k == "--stream") a.stream = true;
@@ -142,6 +148,11 @@ Args parse(int argc, char** argv) {
                                                                                     : StreamOptions::COPY;
         }
         else { usage(); std::exit(2); }
+    }
+    if (a.join_redis && (a.stream || a.columns || a.from_columns)) {
+        std::fprintf(stderr, "--join-redis is batch mode's (the counting chain over events_path): not with --stream, "
+                             "--columns or --from-columns\n");
+        std::exit(2);
     }
     if (a.stream && a.columns) {
         std::fprintf(stderr, "--columns reads events_path in batch mode: not with --stream\n");
@@ -182,16 +193,24 @@ double now_s() {
 
 // --sink none | csv:FILE | redis[:HOST[:PORT]] (the host defaults to the config's redis.host);
 // false (after the usage text) for anything else.
+// The job's Redis: the conf's redis.host (Utils.java), port 6379, unless --sink redis:HOST[:PORT]
+// names another (the sink and --join-redis talk to the same server, as the reference's bolts do).
+void redis_address(const Args& a, const Config& conf, std::string* host, int* port) {
+    *host = conf.get("redis.host", "localhost");
+    *port = 6379;
+    const std::string rest = a.sink.rfind("redis", 0) == 0 && a.sink.size() > 6 ? a.sink.substr(6) : "";
+    if (!rest.empty()) {
+        const size_t c = rest.rfind(':');
+        *host = c == std::string::npos ? rest : rest.substr(0, c);
+        if (c != std::string::npos) *port = std::atoi(rest.c_str() + c + 1);
+    }
+}
+
 bool open_sink(const Args& a, const Config& conf, std::unique_ptr<RedisWindowWriter>& redis, std::string& csv_path) {
     if (a.sink.rfind("redis", 0) == 0) {
-        std::string host = conf.get("redis.host", "localhost");
-        int port = 6379;
-        const std::string rest = a.sink.size() > 6 ? a.sink.substr(6) : "";
-        if (!rest.empty()) {
-            const size_t c = rest.rfind(':');
-            host = c == std::string::npos ? rest : rest.substr(0, c);
-            if (c != std::string::npos) port = std::atoi(rest.c_str() + c + 1);
-        }
+        std::string host;
+        int port;
+        redis_address(a, conf, &host, &port);
         redis.reset(new RedisWindowWriter(host, port));
     } else if (a.sink.rfind("csv:", 0) == 0) {
         csv_path = a.sink.substr(4);
@@ -220,7 +239,18 @@ int run(const Args& a) {
         std::printf("%s}\n", o.c_str());
     }
     // getAdCampaignMap(conf.get("ad_to_campaign_path")) (:67)
-    const AdCampaignMap map = AdCampaignMap::fromFile(conf.get("ad_to_campaign_path"));
+    // -- or, with --join-redis, RedisAdCampaignCache's cold HashMap: the file may be empty or
+    // absent, and the campaign index space is its campaigns joined with Redis' `campaigns` set
+    AdCampaignMap map = a.join_redis ? AdCampaignMap::fromFileOrEmpty(conf.get("ad_to_campaign_path", ""))
+                                     : AdCampaignMap::fromFile(conf.get("ad_to_campaign_path"));
+    std::unique_ptr<RedisAdLookup> lookup;
+    if (a.join_redis && !a.dry && a.replay.empty()) {
+        std::string host;
+        int port;
+        redis_address(a, conf, &host, &port);
+        lookup.reset(new RedisAdLookup(host, port));
+        for (const std::string& c : lookup->campaigns()) map.addCampaign(c);
+    }
     const std::string events = conf.get("events_path");
     const bool tbl = a.format.empty() ? (events.size() > 4 && events.compare(events.size() - 4, 4, ".tbl") == 0)
                                       : a.format == "tbl";
@@ -236,6 +266,7 @@ int run(const Args& a) {
     o.gpuSplit = !a.host_split;
     o.h2dSdma = a.h2d_sdma;
     o.mappedIo = a.io == "mapped" || (a.io == "auto" && o.gpuSplit && !o.h2dSdma);
+    o.parkCapacity = lookup ? (uint64_t)a.park_capacity : 0;
     if (a.io == "mapped" && !o.gpuSplit) {
         std::fprintf(stderr, "--io mapped reads raw lines in place: not with --host-split\n");
         return 2;
@@ -323,12 +354,14 @@ int run(const Args& a) {
         if (rep) src.rewind();
         while (o.mappedIo ? op.submitMapped(src) > 0 : (o.gpuSplit ? op.fillFromRaw(src) : op.fillFrom(src)) > 0) {
             if (!o.mappedIo) op.submit();
+            if (lookup) op.resolveParked(*lookup);   // the batch's misses: GET, put, count
             if (a.flush_ms > 0 && (now_s() - last_flush) * 1000.0 >= (double)a.flush_ms) {
                 flush();
                 last_flush = now_s();
             }
         }
         op.submit();   // a last partial slot
+        if (lookup) op.resolveParked(*lookup);
     }
     op.close();
     const double el_stream = now_s() - t_open;
@@ -345,7 +378,8 @@ int run(const Args& a) {
                 "\"events_per_s\": %.1f, \"stream_seconds\": %.3f, \"stream_events_per_s\": %.1f, "
                 "\"bytes\": %llu, \"stream_GBs\": %.2f, \"line_split\": \"%s\", \"repeat\": %lld, "
                 "\"format\": \"%s\", \"sink\": %s, \"h2d\": \"%s\", \"copy_GBs\": %.2f, \"copy_busy_frac\": %.4f, "
-                "\"fill_s\": %.3f, \"slot_wait_s\": %.3f}\n",
+                "\"fill_s\": %.3f, \"slot_wait_s\": %.3f, \"join_redis\": %s, \"parked_keys\": %llu, "
+                "\"parked_found\": %llu, \"parked_joined\": %llu, \"parked_missed\": %llu, \"join_round_trips\": %llu}\n",
                 (unsigned long long)s.events, (unsigned long long)s.views, (unsigned long long)s.joined,
                 (unsigned long long)s.join_misses, (unsigned long long)s.parse_errors,
                 (unsigned long long)s.time_errors, (unsigned long long)s.out_of_ring,
@@ -356,7 +390,10 @@ int run(const Args& a) {
                 a.repeat, tbl ? "tbl" : "json",
                 json_str(a.sink).c_str(), a.h2d_sdma ? "sdma" : o.mappedIo ? "mapped" : "kernel",
                 copy_ms > 0 ? (double)copy_bytes / (copy_ms * 1e-3) / 1e9 : 0.0,
-                el_stream > 0 ? copy_ms * 1e-3 / el_stream : 0.0, op.fillSeconds(), op.waitSeconds());
+                el_stream > 0 ? copy_ms * 1e-3 / el_stream : 0.0, op.fillSeconds(), op.waitSeconds(),
+                lookup ? "true" : "false", (unsigned long long)op.parkedTotals().keys,
+                (unsigned long long)op.parkedTotals().found, (unsigned long long)op.parkedTotals().joined,
+                (unsigned long long)op.parkedTotals().missed, (unsigned long long)(lookup ? lookup->roundTrips() : 0));
     return s.overflow_dropped ? 3 : 0;
 }
 

@@ -122,6 +122,12 @@ class YsbAdmapDesc(C.Structure):
                 (n, C.c_uint32) for n in ("buckets", "partial", "shard_rank", "shard_n")]
 
 
+class YsbParkedDesc(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("capacity", "parked", "parked_total", "dropped", "resolved_joined",
+                                          "resolved_missed", "resolved_time_errors", "distinct_keys")] + [
+                ("distinct_ms", C.c_double), ("resolve_ms", C.c_double)]
+
+
 class YsbGenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_campaigns", C.c_uint32), ("ads_per_campaign", C.c_uint32),
                 ("t0_ms", C.c_int64), ("events_per_sec", C.c_uint64), ("with_skew", C.c_uint32),
@@ -159,6 +165,11 @@ SIGNATURES = {
     "ysb_ad_map_lookup": (_I, [_P, C.POINTER(C.c_char_p), C.POINTER(_U32), _U64, _PU32, _PU32]),
     "ysb_ad_map_info": (_I, [_P, C.POINTER(YsbAdmapDesc)]),
     "ysb_admap_desc_size": (_U64, []),
+    "ysb_parked_enable": (_I, [_P, _U64]),
+    "ysb_parked_keys": (_I, [_P, C.c_void_p, _PU32, _U64, C.POINTER(_U64)]),
+    "ysb_parked_resolve": (_I, [_P, C.POINTER(YsbParkedDesc)]),
+    "ysb_parked_info": (_I, [_P, C.POINTER(YsbParkedDesc)]),
+    "ysb_parked_info_size": (_U64, []),
     "ysb_slot_buffers": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_P)]),
     "ysb_submit": (_I, [_P, _I, _PU8, _U64, _PU32, _U64]),
     "ysb_wait": (_I, [_P, _I]),
@@ -265,7 +276,8 @@ def lib():
         if L.ysb_colcount_desc_size() != C.sizeof(YsbColcountDesc):
             raise ImportError("ysb_colcount_desc is %d bytes in the library, %d in this binding"
                               % (L.ysb_colcount_desc_size(), C.sizeof(YsbColcountDesc)))
-        for fn, st in ((L.ysb_upsert_info_size, YsbUpsertInfo), (L.ysb_admap_desc_size, YsbAdmapDesc)):
+        for fn, st in ((L.ysb_upsert_info_size, YsbUpsertInfo), (L.ysb_admap_desc_size, YsbAdmapDesc),
+                       (L.ysb_parked_info_size, YsbParkedDesc)):
             if fn() != C.sizeof(st):
                 raise ImportError("%s is %d bytes in the library, %d in this binding"
                                   % (st.__name__, fn(), C.sizeof(st)))

@@ -197,6 +197,56 @@ class YsbContext:
         self._c(lib().ysb_ad_map_info(self._h, C.byref(d)))
         return {n: getattr(d, n) for n, _ in _lib.YsbAdmapDesc._fields_}
 
+    # -- parked views ------------------------------------------------------------------
+    @staticmethod
+    def _parked_desc(d):
+        return {n: getattr(d, n) for n, _ in _lib.YsbParkedDesc._fields_}
+
+    def park_misses(self, capacity):
+        """ysb_parked_enable: from now on a view whose ad is in no device table is parked (up to
+        `capacity` records) instead of being counted as a join miss, until resolve_parked; 0
+        turns parking off.  RedisAdCampaignCache's jedis.get half: see resolve_parked_with."""
+        self._c(lib().ysb_parked_enable(self._h, int(capacity)))
+
+    def parked_keys(self):
+        """ysb_parked_keys: the distinct ad ids of the parked views, a list of bytes in no
+        particular order."""
+        n = C.c_uint64()
+        self._c(lib().ysb_parked_keys(self._h, None, None, 0, C.byref(n)))
+        if not n.value:
+            return []
+        keys = np.zeros(n.value * 56, dtype=np.uint8)
+        lens = np.zeros(n.value, dtype=np.uint32)
+        self._c(lib().ysb_parked_keys(self._h, _ptr(keys), _ptr(lens), n.value, C.byref(n)))
+        return [keys[56 * i:56 * i + int(lens[i])].tobytes() for i in range(n.value)]
+
+    def resolve_parked(self):
+        """ysb_parked_resolve: every parked view against the join tables as they are now --
+        counted as the scan would have counted it if its ad is there, a join miss if not.
+        Returns ysb_parked_desc as a dict (capacity, parked, parked_total, dropped,
+        resolved_joined / _missed / _time_errors, distinct_keys, distinct_ms, resolve_ms)."""
+        d = _lib.YsbParkedDesc()
+        self._c(lib().ysb_parked_resolve(self._h, C.byref(d)))
+        return self._parked_desc(d)
+
+    def parked_info(self):
+        """ysb_parked_info as a dict (the fields of resolve_parked)."""
+        d = _lib.YsbParkedDesc()
+        self._c(lib().ysb_parked_info(self._h, C.byref(d)))
+        return self._parked_desc(d)
+
+    def resolve_parked_with(self, lookup):
+        """The whole miss loop of RedisAdCampaignCache.execute for what is parked now:
+        lookup(list of ad id bytes) returns, per key, a campaign index or None (the ad is
+        unknown there too); the ads found are upserted and the log is resolved.  Returns
+        resolve_parked's dict."""
+        keys = self.parked_keys()
+        if keys:
+            found = [(k, c) for k, c in zip(keys, lookup(keys)) if c is not None]
+            if found:
+                self.upsert_ad_map([k for k, _ in found], [c for _, c in found])
+        return self.resolve_parked()
+
     # -- batches -----------------------------------------------------------------------
     def slot_buffers(self, slot):
         b, o = C.c_void_p(), C.c_void_p()
