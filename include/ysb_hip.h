@@ -53,7 +53,8 @@ extern "C" {
 #define YSB_ERR_HIP      (-2)  /* HIP runtime failure                      */
 #define YSB_ERR_STATE    (-3)  /* call not valid in the current state      */
 #define YSB_ERR_CAPACITY (-4)  /* batch, table or output buffer too small  */
-#define YSB_ERR_FORMAT   (-5)  /* malformed ad map / config                */
+#define YSB_ERR_FORMAT   (-5)  /* malformed ad map / config, or a batch
+                                  with a bad LZ4 block (dropped whole)     */
 #define YSB_ERR_RCCL     (-6)  /* RCCL failure                             */
 #define YSB_ERR_NOMEM    (-7)  /* host or device allocation failed         */
 #define YSB_ERR_DATA     (-8)  /* strict mode: the batch held records the
@@ -473,6 +474,96 @@ int         ysb_submit_mapped(ysb_ctx* ctx, int slot, const uint8_t* bytes, uint
  * line starts (YSB_ERR_CAPACITY, *n = the lines, if more than cap).  Synchronous. */
 int         ysb_split_lines_device(ysb_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, uint32_t* d_off,
                                    uint64_t cap, uint64_t* n);
+/* ---- LZ4-compressed raw batches (additive within ABI 6) ---------------------------------
+ * A source whose bytes arrive compressed -- FileBasedDataSource.run
+ * (AdvertisingTopologyNative.java:144-165) reading a compressed replay file, or a Kafka
+ * consumer's message codec (the reference's Kafka 0.8.2.1 offers LZ4, stream-bench.sh) --
+ * decodes them on a CPU before the first operator sees a line.  Here it hands them over as they
+ * are: fewer bytes cross PCIe, and the GPU decodes them in front of the line split.
+ * A batch is n_blocks independent LZ4 *blocks* (the block format: no frame headers, no
+ * dictionary, a match never reaches before its own block) back to back, and this directory;
+ * the decoded blocks, back to back in directory order, are the raw batch.  A block decodes to
+ * 1..65536 bytes.  Bit 31 of comp_bytes marks a stored block: raw_bytes bytes as they are. */
+typedef struct ysb_lz4_block {
+    uint32_t comp_bytes;   /* the block's bytes in the batch (| YSB_LZ4_STORED)   */
+    uint32_t raw_bytes;    /* what it decodes to: 1..65536                        */
+} ysb_lz4_block;
+#define YSB_LZ4_STORED  0x80000000u
+#define YSB_LZ4_MAX_RAW 65536u
+/* ysb_submit_raw for a compressed batch -- replaces the source's decompress-then-readLine loop:
+ * the compressed bytes (and nothing else) go through the slot's pinned buffer over PCIe, the
+ * blocks are decoded into the slot's device buffer on the stream the split uses, behind the
+ * slot's copy, then split and scanned as a raw batch; double-buffering, ysb_wait, ordering and
+ * the sticky-error rule are ysb_submit_raw's.  comp_bytes and the sum of raw_bytes must each be
+ * <= max_batch_bytes (YSB_ERR_CAPACITY); YSB_ERR_ARG for a raw_bytes of 0 or above 65536 and for
+ * a directory whose sizes do not sum to comp_bytes; n_blocks = 0 is an empty batch.  A batch
+ * with any block that breaks the format's rules is dropped whole -- none of its lines is
+ * counted -- and YSB_ERR_FORMAT, its message naming the first bad block, is returned by the call
+ * that would have launched it and by every later one that orders work after it, until
+ * ysb_reset.  (The layout sample is taken from block 0 decoded on the host; counts never depend
+ * on it.) */
+int         ysb_submit_raw_lz4(ysb_ctx* ctx, int slot, const uint8_t* bytes, uint64_t comp_bytes,
+                               const ysb_lz4_block* dir, uint32_t n_blocks);
+/* The decode alone, as ysb_split_lines_device is the split alone (the codec call of a Kafka
+ * consumer or a compressed-file reader, on bytes already in HBM): d_comp (device, any
+ * alignment) holds the blocks, dir is host memory, d_out (device, out_cap bytes) receives
+ * *raw_bytes bytes.  Synchronous.  *first_bad: the first bad block, or 0xFFFFFFFF; a bad
+ * block's output range is left as it was, the other blocks are decoded, and the call returns
+ * YSB_ERR_FORMAT.  Argument and capacity errors as above (the capacity is out_cap). */
+int         ysb_lz4_decode_device(ysb_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes,
+                                  const ysb_lz4_block* dir, uint32_t n_blocks, uint8_t* d_out,
+                                  uint64_t out_cap, uint64_t* raw_bytes, uint32_t* first_bad);
+/* The last compressed batch whose decode has been read back (ysb_submit_raw_lz4: at its launch;
+ * ysb_lz4_decode_device: at once).  Read-only measurement and test support; replaces nothing
+ * in the reference.  Waits for everything submitted. */
+typedef struct ysb_lz4_desc {
+    uint64_t batches;        /* compressed batches since ysb_open / ysb_reset      */
+    uint64_t blocks;         /* the last batch: its blocks ...                     */
+    uint64_t stored_blocks;  /* ... those stored                                   */
+    uint64_t comp_bytes;
+    uint64_t raw_bytes;
+    uint64_t bad_blocks;
+    uint64_t first_bad;      /* 0xFFFFFFFF: none                                   */
+    double   decode_ms;      /* YSB_F_TIMING: HIP events around its decode kernel  */
+} ysb_lz4_desc;
+int         ysb_lz4_info(ysb_ctx* ctx, ysb_lz4_desc* info);
+uint64_t    ysb_lz4_desc_size(void);   /* sizeof(ysb_lz4_desc) */
+/* The host model of the format (csrc/ysb_lz4.h), for callers and tests: what a source without
+ * a compressor of its own (or a test) uses in place of the codec library of a Kafka producer.
+ * compress_block: src[0, raw_bytes) (1..65536) into dst (cap >= ysb_lz4_compress_bound(raw_bytes),
+ * else YSB_ERR_CAPACITY), *entry its directory entry -- stored when allow_stored and the block did
+ * not shrink.  decompress_block: YSB_ERR_FORMAT for a block that breaks the rules,
+ * YSB_ERR_CAPACITY if cap < entry->raw_bytes.
+ * ysb_lz4_pack: a whole buffer cut into blocks of block_bytes (1..65536; with line_aligned
+ * every block but the last ends behind a line terminator where its range holds one), *dst_bytes
+ * and *n_blocks out; dst_cap >= nbytes + nbytes / 255 + 16 * blocks and dir_cap >= the blocks
+ * (ceil(nbytes / block_bytes) without line_aligned), else YSB_ERR_CAPACITY with both counts set
+ * to what is needed.  threads > 1 compresses blocks in parallel (at most 16). */
+uint32_t    ysb_lz4_compress_bound(uint32_t raw_bytes);
+int         ysb_lz4_compress_block(const uint8_t* src, uint32_t raw_bytes, uint8_t* dst, uint32_t cap,
+                                   int allow_stored, ysb_lz4_block* entry);
+int         ysb_lz4_decompress_block(const uint8_t* src, const ysb_lz4_block* entry, uint8_t* dst,
+                                     uint32_t cap);
+int         ysb_lz4_pack(const uint8_t* src, uint64_t nbytes, uint32_t block_bytes, int line_aligned,
+                         int allow_stored, int threads, uint8_t* dst, uint64_t dst_cap, uint64_t* dst_bytes,
+                         ysb_lz4_block* dir, uint64_t dir_cap, uint64_t* n_blocks);
+/* A compressed replay file (ysb_gen --lz4 writes it, ysb_topology --lz4 reads it): this header,
+ * n_blocks directory entries, then the blocks back to back; all fields little-endian.  With
+ * YSB_LZ4_FILE_LINE_ALIGNED every block ends behind a line terminator (or at the file's end),
+ * so any run of whole blocks is a raw batch of whole lines.  ysb_lz4_write_file compresses
+ * src[0, nbytes) with ysb_lz4_pack's parameters into `path` (YSB_ERR_ARG if it cannot be
+ * written). */
+typedef struct ysb_lz4_file_header {
+    char     magic[8];     /* YSB_LZ4_FILE_MAGIC                          */
+    uint32_t version;      /* 1                                           */
+    uint32_t flags;        /* YSB_LZ4_FILE_LINE_ALIGNED                   */
+    uint64_t n_blocks;
+    uint64_t raw_bytes;    /* the sum of the directory's raw_bytes        */
+} ysb_lz4_file_header;
+#define YSB_LZ4_FILE_MAGIC        "YSBLZ4B\n"   /* 8 bytes, no terminator */
+#define YSB_LZ4_FILE_LINE_ALIGNED 1u
+int         ysb_lz4_write_file(const char* path, const uint8_t* src, uint64_t nbytes, uint32_t block_bytes,
+                               int line_aligned, int allow_stored, int threads);
 /* Device-resident batch (HBM pointers, e.g. from ysb_device_alloc). Asynchronous.  The batch
  * must be complete when submitted, or its producer ordered before the compute stream
  * (hipStreamWaitEvent(ysb_stream(ctx), ...), or produced on that stream).  Unless

@@ -856,6 +856,7 @@ int ysb_reset(ysb_ctx* c) {
     if ((rc = park_reset(c))) return rc;   // the log of parked views emptied; parking stays enabled
     c->side.clear();
     c->batches = 0;
+    c->lz4_last = ysb_lz4_desc{};
     return YSB_OK;
 }
 

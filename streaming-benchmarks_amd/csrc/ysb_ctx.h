@@ -9,6 +9,9 @@
 //   ysb_recplan.h   record mode's plan of a launch (no HIP: tests/native/recplan_logic.cpp)
 //   ysb_parked_api.cpp  parked views: the log of the views of unknown ads, its keys, its resolve
 //   ysb_parked.h    their record format, rules and host model (no HIP: tests/native/parked_logic.cpp)
+//   ysb_lz4_api.cpp LZ4 batches: the directory's checks, the decode's staging, the host codec entries
+//   ysb_lz4.h       their format, its one sequence reader and the host model (no HIP:
+//                   tests/native/lz4_logic.cpp)
 //   ysb_group.cpp   multi-GPU: the RCCL / host-collective group and the keyBy exchange
 //   ysb_gen_api.cpp the synthetic generator (host and device) and its truth tables
 // Internal: nothing here is part of the ABI (the shared helpers have hidden visibility).
@@ -219,6 +222,24 @@ struct ysb_ctx {
     Event ev_park[2];
     u64 park_resolved_total = 0;
     ysb_parked_desc park_last{};
+    // LZ4 batches (ysb_lz4_api.cpp; ysb_lz4.h): per slot the compressed bytes in HBM (the
+    // slot's pinned buffer carries them over PCIe; d_bytes[slot] receives the decode) and the
+    // block descriptors -- pinned and device, LZ4_DESC_HEAD bytes of {first bad, bad blocks}
+    // in front, initialised by the same copy --; the pair read back to pinned memory behind the
+    // decode (h_lz4bad[2 * slot]); whether the slot's pending raw batch is a compressed one;
+    // its figures until its launch settles them into lz4_last; YSB_F_TIMING's event pair
+    DevBuf<u8> d_lz4[2];
+    PinBuf<u8> h_lz4desc[2];
+    u8* hd_lz4desc[2] = {nullptr, nullptr};
+    DevBuf<u8> d_lz4desc[2];
+    u64 lz4desc_cap[2] = {0, 0};
+    PinBuf<u32> h_lz4bad;
+    bool raw_lz4[2] = {false, false};
+    ysb_lz4_desc lz4_pend[2]{}, lz4_last{};
+    u32 lz4_max_raw[2] = {0, 0};                // the pending batch's largest block (the LDS window)
+    Event ev_lz4[2][2];
+    DevBuf<u8> d_lz4desc_sync;                  // ysb_lz4_decode_device's descriptors
+    std::vector<u8> lz4_sample;                 // block 0 decoded on the host: the layout sample
     // counts
     u32 c_pad = 0;                        // campaigns padded to the group size
     DevBuf<unsigned long long> d_counts;      // [c_pad][W]
@@ -405,6 +426,18 @@ YSB_INTERNAL bool park_params(const ysb_ctx* c, ParkParams* out);
 // the log's device counters into h_park_ctr (a small read on the compute stream; waits for it)
 YSB_INTERNAL int park_counters(ysb_ctx* c);
 YSB_INTERNAL int park_reset(ysb_ctx* c);         // ysb_reset's part: the log emptied, the counters zero
+// ysb_lz4_api.cpp
+// A compressed batch's directory checked and its bytes and descriptors placed in the slot's
+// pinned memory (the caller has waited for the slot's previous copy); *raw_total its raw size
+YSB_INTERNAL int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
+                           uint32_t n_blocks, uint64_t* raw_total);
+// the slot's two copies (compressed bytes, descriptors) as copy_slot_ranges takes them
+YSB_INTERNAL void lz4_copies(ysb_ctx* c, int slot, SlotCopy v[2]);
+// the staged batch decoded into d_bytes[slot] on s, and its {first bad, bad blocks} read back
+YSB_INTERNAL int lz4_enqueue_decode(ysb_ctx* c, int slot, hipStream_t s);
+// at the slot's launch (its decode is complete): lz4_last <- its figures; YSB_ERR_FORMAT, the
+// message naming the first bad block, if it had one
+YSB_INTERNAL int lz4_settle(ysb_ctx* c, int slot);
 // ysb_group.cpp
 YSB_INTERNAL bool grouped(const ysb_ctx* c);
 YSB_INTERNAL int agree_ring(ysb_ctx* c);

@@ -362,4 +362,22 @@ void launch_parked_distinct(const ParkParams& k, u32 n, u32* slots, u32 mask, u8
 // ctr[PK_JOINED / PK_MISSED / PK_TIME_ERR], the ring through global_add, *sp.pend_dirty).
 void launch_parked_resolve(const ScanParams& sp, const ParkParams& k, u32 n, u32* camp, hipStream_t s);
 
+// LZ4 batches (ysb_lz4.hip; the format's rules: ysb_lz4.h).  One descriptor per block, made
+// by the host from the directory: where its compressed bytes start in `in`, where its output
+// starts in `out`, and the directory entry itself (comp with the stored bit).
+struct Lz4Desc {
+    u64 in_off, out_off;
+    u32 comp, raw;
+};
+struct Lz4Params {
+    const u8* in;               // the batch's compressed bytes, any alignment
+    const Lz4Desc* desc;        // [n_blocks]
+    u32 n_blocks;
+    u32 max_raw;                // the largest raw of the batch (sizes the LDS window)
+    u8* out;                    // block i's bytes go to out[desc[i].out_off, + raw)
+    u32* bad;                   // [2]: {first bad block (LZ4_NO_BAD before), bad blocks (0 before)}
+};
+// Every block decoded (a bad block writes nothing and is recorded in bad[]).  Asynchronous on s.
+hipError_t launch_lz4_decode(const Lz4Params& p, hipStream_t s);
+
 }  // namespace ysb

@@ -3,6 +3,7 @@
 // layout samples that pick the scan instantiation (their rules: ysb_layout.h), record-mode
 // planning and the launch sequence itself (scan, deferred lines, record partition + count).
 #include "ysb_ctx.h"
+#include "ysb_lz4.h"
 
 using namespace ysb;
 
@@ -508,6 +509,8 @@ int launch_pending_raw(ysb_ctx* c) {
     if (hipSetDevice(c->device) != hipSuccess || hipEventSynchronize(c->ev_raw[slot]) != hipSuccess ||
         hipStreamWaitEvent(c->s_comp, c->ev_raw[slot], 0) != hipSuccess) {
         rc = fail(c, YSB_ERR_HIP, "raw batch (slot %d): waiting for its line split failed", slot);
+    } else if (c->raw_lz4[slot] && (rc = lz4_settle(c, slot))) {
+        // a compressed batch with a bad block: dropped whole (YSB_ERR_FORMAT, the message lz4_settle's)
     } else if (c->raw_rebase_on[slot] && c->h_rawn[slot] > c->rebase_n - c->raw_rebase[slot].first_line) {
         rc = fail(c, YSB_ERR_ARG, "raw batch (slot %d): %llu lines, more than the rebase table holds from line %llu",
                   slot, (unsigned long long)c->h_rawn[slot], (unsigned long long)c->raw_rebase[slot].first_line);
@@ -523,6 +526,7 @@ int launch_pending_raw(ysb_ctx* c) {
     if (hipEventRecord(c->ev_kdone[slot], c->s_comp) != hipSuccess && !rc)
         rc = fail(c, YSB_ERR_HIP, "hipEventRecord failed");
     c->raw_pend = -1;
+    c->raw_lz4[slot] = false;
     if (rc) {
         c->raw_fail = rc;
         c->raw_fail_msg = c->err;
@@ -597,6 +601,57 @@ int ysb_submit_raw(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes) 
     HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
     if (bytes != c->h_bytes[slot] && nbytes) std::memcpy(c->h_bytes[slot], bytes, nbytes);
     return enqueue_raw(c, slot, c->h_bytes[slot], c->hd_bytes[slot], nbytes, nullptr);
+}
+
+// ---- LZ4-compressed raw batches (ysb_lz4_api.cpp, ysb_lz4.hip) --------------------------------
+
+// enqueue_raw for a staged compressed batch (lz4_stage): the compressed bytes and the block
+// descriptors over PCIe, the decode into the slot's device buffer on the stream of the split
+// -- behind the slot's copy, never on the copy stream, which goes on with the other slot's
+// copy --, then the split as for any raw batch; its scan launches at the next call.
+static int enqueue_raw_lz4(ysb_ctx* c, int slot, u64 raw_bytes) {
+    int rc;
+    c->raw_layout[slot] = -1;
+    if (layout_sampling(c) && !c->lz4_sample.empty())
+        c->raw_layout[slot] = hinted_layout(flat_first(c), sniff_raw(require_mask(c), c->lz4_sample.data(),
+                                                                     c->lz4_sample.size(), &c->raw_learn[slot]));
+    hipStream_t ss = c->split_place == 2 ? c->s_comp : c->s_split;
+    SlotCopy v[2];
+    lz4_copies(c, slot, v);
+    if ((rc = copy_slot_ranges(c, slot, v, 2))) return rc;
+    HIPCHK(c, hipStreamWaitEvent(ss, c->ev_h2d[slot], 0));
+    c->raw_rebase_on[slot] = false;
+    if ((rc = lz4_enqueue_decode(c, slot, ss))) return rc;
+    if (raw_bytes) {
+        HIPCHK(c, launch_split_lines(c->d_bytes[slot], raw_bytes, c->d_split_chunk, c->d_roff[slot],
+                                     c->raw_lines_cap, c->h_rawn + slot, ss));
+    } else {
+        c->h_rawn[slot] = 0;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_raw[slot], ss));
+    c->raw_nbytes[slot] = raw_bytes;
+    rc = launch_pending_raw(c);
+    c->raw_pend = slot;
+    c->raw_lz4[slot] = true;
+    return rc;
+}
+
+int ysb_submit_raw_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
+                       uint32_t n_blocks) {
+    if (!c) return YSB_ERR_ARG;
+    if (slot < 0 || slot > 1) return fail(c, YSB_ERR_ARG, "slot must be 0 or 1");
+    if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
+    // the slot's own earlier batch launches first (its device buffers are about to be reused)
+    int rc = c->raw_pend == slot ? launch_pending_raw(c) : YSB_OK;
+    if (!rc) rc = ensure_slots(c);
+    if (!rc) rc = ensure_raw(c);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the slot's previous H2D must be done before its pinned buffers are rewritten
+    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
+    u64 raw_bytes = 0;
+    if ((rc = lz4_stage(c, slot, bytes, comp_bytes, dir, n_blocks, &raw_bytes))) return rc;
+    return enqueue_raw_lz4(c, slot, raw_bytes);
 }
 
 // ---- zero-copy raw batches from registered caller memory (ABI 5) ----------------------------

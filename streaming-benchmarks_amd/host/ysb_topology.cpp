@@ -579,6 +579,45 @@ void GpuAdCampaignOperator::submit() {
     waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+void GpuAdCampaignOperator::submitLz4(const uint8_t* blocks, uint64_t compBytes, const ysb_lz4_block* dir,
+                                      uint32_t nBlocks) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (compBytes) std::memcpy(bytes_[cur_], blocks, compBytes);   // (the slot is free: submit's ysb_wait)
+    fillS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    check(ysb_submit_raw_lz4(ctx_, cur_, bytes_[cur_], compBytes, dir, nBlocks), "ysb_submit_raw_lz4");
+    cur_ ^= 1;
+    const auto t1 = std::chrono::steady_clock::now();
+    check(ysb_wait(ctx_, cur_), "ysb_wait");   // the other slot's H2D is done: refill it
+    waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+}
+
+Lz4Container Lz4Container::parse(const std::string& file, const std::string& name) {
+    ysb_lz4_file_header h;
+    if (file.size() < sizeof h) throw std::runtime_error(name + ": not a compressed replay file (too short)");
+    std::memcpy(&h, file.data(), sizeof h);
+    if (std::memcmp(h.magic, YSB_LZ4_FILE_MAGIC, 8) != 0 || h.version != 1)
+        throw std::runtime_error(name + ": not a compressed replay file (ysb_gen --lz4 writes one)");
+    if (h.n_blocks > (file.size() - sizeof h) / sizeof(ysb_lz4_block))
+        throw std::runtime_error(name + ": its directory is longer than the file");
+    Lz4Container c;
+    c.lineAligned = (h.flags & YSB_LZ4_FILE_LINE_ALIGNED) != 0;
+    c.nBlocks = h.n_blocks;
+    c.rawBytes = h.raw_bytes;
+    c.dir = reinterpret_cast<const ysb_lz4_block*>(file.data() + sizeof h);   // (32 bytes in: aligned for its u32 fields)
+    c.blocks = reinterpret_cast<const uint8_t*>(file.data()) + sizeof h + h.n_blocks * sizeof(ysb_lz4_block);
+    c.start.resize(c.nBlocks + 1);
+    uint64_t at = 0, raw = 0;
+    for (uint64_t i = 0; i < c.nBlocks; ++i) {
+        c.start[i] = at;
+        at += c.dir[i].comp_bytes & ~YSB_LZ4_STORED;
+        raw += c.dir[i].raw_bytes;
+    }
+    c.start[c.nBlocks] = at;
+    if (at != file.size() - sizeof h - h.n_blocks * sizeof(ysb_lz4_block) || raw != h.raw_bytes)
+        throw std::runtime_error(name + ": the directory does not match the file's size");
+    return c;
+}
+
 void GpuAdCampaignOperator::submitColumnsFile(const std::string& path, uint64_t rows) {
     ysb_columns_layout lay;
     uint64_t off[4], len[4];

@@ -186,6 +186,9 @@ public:
     void registerSource(FileBasedDataSource& src);         // pin + map the source's mapping (mappedIo)
     uint64_t submitMapped(FileBasedDataSource& src);       // the next whole lines, read in place: bytes
     void submit();                                         // hand the open slot to the GPU
+    // a batch of whole lines as LZ4 blocks (ysb_submit_raw_lz4): copied into the open slot's
+    // pinned buffer compressed, decoded on the GPU
+    void submitLz4(const uint8_t* blocks, uint64_t compBytes, const ysb_lz4_block* dir, uint32_t nBlocks);
     // One file image of WindowedArrowFormatBolter (<shared_file>_<k>, :303-317) of `rows` rows
     // counted from its columns (ysb_submit_columns, longs big-endian): only the ranges the count
     // reads are read from the file, straight into the open slot.  Throws, naming the file, if
@@ -221,6 +224,18 @@ private:
     uint64_t fillBytes_ = 0, fillEvents_ = 0, submitted_ = 0, rawBytes_ = 0;
     Parked parked_;
     void check(int rc, const char* what);
+};
+
+// A compressed replay file (include/ysb_hip.h ysb_lz4_file_header: header, directory, blocks)
+// as a view into its bytes.  parse throws, naming the file, for anything that is not one.
+struct Lz4Container {
+    bool lineAligned = false;
+    uint64_t nBlocks = 0, rawBytes = 0;
+    const ysb_lz4_block* dir = nullptr;
+    const uint8_t* blocks = nullptr;
+    std::vector<uint64_t> start;                            // block i's first byte in blocks; [nBlocks]: their size
+    uint64_t blockStart(uint64_t i) const { return start[i]; }
+    static Lz4Container parse(const std::string& file, const std::string& name);
 };
 
 // ---- output -------------------------------------------------------------------------------------------

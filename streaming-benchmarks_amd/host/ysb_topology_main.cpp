@@ -55,6 +55,9 @@ struct Args {
     // map does not hold are parked, looked up with GET after each batch, upserted and resolved
     bool join_redis = false;
     long long park_capacity = 1 << 20;
+    // --lz4: events_path is a compressed replay file (ysb_gen --lz4): runs of whole LZ4 blocks go
+    // over PCIe as they are and are decoded on the GPU (ysb_submit_raw_lz4)
+    bool lz4 = false;
     // streaming mode (configs[4]): --stream plus its options (ysb_stream.hpp)
     bool stream = false;
     StreamOptions so;
@@ -72,7 +75,7 @@ void usage() {
                  "       [--format json|tbl] [--flush-ms MS] [--batch-mb MB | --batch-bytes B] [--batch-events N]\n"
                  "       [--window-ring W] [--require-ip] [--dry-run] [--print-config] [--replay-rows CSV]\n"
                  "       [--host-split] [--repeat K] [--io-threads T] [--io auto|mapped|mmap|pread]\n"
-                 "       [--h2d-sdma] [--join-redis [--park-capacity N]]\n"
+                 "       [--h2d-sdma] [--join-redis [--park-capacity N]] [--lz4]\n"
                  "   or: ysb_topology --confPath PATH --columns [--device N] [--format json|tbl] [--require-ip]\n"
                  "       [--batch-mb MB | --batch-bytes B]   (window.size rows per <shared_file>_<k>)\n"
                  "   or: ysb_topology --confPath PATH --from-columns [--device N] [--sink none|csv:FILE|redis[:HOST[:PORT]]]\n"
@@ -119,6 +122,7 @@ Args parse(int argc, char** argv) {
         else if (k == "--h2d-sdma") a.h2d_sdma = true;
         else if (k == "--join-redis") a.join_redis = true;
         else if (k == "--park-capacity") a.park_capacity = std::max(1ll, std::atoll(val().c_str()));
+        else if (k == "--lz4") a.lz4 = true;
         else if (k == "--columns") a.columns = true;
         else if (k == "--from-columns") a.from_columns = true;
         else if (k == "--stream") a.stream = true;
@@ -152,6 +156,18 @@ Args parse(int argc, char** argv) {
     if (a.join_redis && (a.stream || a.columns || a.from_columns)) {
         std::fprintf(stderr, "--join-redis is batch mode's (the counting chain over events_path): not with --stream, "
                              "--columns or --from-columns\n");
+        std::exit(2);
+    }
+    if (a.lz4 && a.stream) {
+        std::fprintf(stderr, "--lz4 reads events_path as a compressed replay file in batch mode: not with --stream\n");
+        std::exit(2);
+    }
+    if (a.lz4 && a.columns) {
+        std::fprintf(stderr, "--lz4 feeds the counting chain: not with --columns (the columnar decode reads plain lines)\n");
+        std::exit(2);
+    }
+    if (a.lz4 && a.from_columns) {
+        std::fprintf(stderr, "--lz4 feeds the counting chain: not with --from-columns (column images are not compressed)\n");
         std::exit(2);
     }
     if (a.stream && a.columns) {
@@ -252,7 +268,10 @@ int run(const Args& a) {
         for (const std::string& c : lookup->campaigns()) map.addCampaign(c);
     }
     const std::string events = conf.get("events_path");
-    const bool tbl = a.format.empty() ? (events.size() > 4 && events.compare(events.size() - 4, 4, ".tbl") == 0)
+    // (a compressed replay file is named after what it holds: events.tbl.lz4)
+    const std::string named = a.lz4 && events.size() > 4 && events.compare(events.size() - 4, 4, ".lz4") == 0
+                                  ? events.substr(0, events.size() - 4) : events;
+    const bool tbl = a.format.empty() ? (named.size() > 4 && named.compare(named.size() - 4, 4, ".tbl") == 0)
                                       : a.format == "tbl";
     if (!a.format.empty() && a.format != "json" && a.format != "tbl") { usage(); return 2; }
 
@@ -265,7 +284,7 @@ int run(const Args& a) {
     o.requireIp = a.require_ip;
     o.gpuSplit = !a.host_split;
     o.h2dSdma = a.h2d_sdma;
-    o.mappedIo = a.io == "mapped" || (a.io == "auto" && o.gpuSplit && !o.h2dSdma);
+    o.mappedIo = !a.lz4 && (a.io == "mapped" || (a.io == "auto" && o.gpuSplit && !o.h2dSdma));
     o.parkCapacity = lookup ? (uint64_t)a.park_capacity : 0;
     if (a.io == "mapped" && !o.gpuSplit) {
         std::fprintf(stderr, "--io mapped reads raw lines in place: not with --host-split\n");
@@ -350,7 +369,39 @@ int run(const Args& a) {
         if (!csv_path.empty()) csv.add(d);
     };
     double last_flush = now_s();
-    for (long long rep = 0; rep < a.repeat; ++rep) {
+    // --lz4: the container's blocks in runs that fit a slot, compressed and decoded; the
+    // line-aligned flag makes every run a batch of whole lines
+    std::string lz4_file;
+    Lz4Container lz4;
+    if (a.lz4) {
+        lz4_file = readFile(events);
+        lz4 = Lz4Container::parse(lz4_file, events);
+        if (!lz4.lineAligned)
+            throw std::runtime_error(events + ": its blocks are not line-aligned (ysb_gen --lz4 writes them so): "
+                                     "a run of blocks would cut lines");
+    }
+    uint64_t lz4_comp = 0;
+    for (long long rep = 0; a.lz4 && rep < a.repeat; ++rep) {
+        for (uint64_t b = 0; b < lz4.nBlocks;) {
+            uint64_t e = b, comp = 0, raw = 0;
+            while (e < lz4.nBlocks && comp + (lz4.dir[e].comp_bytes & ~YSB_LZ4_STORED) <= o.batchBytes &&
+                   raw + lz4.dir[e].raw_bytes <= o.batchBytes && e - b < 0xFFFFFFFFull) {
+                comp += lz4.dir[e].comp_bytes & ~YSB_LZ4_STORED;
+                raw += lz4.dir[e].raw_bytes;
+                ++e;
+            }
+            if (e == b) throw std::runtime_error(events + ": block " + std::to_string(b) + " exceeds the slot (--batch-mb)");
+            op.submitLz4(lz4.blocks + lz4.blockStart(b), comp, lz4.dir + b, (uint32_t)(e - b));
+            lz4_comp += comp;
+            b = e;
+            if (lookup) op.resolveParked(*lookup);
+            if (a.flush_ms > 0 && (now_s() - last_flush) * 1000.0 >= (double)a.flush_ms) {
+                flush();
+                last_flush = now_s();
+            }
+        }
+    }
+    for (long long rep = 0; !a.lz4 && rep < a.repeat; ++rep) {
         if (rep) src.rewind();
         while (o.mappedIo ? op.submitMapped(src) > 0 : (o.gpuSplit ? op.fillFromRaw(src) : op.fillFrom(src)) > 0) {
             if (!o.mappedIo) op.submit();
@@ -379,7 +430,8 @@ int run(const Args& a) {
                 "\"bytes\": %llu, \"stream_GBs\": %.2f, \"line_split\": \"%s\", \"repeat\": %lld, "
                 "\"format\": \"%s\", \"sink\": %s, \"h2d\": \"%s\", \"copy_GBs\": %.2f, \"copy_busy_frac\": %.4f, "
                 "\"fill_s\": %.3f, \"slot_wait_s\": %.3f, \"join_redis\": %s, \"parked_keys\": %llu, "
-                "\"parked_found\": %llu, \"parked_joined\": %llu, \"parked_missed\": %llu, \"join_round_trips\": %llu}\n",
+                "\"parked_found\": %llu, \"parked_joined\": %llu, \"parked_missed\": %llu, \"join_round_trips\": %llu, "
+                "\"lz4\": %s, \"lz4_comp_bytes\": %llu, \"lz4_raw_bytes\": %llu}\n",
                 (unsigned long long)s.events, (unsigned long long)s.views, (unsigned long long)s.joined,
                 (unsigned long long)s.join_misses, (unsigned long long)s.parse_errors,
                 (unsigned long long)s.time_errors, (unsigned long long)s.out_of_ring,
@@ -393,7 +445,9 @@ int run(const Args& a) {
                 el_stream > 0 ? copy_ms * 1e-3 / el_stream : 0.0, op.fillSeconds(), op.waitSeconds(),
                 lookup ? "true" : "false", (unsigned long long)op.parkedTotals().keys,
                 (unsigned long long)op.parkedTotals().found, (unsigned long long)op.parkedTotals().joined,
-                (unsigned long long)op.parkedTotals().missed, (unsigned long long)(lookup ? lookup->roundTrips() : 0));
+                (unsigned long long)op.parkedTotals().missed, (unsigned long long)(lookup ? lookup->roundTrips() : 0),
+                a.lz4 ? "true" : "false", (unsigned long long)lz4_comp,
+                (unsigned long long)(a.lz4 ? lz4.rawBytes * (uint64_t)a.repeat : 0));
     return s.overflow_dropped ? 3 : 0;
 }
 

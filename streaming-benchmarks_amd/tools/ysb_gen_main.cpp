@@ -3,12 +3,14 @@
 //
 //   ysb_gen -d DIR [-n EVENTS] [--seed S] [--campaigns C] [--ads-per-campaign A]
 //           [--rate EVENTS_PER_SEC] [--t0 MS] [--with-skew] [--users K]
-//           [--shards K] [--tbl]
+//           [--shards K] [--tbl] [--lz4 [--lz4-block N]]
 //
 // Writes campaign-ids.txt, ad-ids.txt, ad-to-campaign-ids.txt (JSON map lines),
 // ad-to-campaign.csv (the fork's CSV map) and kafka-json.txt into DIR; with --shards K
 // kafka-json.<r>.txt per ad_id-hash shard instead; with --tbl also events.tbl, the
-// fork's pipe-delimited rows (conf/benchmarkConf.yaml:6).
+// fork's pipe-delimited rows (conf/benchmarkConf.yaml:6); with --lz4 also kafka-json.txt.lz4
+// (and events.tbl.lz4): the same bytes as a compressed replay file of line-aligned LZ4 blocks
+// of N bytes (default 8192; include/ysb_hip.h ysb_lz4_file_header) for ysb_topology --lz4.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,7 +26,8 @@ int main(int argc, char** argv) {
     unsigned long long n = 10000000ULL;   // kafka-event-count (core.clj:17)
     const char* dir = nullptr;
     unsigned shards = 0;
-    bool tbl = false;
+    bool tbl = false, lz4 = false;
+    unsigned lz4_block = 8192;
     for (int i = 1; i < argc; ++i) {
         auto val = [&]() -> const char* {
             if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", argv[i]); std::exit(2); }
@@ -41,6 +44,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--users")) p.n_users = (unsigned)std::strtoul(val(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--shards")) shards = (unsigned)std::strtoul(val(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--tbl")) tbl = true;
+        else if (!std::strcmp(argv[i], "--lz4")) lz4 = true;
+        else if (!std::strcmp(argv[i], "--lz4-block")) lz4_block = (unsigned)std::strtoul(val(), nullptr, 10);
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (!dir) { std::fprintf(stderr, "usage: ysb_gen -d DIR [-n EVENTS] [options]\n"); return 2; }
@@ -51,6 +56,21 @@ int main(int argc, char** argv) {
         q.format = YSB_GEN_TBL;
         rc = ysb_gen_dump(&q, n, dir);
         if (rc) { std::fprintf(stderr, "ysb_gen: %s\n", ysb_last_error(nullptr)); return 1; }
+    }
+    if (lz4) {
+        if (shards > 1) { std::fprintf(stderr, "ysb_gen: --lz4 compresses kafka-json.txt / events.tbl: not with --shards\n"); return 2; }
+        for (const char* name : {"kafka-json.txt", "events.tbl"}) {
+            if (!tbl && name[0] == 'e') continue;
+            const std::string path = std::string(dir) + "/" + name;
+            std::vector<uint8_t> data;
+            FILE* f = std::fopen(path.c_str(), "rb");
+            if (!f) { std::fprintf(stderr, "ysb_gen: cannot read %s\n", path.c_str()); return 1; }
+            uint8_t buf[1 << 16];
+            for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) data.insert(data.end(), buf, buf + k);
+            std::fclose(f);
+            rc = ysb_lz4_write_file((path + ".lz4").c_str(), data.data(), data.size(), lz4_block, 1, 1, 16);
+            if (rc) { std::fprintf(stderr, "ysb_gen: %s\n", ysb_last_error(nullptr)); return 1; }
+        }
     }
     return 0;
 }

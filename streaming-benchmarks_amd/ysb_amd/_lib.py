@@ -128,6 +128,15 @@ class YsbParkedDesc(C.Structure):
                 ("distinct_ms", C.c_double), ("resolve_ms", C.c_double)]
 
 
+class YsbLz4Block(C.Structure):
+    _fields_ = [("comp_bytes", C.c_uint32), ("raw_bytes", C.c_uint32)]
+
+
+class YsbLz4Desc(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("batches", "blocks", "stored_blocks", "comp_bytes", "raw_bytes",
+                                          "bad_blocks", "first_bad")] + [("decode_ms", C.c_double)]
+
+
 class YsbGenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_campaigns", C.c_uint32), ("ads_per_campaign", C.c_uint32),
                 ("t0_ms", C.c_int64), ("events_per_sec", C.c_uint64), ("with_skew", C.c_uint32),
@@ -181,6 +190,15 @@ SIGNATURES = {
     "ysb_submit_raw_mapped": (_I, [_P, _I, _PU8, _U64, C.POINTER(YsbRebase)]),
     "ysb_submit_mapped": (_I, [_P, _I, _PU8, _U64, _PU32, _U64, C.POINTER(YsbRebase)]),
     "ysb_split_lines_device": (_I, [_P, _PU8, _U64, _PU32, _U64, C.POINTER(_U64)]),
+    "ysb_submit_raw_lz4": (_I, [_P, _I, _PU8, _U64, _P, _U32]),
+    "ysb_lz4_decode_device": (_I, [_P, _PU8, _U64, _P, _U32, _PU8, _U64, C.POINTER(_U64), C.POINTER(_U32)]),
+    "ysb_lz4_info": (_I, [_P, C.POINTER(YsbLz4Desc)]),
+    "ysb_lz4_desc_size": (_U64, []),
+    "ysb_lz4_compress_bound": (_U32, [_U32]),
+    "ysb_lz4_compress_block": (_I, [_PU8, _U32, _PU8, _U32, _I, C.POINTER(YsbLz4Block)]),
+    "ysb_lz4_decompress_block": (_I, [_PU8, C.POINTER(YsbLz4Block), _PU8, _U32]),
+    "ysb_lz4_write_file": (_I, [C.c_char_p, _PU8, _U64, _U32, _I, _I, _I]),
+    "ysb_lz4_pack": (_I, [_PU8, _U64, _U32, _I, _I, _I, _PU8, _U64, C.POINTER(_U64), _P, _U64, C.POINTER(_U64)]),
     "ysb_copy_time": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_U64), C.POINTER(_U64)]),
     "ysb_submit_device": (_I, [_P, _PU8, _U64, _PU32, _U64]),
     "ysb_submit_device_segments": (_I, [_P, C.c_void_p, _U32]),
@@ -277,7 +295,7 @@ def lib():
             raise ImportError("ysb_colcount_desc is %d bytes in the library, %d in this binding"
                               % (L.ysb_colcount_desc_size(), C.sizeof(YsbColcountDesc)))
         for fn, st in ((L.ysb_upsert_info_size, YsbUpsertInfo), (L.ysb_admap_desc_size, YsbAdmapDesc),
-                       (L.ysb_parked_info_size, YsbParkedDesc)):
+                       (L.ysb_parked_info_size, YsbParkedDesc), (L.ysb_lz4_desc_size, YsbLz4Desc)):
             if fn() != C.sizeof(st):
                 raise ImportError("%s is %d bytes in the library, %d in this binding"
                                   % (st.__name__, fn(), C.sizeof(st)))

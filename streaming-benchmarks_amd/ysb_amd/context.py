@@ -310,6 +310,35 @@ class YsbContext:
                                              C.byref(n)))
         return n.value
 
+    def submit_raw_lz4(self, blocks, directory, slot=0):
+        """ysb_submit_raw_lz4: a raw batch as LZ4 blocks (bytes / uint8 array) and their
+        directory (ysb_amd.lz4.pack's: an (n, 2) uint32 array of comp_bytes | stored bit,
+        raw_bytes); only the compressed bytes cross PCIe, the GPU decodes, splits and scans."""
+        buf = np.frombuffer(blocks, dtype=np.uint8) if isinstance(blocks, (bytes, bytearray)) else np.ascontiguousarray(blocks, dtype=np.uint8)
+        d = np.ascontiguousarray(directory, dtype=np.uint32).reshape(-1, 2)
+        self._c(lib().ysb_submit_raw_lz4(self._h, slot, _ptr(buf), buf.size, _ptr(d), d.shape[0]))
+
+    def lz4_decode_device(self, d_comp, comp_bytes, directory, d_out, out_cap):
+        """ysb_lz4_decode_device: the decode alone, device to device.  Returns (raw bytes, first
+        bad block or None); a bad block does not raise here -- its output range is untouched."""
+        d = np.ascontiguousarray(directory, dtype=np.uint32).reshape(-1, 2)
+        raw, bad = C.c_uint64(), C.c_uint32()
+        rc = lib().ysb_lz4_decode_device(self._h, C.c_void_p(d_comp), comp_bytes, _ptr(d), d.shape[0],
+                                         C.c_void_p(d_out), out_cap, C.byref(raw), C.byref(bad))
+        if rc != -5 or bad.value == 0xFFFFFFFF:   # (YSB_ERR_FORMAT with a bad block: the return value says it)
+            self._c(rc)
+        return raw.value, (None if bad.value == 0xFFFFFFFF else bad.value)
+
+    def lz4_info(self):
+        """ysb_lz4_info as a dict: the last compressed batch (batches, blocks, stored_blocks,
+        comp_bytes, raw_bytes, bad_blocks, first_bad or None, decode_ms with timing=True)."""
+        d = _lib.YsbLz4Desc()
+        self._c(lib().ysb_lz4_info(self._h, C.byref(d)))
+        out = {n: getattr(d, n) for n, _ in d._fields_}
+        if out["first_bad"] == 0xFFFFFFFF:
+            out["first_bad"] = None
+        return out
+
     def copy_time(self):
         """(total ms, copies, bytes) of the slot H2D copies since the last call (timing=True)."""
         t, k, b = C.c_double(), C.c_uint64(), C.c_uint64()

@@ -1,0 +1,177 @@
+"""The drop-in path with LZ4-compressed batches, timed against itself uncompressed.
+
+Same staging as `bench_dropin.py staged --raw`: two distinct ~256 MB batches of configs[1]'s
+events, generated once, resubmitted alternately through the pinned double-buffered slots, each
+leg with a generator-truth check.  One leg submits the raw lines (ysb_submit_raw: the parent's
+path, the yardstick), the other the same batches compressed on the host by blocks
+(ysb_submit_raw_lz4: compressed bytes over PCIe, decoded on the GPU).  The legs alternate
+--repeats times in one process.  Plus the decode alone (ysb_lz4_decode_device) at several
+block sizes.
+
+Per leg: events/s, the H2D rate (bytes copied / copy time, HIP events on the copy stream), the
+copy queue's busy share; for the compressed leg the compression ratio and the decode's rate in
+GB/s of output.  Everything goes to profiles/lz4_bench.json and, as one JSON line, to stdout.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "streaming-benchmarks_amd"))
+
+import numpy as np  # noqa: E402
+
+
+def log(*a):
+    print(*a, file=sys.stderr, flush=True)
+
+
+def view(addr, n):
+    return np.ctypeslib.as_array((C.c_uint8 * n).from_address(addr))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--events", type=int, default=40_000_000, help="events per timed leg")
+    ap.add_argument("--slot-mb", type=int, default=256)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--block", type=int, default=None, help="LZ4 block size of the chain legs (default: the tools')")
+    ap.add_argument("--decode-blocks", default="4096,8192,16384,65536")
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lz4_bench.json"))
+    a = ap.parse_args()
+
+    from ysb_amd import GenParams, YsbContext, lz4
+    from ysb_amd._lib import check, lib
+    block = a.block or lz4.DEFAULT_BLOCK
+    threads = max(1, min(a.threads, 16))
+    g = GenParams(seed=42, events_per_sec=100_000)
+    _, aids = g.ids()
+    per = int((a.slot_mb << 20) // g.max_line_bytes())
+    res = {"events_per_batch": per, "slot_MB": a.slot_mb, "block_bytes": block, "repeats": a.repeats, "legs": []}
+    with YsbContext(device=a.device, n_campaigns=100, window_ring=1024, timing=True, max_batch_bytes=a.slot_mb << 20,
+                    max_batch_events=per, ring_base_bucket=g.c.t0_ms // 10000 - 8) as ctx:
+        ctx.load_ad_map(aids, g.ad_campaign_index())
+        raw = []
+        for s in (0, 1):   # two distinct batches, generated on the device, kept on the host
+            cap = per * g.max_line_bytes()
+            d_b, d_o = ctx.device_alloc(cap), ctx.device_alloc(4 * per + 64)
+            nb = ctx.gen_events_device(g, s * per, per, d_b, cap, d_o)
+            raw.append(ctx.d2h(np.empty(nb, dtype=np.uint8), d_b))
+            ctx.device_free(d_b)
+            ctx.device_free(d_o)
+        t0 = time.perf_counter()
+        comp = [lz4.pack(r, block, line_aligned=True, threads=threads) for r in raw]
+        t_pack = time.perf_counter() - t0
+        raw_bytes = sum(r.size for r in raw)
+        comp_bytes = sum(b.size for b, _ in comp)
+        res["compress"] = {"threads": threads, "seconds": round(t_pack, 3), "GBs_in": round(raw_bytes / t_pack / 1e9, 3),
+                           "raw_bytes": raw_bytes, "comp_bytes": comp_bytes, "ratio": round(raw_bytes / comp_bytes, 4),
+                           "blocks": [int(d.shape[0]) for _, d in comp],
+                           "stored_blocks": [int((d[:, 0] >> 31).sum()) for _, d in comp]}
+        log("compressed %d B -> %d B (%.3fx) in %.2f s" % (raw_bytes, comp_bytes, raw_bytes / comp_bytes, t_pack))
+        slot = [view(ctx.slot_buffers(s)[0], a.slot_mb << 20) for s in (0, 1)]
+        dirs = [np.ascontiguousarray(d, dtype=np.uint32) for _, d in comp]
+
+        def leg(kind):
+            for s in (0, 1):   # staged once per leg: the slot's pinned buffer holds what crosses PCIe
+                ctx.wait(s)
+                src = raw[s] if kind == "raw" else comp[s][0]
+                slot[s][:src.size] = src
+
+            def submit(s):
+                if kind == "raw":
+                    check(lib().ysb_submit_raw(ctx._h, s, C.c_void_p(slot[s].ctypes.data), raw[s].size), ctx._h)
+                else:
+                    check(lib().ysb_submit_raw_lz4(ctx._h, s, C.c_void_p(slot[s].ctypes.data), comp[s][0].size,
+                                                   C.c_void_p(dirs[s].ctypes.data), dirs[s].shape[0]), ctx._h)
+            for s in (0, 1, 0, 1):   # warmup
+                submit(s)
+            ctx.sync()
+            ctx.kernel_time()
+            ctx.copy_time()
+            ctx.reset()
+            nsub = max(2, -(-a.events // per))
+            t = time.perf_counter()
+            for i in range(nsub):
+                submit(i & 1)   # waits for the slot's previous H2D inside
+            ctx.sync()
+            el = time.perf_counter() - t
+            kms, launches = ctx.kernel_time()
+            cms, copies, cbytes = ctx.copy_time()
+            st = ctx.stats()
+            info = ctx.lz4_info() if kind == "lz4" else None
+            for i in range(nsub):
+                ctx.truth_accumulate(g, (i & 1) * per, per)
+            mism, truth, counted = ctx.truth_compare()
+            n = nsub * per
+            out = {"leg": kind, "events": n, "batches": nsub, "seconds": round(el, 4), "events_per_s": round(n / el, 1),
+                   "h2d_bytes": cbytes, "h2d_GBs": round(cbytes / (cms * 1e-3) / 1e9, 2) if cms else 0.0,
+                   "copy_busy_frac": round(cms * 1e-3 / el, 4), "scan_ms_per_batch": round(kms / max(launches, 1), 4),
+                   "check": {"truth_mismatched_cells": mism, "truth_views": truth, "counted_views": counted,
+                             "events": st["events"], "parse_errors": st["parse_errors"]}}
+            if info:
+                out["decode_ms_last_batch"] = round(info["decode_ms"], 4)
+                out["decode_GBs_out_last_batch"] = round(info["raw_bytes"] / (info["decode_ms"] * 1e-3) / 1e9, 2) \
+                    if info["decode_ms"] else 0.0
+                out["bad_blocks"] = info["bad_blocks"]
+            log(json.dumps(out))
+            return out
+
+        for _ in range(a.repeats):
+            for kind in ("raw", "lz4"):
+                res["legs"].append(leg(kind))
+        ctx.sync()
+
+        # the decode alone, device to device, at several block sizes
+        res["decode_alone"] = []
+        d_out = ctx.device_alloc(raw[0].size + 64)
+        for bb in [int(x) for x in a.decode_blocks.split(",") if x]:
+            blob, d = (comp[0] if bb == block else lz4.pack(raw[0], bb, line_aligned=True, threads=threads))
+            d_in = ctx.device_alloc(blob.size + 64)
+            ctx.h2d(d_in, blob)
+            ms = []
+            for _ in range(7):
+                got, bad = ctx.lz4_decode_device(d_in, blob.size, d, d_out, raw[0].size)
+                assert got == raw[0].size and bad is None
+                ms.append(ctx.lz4_info()["decode_ms"])
+            same = bool((ctx.d2h(np.empty(raw[0].size, dtype=np.uint8), d_out) == raw[0]).all())
+            ctx.device_free(d_in)
+            med = statistics.median(ms[2:])
+            res["decode_alone"].append({"block_bytes": bb, "blocks": int(d.shape[0]), "ratio": round(raw[0].size / blob.size, 4),
+                                        "ms": [round(x, 4) for x in ms], "median_ms": round(med, 4),
+                                        "GBs_out": round(raw[0].size / (med * 1e-3) / 1e9, 2),
+                                        "GBs_in": round(blob.size / (med * 1e-3) / 1e9, 2), "output_equal": same})
+            log(json.dumps(res["decode_alone"][-1]))
+        ctx.device_free(d_out)
+
+    def summary(kind):
+        v = [l["events_per_s"] for l in res["legs"] if l["leg"] == kind]
+        return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    r, z = summary("raw"), summary("lz4")
+    h2d = statistics.median(l["h2d_GBs"] for l in res["legs"] if l["leg"] == "raw")
+    dec = next((x["GBs_out"] for x in res["decode_alone"] if x["block_bytes"] == block), None)
+    res["summary"] = {"raw_events_per_s": r, "lz4_events_per_s": z, "ratio": res["compress"]["ratio"],
+                      "lz4_over_raw_median": round(z["median"] / r["median"], 4),
+                      "lz4_median_above_raw_max": z["median"] > r["max"],
+                      "raw_h2d_GBs": h2d, "decode_GBs_out": dec,
+                      "decoder_bound": (dec is not None and dec < h2d * res["compress"]["ratio"]),
+                      "all_checks_exact": all(l["check"]["truth_mismatched_cells"] == 0 and
+                                              l["check"]["truth_views"] == l["check"]["counted_views"] for l in res["legs"])}
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res["summary"]), flush=True)
+
+
+if __name__ == "__main__":
+    main()
