@@ -504,6 +504,29 @@ typedef struct ysb_lz4_block {
  * on it.) */
 int         ysb_submit_raw_lz4(ysb_ctx* ctx, int slot, const uint8_t* bytes, uint64_t comp_bytes,
                                const ysb_lz4_block* dir, uint32_t n_blocks);
+/* The same for a compressed batch that lies in a registered range (ysb_host_register) -- the
+ * compressed form of ysb_submit_raw_mapped and ysb_submit_mapped (additive within ABI 6).
+ * bytes[0, comp_bytes) are the blocks back to back, at any byte address; the span widened to
+ * 16-byte boundaries on both sides must lie inside one registered range.  dir is host memory.
+ * The copy kernel (or, YSB_F_H2D_SDMA, the DMA engine) reads the compressed bytes in place into
+ * the slot's device staging; the slot's pinned byte buffer is not used and the host makes no
+ * pass over the bytes (block 0 apart, which the host model decodes as the layout sample; counts
+ * never depend on it); the block descriptors go through the slot's pinned descriptor buffer.
+ * The decode runs on the split's stream behind the slot's copy.  Then
+ *   d_line_off == NULL (n_events must be 0): the GPU line split;
+ *   otherwise: no split, d_line_off[0, n_events) are device offsets into the DECODED batch;
+ * then, with rebase != NULL, the rebase on the decoded bytes (from the split: YSB_ERR_ARG at the
+ * launch if the batch has more lines than the table holds from first_line; with offsets: at the
+ * call).  With offsets too the scan is launched by the next call that orders work, not at once
+ * as ysb_submit_mapped's: the verdict on the blocks must be known before a line is counted.
+ * The rules are the union of ysb_submit_raw_lz4's (directory, capacity, a bad block drops the
+ * batch whole with a sticky YSB_ERR_FORMAT, n_blocks = 0 is an empty batch) and the mapped
+ * calls' (registration, rebase arguments, at most two copies in flight: the call first waits
+ * for the slot's previous copy; the caller must not rewrite the bytes until
+ * ysb_wait(ctx, slot)).  ysb_lz4_info and ysb_copy_time account these batches like the others. */
+int         ysb_submit_lz4_mapped(ysb_ctx* ctx, int slot, const uint8_t* bytes, uint64_t comp_bytes,
+                                  const ysb_lz4_block* dir, uint32_t n_blocks,
+                                  const uint32_t* d_line_off, uint64_t n_events, const ysb_rebase* rebase);
 /* The decode alone, as ysb_split_lines_device is the split alone (the codec call of a Kafka
  * consumer or a compressed-file reader, on bytes already in HBM): d_comp (device, any
  * alignment) holds the blocks, dir is host memory, d_out (device, out_cap bytes) receives

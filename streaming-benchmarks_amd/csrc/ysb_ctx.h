@@ -176,6 +176,7 @@ struct ysb_ctx {
     u64 raw_nbytes[2] = {0, 0};
     int raw_layout[2] = {-1, -1};               // its first line's layout (sampled on the host)
     LearnDesc raw_learn[2]{};
+    const u32* raw_off[2] = {nullptr, nullptr}; // the caller's device line offsets (ysb_submit_lz4_mapped); NULL: d_roff
     // H2D timing (YSB_F_TIMING): {start, end} of each slot copy since the last ysb_copy_time
     EventLog<2> cev;
     u64 copy_bytes = 0;
@@ -223,12 +224,16 @@ struct ysb_ctx {
     u64 park_resolved_total = 0;
     ysb_parked_desc park_last{};
     // LZ4 batches (ysb_lz4_api.cpp; ysb_lz4.h): per slot the compressed bytes in HBM (the
-    // slot's pinned buffer carries them over PCIe; d_bytes[slot] receives the decode) and the
+    // slot's pinned buffer carries them over PCIe, or they are read in place from a registered
+    // range: lz4_hsrc / lz4_dsrc, the staged batch's source as host and device address;
+    // d_bytes[slot] receives the decode) and the
     // block descriptors -- pinned and device, LZ4_DESC_HEAD bytes of {first bad, bad blocks}
     // in front, initialised by the same copy --; the pair read back to pinned memory behind the
     // decode (h_lz4bad[2 * slot]); whether the slot's pending raw batch is a compressed one;
     // its figures until its launch settles them into lz4_last; YSB_F_TIMING's event pair
     DevBuf<u8> d_lz4[2];
+    const u8* lz4_hsrc[2] = {nullptr, nullptr};
+    const u8* lz4_dsrc[2] = {nullptr, nullptr};
     PinBuf<u8> h_lz4desc[2];
     u8* hd_lz4desc[2] = {nullptr, nullptr};
     DevBuf<u8> d_lz4desc[2];
@@ -428,9 +433,11 @@ YSB_INTERNAL int park_counters(ysb_ctx* c);
 YSB_INTERNAL int park_reset(ysb_ctx* c);         // ysb_reset's part: the log emptied, the counters zero
 // ysb_lz4_api.cpp
 // A compressed batch's directory checked and its bytes and descriptors placed in the slot's
-// pinned memory (the caller has waited for the slot's previous copy); *raw_total its raw size
+// pinned memory (the caller has waited for the slot's previous copy); *raw_total its raw size.
+// dsrc != NULL: the bytes stay where they are, in a registered range whose device alias of
+// `bytes` it is, and only the descriptors are placed.
 YSB_INTERNAL int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
-                           uint32_t n_blocks, uint64_t* raw_total);
+                           uint32_t n_blocks, const uint8_t* dsrc, uint64_t* raw_total);
 // the slot's two copies (compressed bytes, descriptors) as copy_slot_ranges takes them
 YSB_INTERNAL void lz4_copies(ysb_ctx* c, int slot, SlotCopy v[2]);
 // the staged batch decoded into d_bytes[slot] on s, and its {first bad, bad blocks} read back

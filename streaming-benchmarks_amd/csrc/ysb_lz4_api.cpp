@@ -1,7 +1,7 @@
 // ysb_lz4_api.cpp -- LZ4 batches above the kernel (ysb_lz4.hip; the rules: ysb_lz4.h): the
-// directory's checks, a slot's staging (compressed bytes and block descriptors in pinned memory,
-// one copy each), the decode's launch and read-back, the synchronous decode alone, the last
-// batch's figures, and the host codec entries.  ysb_submit_raw_lz4 itself sits beside
+// directory's checks, a slot's staging (compressed bytes in pinned memory or left in place in a
+// registered range, block descriptors in pinned memory, one copy each), the decode's launch and read-back, the synchronous decode alone, the last
+// batch's figures, and the host codec entries.  ysb_submit_raw_lz4 and ysb_submit_lz4_mapped sit beside
 // ysb_submit_raw in ysb_submit.cpp.
 #include "ysb_ctx.h"
 #include "ysb_lz4.h"
@@ -53,7 +53,7 @@ static void fill_descs(const ysb_lz4_block* dir, u32 n, u8* out, ysb_lz4_desc* i
 extern "C" {
 
 int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
-              uint32_t n_blocks, uint64_t* raw_total) {
+              uint32_t n_blocks, const uint8_t* dsrc, uint64_t* raw_total) {
     int rc = dir_args(c, bytes, comp_bytes, dir, n_blocks, raw_total);
     if (rc) return rc;
     if (comp_bytes > c->cfg.max_batch_bytes || *raw_total > c->cfg.max_batch_bytes)
@@ -73,21 +73,24 @@ int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, c
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hd_lz4desc[slot]), c->h_lz4desc[slot], 0));
         c->lz4desc_cap[slot] = cap;
     }
-    if (bytes != c->h_bytes[slot] && comp_bytes) std::memcpy(c->h_bytes[slot], bytes, comp_bytes);
+    // the bytes: into the slot's pinned buffer, or read where they lie (a registered range)
+    if (!dsrc && bytes != c->h_bytes[slot] && comp_bytes) std::memcpy(c->h_bytes[slot], bytes, comp_bytes);
+    c->lz4_hsrc[slot] = dsrc ? bytes : c->h_bytes[slot].get();
+    c->lz4_dsrc[slot] = dsrc ? dsrc : c->hd_bytes[slot];
     fill_descs(dir, n_blocks, c->h_lz4desc[slot], &c->lz4_pend[slot], &c->lz4_max_raw[slot]);
     // the layout sample: block 0 as the host model decodes it (nothing if it is bad -- the
     // device decides that for the batch)
     c->lz4_sample.clear();
     if (n_blocks) {
         c->lz4_sample.resize(dir[0].raw_bytes);
-        if (!lz4_decode_block(c->h_bytes[slot], dir[0], c->lz4_sample.data())) c->lz4_sample.clear();
+        if (!lz4_decode_block(c->lz4_hsrc[slot], dir[0], c->lz4_sample.data())) c->lz4_sample.clear();
     }
     return YSB_OK;
 }
 
 void lz4_copies(ysb_ctx* c, int slot, SlotCopy v[2]) {
     const ysb_lz4_desc& p = c->lz4_pend[slot];
-    v[0] = {c->d_lz4[slot], c->hd_bytes[slot], c->h_bytes[slot], p.comp_bytes};
+    v[0] = {c->d_lz4[slot], c->lz4_dsrc[slot], c->lz4_hsrc[slot], p.comp_bytes};
     v[1] = {c->d_lz4desc[slot], c->hd_lz4desc[slot], c->h_lz4desc[slot],
             p.blocks ? LZ4_DESC_HEAD + p.blocks * sizeof(Lz4Desc) : 0};
 }

@@ -514,12 +514,13 @@ int launch_pending_raw(ysb_ctx* c) {
     } else if (c->raw_rebase_on[slot] && c->h_rawn[slot] > c->rebase_n - c->raw_rebase[slot].first_line) {
         rc = fail(c, YSB_ERR_ARG, "raw batch (slot %d): %llu lines, more than the rebase table holds from line %llu",
                   slot, (unsigned long long)c->h_rawn[slot], (unsigned long long)c->raw_rebase[slot].first_line);
-    } else if (c->h_rawn[slot] > c->raw_lines_cap) {
+    } else if (!c->raw_off[slot] && c->h_rawn[slot] > c->raw_lines_cap) {   // (the caller's offsets: no d_roff to fit)
         rc = fail(c, YSB_ERR_CAPACITY, "raw batch (slot %d): %llu lines, more than the %llu its slot holds "
                   "(max(max_batch_events, max_batch_bytes / 32))", slot, (unsigned long long)c->h_rawn[slot],
                   (unsigned long long)c->raw_lines_cap);
     } else {
-        const ysb_segment sg{c->d_bytes[slot], c->raw_nbytes[slot], c->d_roff[slot], c->h_rawn[slot]};
+        const u32* off = c->raw_off[slot] ? c->raw_off[slot] : c->d_roff[slot].get();
+        const ysb_segment sg{c->d_bytes[slot], c->raw_nbytes[slot], off, c->h_rawn[slot]};
         rc = enqueue_scan(c, &sg, 1, {c->raw_layout[slot], c->raw_learn[slot]});
     }
     // the slot's device buffers are free again once this launch (or nothing) has run
@@ -527,6 +528,7 @@ int launch_pending_raw(ysb_ctx* c) {
         rc = fail(c, YSB_ERR_HIP, "hipEventRecord failed");
     c->raw_pend = -1;
     c->raw_lz4[slot] = false;
+    c->raw_off[slot] = nullptr;
     if (rc) {
         c->raw_fail = rc;
         c->raw_fail_msg = c->err;
@@ -605,11 +607,16 @@ int ysb_submit_raw(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes) 
 
 // ---- LZ4-compressed raw batches (ysb_lz4_api.cpp, ysb_lz4.hip) --------------------------------
 
-// enqueue_raw for a staged compressed batch (lz4_stage): the compressed bytes and the block
-// descriptors over PCIe, the decode into the slot's device buffer on the stream of the split
-// -- behind the slot's copy, never on the copy stream, which goes on with the other slot's
-// copy --, then the split as for any raw batch; its scan launches at the next call.
-static int enqueue_raw_lz4(ysb_ctx* c, int slot, u64 raw_bytes) {
+// enqueue_raw for a staged compressed batch (lz4_stage), the ONE statement of its order for
+// ysb_submit_raw_lz4 and ysb_submit_lz4_mapped: the compressed bytes (from the slot's pinned
+// buffer or in place from a registered range) and the block descriptors over PCIe, the decode
+// into the slot's device buffer on the stream of the split -- behind the slot's copy, never on
+// the copy stream, which goes on with the other slot's copy --, then the split as for any raw
+// batch or, with d_line_off, the caller's n device offsets into the decoded batch and no split,
+// then the rebase (rb != NULL) on the decoded bytes on the same stream.  Its scan launches at
+// the next call, with offsets too: the verdict on its blocks must be known before its lines
+// are counted.
+static int enqueue_raw_lz4(ysb_ctx* c, int slot, u64 raw_bytes, const u32* d_line_off, u64 n, const ysb_rebase* rb) {
     int rc;
     c->raw_layout[slot] = -1;
     if (layout_sampling(c) && !c->lz4_sample.empty())
@@ -620,20 +627,48 @@ static int enqueue_raw_lz4(ysb_ctx* c, int slot, u64 raw_bytes) {
     lz4_copies(c, slot, v);
     if ((rc = copy_slot_ranges(c, slot, v, 2))) return rc;
     HIPCHK(c, hipStreamWaitEvent(ss, c->ev_h2d[slot], 0));
-    c->raw_rebase_on[slot] = false;
+    c->raw_rebase_on[slot] = rb != nullptr;
+    if (rb) c->raw_rebase[slot] = *rb;
     if ((rc = lz4_enqueue_decode(c, slot, ss))) return rc;
-    if (raw_bytes) {
+    const i64 lead = rb ? c->rebase_base + rb->lead_shift : 0;
+    if (d_line_off) {
+        c->h_rawn[slot] = n;
+        if (rb) launch_rebase(c->d_bytes[slot], raw_bytes, d_line_off, n, nullptr, n, c->d_rebase + rb->first_line,
+                              c->rebase_n - rb->first_line, lead, c->cus, ss);
+    } else if (raw_bytes) {
         HIPCHK(c, launch_split_lines(c->d_bytes[slot], raw_bytes, c->d_split_chunk, c->d_roff[slot],
                                      c->raw_lines_cap, c->h_rawn + slot, ss));
+        if (rb) launch_rebase(c->d_bytes[slot], raw_bytes, c->d_roff[slot], c->raw_lines_cap, c->h_rawn + slot, 0,
+                              c->d_rebase + rb->first_line, c->rebase_n - rb->first_line, lead, c->cus, ss);
     } else {
         c->h_rawn[slot] = 0;
     }
+    if (rb) HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_raw[slot], ss));
     c->raw_nbytes[slot] = raw_bytes;
     rc = launch_pending_raw(c);
     c->raw_pend = slot;
     c->raw_lz4[slot] = true;
+    c->raw_off[slot] = d_line_off;
     return rc;
+}
+
+// What both compressed submits do once their own arguments are checked: the slot's earlier
+// batch launched, its buffers there and free, the batch staged (dsrc: lz4_stage), enqueued.
+static int submit_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, u64 comp_bytes, const ysb_lz4_block* dir, u32 n_blocks,
+                      const u8* dsrc, const u32* d_line_off, u64 n, const ysb_rebase* rb) {
+    // the slot's own earlier batch launches first (its device buffers are about to be reused)
+    int rc = c->raw_pend == slot ? launch_pending_raw(c) : YSB_OK;
+    if (!rc) rc = ensure_slots(c);
+    if (!rc) rc = ensure_raw(c);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the slot's previous H2D must be done before its pinned buffers are rewritten (in place:
+    // the descriptors'; so at most two copies are in flight)
+    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
+    u64 raw_bytes = 0;
+    if ((rc = lz4_stage(c, slot, bytes, comp_bytes, dir, n_blocks, dsrc, &raw_bytes))) return rc;
+    return enqueue_raw_lz4(c, slot, raw_bytes, d_line_off, n, rb);
 }
 
 int ysb_submit_raw_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
@@ -641,17 +676,7 @@ int ysb_submit_raw_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp
     if (!c) return YSB_ERR_ARG;
     if (slot < 0 || slot > 1) return fail(c, YSB_ERR_ARG, "slot must be 0 or 1");
     if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
-    // the slot's own earlier batch launches first (its device buffers are about to be reused)
-    int rc = c->raw_pend == slot ? launch_pending_raw(c) : YSB_OK;
-    if (!rc) rc = ensure_slots(c);
-    if (!rc) rc = ensure_raw(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    // the slot's previous H2D must be done before its pinned buffers are rewritten
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
-    u64 raw_bytes = 0;
-    if ((rc = lz4_stage(c, slot, bytes, comp_bytes, dir, n_blocks, &raw_bytes))) return rc;
-    return enqueue_raw_lz4(c, slot, raw_bytes);
+    return submit_lz4(c, slot, bytes, comp_bytes, dir, n_blocks, nullptr, nullptr, 0, nullptr);
 }
 
 // ---- zero-copy raw batches from registered caller memory (ABI 5) ----------------------------
@@ -759,6 +784,27 @@ int ysb_submit_raw_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t n
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     return enqueue_raw(c, slot, bytes, dsrc, nbytes, rb);
+}
+
+// A compressed batch read in place from a registered range: the union of
+// ysb_submit_raw_lz4's rules and the mapped calls'.  The copy kernel (the DMA engine with
+// YSB_F_H2D_SDMA) reads the blocks where they lie into d_lz4[slot]; the slot's pinned byte
+// buffer is not used and the host makes no pass over the bytes (block 0 apart: the layout
+// sample).  d_line_off NULL: the GPU line split; otherwise n device offsets into the decoded batch.
+int ysb_submit_lz4_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
+                          uint32_t n_blocks, const uint32_t* d_line_off, uint64_t n, const ysb_rebase* rb) {
+    if (!c) return YSB_ERR_ARG;
+    if (slot < 0 || slot > 1) return fail(c, YSB_ERR_ARG, "slot must be 0 or 1");
+    if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
+    if (comp_bytes && !bytes) return fail(c, YSB_ERR_ARG, "NULL batch buffer");
+    if (!d_line_off && n) return fail(c, YSB_ERR_ARG, "n_events without line offsets (NULL d_line_off: the GPU split, n_events 0)");
+    if (d_line_off && !n) return fail(c, YSB_ERR_ARG, "line offsets without n_events");
+    if (n > 0x7FFFFFFFull) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 events per batch");
+    const u8* dsrc = nullptr;
+    int rc = mapped_src_or_fail(c, bytes, comp_bytes, &dsrc);
+    if (!rc) rc = rebase_args(c, rb, d_line_off ? &n : nullptr);
+    if (rc) return rc;
+    return submit_lz4(c, slot, bytes, comp_bytes, dir, n_blocks, dsrc, d_line_off, n, rb);
 }
 
 // A mapped batch whose line offsets are already in HBM: nothing waits for a line count, so the

@@ -42,6 +42,13 @@ struct ReplayCycle {
     };
     std::vector<Batch> batches;
     uint64_t lines() const { return start.size(); }
+    // The bytes given back (a compressed replay keeps the cycle's blocks, not its lines); the
+    // index and the batches stay.
+    void releaseBytes() {
+        if (bytes) munmap(bytes, reserved);
+        bytes = nullptr;
+        reserved = 0;
+    }
     ReplayCycle() = default;
     ReplayCycle(const ReplayCycle&) = delete;
     ReplayCycle& operator=(const ReplayCycle&) = delete;

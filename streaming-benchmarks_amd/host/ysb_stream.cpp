@@ -109,6 +109,7 @@ struct StreamingJob::Shard {
     double prepareS = 0, registerS = 0;
     std::string error;
     ReplayCycle cyc;
+    Lz4Cycle z;                           // (--stream-lz4) the cycle compressed: what is registered
     std::unique_ptr<ysb_ctx, CtxClose> ctx;
     std::unique_ptr<DeviceBuf> lineOff;   // (mapped) every line's offset within its batch, in HBM
     uint8_t* slot[2] = {nullptr, nullptr};
@@ -120,6 +121,8 @@ StreamingJob::StreamingJob(const StreamOptions& o) : o_(o) {
     if (o_.t0Ms % BUCKET_MS) throw std::runtime_error("t0 must be a multiple of 10 000 ms");
     if (o_.shards < 1 || o_.eventRate < 1 || o_.speedup <= 0) throw std::runtime_error("bad stream options");
     if (o_.skew < 0 || o_.skew > 2) throw std::runtime_error("skew must be 0 (off), 1 (skew + late events) or 2 (skew only)");
+    if (o_.streamLz4 && o_.replay == StreamOptions::COPY) throw std::runtime_error("a compressed replay is read in place: not with the copy replay");
+    if (o_.streamLz4 && (o_.lz4Block < 1 || o_.lz4Block > YSB_LZ4_MAX_RAW)) throw std::runtime_error("the LZ4 block size must be in 1..65536");
 }
 
 StreamingJob::~StreamingJob() = default;
@@ -234,9 +237,14 @@ void StreamingJob::prepareShard(Shard& sh, const std::vector<const char*>& keys,
         sh.gen.n_ad_subset = (uint32_t)sh.subset.size();
     }
     build_cycle(ctx, sh.gen, o_, sh.cyc, pool);
+    // --stream-lz4: every batch compressed on its own on the shard's pool (its pages on this node)
+    if (o_.streamLz4) compress_cycle(sh.cyc, o_.lz4Block, sh.z, pool);
     const double t1 = wall_s();
     if (o_.replay != StreamOptions::COPY) {
-        check_ctx(ysb_host_register(ctx, sh.cyc.bytes, (sh.cyc.used + 4095) / 4096 * 4096), ctx, "ysb_host_register");
+        // the compressed cycle is registered, the raw one is not
+        uint8_t* const base = o_.streamLz4 ? sh.z.bytes : sh.cyc.bytes;
+        const uint64_t used = o_.streamLz4 ? sh.z.used : sh.cyc.used;
+        check_ctx(ysb_host_register(ctx, base, (used + 4095) / 4096 * 4096), ctx, "ysb_host_register");
         check_ctx(ysb_rebase_table(ctx, sh.cyc.timeAt.data(), sh.cyc.lines(), sh.cyc.upperMin), ctx, "ysb_rebase_table");
     }
     if (o_.replay == StreamOptions::MAPPED) {   // the line offsets, once for every cycle
@@ -246,6 +254,8 @@ void StreamingJob::prepareShard(Shard& sh, const std::vector<const char*>& keys,
         sh.lineOff = std::make_unique<DeviceBuf>(ctx, lo.size() * 4 + 64);
         check_ctx(ysb_memcpy_h2d(ctx, sh.lineOff->p, lo.data(), lo.size() * 4), ctx, "ysb_memcpy_h2d");
     }
+    // the raw lines are not needed again: the line offsets and the rebase table are on the device
+    if (o_.streamLz4) sh.cyc.releaseBytes();
     sh.registerS = wall_s() - t1;
     sh.prepareS = wall_s() - t0;
 }
@@ -306,7 +316,14 @@ bool StreamingJob::Feeder::submitNext() {
     maxBehindMs = std::max(maxBehindMs, (w - due) * 1e3);
     const double t0 = wall_s();
     const ysb_rebase rb{b.a, (int64_t)cycle * (o_.cycleMs / BUCKET_MS)};
-    if (o_.replay == StreamOptions::MAPPED) {
+    if (o_.streamLz4) {   // the batch's blocks in place; mapped: the cycle's HBM line offsets, mapped-raw: the GPU split
+        const Lz4Cycle::Batch& zb = s_.z.batches[next];
+        const bool offs = o_.replay == StreamOptions::MAPPED;
+        check(ysb_submit_lz4_mapped(ctx_, cur_, s_.z.bytes + zb.off, zb.nbytes, s_.z.dir.data() + zb.firstBlock,
+                                    (uint32_t)zb.blocks, offs ? (uint32_t*)s_.lineOff->p + b.a : nullptr,
+                                    offs ? b.b - b.a : 0, &rb),
+              "ysb_submit_lz4_mapped");
+    } else if (o_.replay == StreamOptions::MAPPED) {
         check(ysb_submit_mapped(ctx_, cur_, s_.cyc.bytes + b.off, b.nbytes, (uint32_t*)s_.lineOff->p + b.a, b.b - b.a, &rb),
               "ysb_submit_mapped");
     } else if (o_.replay == StreamOptions::MAPPED_RAW) {
@@ -476,7 +493,10 @@ StreamReport StreamingJob::report(const std::vector<std::unique_ptr<Feeder>>& fe
         sr.feederCpuS = f.cpuS;
         sr.maxBehindMs = f.maxBehindMs;
         sr.ringAdvances = f.ringAdvances;
-        sr.replayGB = (double)s.cyc.used / 1e9;
+        sr.replayGB = (double)(o_.streamLz4 ? s.z.used : s.cyc.used) / 1e9;   // what is resident
+        rep.lz4CompBytesPerCycle += s.z.compBytes;
+        rep.lz4RawBytesPerCycle += s.z.rawBytes;
+        rep.lz4BlocksPerCycle += s.z.dir.size();
         sr.prepareS = s.prepareS;
         sr.registerS = s.registerS;
         rep.shards.push_back(sr);
@@ -510,6 +530,16 @@ StreamReport StreamingJob::report(const std::vector<std::unique_ptr<Feeder>>& fe
     rep.targetEventsPerSecond = o_.eventRate * o_.speedup * (double)shards_.size();
     rep.copyGBs = rep.copyMs > 0 ? (double)rep.copyBytes / (rep.copyMs * 1e-3) / 1e9 : 0;
     rep.copyBusyFrac = rep.wallSeconds > 0 ? rep.copyMs * 1e-3 / rep.wallSeconds / (double)shards_.size() : 0;
+    {   // measured when the copies were timed, the cycle's own figure otherwise
+        uint64_t cyc_bytes = 0, cyc_lines = 0;
+        for (const auto& s : shards_) {
+            cyc_lines += s->cyc.lines();
+            if (o_.streamLz4) cyc_bytes += s->z.compBytes;
+            else for (const auto& b : s->cyc.batches) cyc_bytes += b.nbytes;
+        }
+        rep.pcieBytesPerEvent = rep.copyBytes && rep.events ? (double)rep.copyBytes / (double)rep.events
+                                                            : cyc_lines ? (double)cyc_bytes / (double)cyc_lines : 0;
+    }
     rep.flushes = st.flushes;
     rep.rowsWritten = st.rows;
     rep.closeReplayMs = st.windows.closeMs;

@@ -28,6 +28,12 @@
 //                  nothing but copies on the copy queue.  (mapped-raw: the same with the line
 //                  split on the GPU, ysb_submit_raw_mapped; copy, round 5's path: the feeder
 //                  copies the batch into the pinned slot and patches the digits itself.)
+//                  (--stream-lz4, with mapped or mapped-raw: the cycle is compressed batch by batch
+//                  into line-aligned LZ4 blocks, ysb_replay_lz4.hpp; the compressed cycle is what
+//                  is registered, the raw one is released once its line offsets and rebase table
+//                  are on the device; a batch's blocks are handed over in place,
+//                  ysb_submit_lz4_mapped, decoded on the GPU behind their copy, then rebased and
+//                  scanned as before -- only compressed bytes cross PCIe.)
 //   * watermark    per shard the largest event_time submitted minus the out-of-orderness bound;
 //                  a merged flush's watermark is the minimum over the shards at their begins
 //                  (Flink's watermark at a keyed operator);
@@ -50,6 +56,7 @@
 
 #include "ysb_flush_merge.hpp"
 #include "ysb_replay.hpp"
+#include "ysb_replay_lz4.hpp"
 #include "ysb_topology.hpp"
 
 namespace ysb {
@@ -79,6 +86,11 @@ struct StreamOptions {
     enum Replay { MAPPED = 0, MAPPED_RAW = 1, COPY = 2 };
     int replay = MAPPED;
     bool pinNuma = true;              // feeder threads (and the cycle's pages) on the GPU's NUMA node
+    // --stream-lz4 (MAPPED / MAPPED_RAW only): the cycle compressed into LZ4 blocks of lz4Block
+    // raw bytes at most, registered in place of the raw cycle and submitted in place
+    // (ysb_submit_lz4_mapped)
+    bool streamLz4 = false;
+    uint32_t lz4Block = STREAM_LZ4_BLOCK;
 };
 
 struct ShardReport {
@@ -114,6 +126,11 @@ struct StreamReport {
     uint64_t openAtEnd = 0;
     int64_t finalWatermarkMs = 0;     // the watermark at the last flush: windows ending by it are closed
     uint64_t overflowDropped = 0, parseErrors = 0, joinMisses = 0;
+    // --stream-lz4: a cycle's compressed and raw bytes and its blocks, summed over the shards
+    uint64_t lz4CompBytesPerCycle = 0, lz4RawBytesPerCycle = 0, lz4BlocksPerCycle = 0;
+    // bytes a cycle puts on the link per event: the batches' bytes (compressed: the blocks and
+    // their descriptors' share is in copyBytes, which is what is reported when timing is on)
+    double pcieBytesPerEvent = 0;
 };
 
 class StreamingJob {

@@ -12,21 +12,32 @@ namespace topology {
 
 // The replay: a cycle from the host generator, each batch of each of `cycles` rebased into a
 // buffer (fill_batch) and compared byte for byte with the host generator's own lines of that
-// cycle (t0 moved by cycle * cycleMs).
+// cycle (t0 moved by cycle * cycleMs).  With streamLz4 the cycle is compressed first and each
+// batch comes out of its blocks instead (fill_batch_lz4: the host model's decode, then the
+// rebase on the decoded bytes), and for cycle 0 the decode alone is compared with fill_batch's bytes.
 std::string replaySelfCheck(const StreamOptions& o, const std::vector<uint64_t>& cycles) {
     const ysb_gen_params g = shard_gen(o, 1);
     const unsigned T = default_threads(o);
     WorkerPool pool(T);
     ReplayCycle c;
     build_cycle(nullptr, g, o, c, pool);
+    Lz4Cycle z;
+    if (o.streamLz4) compress_cycle(c, o.lz4Block, z, pool);
     std::vector<uint8_t> buf(o.slotBytes + 64), ref(o.slotBytes + 64);
     std::vector<uint32_t> off(c.lines() + 1);
-    uint64_t lines = 0, bad = 0, batches = 0, misaligned = 0;
+    uint64_t lines = 0, bad = 0, batches = 0, misaligned = 0, lz4_bad = 0;
+    for (size_t k = 0; o.streamLz4 && k < c.batches.size(); ++k) {   // the decode alone against cycle 0's bytes
+        const ReplayCycle::Batch& b = c.batches[k];
+        fill_batch(c, b, 0, o.cycleMs, ref.data(), pool, T);
+        if (!decode_batch(z, k, b.nbytes, buf.data()) || std::memcmp(buf.data(), ref.data(), b.nbytes) != 0) ++lz4_bad;
+    }
     for (uint64_t cy : cycles) {
         ysb_gen_params gc = g;
         gc.t0_ms = o.t0Ms + (int64_t)cy * o.cycleMs;   // the generator's own lines of that cycle
         for (const auto& b : c.batches) {
-            const uint64_t nb = fill_batch(c, b, cy, o.cycleMs, buf.data(), pool, T);
+            uint64_t nb = b.nbytes;
+            if (!o.streamLz4) nb = fill_batch(c, b, cy, o.cycleMs, buf.data(), pool, T);
+            else if (!fill_batch_lz4(c, z, (size_t)(&b - c.batches.data()), cy, o.cycleMs, buf.data())) nb = 0;
             uint64_t rb = 0;
             if (ysb_gen_events_host(&gc, b.a, b.b - b.a, ref.data(), ref.size(), off.data(), &rb) != YSB_OK)
                 throw std::runtime_error("ysb_gen_events_host failed");
@@ -36,11 +47,15 @@ std::string replaySelfCheck(const StreamOptions& o, const std::vector<uint64_t>&
             ++batches;
         }
     }
-    char o2[320];
+    char o2[640];
     std::snprintf(o2, sizeof o2, "{\"mode\": \"stream-self-check\", \"lines_per_cycle\": %llu, \"batches\": %llu, "
-                  "\"lines\": %llu, \"mismatched_batches\": %llu, \"misaligned_batches\": %llu, \"upper_values\": %u}",
+                  "\"lines\": %llu, \"mismatched_batches\": %llu, \"misaligned_batches\": %llu, \"upper_values\": %u, "
+                  "\"stream_lz4\": %s, \"lz4_block\": %u, \"lz4_blocks\": %zu, \"lz4_comp_bytes\": %llu, "
+                  "\"lz4_raw_bytes\": %llu, \"lz4_mismatched_batches\": %llu}",
                   (unsigned long long)c.lines(), (unsigned long long)batches, (unsigned long long)lines,
-                  (unsigned long long)bad, (unsigned long long)misaligned, c.nUpper);
+                  (unsigned long long)bad, (unsigned long long)misaligned, c.nUpper, o.streamLz4 ? "true" : "false",
+                  o.streamLz4 ? o.lz4Block : 0u, z.dir.size(), (unsigned long long)z.compBytes,
+                  (unsigned long long)z.rawBytes, (unsigned long long)lz4_bad);
     return o2;
 }
 
@@ -54,12 +69,28 @@ std::string feedCheck(const StreamOptions& o, double seconds) {
     std::vector<std::unique_ptr<ReplayCycle>> cyc(S);
     std::vector<std::thread> th;
     std::vector<std::string> err(S);
+    // streamLz4: every shard's cycle compressed as the GPU run compresses it, and every batch's
+    // blocks decoded by the host model against fill_batch's bytes of cycle 0
+    std::vector<uint64_t> lz4_bad(S, 0), lz4_comp(S, 0), lz4_raw(S, 0);
     for (int s = 0; s < S; ++s)
         th.emplace_back([&, s] {
             try {
                 WorkerPool pool(default_threads(o));
                 cyc[s].reset(new ReplayCycle());
                 build_cycle(nullptr, shard_gen(o, 1 + (uint32_t)s), o, *cyc[s], pool);
+                if (o.streamLz4) {
+                    Lz4Cycle z;
+                    compress_cycle(*cyc[s], o.lz4Block, z, pool);
+                    std::vector<uint8_t> got(o.slotBytes + 64), want(o.slotBytes + 64);
+                    for (size_t k = 0; k < cyc[s]->batches.size(); ++k) {
+                        const ReplayCycle::Batch& b = cyc[s]->batches[k];
+                        fill_batch(*cyc[s], b, 0, o.cycleMs, want.data(), pool, pool.size());
+                        if (!decode_batch(z, k, b.nbytes, got.data()) || std::memcmp(got.data(), want.data(), b.nbytes) != 0)
+                            ++lz4_bad[s];
+                    }
+                    lz4_comp[s] = z.compBytes;
+                    lz4_raw[s] = z.rawBytes;
+                }
             } catch (const std::exception& e) {
                 err[s] = e.what();
             }
@@ -105,12 +136,17 @@ std::string feedCheck(const StreamOptions& o, double seconds) {
     }
     const double rate = mx > 0 ? (double)total / mx : 0;
     const double lineBytes = (double)(cyc[0]->used) / (double)cyc[0]->lines();
-    char out[512];
+    uint64_t zbad = 0, zcomp = 0, zraw = 0;
+    for (int s = 0; s < S; ++s) zbad += lz4_bad[s], zcomp += lz4_comp[s], zraw += lz4_raw[s];
+    char out[768];
     std::snprintf(out, sizeof out, "{\"mode\": \"stream-feed-check\", \"shards\": %d, \"seconds\": %.2f, "
                   "\"lines_per_cycle\": %llu, \"batches_per_cycle\": %zu, \"copy_events_per_s\": %.1f, "
-                  "\"copy_GBs\": %.2f, \"hardware_threads\": %u}",
+                  "\"copy_GBs\": %.2f, \"hardware_threads\": %u, \"stream_lz4\": %s, \"lz4_block\": %u, "
+                  "\"lz4_comp_bytes\": %llu, \"lz4_raw_bytes\": %llu, \"lz4_mismatched_batches\": %llu}",
                   S, seconds, (unsigned long long)cyc[0]->lines(), cyc[0]->batches.size(), rate,
-                  rate * lineBytes / 1e9, std::thread::hardware_concurrency());
+                  rate * lineBytes / 1e9, std::thread::hardware_concurrency(), o.streamLz4 ? "true" : "false",
+                  o.streamLz4 ? o.lz4Block : 0u, (unsigned long long)zcomp, (unsigned long long)zraw,
+                  (unsigned long long)zbad);
     return out;
 }
 

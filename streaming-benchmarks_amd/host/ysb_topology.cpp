@@ -591,20 +591,29 @@ void GpuAdCampaignOperator::submitLz4(const uint8_t* blocks, uint64_t compBytes,
     waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 }
 
-Lz4Container Lz4Container::parse(const std::string& file, const std::string& name) {
+void GpuAdCampaignOperator::submitLz4Mapped(const uint8_t* blocks, uint64_t compBytes, const ysb_lz4_block* dir,
+                                            uint32_t nBlocks) {
+    check(ysb_submit_lz4_mapped(ctx_, cur_, blocks, compBytes, dir, nBlocks, nullptr, 0, nullptr), "ysb_submit_lz4_mapped");
+    cur_ ^= 1;
+    const auto t1 = std::chrono::steady_clock::now();
+    check(ysb_wait(ctx_, cur_), "ysb_wait");   // at most two batches in flight
+    waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+}
+
+Lz4Container Lz4Container::parse(const uint8_t* file, uint64_t size, const std::string& name) {
     ysb_lz4_file_header h;
-    if (file.size() < sizeof h) throw std::runtime_error(name + ": not a compressed replay file (too short)");
-    std::memcpy(&h, file.data(), sizeof h);
+    if (size < sizeof h) throw std::runtime_error(name + ": not a compressed replay file (too short)");
+    std::memcpy(&h, file, sizeof h);
     if (std::memcmp(h.magic, YSB_LZ4_FILE_MAGIC, 8) != 0 || h.version != 1)
         throw std::runtime_error(name + ": not a compressed replay file (ysb_gen --lz4 writes one)");
-    if (h.n_blocks > (file.size() - sizeof h) / sizeof(ysb_lz4_block))
+    if (h.n_blocks > (size - sizeof h) / sizeof(ysb_lz4_block))
         throw std::runtime_error(name + ": its directory is longer than the file");
     Lz4Container c;
     c.lineAligned = (h.flags & YSB_LZ4_FILE_LINE_ALIGNED) != 0;
     c.nBlocks = h.n_blocks;
     c.rawBytes = h.raw_bytes;
-    c.dir = reinterpret_cast<const ysb_lz4_block*>(file.data() + sizeof h);   // (32 bytes in: aligned for its u32 fields)
-    c.blocks = reinterpret_cast<const uint8_t*>(file.data()) + sizeof h + h.n_blocks * sizeof(ysb_lz4_block);
+    c.dir = reinterpret_cast<const ysb_lz4_block*>(file + sizeof h);   // (32 bytes in: aligned for its u32 fields)
+    c.blocks = file + sizeof h + h.n_blocks * sizeof(ysb_lz4_block);
     c.start.resize(c.nBlocks + 1);
     uint64_t at = 0, raw = 0;
     for (uint64_t i = 0; i < c.nBlocks; ++i) {
@@ -613,7 +622,7 @@ Lz4Container Lz4Container::parse(const std::string& file, const std::string& nam
         raw += c.dir[i].raw_bytes;
     }
     c.start[c.nBlocks] = at;
-    if (at != file.size() - sizeof h - h.n_blocks * sizeof(ysb_lz4_block) || raw != h.raw_bytes)
+    if (at != size - sizeof h - h.n_blocks * sizeof(ysb_lz4_block) || raw != h.raw_bytes)
         throw std::runtime_error(name + ": the directory does not match the file's size");
     return c;
 }

@@ -113,6 +113,7 @@ public:
     // The mapping (NULL without mmap) and its registrable length (whole pages).
     const uint8_t* mapping() const { return map_; }
     uint64_t mappingBytes() const;
+    uint64_t fileBytes() const { return size_; }
     // Back to the file's start (a replay source read again).
     void rewind();
     uint64_t linesRead() const { return lines_; }
@@ -189,6 +190,9 @@ public:
     // a batch of whole lines as LZ4 blocks (ysb_submit_raw_lz4): copied into the open slot's
     // pinned buffer compressed, decoded on the GPU
     void submitLz4(const uint8_t* blocks, uint64_t compBytes, const ysb_lz4_block* dir, uint32_t nBlocks);
+    // the same read where the blocks lie, in the registered mapping of the container
+    // (ysb_submit_lz4_mapped after registerSource): no copy into a slot
+    void submitLz4Mapped(const uint8_t* blocks, uint64_t compBytes, const ysb_lz4_block* dir, uint32_t nBlocks);
     // One file image of WindowedArrowFormatBolter (<shared_file>_<k>, :303-317) of `rows` rows
     // counted from its columns (ysb_submit_columns, longs big-endian): only the ranges the count
     // reads are read from the file, straight into the open slot.  Throws, naming the file, if
@@ -235,7 +239,10 @@ struct Lz4Container {
     const uint8_t* blocks = nullptr;
     std::vector<uint64_t> start;                            // block i's first byte in blocks; [nBlocks]: their size
     uint64_t blockStart(uint64_t i) const { return start[i]; }
-    static Lz4Container parse(const std::string& file, const std::string& name);
+    static Lz4Container parse(const uint8_t* file, uint64_t size, const std::string& name);
+    static Lz4Container parse(const std::string& file, const std::string& name) {
+        return parse(reinterpret_cast<const uint8_t*>(file.data()), file.size(), name);
+    }
 };
 
 // ---- output -------------------------------------------------------------------------------------------

@@ -16,8 +16,10 @@
 // rows of a CSV through the sink without a GPU (the Redis writer on its own).  The events
 // file is read as raw lines and the GPU finds the line starts (ysb_submit_raw); --host-split
 // splits the lines on the host instead (ysb_submit with offsets).  --repeat K reads the file
-// K times (a replay source; the counts are K times the file's).  The last stdout line is a
-// JSON summary.
+// K times (a replay source; the counts are K times the file's).  --lz4 reads events_path as a
+// compressed replay file through the slots; --lz4 --io mapped maps it instead and hands runs of
+// its blocks over where they lie (ysb_submit_lz4_mapped).  The last stdout line is a JSON
+// summary.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -84,7 +86,7 @@ void usage() {
                  "       [--seed S] [--campaigns C] [--ads-per-campaign A] [--event-rate E] [--speedup F]\n"
                  "       [--cycle-ms MS] [--flush-ms MS] [--batch-ms MS] [--ooo-ms MS] [--seconds S]\n"
                  "       [--batch-mb MB] [--window-ring W] [--skew 0|1|2] [--io-threads T] [--totals CSV]\n"
-                 "       [--replay mapped|mapped-raw|copy] [--no-numa] [--no-timing]\n"
+                 "       [--replay mapped|mapped-raw|copy] [--no-numa] [--no-timing] [--stream-lz4 [--lz4-block N]]\n"
                  "   or: ysb_topology --stream-self-check | --stream-feed-check [--shards N] [--feed-seconds S] ...\n"
                  "   or: ysb_topology --stream-merge-check [--shards N] [--merge-flushes F] [--seed S]\n");
 }
@@ -145,6 +147,15 @@ Args parse(int argc, char** argv) {
         else if (k == "--merge-flushes") a.merge_flushes = std::atoi(val().c_str());
         else if (k == "--no-numa") a.so.pinNuma = false;
         else if (k == "--no-timing") a.so.timing = false;
+        else if (k == "--stream-lz4") a.so.streamLz4 = true;
+        else if (k == "--lz4-block") {
+            const long long n = std::atoll(val().c_str());
+            if (n < 1 || n > (long long)YSB_LZ4_MAX_RAW) {
+                std::fprintf(stderr, "--lz4-block must be in 1..65536\n");
+                std::exit(2);
+            }
+            a.so.lz4Block = (uint32_t)n;
+        }
         else if (k == "--replay") {
             const std::string m = val();
             if (m != "mapped" && m != "mapped-raw" && m != "copy") { usage(); std::exit(2); }
@@ -156,6 +167,15 @@ Args parse(int argc, char** argv) {
     if (a.join_redis && (a.stream || a.columns || a.from_columns)) {
         std::fprintf(stderr, "--join-redis is batch mode's (the counting chain over events_path): not with --stream, "
                              "--columns or --from-columns\n");
+        std::exit(2);
+    }
+    if (a.so.streamLz4 && !a.stream) {
+        std::fprintf(stderr, "--stream-lz4 compresses the streaming replay's cycle: only with --stream\n");
+        std::exit(2);
+    }
+    if (a.so.streamLz4 && a.so.replay == StreamOptions::COPY) {
+        std::fprintf(stderr, "--stream-lz4 is read in place from the registered cycle: not with --replay copy "
+                             "(--replay mapped or mapped-raw)\n");
         std::exit(2);
     }
     if (a.lz4 && a.stream) {
@@ -359,6 +379,17 @@ int run(const Args& a) {
             o.mappedIo = false;
         }
     }
+    // --lz4 --io mapped: the container's mapping (the source's) registered; a refused
+    // registration falls back to the slot path, as the uncompressed runner's does
+    bool lz4_mapped = a.lz4 && a.io == "mapped";
+    if (lz4_mapped) {
+        try {
+            op.registerSource(src);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "note: the container's mapping cannot be read in place (%s): slot copies\n", e.what());
+            lz4_mapped = false;
+        }
+    }
     const double t_open = now_s();   // the stream itself: from the first read to close
     uint64_t rows = 0, flushes = 0;
     auto flush = [&]() {
@@ -371,11 +402,17 @@ int run(const Args& a) {
     double last_flush = now_s();
     // --lz4: the container's blocks in runs that fit a slot, compressed and decoded; the
     // line-aligned flag makes every run a batch of whole lines
+    // --lz4 --io mapped: the container is mapped (the source's mapping), not read, and every
+    // run is read where it lies (ysb_submit_lz4_mapped)
     std::string lz4_file;
     Lz4Container lz4;
     if (a.lz4) {
-        lz4_file = readFile(events);
-        lz4 = Lz4Container::parse(lz4_file, events);
+        if (lz4_mapped) {
+            lz4 = Lz4Container::parse(src.mapping(), src.fileBytes(), events);
+        } else {
+            lz4_file = readFile(events);
+            lz4 = Lz4Container::parse(lz4_file, events);
+        }
         if (!lz4.lineAligned)
             throw std::runtime_error(events + ": its blocks are not line-aligned (ysb_gen --lz4 writes them so): "
                                      "a run of blocks would cut lines");
@@ -391,7 +428,8 @@ int run(const Args& a) {
                 ++e;
             }
             if (e == b) throw std::runtime_error(events + ": block " + std::to_string(b) + " exceeds the slot (--batch-mb)");
-            op.submitLz4(lz4.blocks + lz4.blockStart(b), comp, lz4.dir + b, (uint32_t)(e - b));
+            if (lz4_mapped) op.submitLz4Mapped(lz4.blocks + lz4.blockStart(b), comp, lz4.dir + b, (uint32_t)(e - b));
+            else op.submitLz4(lz4.blocks + lz4.blockStart(b), comp, lz4.dir + b, (uint32_t)(e - b));
             lz4_comp += comp;
             b = e;
             if (lookup) op.resolveParked(*lookup);
@@ -431,7 +469,7 @@ int run(const Args& a) {
                 "\"format\": \"%s\", \"sink\": %s, \"h2d\": \"%s\", \"copy_GBs\": %.2f, \"copy_busy_frac\": %.4f, "
                 "\"fill_s\": %.3f, \"slot_wait_s\": %.3f, \"join_redis\": %s, \"parked_keys\": %llu, "
                 "\"parked_found\": %llu, \"parked_joined\": %llu, \"parked_missed\": %llu, \"join_round_trips\": %llu, "
-                "\"lz4\": %s, \"lz4_comp_bytes\": %llu, \"lz4_raw_bytes\": %llu}\n",
+                "\"lz4\": %s, \"lz4_comp_bytes\": %llu, \"lz4_raw_bytes\": %llu, \"lz4_io\": \"%s\"}\n",
                 (unsigned long long)s.events, (unsigned long long)s.views, (unsigned long long)s.joined,
                 (unsigned long long)s.join_misses, (unsigned long long)s.parse_errors,
                 (unsigned long long)s.time_errors, (unsigned long long)s.out_of_ring,
@@ -447,7 +485,8 @@ int run(const Args& a) {
                 (unsigned long long)op.parkedTotals().found, (unsigned long long)op.parkedTotals().joined,
                 (unsigned long long)op.parkedTotals().missed, (unsigned long long)(lookup ? lookup->roundTrips() : 0),
                 a.lz4 ? "true" : "false", (unsigned long long)lz4_comp,
-                (unsigned long long)(a.lz4 ? lz4.rawBytes * (uint64_t)a.repeat : 0));
+                (unsigned long long)(a.lz4 ? lz4.rawBytes * (uint64_t)a.repeat : 0),
+                !a.lz4 ? "" : lz4_mapped ? "mapped" : "slot");
     return s.overflow_dropped ? 3 : 0;
 }
 
@@ -698,7 +737,8 @@ int run_stream(const Args& a) {
                 "\"ooo_ms\": %lld, \"skew\": %d, \"seed\": %llu, \"campaigns\": %u, \"ads_per_campaign\": %u, "
                 "\"t0_ms\": %lld, \"lines_per_cycle\": %llu, \"cycles\": %s, \"partial_lines\": %s, "
                 "\"overflow_dropped\": %llu, \"parse_errors\": %llu, \"join_misses\": %llu, \"prepare_s\": %.2f, "
-                "\"sink\": %s}\n",
+                "\"sink\": %s, \"stream_lz4\": %s, \"lz4_block\": %u, \"lz4_comp_bytes_per_cycle\": %llu, "
+                "\"lz4_raw_bytes_per_cycle\": %llu, \"lz4_blocks_per_cycle\": %llu, \"pcie_bytes_per_event\": %.2f}\n",
                 a.so.replay == StreamOptions::MAPPED ? "mapped" : a.so.replay == StreamOptions::MAPPED_RAW ? "mapped-raw" : "copy",
                 a.so.shards, (unsigned long long)r.events, (unsigned long long)r.batches,
                 r.wallSeconds, r.submitEventsPerSecond, per.c_str(), r.eventsPerSecond,
@@ -711,7 +751,10 @@ int run_stream(const Args& a) {
                 (long long)a.so.flushMs, (long long)a.so.batchMs, (long long)a.so.oooMs, a.so.skew,
                 (unsigned long long)a.so.seed, a.so.campaigns, a.so.adsPerCampaign, (long long)a.so.t0Ms,
                 (unsigned long long)r.linesPerCycle, cyc.c_str(), part.c_str(), (unsigned long long)r.overflowDropped,
-                (unsigned long long)r.parseErrors, (unsigned long long)r.joinMisses, prep_s, json_str(a.sink).c_str());
+                (unsigned long long)r.parseErrors, (unsigned long long)r.joinMisses, prep_s, json_str(a.sink).c_str(),
+                a.so.streamLz4 ? "true" : "false", a.so.streamLz4 ? a.so.lz4Block : 0u,
+                (unsigned long long)r.lz4CompBytesPerCycle, (unsigned long long)r.lz4RawBytesPerCycle,
+                (unsigned long long)r.lz4BlocksPerCycle, r.pcieBytesPerEvent);
     return r.overflowDropped ? 3 : 0;
 }
 

@@ -191,6 +191,7 @@ SIGNATURES = {
     "ysb_submit_mapped": (_I, [_P, _I, _PU8, _U64, _PU32, _U64, C.POINTER(YsbRebase)]),
     "ysb_split_lines_device": (_I, [_P, _PU8, _U64, _PU32, _U64, C.POINTER(_U64)]),
     "ysb_submit_raw_lz4": (_I, [_P, _I, _PU8, _U64, _P, _U32]),
+    "ysb_submit_lz4_mapped": (_I, [_P, _I, _PU8, _U64, _P, _U32, _PU32, _U64, C.POINTER(YsbRebase)]),
     "ysb_lz4_decode_device": (_I, [_P, _PU8, _U64, _P, _U32, _PU8, _U64, C.POINTER(_U64), C.POINTER(_U32)]),
     "ysb_lz4_info": (_I, [_P, C.POINTER(YsbLz4Desc)]),
     "ysb_lz4_desc_size": (_U64, []),

@@ -318,6 +318,18 @@ class YsbContext:
         d = np.ascontiguousarray(directory, dtype=np.uint32).reshape(-1, 2)
         self._c(lib().ysb_submit_raw_lz4(self._h, slot, _ptr(buf), buf.size, _ptr(d), d.shape[0]))
 
+    def submit_lz4_mapped(self, arr, offset, comp_bytes, directory, slot=0, d_off=None, n=0, rebase=None):
+        """ysb_submit_lz4_mapped: the LZ4 blocks arr[offset:offset + comp_bytes] of a registered
+        array, read in place by the device, with their directory (host memory, as
+        submit_raw_lz4's).  d_off None: the GPU splits the decoded lines (n must be 0);
+        otherwise d_off holds n line offsets into the decoded batch in device memory.
+        rebase = (first_line, lead_shift) or None."""
+        d = np.ascontiguousarray(directory, dtype=np.uint32).reshape(-1, 2)
+        rb = _lib.YsbRebase(*rebase) if rebase is not None else None
+        self._c(lib().ysb_submit_lz4_mapped(self._h, slot, C.c_void_p(arr.ctypes.data + offset), comp_bytes,
+                                            _ptr(d), d.shape[0], C.c_void_p(d_off) if d_off else None, n,
+                                            C.byref(rb) if rb is not None else None))
+
     def lz4_decode_device(self, d_comp, comp_bytes, directory, d_out, out_cap):
         """ysb_lz4_decode_device: the decode alone, device to device.  Returns (raw bytes, first
         bad block or None); a bad block does not raise here -- its output range is untouched."""

@@ -98,3 +98,98 @@ class FileBasedDataSource:
 
     def __exit__(self, *a):
         self.close()
+
+
+class Lz4FileDataSource:
+    """A compressed replay file (ysb_gen --lz4, ysb_amd.lz4.write_file: header, directory,
+    blocks), mapped read-only: `runs(cap)` yields (offset into the mapping, compressed bytes,
+    first block, blocks) of runs of whole blocks whose compressed and decoded sizes both fit
+    cap; `run(ctx, cap)` registers the mapping and submits every run where it lies
+    (ysb_submit_lz4_mapped: only compressed bytes cross PCIe, and none passes through a host
+    copy).  A container whose blocks are not line-aligned is refused: a run of its blocks
+    would not be a batch of whole lines."""
+
+    HEADER = 32
+
+    def __init__(self, path: str):
+        from . import lz4
+        self.path = str(path)
+        self.size = os.path.getsize(self.path)
+        self._mm = None
+        self.data = np.zeros(0, dtype=np.uint8)
+        if self.size:
+            with open(self.path, "rb") as f:
+                self._mm = mmap.mmap(f.fileno(), 0, flags=mmap.MAP_SHARED, prot=mmap.PROT_READ)
+            self.data = np.frombuffer(self._mm, dtype=np.uint8)
+        if self.size < self.HEADER or self.data[:8].tobytes() != lz4.FILE_MAGIC:
+            raise ValueError("%s: not a compressed replay file (ysb_gen --lz4 writes one)" % self.path)
+        version, flags = (int(x) for x in self.data[8:16].view(np.uint32))
+        n, raw = (int(x) for x in self.data[16:32].view(np.uint64))
+        if version != 1:
+            raise ValueError("%s: not a compressed replay file (ysb_gen --lz4 writes one)" % self.path)
+        if n > (self.size - self.HEADER) // 8:
+            raise ValueError("%s: its directory is longer than the file" % self.path)
+        self.directory = self.data[self.HEADER:self.HEADER + 8 * n].view(np.uint32).reshape(-1, 2)
+        self.blocks_at = self.HEADER + 8 * n
+        self.comp = (self.directory[:, 0] & 0x7FFFFFFF).astype(np.int64)
+        self.start = np.concatenate(([0], np.cumsum(self.comp)))
+        if int(self.start[-1]) != self.size - self.blocks_at or int(self.directory[:, 1].sum()) != raw:
+            raise ValueError("%s: the directory does not match the file's size" % self.path)
+        if not flags & lz4.FILE_LINE_ALIGNED:
+            raise ValueError("%s: its blocks are not line-aligned (ysb_gen --lz4 writes them so): "
+                             "a run of blocks would cut lines" % self.path)
+        self.raw_bytes = raw
+        self.comp_bytes = 0
+        self.batches = 0
+
+    @property
+    def mapping_bytes(self) -> int:
+        return (self.size + PAGE - 1) // PAGE * PAGE
+
+    def runs(self, cap: int):
+        if cap <= 0:
+            raise ValueError("cap must be positive")
+        n, b = self.directory.shape[0], 0
+        while b < n:
+            e, comp, raw = b, 0, 0
+            while e < n and comp + int(self.comp[e]) <= cap and raw + int(self.directory[e, 1]) <= cap:
+                comp += int(self.comp[e])
+                raw += int(self.directory[e, 1])
+                e += 1
+            if e == b:
+                raise ValueError("%s: block %d exceeds the slot" % (self.path, b))
+            yield self.blocks_at + int(self.start[b]), comp, b, e - b
+            b = e
+
+    def run(self, ctx, cap: int):
+        """Every run of the container through ctx (a YsbContext), in place; returns the
+        compressed bytes submitted.  At most two batches in flight."""
+        ctx.host_register(self.data, self.mapping_bytes)
+        try:
+            slot = 0
+            for off, comp, b, k in self.runs(cap):
+                ctx.submit_lz4_mapped(self.data, off, comp, self.directory[b:b + k], slot=slot)
+                slot ^= 1
+                ctx.wait(slot)
+                self.comp_bytes += comp
+                self.batches += 1
+            ctx.sync()
+        finally:
+            ctx.host_unregister(self.data)
+        return self.comp_bytes
+
+    def close(self):
+        self.data = np.zeros(0, dtype=np.uint8)
+        self.directory = np.zeros((0, 2), dtype=np.uint32)
+        if self._mm is not None:
+            try:
+                self._mm.close()
+            except BufferError:   # a caller still holds a view of the mapping: it stays until freed
+                pass
+            self._mm = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

@@ -4,8 +4,10 @@ Same staging as `bench_dropin.py staged --raw`: two distinct ~256 MB batches of 
 events, generated once, resubmitted alternately through the pinned double-buffered slots, each
 leg with a generator-truth check.  One leg submits the raw lines (ysb_submit_raw: the parent's
 path, the yardstick), the other the same batches compressed on the host by blocks
-(ysb_submit_raw_lz4: compressed bytes over PCIe, decoded on the GPU).  The legs alternate
---repeats times in one process.  Plus the decode alone (ysb_lz4_decode_device) at several
+(ysb_submit_raw_lz4: compressed bytes over PCIe, decoded on the GPU).  Two more legs read the
+same batches in place from one registered array each, without the pinned slots: `mapped` the
+compressed ones (ysb_submit_lz4_mapped) and `raw_mapped` the raw lines (ysb_submit_raw_mapped).
+The legs alternate --repeats times in one process.  Plus the decode alone (ysb_lz4_decode_device) at several
 block sizes.
 
 Per leg: events/s, the H2D rate (bytes copied / copy time, HIP events on the copy stream), the
@@ -81,15 +83,36 @@ def main():
         slot = [view(ctx.slot_buffers(s)[0], a.slot_mb << 20) for s in (0, 1)]
         dirs = [np.ascontiguousarray(d, dtype=np.uint32) for _, d in comp]
 
+        def registered(parts):
+            """The parts in one 4096-byte aligned array, each at a 64-byte boundary, registered
+            with the context: (array, [offset of each part])."""
+            at, pos = [], 0
+            for p in parts:
+                at.append(pos)
+                pos += (p.size + 63) // 64 * 64 + 64
+            buf = np.empty(pos + 8192, dtype=np.uint8)
+            buf = buf[(-buf.ctypes.data) % 4096:][:(pos + 4095) // 4096 * 4096]
+            for o, p in zip(at, parts):
+                buf[o:o + p.size] = p
+            ctx.host_register(buf)
+            return buf, at
+        reg_comp, at_comp = registered([b for b, _ in comp])
+        reg_raw, at_raw = registered(raw)
+
         def leg(kind):
             for s in (0, 1):   # staged once per leg: the slot's pinned buffer holds what crosses PCIe
                 ctx.wait(s)
-                src = raw[s] if kind == "raw" else comp[s][0]
-                slot[s][:src.size] = src
+                if kind in ("raw", "lz4"):
+                    src = raw[s] if kind == "raw" else comp[s][0]
+                    slot[s][:src.size] = src
 
             def submit(s):
                 if kind == "raw":
                     check(lib().ysb_submit_raw(ctx._h, s, C.c_void_p(slot[s].ctypes.data), raw[s].size), ctx._h)
+                elif kind == "raw_mapped":
+                    ctx.submit_raw_mapped(reg_raw, at_raw[s], raw[s].size, slot=s)
+                elif kind == "mapped":
+                    ctx.submit_lz4_mapped(reg_comp, at_comp[s], comp[s][0].size, dirs[s], slot=s)
                 else:
                     check(lib().ysb_submit_raw_lz4(ctx._h, s, C.c_void_p(slot[s].ctypes.data), comp[s][0].size,
                                                    C.c_void_p(dirs[s].ctypes.data), dirs[s].shape[0]), ctx._h)
@@ -108,7 +131,7 @@ def main():
             kms, launches = ctx.kernel_time()
             cms, copies, cbytes = ctx.copy_time()
             st = ctx.stats()
-            info = ctx.lz4_info() if kind == "lz4" else None
+            info = ctx.lz4_info() if kind in ("lz4", "mapped") else None
             for i in range(nsub):
                 ctx.truth_accumulate(g, (i & 1) * per, per)
             mism, truth, counted = ctx.truth_compare()
@@ -127,9 +150,11 @@ def main():
             return out
 
         for _ in range(a.repeats):
-            for kind in ("raw", "lz4"):
+            for kind in ("raw", "lz4", "raw_mapped", "mapped"):
                 res["legs"].append(leg(kind))
         ctx.sync()
+        ctx.host_unregister(reg_comp)
+        ctx.host_unregister(reg_raw)
 
         # the decode alone, device to device, at several block sizes
         res["decode_alone"] = []
@@ -156,10 +181,18 @@ def main():
     def summary(kind):
         v = [l["events_per_s"] for l in res["legs"] if l["leg"] == kind]
         return {"median": statistics.median(v), "min": min(v), "max": max(v)}
-    r, z = summary("raw"), summary("lz4")
+    r, z, rm, zm = summary("raw"), summary("lz4"), summary("raw_mapped"), summary("mapped")
     h2d = statistics.median(l["h2d_GBs"] for l in res["legs"] if l["leg"] == "raw")
     dec = next((x["GBs_out"] for x in res["decode_alone"] if x["block_bytes"] == block), None)
-    res["summary"] = {"raw_events_per_s": r, "lz4_events_per_s": z, "ratio": res["compress"]["ratio"],
+    busy = {k: statistics.median(l["copy_busy_frac"] for l in res["legs"] if l["leg"] == k)
+            for k in ("raw", "lz4", "raw_mapped", "mapped")}
+    res["summary"] = {"raw_events_per_s": r, "lz4_events_per_s": z, "raw_mapped_events_per_s": rm,
+                      "lz4_mapped_events_per_s": zm, "copy_busy_frac_median": busy,
+                      "mapped_over_lz4_median": round(zm["median"] / z["median"], 4),
+                      # the expectation: in place is not below the slot leg by more than that leg's own spread
+                      "mapped_within_lz4_spread": zm["median"] >= z["median"] - (z["max"] - z["min"]),
+                      "mapped_over_raw_mapped_median": round(zm["median"] / rm["median"], 4),
+                      "ratio": res["compress"]["ratio"],
                       "lz4_over_raw_median": round(z["median"] / r["median"], 4),
                       "lz4_median_above_raw_max": z["median"] > r["max"],
                       "raw_h2d_GBs": h2d, "decode_GBs_out": dec,

@@ -70,7 +70,7 @@ def truth_table(device, summary):
 
 def stream_native(device=0, seconds=12.0, event_rate=5_000_000, speedup=32.0, shards=1, slot_mb=256,
                   flush_ms=1000, batch_ms=100, ooo_ms=100, skew=2, threads=0, workdir=None, window_ring=64,
-                  replay="mapped"):
+                  replay="mapped", stream_lz4=False, lz4_block=None):
     from fake_redis import FakeRedis
     from ysb_amd import GenParams
     from ysb_amd.redis_sink import RespClient, check_correct, get_stats, new_setup
@@ -87,6 +87,8 @@ def stream_native(device=0, seconds=12.0, event_rate=5_000_000, speedup=32.0, sh
                "--flush-ms", str(flush_ms), "--batch-ms", str(batch_ms), "--ooo-ms", str(ooo_ms),
                "--skew", str(skew), "--io-threads", str(threads), "--window-ring", str(window_ring),
                "--replay", replay]
+        if stream_lz4:   # the cycle compressed and read in place (ysb_submit_lz4_mapped); the default adds nothing
+            cmd += ["--stream-lz4"] + (["--lz4-block", str(lz4_block)] if lz4_block else [])
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             raise RuntimeError("ysb_topology --stream exited %d: %s" % (r.returncode, r.stderr[-2000:]))
@@ -143,6 +145,12 @@ def stream_native(device=0, seconds=12.0, event_rate=5_000_000, speedup=32.0, sh
                      "+-50 ms, no late events" if s["skew"] == 2 else ("+-50 ms and 1e-5 late < 60 s" if s["skew"] else "off"),
                      s["ooo_ms"], s["flush_ms"]),
         "replay": s.get("replay"),
+        "stream_lz4": bool(s.get("stream_lz4")), "lz4_block": s.get("lz4_block"),
+        "lz4_comp_bytes_per_cycle": s.get("lz4_comp_bytes_per_cycle"),
+        "lz4_raw_bytes_per_cycle": s.get("lz4_raw_bytes_per_cycle"),
+        "pcie_bytes_per_event": s.get("pcie_bytes_per_event"),
+        "raw_bytes_per_event": (s["lz4_raw_bytes_per_cycle"] / (s["lines_per_cycle"] * s["shards"])
+                                if s.get("lz4_raw_bytes_per_cycle") else None),
         "events": s["events"], "events_per_s": s["events_per_s"], "target_events_per_s": s["target_events_per_s"],
         "submit_events_per_s": s.get("submit_events_per_s"),
         "per_gpu_events_per_s": round(s["events_per_s"] / s["shards"], 1),
@@ -189,9 +197,12 @@ def main():
     ap.add_argument("--skew", type=int, default=2)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--replay", choices=("mapped", "mapped-raw", "copy"), default="mapped")
+    ap.add_argument("--stream-lz4", action="store_true", help="the replay cycle as LZ4 blocks, read in place")
+    ap.add_argument("--lz4-block", type=int, default=None)
     a = ap.parse_args()
     print(json.dumps(stream_native(a.device, a.seconds, a.event_rate, a.speedup, a.shards, a.slot_mb, a.flush_ms,
-                                   a.batch_ms, skew=a.skew, threads=a.threads, replay=a.replay)), flush=True)
+                                   a.batch_ms, skew=a.skew, threads=a.threads, replay=a.replay,
+                                   stream_lz4=a.stream_lz4, lz4_block=a.lz4_block)), flush=True)
 
 
 if __name__ == "__main__":
