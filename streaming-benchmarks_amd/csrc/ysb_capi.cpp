@@ -139,11 +139,6 @@ static int init(ysb_ctx* c) {
         if (v > 0 && v < c->delta_limit) c->delta_limit = v;
     }
     if (const char* e = getenv("YSB_DYN_CHUNK")) c->dyn_chunk = (u32)strtoul(e, nullptr, 10);
-    // the raw path's A/B knobs
-    if (const char* e = getenv("YSB_SPLIT_STREAM")) c->split_place = std::atoi(e);
-    if (const char* e = getenv("YSB_H2D_WG")) c->h2d_wg = std::max(1, std::atoi(e));
-    if (const char* e = getenv("YSB_H2D_PRIO")) c->h2d_prio = std::atoi(e) != 0;
-    if (const char* e = getenv("YSB_H2D_GRID")) c->h2d_grid = std::max(0, std::atoi(e));
     if (hipStreamCreateWithFlags(&c->s_comp, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking) != hipSuccess)
         return fail(c, YSB_ERR_HIP, "stream creation failed");

@@ -188,7 +188,7 @@ int ysb_submit_columns_device(ysb_ctx* c, const uint8_t* d_cols, uint64_t batch_
 int ysb_submit_columns(ysb_ctx* c, int slot, const uint8_t* image, uint64_t batch_rows, uint64_t n_rows,
                        uint32_t flags) {
     if (!c) return YSB_ERR_ARG;
-    if (slot < 0 || slot > 1) return fail(c, YSB_ERR_ARG, "slot must be 0 or 1");
+    if (int rc = slot_arg(c, slot)) return rc;
     ysb_columns_layout lay;
     u64 total = 0;
     int rc = colcount_args(c, image, batch_rows, n_rows, flags, &lay, &total);

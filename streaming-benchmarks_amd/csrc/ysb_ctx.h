@@ -1,7 +1,8 @@
 // ysb_ctx.h -- the library context behind the C ABI (include/ysb_hip.h), shared by the
 // library's host translation units:
 //   ysb_capi.cpp    context lifecycle, the ad -> campaign tables, sync / drain / ring / stats
-//   ysb_submit.cpp  batches: slots, raw lines, device batches, the layout samples, the launches
+//   ysb_submit.cpp  segments into launches: slots, device batches, the layout samples, the scan launch
+//   ysb_raw.cpp     batches that cross PCIe into a slot and launch a call later (raw, mapped, LZ4)
 //   ysb_columns.cpp the columnar decode and the columnar count's submits
 //   ysb_layout.h    the layout sampling's rules (no HIP: tests/native/layout_logic.cpp)
 //   ysb_admap.h     the join tables as host data and the live map's rules (no HIP:
@@ -26,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <optional>
 #include <string>
 #include <thread>
 #include <utility>
@@ -135,6 +137,34 @@ struct EventLog {
     }
 };
 
+// The scan instantiation a submit chose for its batch: layout -1 is the flags'; learn the key
+// order of layouts 3 and 4.
+struct Layout {
+    int layout = -1;
+    LearnDesc learn{};
+};
+
+// A compressed batch as lz4_stage leaves it: its source as host and device address (the slot's
+// pinned buffer, or the bytes where they lie in a registered range), its figures until its
+// launch settles them into lz4_last, and its largest block (the decode's LDS window).
+struct Lz4Staged {
+    const u8* hsrc = nullptr;
+    const u8* dsrc = nullptr;
+    ysb_lz4_desc info{};
+    u32 max_raw = 0;
+};
+
+// A slot's batch between its submit and its launch one call later (ysb_raw.cpp).  Every submit
+// assigns the whole record and launch_pending_raw resets it whole.
+struct RawBatch {
+    u64 nbytes = 0;                      // decoded bytes in d_bytes[slot]
+    Layout lay;                          // its first lines' layout (sampled on the host)
+    const u32* off = nullptr;            // the caller's n_off device line offsets; NULL: the GPU
+    u64 n_off = 0;                       //   split's, in d_roff[slot]
+    std::optional<ysb_rebase> rebase;    // its lines' event times rebased before the scan
+    std::optional<Lz4Staged> lz4;        // a decode precedes the split
+};
+
 struct ysb_ctx {
     int device = 0;
     ysb_config cfg{};
@@ -173,10 +203,7 @@ struct ysb_ctx {
     int raw_pend = -1;                          // the slot whose raw batch awaits its launch
     int raw_fail = 0;                           // a raw batch that could not launch: sticky until ysb_reset
     std::string raw_fail_msg;
-    u64 raw_nbytes[2] = {0, 0};
-    int raw_layout[2] = {-1, -1};               // its first line's layout (sampled on the host)
-    LearnDesc raw_learn[2]{};
-    const u32* raw_off[2] = {nullptr, nullptr}; // the caller's device line offsets (ysb_submit_lz4_mapped); NULL: d_roff
+    RawBatch raw[2];                            // the slot's batch while it awaits its launch
     // H2D timing (YSB_F_TIMING): {start, end} of each slot copy since the last ysb_copy_time
     EventLog<2> cev;
     u64 copy_bytes = 0;
@@ -187,18 +214,11 @@ struct ysb_ctx {
         u8* dptr;
     };
     std::map<uintptr_t, HostRange> host_ranges;
-    // the replay's rebase table (ysb_rebase_table) and each slot's pending rebase
+    // the replay's rebase table (ysb_rebase_table)
     DevBuf<u32> d_rebase;
     u64 rebase_n = 0;
     i64 rebase_base = 0;
     u32 rebase_kmax = 0;                        // the largest bucket index in it
-    bool raw_rebase_on[2] = {false, false};
-    // A/B knobs, read from the environment by ysb_open
-    int split_place = 1;                        // YSB_SPLIT_STREAM: raw split on 1 s_split (default), 0 the copy stream, 2 s_comp
-    int h2d_wg = 1;                             // YSB_H2D_WG: copy-kernel workgroups per CU
-    bool h2d_prio = false;                      // YSB_H2D_PRIO: copy kernel at raised wave priority
-    int h2d_grid = 32;                          // YSB_H2D_GRID: copy-kernel workgroups (0: one per CU)
-    ysb_rebase raw_rebase[2]{};
     CuckooSeed cseed{};
     bool ctable_partial = false;
     bool table_loaded = false;
@@ -225,26 +245,19 @@ struct ysb_ctx {
     ysb_parked_desc park_last{};
     // LZ4 batches (ysb_lz4_api.cpp; ysb_lz4.h): per slot the compressed bytes in HBM (the
     // slot's pinned buffer carries them over PCIe, or they are read in place from a registered
-    // range: lz4_hsrc / lz4_dsrc, the staged batch's source as host and device address;
-    // d_bytes[slot] receives the decode) and the
+    // range: Lz4Staged; d_bytes[slot] receives the decode) and the
     // block descriptors -- pinned and device, LZ4_DESC_HEAD bytes of {first bad, bad blocks}
     // in front, initialised by the same copy --; the pair read back to pinned memory behind the
-    // decode (h_lz4bad[2 * slot]); whether the slot's pending raw batch is a compressed one;
-    // its figures until its launch settles them into lz4_last; YSB_F_TIMING's event pair
+    // decode (h_lz4bad[2 * slot]); the last settled batch's figures; YSB_F_TIMING's event pair
     DevBuf<u8> d_lz4[2];
-    const u8* lz4_hsrc[2] = {nullptr, nullptr};
-    const u8* lz4_dsrc[2] = {nullptr, nullptr};
     PinBuf<u8> h_lz4desc[2];
     u8* hd_lz4desc[2] = {nullptr, nullptr};
     DevBuf<u8> d_lz4desc[2];
     u64 lz4desc_cap[2] = {0, 0};
     PinBuf<u32> h_lz4bad;
-    bool raw_lz4[2] = {false, false};
-    ysb_lz4_desc lz4_pend[2]{}, lz4_last{};
-    u32 lz4_max_raw[2] = {0, 0};                // the pending batch's largest block (the LDS window)
+    ysb_lz4_desc lz4_last{};
     Event ev_lz4[2][2];
     DevBuf<u8> d_lz4desc_sync;                  // ysb_lz4_decode_device's descriptors
-    std::vector<u8> lz4_sample;                 // block 0 decoded on the host: the layout sample
     // counts
     u32 c_pad = 0;                        // campaigns padded to the group size
     DevBuf<unsigned long long> d_counts;      // [c_pad][W]
@@ -407,6 +420,7 @@ extern thread_local std::string g_open_err;
     } while (0)
 
 inline bool is_pow2(u64 x) { return x && !(x & (x - 1)); }   // (log2u: ysb_recplan.h)
+inline int slot_arg(ysb_ctx* c, int slot) { return slot < 0 || slot > 1 ? fail(c, YSB_ERR_ARG, "slot must be 0 or 1") : YSB_OK; }
 
 extern "C" {
 // ysb_capi.cpp
@@ -417,14 +431,19 @@ YSB_INTERNAL int read_ring(ysb_ctx* c);          // ... read with a wait
 YSB_INTERNAL int move_ring(ysb_ctx* c, i64 new_lo);
 YSB_INTERNAL int fold_delta(ysb_ctx* c);         // record mode's u8 delta ring into the u64 ring
 // ysb_submit.cpp
-YSB_INTERNAL int launch_pending_raw(ysb_ctx* c); // the raw batch awaiting its launch
 YSB_INTERNAL int ensure_slots(ysb_ctx* c);       // the pinned slots and their device buffers
+// the launch of 1..MAX_SEGS device-resident segments (empty ones skipped) on the compute stream
+YSB_INTERNAL int enqueue_scan(ysb_ctx* c, const ysb_segment* segs, u32 nseg, const Layout& lay);
+// the hinted layout of a raw batch from these host bytes of it (the flags' if batches are not sampled)
+YSB_INTERNAL void sampled_layout(const ysb_ctx* c, const u8* bytes, u64 nbytes, Layout* out);
 // n copies of a slot on the copy stream once its previous kernel has run; ev_h2d[slot] marks them done
 YSB_INTERNAL int copy_slot_ranges(ysb_ctx* c, int slot, const SlotCopy* v, int n);
 // the out-of-ring map emptied into the host list if an earlier launch left it a quarter full
 YSB_INTERNAL int drain_side_if_due(ysb_ctx* c);
 // the context's join tables, ring, out-of-ring map and stats as a launch's parameters (no batch)
 YSB_INTERNAL void context_params(ysb_ctx* c, ScanParams* out);
+// ysb_raw.cpp
+YSB_INTERNAL int launch_pending_raw(ysb_ctx* c); // the raw batch awaiting its launch
 // ysb_parked_api.cpp
 // the context's log as a launch's park sites take it; false: parking is off
 YSB_INTERNAL bool park_params(const ysb_ctx* c, ParkParams* out);
@@ -433,18 +452,19 @@ YSB_INTERNAL int park_counters(ysb_ctx* c);
 YSB_INTERNAL int park_reset(ysb_ctx* c);         // ysb_reset's part: the log emptied, the counters zero
 // ysb_lz4_api.cpp
 // A compressed batch's directory checked and its bytes and descriptors placed in the slot's
-// pinned memory (the caller has waited for the slot's previous copy); *raw_total its raw size.
-// dsrc != NULL: the bytes stay where they are, in a registered range whose device alias of
-// `bytes` it is, and only the descriptors are placed.
+// pinned memory (the caller has waited for the slot's previous copy): batch->lz4 the staged
+// batch, batch->nbytes its raw size, *sample its block 0 decoded on the host (the layout sample;
+// empty if there is none or it is bad).  dsrc != NULL: the bytes stay where they are, in a
+// registered range whose device alias of `bytes` it is, and only the descriptors are placed.
 YSB_INTERNAL int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
-                           uint32_t n_blocks, const uint8_t* dsrc, uint64_t* raw_total);
-// the slot's two copies (compressed bytes, descriptors) as copy_slot_ranges takes them
-YSB_INTERNAL void lz4_copies(ysb_ctx* c, int slot, SlotCopy v[2]);
+                           uint32_t n_blocks, const uint8_t* dsrc, RawBatch* batch, std::vector<u8>* sample);
+// the staged batch's two copies (compressed bytes, descriptors) as copy_slot_ranges takes them
+YSB_INTERNAL void lz4_copies(ysb_ctx* c, int slot, const Lz4Staged& b, SlotCopy v[2]);
 // the staged batch decoded into d_bytes[slot] on s, and its {first bad, bad blocks} read back
-YSB_INTERNAL int lz4_enqueue_decode(ysb_ctx* c, int slot, hipStream_t s);
-// at the slot's launch (its decode is complete): lz4_last <- its figures; YSB_ERR_FORMAT, the
+YSB_INTERNAL int lz4_enqueue_decode(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s);
+// at the batch's launch (its decode is complete): lz4_last <- its figures; YSB_ERR_FORMAT, the
 // message naming the first bad block, if it had one
-YSB_INTERNAL int lz4_settle(ysb_ctx* c, int slot);
+YSB_INTERNAL int lz4_settle(ysb_ctx* c, int slot, const Lz4Staged& b);
 // ysb_group.cpp
 YSB_INTERNAL bool grouped(const ysb_ctx* c);
 YSB_INTERNAL int agree_ring(ysb_ctx* c);

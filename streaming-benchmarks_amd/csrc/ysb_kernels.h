@@ -209,7 +209,7 @@ void launch_checksum(const unsigned long long* table, u32 rows, u32 W, i64 ring_
 // split_chunks(nbytes) u32 of scratch.  Asynchronous on s.
 u64 split_chunks(u64 nbytes);
 // the slots' host -> device copy by a kernel (ysb_split.hip): src a device-visible pinned host pointer
-void launch_h2d_copy(void* dst, const void* src, u64 bytes, int cus, hipStream_t s, bool prio = false);
+void launch_h2d_copy(void* dst, const void* src, u64 bytes, int wgs, hipStream_t s);
 // the same from a device-visible host address at any byte alignment (reads up to 31 bytes
 // past src + bytes, from the 16-byte boundary below src)
 void launch_h2d_copy_unaligned(void* dst, const void* src, u64 bytes, int wgs, hipStream_t s);

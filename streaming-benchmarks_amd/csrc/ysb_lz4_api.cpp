@@ -1,8 +1,9 @@
 // ysb_lz4_api.cpp -- LZ4 batches above the kernel (ysb_lz4.hip; the rules: ysb_lz4.h): the
 // directory's checks, a slot's staging (compressed bytes in pinned memory or left in place in a
-// registered range, block descriptors in pinned memory, one copy each), the decode's launch and read-back, the synchronous decode alone, the last
-// batch's figures, and the host codec entries.  ysb_submit_raw_lz4 and ysb_submit_lz4_mapped sit beside
-// ysb_submit_raw in ysb_submit.cpp.
+// registered range, block descriptors in pinned memory, one copy each), the decode's one launch
+// and read-back (launch_decode), the synchronous decode alone, the last batch's figures, and the
+// host codec entries.  ysb_submit_raw_lz4 and ysb_submit_lz4_mapped sit beside ysb_submit_raw in
+// ysb_raw.cpp.
 #include "ysb_ctx.h"
 #include "ysb_lz4.h"
 
@@ -52,13 +53,33 @@ static void fill_descs(const ysb_lz4_block* dir, u32 n, u8* out, ysb_lz4_desc* i
 
 extern "C" {
 
+// One decode launch on s: the n_blocks blocks of d_comp, by the descriptors behind the
+// LZ4_DESC_HEAD bytes of {first bad, bad blocks} in d_descs, into d_out; that pair's read-back
+// to h_bad queued behind it.  ev: YSB_F_TIMING's event pair around the kernel (created on
+// demand), or NULL.
+static int launch_decode(ysb_ctx* c, const u8* d_comp, u8* d_descs, u32 n_blocks, u32 max_raw, u8* d_out, hipStream_t s,
+                         Event* ev, u32* h_bad) {
+    if (ev) {
+        for (int k = 0; k < 2; ++k)
+            if (!ev[k]) HIPCHK(c, ev[k].create(hipEventDefault));
+        HIPCHK(c, hipEventRecord(ev[0], s));
+    }
+    u32* bad = reinterpret_cast<u32*>(d_descs);
+    const Lz4Params lp{d_comp, reinterpret_cast<const Lz4Desc*>(d_descs + LZ4_DESC_HEAD), n_blocks, max_raw, d_out, bad};
+    HIPCHK(c, launch_lz4_decode(lp, s));
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, hipMemcpyAsync(h_bad, bad, 8, hipMemcpyDeviceToHost, s));
+    return YSB_OK;
+}
+
 int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
-              uint32_t n_blocks, const uint8_t* dsrc, uint64_t* raw_total) {
-    int rc = dir_args(c, bytes, comp_bytes, dir, n_blocks, raw_total);
+              uint32_t n_blocks, const uint8_t* dsrc, RawBatch* batch, std::vector<u8>* sample) {
+    u64 raw_total = 0;
+    int rc = dir_args(c, bytes, comp_bytes, dir, n_blocks, &raw_total);
     if (rc) return rc;
-    if (comp_bytes > c->cfg.max_batch_bytes || *raw_total > c->cfg.max_batch_bytes)
+    if (comp_bytes > c->cfg.max_batch_bytes || raw_total > c->cfg.max_batch_bytes)
         return fail(c, YSB_ERR_CAPACITY, "LZ4 batch of %llu B (%llu B decoded) exceeds max_batch_bytes",
-                    (unsigned long long)comp_bytes, (unsigned long long)*raw_total);
+                    (unsigned long long)comp_bytes, (unsigned long long)raw_total);
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->d_lz4[slot]) HIPCHK(c, c->d_lz4[slot].alloc(c->cfg.max_batch_bytes + 64));
     if (!c->h_lz4bad) {
@@ -75,49 +96,38 @@ int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, c
     }
     // the bytes: into the slot's pinned buffer, or read where they lie (a registered range)
     if (!dsrc && bytes != c->h_bytes[slot] && comp_bytes) std::memcpy(c->h_bytes[slot], bytes, comp_bytes);
-    c->lz4_hsrc[slot] = dsrc ? bytes : c->h_bytes[slot].get();
-    c->lz4_dsrc[slot] = dsrc ? dsrc : c->hd_bytes[slot];
-    fill_descs(dir, n_blocks, c->h_lz4desc[slot], &c->lz4_pend[slot], &c->lz4_max_raw[slot]);
+    batch->nbytes = raw_total;
+    Lz4Staged* out = &batch->lz4.emplace();
+    out->hsrc = dsrc ? bytes : c->h_bytes[slot].get();
+    out->dsrc = dsrc ? dsrc : c->hd_bytes[slot];
+    fill_descs(dir, n_blocks, c->h_lz4desc[slot], &out->info, &out->max_raw);
     // the layout sample: block 0 as the host model decodes it (nothing if it is bad -- the
     // device decides that for the batch)
-    c->lz4_sample.clear();
+    sample->clear();
     if (n_blocks) {
-        c->lz4_sample.resize(dir[0].raw_bytes);
-        if (!lz4_decode_block(c->lz4_hsrc[slot], dir[0], c->lz4_sample.data())) c->lz4_sample.clear();
+        sample->resize(dir[0].raw_bytes);
+        if (!lz4_decode_block(out->hsrc, dir[0], sample->data())) sample->clear();
     }
     return YSB_OK;
 }
 
-void lz4_copies(ysb_ctx* c, int slot, SlotCopy v[2]) {
-    const ysb_lz4_desc& p = c->lz4_pend[slot];
-    v[0] = {c->d_lz4[slot], c->lz4_dsrc[slot], c->lz4_hsrc[slot], p.comp_bytes};
+void lz4_copies(ysb_ctx* c, int slot, const Lz4Staged& b, SlotCopy v[2]) {
+    v[0] = {c->d_lz4[slot], b.dsrc, b.hsrc, b.info.comp_bytes};
     v[1] = {c->d_lz4desc[slot], c->hd_lz4desc[slot], c->h_lz4desc[slot],
-            p.blocks ? LZ4_DESC_HEAD + p.blocks * sizeof(Lz4Desc) : 0};
+            b.info.blocks ? LZ4_DESC_HEAD + b.info.blocks * sizeof(Lz4Desc) : 0};
 }
 
-int lz4_enqueue_decode(ysb_ctx* c, int slot, hipStream_t s) {
-    const ysb_lz4_desc& p = c->lz4_pend[slot];
+int lz4_enqueue_decode(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s) {
     c->h_lz4bad[2 * slot] = LZ4_NO_BAD;
     c->h_lz4bad[2 * slot + 1] = 0;
-    if (!p.blocks) return YSB_OK;
-    const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
-    if (timed) {
-        for (Event& e : c->ev_lz4[slot])
-            if (!e) HIPCHK(c, e.create(hipEventDefault));
-        HIPCHK(c, hipEventRecord(c->ev_lz4[slot][0], s));
-    }
-    u32* bad = reinterpret_cast<u32*>(c->d_lz4desc[slot].get());
-    const Lz4Params lp{c->d_lz4[slot], reinterpret_cast<const Lz4Desc*>(c->d_lz4desc[slot].get() + LZ4_DESC_HEAD),
-                       (u32)p.blocks, c->lz4_max_raw[slot], c->d_bytes[slot], bad};
-    HIPCHK(c, launch_lz4_decode(lp, s));
-    if (timed) HIPCHK(c, hipEventRecord(c->ev_lz4[slot][1], s));
+    if (!b.info.blocks) return YSB_OK;
     // the bad-block pair comes back through pinned memory with the line count: no host wait here
-    HIPCHK(c, hipMemcpyAsync(c->h_lz4bad + 2 * slot, bad, 8, hipMemcpyDeviceToHost, s));
-    return YSB_OK;
+    return launch_decode(c, c->d_lz4[slot], c->d_lz4desc[slot], (u32)b.info.blocks, b.max_raw, c->d_bytes[slot], s,
+                         (c->cfg.flags & YSB_F_TIMING) ? c->ev_lz4[slot] : nullptr, c->h_lz4bad + 2 * slot);
 }
 
-int lz4_settle(ysb_ctx* c, int slot) {
-    ysb_lz4_desc d = c->lz4_pend[slot];
+int lz4_settle(ysb_ctx* c, int slot, const Lz4Staged& b) {
+    ysb_lz4_desc d = b.info;
     d.batches = c->lz4_last.batches + 1;
     d.first_bad = c->h_lz4bad[2 * slot];
     d.bad_blocks = c->h_lz4bad[2 * slot + 1];
@@ -158,16 +168,8 @@ int ysb_lz4_decode_device(ysb_ctx* c, const uint8_t* d_comp, uint64_t comp_bytes
         HIPCHK(c, hipMemcpyAsync(c->d_lz4desc_sync, descs.data(), descs.size(), hipMemcpyHostToDevice, c->s_comp));
         const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
         Event ev[2];
-        if (timed) {
-            for (Event& e : ev) HIPCHK(c, e.create(hipEventDefault));
-            HIPCHK(c, hipEventRecord(ev[0], c->s_comp));
-        }
-        u32* d_bad = reinterpret_cast<u32*>(c->d_lz4desc_sync.get());
-        const Lz4Params lp{d_comp, reinterpret_cast<const Lz4Desc*>(c->d_lz4desc_sync.get() + LZ4_DESC_HEAD), n_blocks,
-                           max_raw, d_out, d_bad};
-        HIPCHK(c, launch_lz4_decode(lp, c->s_comp));
-        if (timed) HIPCHK(c, hipEventRecord(ev[1], c->s_comp));
-        HIPCHK(c, hipMemcpyAsync(bad, d_bad, 8, hipMemcpyDeviceToHost, c->s_comp));
+        if ((rc = launch_decode(c, d_comp, c->d_lz4desc_sync, n_blocks, max_raw, d_out, c->s_comp, timed ? ev : nullptr, bad)))
+            return rc;
         HIPCHK(c, hipStreamSynchronize(c->s_comp));
         float ms = 0;
         if (timed && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) info.decode_ms = ms;

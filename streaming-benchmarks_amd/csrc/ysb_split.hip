@@ -40,10 +40,8 @@ constexpr int H2D_TPB = 256, H2D_UNROLL = 4;
 
 typedef u32 h2d_v4 __attribute__((ext_vector_type(4)));
 
-template <bool PRIO>
 __global__ __launch_bounds__(H2D_TPB) void h2d_copy_kernel(const h2d_v4* __restrict__ src, h2d_v4* __restrict__ dst,
                                                            u64 vecs) {
-    if (PRIO) __builtin_amdgcn_s_setprio(3);   // issue ahead of a concurrent scan's waves on the SIMD
     const u64 stride = (u64)gridDim.x * H2D_TPB;
     u64 i = (u64)blockIdx.x * H2D_TPB + threadIdx.x;
     for (; i + (H2D_UNROLL - 1) * stride < vecs; i += H2D_UNROLL * stride) {
@@ -57,19 +55,15 @@ __global__ __launch_bounds__(H2D_TPB) void h2d_copy_kernel(const h2d_v4* __restr
 }
 
 // bytes rounded up to whole 16-byte vectors: both buffers have >= 64 bytes of slack
-void launch_h2d_copy(void* dst, const void* src, u64 bytes, int cus, hipStream_t s, bool prio) {
+void launch_h2d_copy(void* dst, const void* src, u64 bytes, int wgs, hipStream_t s) {
     const u64 vecs = (bytes + 15) / 16;
     if (!vecs) return;
-    // `cus` workgroups: the caller's choice (32: 512 KiB in flight, well above PCIe's bandwidth
+    // `wgs` workgroups: the caller's choice (32: 512 KiB in flight, well above PCIe's bandwidth
     // x latency, and few enough slow PCIe requests that HBM work beside the copy is not starved;
-    // ysb_submit.cpp enqueue_raw)
-    const u64 grid = std::max<u64>(1, std::min<u64>((u64)cus, (vecs + H2D_TPB - 1) / H2D_TPB));
-    if (prio)
-        hipLaunchKernelGGL(h2d_copy_kernel<true>, dim3((unsigned)grid), dim3(H2D_TPB), 0, s,
-                           static_cast<const h2d_v4*>(src), static_cast<h2d_v4*>(dst), vecs);
-    else
-        hipLaunchKernelGGL(h2d_copy_kernel<false>, dim3((unsigned)grid), dim3(H2D_TPB), 0, s,
-                           static_cast<const h2d_v4*>(src), static_cast<h2d_v4*>(dst), vecs);
+    // ysb_raw.cpp enqueue_deferred), at most one per H2D_TPB vectors
+    const u64 grid = std::max<u64>(1, std::min<u64>((u64)wgs, (vecs + H2D_TPB - 1) / H2D_TPB));
+    hipLaunchKernelGGL(h2d_copy_kernel, dim3((unsigned)grid), dim3(H2D_TPB), 0, s, static_cast<const h2d_v4*>(src),
+                       static_cast<h2d_v4*>(dst), vecs);
 }
 
 // The same from a source at any byte address (a file mapping's batch starts where the previous

@@ -1,22 +1,15 @@
-// ysb_submit.cpp -- batches into launches: the pinned double-buffered slots (ysb_submit),
-// raw lines split on the GPU (ysb_submit_raw), device batches (ysb_submit_device*), the
-// layout samples that pick the scan instantiation (their rules: ysb_layout.h), record-mode
-// planning and the launch sequence itself (scan, deferred lines, record partition + count).
+// ysb_submit.cpp -- segments into launches: the pinned double-buffered slots (ysb_submit) and
+// their copies, device batches (ysb_submit_device*), the layout samples that pick the scan
+// instantiation (their rules: ysb_layout.h), record-mode planning and the launch sequence
+// itself (scan, deferred lines, record partition + count).  The batches that launch a call
+// after their submit (raw lines, mapped, compressed) are ysb_raw.cpp's.
 #include "ysb_ctx.h"
-#include "ysb_lz4.h"
 
 using namespace ysb;
 
 extern "C" {
 
 // ---- batches ---------------------------------------------------------------------------
-
-// The scan instantiation a submit chose for its batch: layout -1 is the flags'; learn the key
-// order of layouts 3 and 4.
-struct Layout {
-    int layout = -1;
-    LearnDesc learn{};
-};
 
 static u32 require_mask(const ysb_ctx* c) { return (c->cfg.flags & YSB_F_REQUIRE_IP) ? 0x7Fu : 0x3Fu; }
 static bool flat_first(const ysb_ctx* c) { return (c->cfg.flags & YSB_F_FLAT_FIRST) != 0; }
@@ -196,7 +189,7 @@ void context_params(ysb_ctx* c, ScanParams* out) {
     *out = make_params(c, &none, 1, Layout{});
 }
 
-static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout& lay) {
+int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout& lay) {
     if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
     ysb_segment segs[MAX_SEGS];
     u32 nseg = 0;
@@ -282,6 +275,11 @@ static int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout
 static bool layout_sampling(const ysb_ctx* c) {
     const u32 f = c->cfg.flags;
     return !(f & (YSB_F_LAYOUT_FIXED | YSB_F_COMPACT_FIRST | YSB_F_FORMAT_TBL));
+}
+
+void sampled_layout(const ysb_ctx* c, const u8* bytes, u64 nbytes, Layout* out) {
+    *out = Layout{};
+    if (layout_sampling(c)) out->layout = hinted_layout(flat_first(c), sniff_raw(require_mask(c), bytes, nbytes, &out->learn));
 }
 
 // Device batches: SAMPLE_LINES lines spread over the launch's segments (as sniff_layout
@@ -390,12 +388,13 @@ int ensure_slots(ysb_ctx* c) {
 // A slot's host -> device copy on the copy stream: by the CUs from the pinned slot's device
 // address (launch_h2d_copy, the default: ysb_split.hip says why; a mapped batch that does not
 // start on a 16-byte boundary by launch_h2d_copy_unaligned), or by the DMA engine with
-// YSB_F_H2D_SDMA.
+// YSB_F_H2D_SDMA.  H2D_WGS: the copy kernels' grid (clamped to the vectors there are by their
+// launch functions; why 32: ysb_raw.cpp enqueue_deferred).
+constexpr int H2D_WGS = 32;
 static hipError_t h2d(ysb_ctx* c, void* dst, const void* dsrc, const void* hsrc, u64 bytes) {
     if (c->cfg.flags & YSB_F_H2D_SDMA) return hipMemcpyAsync(dst, hsrc, bytes, hipMemcpyHostToDevice, c->s_copy);
-    const int wgs = c->h2d_grid ? c->h2d_grid : c->cus * c->h2d_wg;
-    if (reinterpret_cast<uintptr_t>(dsrc) & 15) launch_h2d_copy_unaligned(dst, dsrc, bytes, wgs, c->s_copy);
-    else launch_h2d_copy(dst, dsrc, bytes, wgs, c->s_copy, c->h2d_prio);
+    if (reinterpret_cast<uintptr_t>(dsrc) & 15) launch_h2d_copy_unaligned(dst, dsrc, bytes, H2D_WGS, c->s_copy);
+    else launch_h2d_copy(dst, dsrc, bytes, H2D_WGS, c->s_copy);
     return hipGetLastError();
 }
 
@@ -416,14 +415,11 @@ int copy_slot_ranges(ysb_ctx* c, int slot, const SlotCopy* v, int n) {
     HIPCHK(c, hipEventRecord(c->ev_h2d[slot], c->s_copy));
     return YSB_OK;
 }
-static int copy_slot(ysb_ctx* c, int slot, const SlotCopy& a, const SlotCopy& b = {}) {
-    const SlotCopy v[2] = {a, b};
-    return copy_slot_ranges(c, slot, v, 2);
-}
 
 int ysb_slot_buffers(ysb_ctx* c, int slot, uint8_t** bytes, uint32_t** line_off) {
-    if (!c || slot < 0 || slot > 1) return c ? fail(c, YSB_ERR_ARG, "slot must be 0 or 1") : YSB_ERR_ARG;
-    int rc = ensure_slots(c);
+    if (!c) return YSB_ERR_ARG;
+    int rc = slot_arg(c, slot);
+    if (!rc) rc = ensure_slots(c);
     if (rc) return rc;
     if (bytes) *bytes = c->h_bytes[slot];
     if (line_off) *line_off = c->h_off[slot];
@@ -433,7 +429,7 @@ int ysb_slot_buffers(ysb_ctx* c, int slot, uint8_t** bytes, uint32_t** line_off)
 int ysb_submit(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const uint32_t* line_off,
                uint64_t n) {
     if (!c) return YSB_ERR_ARG;
-    if (slot < 0 || slot > 1) return fail(c, YSB_ERR_ARG, "slot must be 0 or 1");
+    if (int rc = slot_arg(c, slot)) return rc;
     if (nbytes > c->cfg.max_batch_bytes || n > c->cfg.max_batch_events)
         return fail(c, YSB_ERR_CAPACITY, "batch (%llu B, %llu events) exceeds max_batch_bytes/max_batch_events",
                     (unsigned long long)nbytes, (unsigned long long)n);
@@ -447,9 +443,9 @@ int ysb_submit(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, cons
     if (bytes != c->h_bytes[slot] && nbytes) std::memcpy(c->h_bytes[slot], bytes, nbytes);
     if (line_off != c->h_off[slot] && n) std::memcpy(c->h_off[slot], line_off, n * 4);
     // ... and the slot's previous kernel must be done before its device buffers are
-    if ((rc = copy_slot(c, slot, {c->d_bytes[slot], c->hd_bytes[slot], c->h_bytes[slot], nbytes},
-                        {c->d_off[slot], c->hd_off[slot], c->h_off[slot], n * 4})))
-        return rc;
+    const SlotCopy v[2] = {{c->d_bytes[slot], c->hd_bytes[slot], c->h_bytes[slot], nbytes},
+                           {c->d_off[slot], c->hd_off[slot], c->h_off[slot], n * 4}};
+    if ((rc = copy_slot_ranges(c, slot, v, 2))) return rc;
     HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_h2d[slot], 0));
     const ysb_segment sg{c->d_bytes[slot], nbytes, c->d_off[slot], n};
     // the scan instantiation named by the batch's first line, which the host holds in the
@@ -465,402 +461,9 @@ int ysb_submit(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, cons
 
 int ysb_wait(ysb_ctx* c, int slot) {
     if (!c) return YSB_ERR_ARG;
-    if (slot < 0 || slot > 1) return fail(c, YSB_ERR_ARG, "slot must be 0 or 1");
+    if (const int rc = slot_arg(c, slot)) return rc;
     if (!c->h_bytes[0]) return YSB_OK;
     HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
-    return YSB_OK;
-}
-
-// ---- raw batches (ysb_submit_raw): the line split on the GPU ----------------------------------
-
-// Lines a raw batch may hold: max_batch_events, or one per 32 bytes of the slot if that is
-// more (an event line is > 60 bytes; the device's line-start array is 4 B per line, not per
-// byte); at most one per byte.  A batch with more lines fails its launch (YSB_ERR_CAPACITY).
-static u64 raw_line_cap(const ysb_config& cfg) {
-    return std::min<u64>(cfg.max_batch_bytes + 1, std::max<u64>(cfg.max_batch_events, cfg.max_batch_bytes / 32) + 1);
-}
-
-static int ensure_raw(ysb_ctx* c) {
-    if (c->h_rawn) return YSB_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    c->raw_lines_cap = raw_line_cap(c->cfg);
-    for (int s = 0; s < 2; ++s) {   // (a failed earlier attempt may have left some of these)
-        HIPCHK(c, c->d_roff[s].alloc(c->raw_lines_cap * 4));
-        if (!c->ev_raw[s]) HIPCHK(c, c->ev_raw[s].create());
-    }
-    if (!c->s_split) HIPCHK(c, hipStreamCreateWithFlags(&c->s_split, hipStreamNonBlocking));
-    const u64 chunk_bytes = (split_chunks(c->cfg.max_batch_bytes) + 1) * 4;
-    const int rc = grow_device(c, c->d_split_chunk, chunk_bytes, 0);
-    if (rc) return rc;
-    HIPCHK(c, c->h_rawn.alloc(16));
-    return YSB_OK;
-}
-
-// The raw batch waiting for its launch (if any): its line count is back from the device
-// (ev_raw), so its scan is enqueued now -- the order of submission is kept.  A batch that
-// cannot launch (more lines than raw_lines_cap, a failed enqueue) is dropped and its error
-// is sticky: every later call on the context that would order work after it returns it,
-// until ysb_reset -- counts after a lost batch are not the stream's.
-int launch_pending_raw(ysb_ctx* c) {
-    if (c->raw_fail) return fail(c, c->raw_fail, "%s", c->raw_fail_msg.c_str());
-    if (c->raw_pend < 0) return YSB_OK;
-    const int slot = c->raw_pend;
-    int rc = YSB_OK;
-    if (hipSetDevice(c->device) != hipSuccess || hipEventSynchronize(c->ev_raw[slot]) != hipSuccess ||
-        hipStreamWaitEvent(c->s_comp, c->ev_raw[slot], 0) != hipSuccess) {
-        rc = fail(c, YSB_ERR_HIP, "raw batch (slot %d): waiting for its line split failed", slot);
-    } else if (c->raw_lz4[slot] && (rc = lz4_settle(c, slot))) {
-        // a compressed batch with a bad block: dropped whole (YSB_ERR_FORMAT, the message lz4_settle's)
-    } else if (c->raw_rebase_on[slot] && c->h_rawn[slot] > c->rebase_n - c->raw_rebase[slot].first_line) {
-        rc = fail(c, YSB_ERR_ARG, "raw batch (slot %d): %llu lines, more than the rebase table holds from line %llu",
-                  slot, (unsigned long long)c->h_rawn[slot], (unsigned long long)c->raw_rebase[slot].first_line);
-    } else if (!c->raw_off[slot] && c->h_rawn[slot] > c->raw_lines_cap) {   // (the caller's offsets: no d_roff to fit)
-        rc = fail(c, YSB_ERR_CAPACITY, "raw batch (slot %d): %llu lines, more than the %llu its slot holds "
-                  "(max(max_batch_events, max_batch_bytes / 32))", slot, (unsigned long long)c->h_rawn[slot],
-                  (unsigned long long)c->raw_lines_cap);
-    } else {
-        const u32* off = c->raw_off[slot] ? c->raw_off[slot] : c->d_roff[slot].get();
-        const ysb_segment sg{c->d_bytes[slot], c->raw_nbytes[slot], off, c->h_rawn[slot]};
-        rc = enqueue_scan(c, &sg, 1, {c->raw_layout[slot], c->raw_learn[slot]});
-    }
-    // the slot's device buffers are free again once this launch (or nothing) has run
-    if (hipEventRecord(c->ev_kdone[slot], c->s_comp) != hipSuccess && !rc)
-        rc = fail(c, YSB_ERR_HIP, "hipEventRecord failed");
-    c->raw_pend = -1;
-    c->raw_lz4[slot] = false;
-    c->raw_off[slot] = nullptr;
-    if (rc) {
-        c->raw_fail = rc;
-        c->raw_fail_msg = c->err;
-    }
-    return rc;
-}
-
-static int raw_args(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes) {
-    if (slot < 0 || slot > 1) return fail(c, YSB_ERR_ARG, "slot must be 0 or 1");
-    if (nbytes > c->cfg.max_batch_bytes)
-        return fail(c, YSB_ERR_CAPACITY, "raw batch of %llu B exceeds max_batch_bytes", (unsigned long long)nbytes);
-    if (nbytes && !bytes) return fail(c, YSB_ERR_ARG, "NULL batch buffer");
-    if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
-    return YSB_OK;
-}
-
-// A raw batch from hsrc (host address: the layout sample, the DMA engine) / dsrc (its device
-// address: the copy kernel) into the slot's device buffer, split, optionally rebased; its scan
-// launches at the next call.  The caller has waited for the slot's previous copy.
-static int enqueue_raw(ysb_ctx* c, int slot, const u8* hsrc, const u8* dsrc, u64 nbytes, const ysb_rebase* rb) {
-    int rc;
-    c->raw_layout[slot] = -1;
-    if (layout_sampling(c) && nbytes)
-        c->raw_layout[slot] = hinted_layout(flat_first(c), sniff_raw(require_mask(c), hsrc, nbytes, &c->raw_learn[slot]));
-    // H2D once the slot's previous kernel has run.  The split on a stream of its own behind its
-    // copy, so the next slot's copy queues right behind this one.  Round 5 kept it on the copy
-    // stream: beside a copy kernel of one workgroup per CU the split was starved (its 32 us
-    // count took 2.7 ms, and the slot's scan waited behind it).  The copy kernel's grid is now 32
-    // workgroups (h2d_grid): still far more bytes in flight than PCIe's bandwidth x latency, and
-    // the HBM work beside it (split, scan) no longer queues behind its slow requests.  Same-box
-    // A/B (gpurun_out/r6r, r6s): raw host-staged 210 -> 214-218 M events/s, the raw streaming
-    // replay 197 -> 206-209 (copy queue busy 0.958 -> 0.986).  (YSB_SPLIT_STREAM: 0 the copy
-    // stream, 2 the compute stream -- A/B only.)
-    const bool sdma = (c->cfg.flags & YSB_F_H2D_SDMA) != 0u;
-    hipStream_t ss = sdma || c->split_place == 1 ? c->s_split : c->split_place == 2 ? c->s_comp : c->s_copy;
-    if ((rc = copy_slot(c, slot, {c->d_bytes[slot], dsrc, hsrc, nbytes}))) return rc;
-    if (ss != c->s_copy) HIPCHK(c, hipStreamWaitEvent(ss, c->ev_h2d[slot], 0));
-    c->raw_rebase_on[slot] = rb != nullptr;
-    if (rb) c->raw_rebase[slot] = *rb;
-    if (nbytes) {
-        // the line count goes straight to pinned memory (read at the launch)
-        HIPCHK(c, launch_split_lines(c->d_bytes[slot], nbytes, c->d_split_chunk, c->d_roff[slot],
-                                     c->raw_lines_cap, c->h_rawn + slot, ss));
-        if (rb) {
-            launch_rebase(c->d_bytes[slot], nbytes, c->d_roff[slot], c->raw_lines_cap, c->h_rawn + slot, 0,
-                          c->d_rebase + rb->first_line, c->rebase_n - rb->first_line,
-                          c->rebase_base + rb->lead_shift, c->cus, ss);
-            HIPCHK(c, hipGetLastError());
-        }
-    } else {
-        c->h_rawn[slot] = 0;
-    }
-    HIPCHK(c, hipEventRecord(c->ev_raw[slot], ss));
-    c->raw_nbytes[slot] = nbytes;
-    // the other slot's batch, submitted before this one, launches now; this one at the next call
-    rc = launch_pending_raw(c);
-    c->raw_pend = slot;
-    return rc;
-}
-
-int ysb_submit_raw(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes) {
-    if (!c) return YSB_ERR_ARG;
-    int rc = raw_args(c, slot, bytes, nbytes);
-    if (rc) return rc;
-    // the slot's own earlier batch launches first (its device buffers are about to be reused)
-    rc = c->raw_pend == slot ? launch_pending_raw(c) : YSB_OK;
-    if (!rc) rc = ensure_slots(c);
-    if (!rc) rc = ensure_raw(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    // the slot's previous H2D must be done before its pinned buffer is rewritten
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
-    if (bytes != c->h_bytes[slot] && nbytes) std::memcpy(c->h_bytes[slot], bytes, nbytes);
-    return enqueue_raw(c, slot, c->h_bytes[slot], c->hd_bytes[slot], nbytes, nullptr);
-}
-
-// ---- LZ4-compressed raw batches (ysb_lz4_api.cpp, ysb_lz4.hip) --------------------------------
-
-// enqueue_raw for a staged compressed batch (lz4_stage), the ONE statement of its order for
-// ysb_submit_raw_lz4 and ysb_submit_lz4_mapped: the compressed bytes (from the slot's pinned
-// buffer or in place from a registered range) and the block descriptors over PCIe, the decode
-// into the slot's device buffer on the stream of the split -- behind the slot's copy, never on
-// the copy stream, which goes on with the other slot's copy --, then the split as for any raw
-// batch or, with d_line_off, the caller's n device offsets into the decoded batch and no split,
-// then the rebase (rb != NULL) on the decoded bytes on the same stream.  Its scan launches at
-// the next call, with offsets too: the verdict on its blocks must be known before its lines
-// are counted.
-static int enqueue_raw_lz4(ysb_ctx* c, int slot, u64 raw_bytes, const u32* d_line_off, u64 n, const ysb_rebase* rb) {
-    int rc;
-    c->raw_layout[slot] = -1;
-    if (layout_sampling(c) && !c->lz4_sample.empty())
-        c->raw_layout[slot] = hinted_layout(flat_first(c), sniff_raw(require_mask(c), c->lz4_sample.data(),
-                                                                     c->lz4_sample.size(), &c->raw_learn[slot]));
-    hipStream_t ss = c->split_place == 2 ? c->s_comp : c->s_split;
-    SlotCopy v[2];
-    lz4_copies(c, slot, v);
-    if ((rc = copy_slot_ranges(c, slot, v, 2))) return rc;
-    HIPCHK(c, hipStreamWaitEvent(ss, c->ev_h2d[slot], 0));
-    c->raw_rebase_on[slot] = rb != nullptr;
-    if (rb) c->raw_rebase[slot] = *rb;
-    if ((rc = lz4_enqueue_decode(c, slot, ss))) return rc;
-    const i64 lead = rb ? c->rebase_base + rb->lead_shift : 0;
-    if (d_line_off) {
-        c->h_rawn[slot] = n;
-        if (rb) launch_rebase(c->d_bytes[slot], raw_bytes, d_line_off, n, nullptr, n, c->d_rebase + rb->first_line,
-                              c->rebase_n - rb->first_line, lead, c->cus, ss);
-    } else if (raw_bytes) {
-        HIPCHK(c, launch_split_lines(c->d_bytes[slot], raw_bytes, c->d_split_chunk, c->d_roff[slot],
-                                     c->raw_lines_cap, c->h_rawn + slot, ss));
-        if (rb) launch_rebase(c->d_bytes[slot], raw_bytes, c->d_roff[slot], c->raw_lines_cap, c->h_rawn + slot, 0,
-                              c->d_rebase + rb->first_line, c->rebase_n - rb->first_line, lead, c->cus, ss);
-    } else {
-        c->h_rawn[slot] = 0;
-    }
-    if (rb) HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_raw[slot], ss));
-    c->raw_nbytes[slot] = raw_bytes;
-    rc = launch_pending_raw(c);
-    c->raw_pend = slot;
-    c->raw_lz4[slot] = true;
-    c->raw_off[slot] = d_line_off;
-    return rc;
-}
-
-// What both compressed submits do once their own arguments are checked: the slot's earlier
-// batch launched, its buffers there and free, the batch staged (dsrc: lz4_stage), enqueued.
-static int submit_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, u64 comp_bytes, const ysb_lz4_block* dir, u32 n_blocks,
-                      const u8* dsrc, const u32* d_line_off, u64 n, const ysb_rebase* rb) {
-    // the slot's own earlier batch launches first (its device buffers are about to be reused)
-    int rc = c->raw_pend == slot ? launch_pending_raw(c) : YSB_OK;
-    if (!rc) rc = ensure_slots(c);
-    if (!rc) rc = ensure_raw(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    // the slot's previous H2D must be done before its pinned buffers are rewritten (in place:
-    // the descriptors'; so at most two copies are in flight)
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
-    u64 raw_bytes = 0;
-    if ((rc = lz4_stage(c, slot, bytes, comp_bytes, dir, n_blocks, dsrc, &raw_bytes))) return rc;
-    return enqueue_raw_lz4(c, slot, raw_bytes, d_line_off, n, rb);
-}
-
-int ysb_submit_raw_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
-                       uint32_t n_blocks) {
-    if (!c) return YSB_ERR_ARG;
-    if (slot < 0 || slot > 1) return fail(c, YSB_ERR_ARG, "slot must be 0 or 1");
-    if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
-    return submit_lz4(c, slot, bytes, comp_bytes, dir, n_blocks, nullptr, nullptr, 0, nullptr);
-}
-
-// ---- zero-copy raw batches from registered caller memory (ABI 5) ----------------------------
-
-int ysb_host_register(ysb_ctx* c, void* host, uint64_t bytes) {
-    if (!c) return YSB_ERR_ARG;
-    if (!host || !bytes) return fail(c, YSB_ERR_ARG, "empty host range");
-    const uintptr_t a = reinterpret_cast<uintptr_t>(host);
-    for (const auto& r : c->host_ranges)
-        if (a < r.first + r.second.bytes && r.first < a + bytes) return fail(c, YSB_ERR_ARG, "host range overlaps a registered one");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipHostRegister(host, bytes, hipHostRegisterMapped));
-    void* d = nullptr;
-    if (hipHostGetDevicePointer(&d, host, 0) != hipSuccess) {
-        hipHostUnregister(host);
-        return fail(c, YSB_ERR_HIP, "hipHostGetDevicePointer of a registered range failed");
-    }
-    if ((reinterpret_cast<uintptr_t>(d) ^ a) & 15) {   // the copy's 16-byte widening assumes it
-        hipHostUnregister(host);
-        return fail(c, YSB_ERR_HIP, "the device alias of a registered range is not 16-byte congruent to it");
-    }
-    c->host_ranges[a] = {bytes, static_cast<u8*>(d)};
-    return YSB_OK;
-}
-
-int ysb_host_unregister(ysb_ctx* c, void* host) {
-    if (!c) return YSB_ERR_ARG;
-    auto it = c->host_ranges.find(reinterpret_cast<uintptr_t>(host));
-    if (it == c->host_ranges.end()) return fail(c, YSB_ERR_ARG, "not a registered range");
-    // nothing queued may still read it
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->s_copy));
-    HIPCHK(c, hipHostUnregister(host));
-    c->host_ranges.erase(it);
-    return YSB_OK;
-}
-
-int ysb_rebase_table(ysb_ctx* c, const uint32_t* time_at, uint64_t n_lines, int64_t lead_base) {
-    if (!c) return YSB_ERR_ARG;
-    if (n_lines && !time_at) return fail(c, YSB_ERR_ARG, "NULL table");
-    HIPCHK(c, hipSetDevice(c->device));
-    // batches queued with the old table must be done with it
-    HIPCHK(c, hipStreamSynchronize(c->s_copy));
-    if (c->s_split) HIPCHK(c, hipStreamSynchronize(c->s_split));
-    c->d_rebase.reset();
-    c->rebase_n = 0;
-    if (!n_lines) return YSB_OK;
-    u32 kmax = 0;
-    for (u64 i = 0; i < n_lines; ++i) kmax = std::max(kmax, time_at[i] >> 16);
-    if (lead_base < 0 || lead_base + kmax >= 1000000000LL) return fail(c, YSB_ERR_ARG, "leading digits out of [0, 10^9)");
-    HIPCHK(c, c->d_rebase.alloc(n_lines * 4));
-    HIPCHK(c, hipMemcpy(c->d_rebase, time_at, n_lines * 4, hipMemcpyHostToDevice));
-    c->rebase_n = n_lines;
-    c->rebase_base = lead_base;
-    c->rebase_kmax = kmax;
-    return YSB_OK;
-}
-
-// The device alias of a mapped batch, or NULL when the batch widened to 16-byte boundaries on
-// both sides (what the copy reads: launch_h2d_copy / launch_h2d_copy_unaligned) is not inside
-// one registered range.
-static const u8* mapped_src(const ysb_ctx* c, const uint8_t* bytes, u64 nbytes) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(bytes);
-    auto it = c->host_ranges.upper_bound(a);
-    if (it == c->host_ranges.begin()) return nullptr;
-    --it;
-    const uintptr_t lo = a & ~uintptr_t(15), hi = (a + nbytes + 15) & ~uintptr_t(15);
-    if (lo < it->first || hi > it->first + it->second.bytes) return nullptr;
-    return it->second.dptr + (a - it->first);
-}
-
-// ... or the error: a batch with bytes must have one.
-static int mapped_src_or_fail(ysb_ctx* c, const uint8_t* bytes, u64 nbytes, const u8** dsrc) {
-    *dsrc = mapped_src(c, bytes, nbytes);
-    if (nbytes && !*dsrc)
-        return fail(c, YSB_ERR_ARG, "the batch (widened to 16-byte boundaries) is not inside a registered range");
-    return YSB_OK;
-}
-
-// A mapped batch's rebase argument (NULL: none) against the context's table.  A raw batch
-// (n_lines NULL: its line count is not known yet, launch_pending_raw checks it) must start
-// inside the table; a batch with offsets must fit its *n_lines lines.
-static int rebase_args(ysb_ctx* c, const ysb_rebase* rb, const u64* n_lines) {
-    if (!rb) return YSB_OK;
-    if (!c->d_rebase) return fail(c, YSB_ERR_STATE, "no rebase table (ysb_rebase_table)");
-    if (!n_lines && rb->first_line >= c->rebase_n) return fail(c, YSB_ERR_ARG, "first_line beyond the rebase table");
-    if (n_lines && (rb->first_line > c->rebase_n || *n_lines > c->rebase_n - rb->first_line))
-        return fail(c, YSB_ERR_ARG, "the batch's lines run past the rebase table");
-    const i64 lo = c->rebase_base + rb->lead_shift;
-    if (lo < 0 || lo + (i64)c->rebase_kmax >= 1000000000LL)
-        return fail(c, YSB_ERR_ARG, "rebased leading digits out of [0, 10^9)");
-    return YSB_OK;
-}
-
-int ysb_submit_raw_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_rebase* rb) {
-    if (!c) return YSB_ERR_ARG;
-    int rc = raw_args(c, slot, bytes, nbytes);
-    const u8* dsrc = nullptr;
-    if (!rc) rc = mapped_src_or_fail(c, bytes, nbytes, &dsrc);
-    if (!rc) rc = rebase_args(c, rb, nullptr);
-    if (rc) return rc;
-    rc = c->raw_pend == slot ? launch_pending_raw(c) : YSB_OK;
-    if (!rc) rc = ensure_slots(c);
-    if (!rc) rc = ensure_raw(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    return enqueue_raw(c, slot, bytes, dsrc, nbytes, rb);
-}
-
-// A compressed batch read in place from a registered range: the union of
-// ysb_submit_raw_lz4's rules and the mapped calls'.  The copy kernel (the DMA engine with
-// YSB_F_H2D_SDMA) reads the blocks where they lie into d_lz4[slot]; the slot's pinned byte
-// buffer is not used and the host makes no pass over the bytes (block 0 apart: the layout
-// sample).  d_line_off NULL: the GPU line split; otherwise n device offsets into the decoded batch.
-int ysb_submit_lz4_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
-                          uint32_t n_blocks, const uint32_t* d_line_off, uint64_t n, const ysb_rebase* rb) {
-    if (!c) return YSB_ERR_ARG;
-    if (slot < 0 || slot > 1) return fail(c, YSB_ERR_ARG, "slot must be 0 or 1");
-    if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
-    if (comp_bytes && !bytes) return fail(c, YSB_ERR_ARG, "NULL batch buffer");
-    if (!d_line_off && n) return fail(c, YSB_ERR_ARG, "n_events without line offsets (NULL d_line_off: the GPU split, n_events 0)");
-    if (d_line_off && !n) return fail(c, YSB_ERR_ARG, "line offsets without n_events");
-    if (n > 0x7FFFFFFFull) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 events per batch");
-    const u8* dsrc = nullptr;
-    int rc = mapped_src_or_fail(c, bytes, comp_bytes, &dsrc);
-    if (!rc) rc = rebase_args(c, rb, d_line_off ? &n : nullptr);
-    if (rc) return rc;
-    return submit_lz4(c, slot, bytes, comp_bytes, dir, n_blocks, dsrc, d_line_off, n, rb);
-}
-
-// A mapped batch whose line offsets are already in HBM: nothing waits for a line count, so the
-// copy queue holds copies only (a raw batch's split and rebase between copies cost the copy
-// queue ~4 % of its time: DESIGN.md section 11) and the scan is enqueued at once behind the
-// copy on the compute stream.
-int ysb_submit_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const uint32_t* d_line_off,
-                      uint64_t n, const ysb_rebase* rb) {
-    if (!c) return YSB_ERR_ARG;
-    int rc = raw_args(c, slot, bytes, nbytes);
-    if (rc) return rc;
-    if (n > 0x7FFFFFFFull) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 events per batch");
-    if (n && !d_line_off) return fail(c, YSB_ERR_ARG, "NULL line offsets");
-    const u8* dsrc = nullptr;
-    if ((rc = mapped_src_or_fail(c, bytes, nbytes, &dsrc)) || (rc = rebase_args(c, rb, &n))) return rc;
-    if (!n) return YSB_OK;
-    rc = launch_pending_raw(c);   // batches launch in submission order
-    if (!rc) rc = ensure_slots(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    // at most two copies in flight: the slot's previous one must be done (its device buffer is
-    // then only still read by its scan, which the copy waits for on the device)
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
-    Layout lay;
-    if (layout_sampling(c)) lay.layout = hinted_layout(flat_first(c), sniff_raw(require_mask(c), bytes, nbytes, &lay.learn));
-    if ((rc = copy_slot(c, slot, {c->d_bytes[slot], dsrc, bytes, nbytes}))) return rc;
-    HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_h2d[slot], 0));
-    if (rb) {
-        launch_rebase(c->d_bytes[slot], nbytes, d_line_off, n, nullptr, n, c->d_rebase + rb->first_line,
-                      c->rebase_n - rb->first_line, c->rebase_base + rb->lead_shift, c->cus, c->s_comp);
-        HIPCHK(c, hipGetLastError());
-    }
-    const ysb_segment sg{c->d_bytes[slot], nbytes, d_line_off, n};
-    if ((rc = enqueue_scan(c, &sg, 1, lay))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_kdone[slot], c->s_comp));
-    return YSB_OK;
-}
-
-int ysb_split_lines_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, uint32_t* d_off, uint64_t cap,
-                           uint64_t* n) {
-    if (!c || !n) return c ? fail(c, YSB_ERR_ARG, "n is NULL") : YSB_ERR_ARG;
-    if (nbytes > (4ull << 30) - 64) return fail(c, YSB_ERR_CAPACITY, "batch larger than 4 GiB (u32 offsets)");
-    if ((nbytes && !d_bytes) || (cap && !d_off)) return fail(c, YSB_ERR_ARG, "NULL buffers");
-    if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(c, YSB_ERR_ARG, "d_bytes must be 16-byte aligned");
-    int rc = launch_pending_raw(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = grow_device(c, c->d_split_chunk, (split_chunks(nbytes) + 1) * 4, 0))) return rc;
-    if ((rc = first_use(c, c->d_cmp, 32))) return rc;
-    unsigned long long* d_n = c->d_cmp + 3;
-    HIPCHK(c, launch_split_lines(d_bytes, nbytes, c->d_split_chunk, d_off, cap, d_n, c->s_comp));
-    unsigned long long got = 0;
-    HIPCHK(c, hipMemcpyAsync(&got, d_n, 8, hipMemcpyDeviceToHost, c->s_comp));
-    HIPCHK(c, hipStreamSynchronize(c->s_comp));
-    *n = got;
-    if (got > cap) return fail(c, YSB_ERR_CAPACITY, "%llu lines, cap %llu", (unsigned long long)got, (unsigned long long)cap);
     return YSB_OK;
 }
 
@@ -868,20 +471,6 @@ int ysb_slot_capacity(ysb_ctx* c, uint64_t* max_bytes, uint64_t* max_events) {
     if (!c) return YSB_ERR_ARG;
     if (max_bytes) *max_bytes = c->cfg.max_batch_bytes;
     if (max_events) *max_events = c->cfg.max_batch_events;
-    return YSB_OK;
-}
-
-int ysb_copy_time(ysb_ctx* c, double* total_ms, uint64_t* copies, uint64_t* bytes) {
-    if (!c) return YSB_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->s_copy));
-    double t[2] = {0, 0};
-    u64 n = 0;
-    HIPCHK(c, c->cev.collect(t, &n));
-    if (total_ms) *total_ms = t[1];
-    if (copies) *copies = n;
-    if (bytes) *bytes = c->copy_bytes;
-    c->copy_bytes = 0;
     return YSB_OK;
 }
 

@@ -276,6 +276,67 @@ def test_a_bad_block_drops_its_batch(name):
         assert ctx.stats() == first and ctx.drain() == rows
 
 
+def test_each_slot_takes_every_kind_of_batch_in_turn():
+    """One context, tests/golden/gen_s7.jsonl in six batches of 250 lines on alternating slots:
+    slot 0 takes a plain raw batch, a compressed one in place with device offsets and a rebase,
+    a compressed one in place with the GPU split and no rebase; slot 1 a compressed slot batch, a
+    mapped raw one with a rebase, a plain raw one.  Nothing of a slot's earlier batch outlives
+    its launch: with a rebase of 0 buckets the counts are the file's golden counts, and the
+    last compressed batch's figures are the fifth batch's.  Then a malformed compressed batch and a
+    plain raw batch behind it on its slot: the error is sticky, and after ysb_reset the plain
+    batch alone counts exactly."""
+    raw, offs = gd.events("gen_s7")
+    exp = gd.expected("gen_s7")
+    data = np.frombuffer(raw, dtype=np.uint8)
+    off = np.asarray(offs, dtype=np.uint32)
+    assert off.size == 1500
+    tab, base = time_table(data, off)
+    ends = np.append(off[1:], data.size).astype(np.int64)
+    part = [data[off[a]:ends[a + 249]] for a in range(0, 1500, 250)]
+    packed = {i: lz4.pack(part[i], 64) for i in (1, 2, 4)}
+    assert all(d.shape[0] > 500 for _, d in packed.values())   # many blocks each
+    # what is read in place, each at another byte residue of one registered array
+    items, at, pos = [packed[2][0], part[3], packed[4][0]], [], 0
+    for k, it in enumerate(items):
+        pos += (4 * k + 3 - pos) % 16
+        at.append(pos)
+        pos += it.size
+    buf = aligned(pos)
+    for p, it in zip(at, items):
+        buf[p:p + it.size] = it
+    lo = (off[500:750] - off[500]).astype(np.uint32)   # batch 3's line offsets in its decoded bytes
+    with make_ctx(max_batch_bytes=SLOT) as ctx:
+        ctx.host_register(buf)
+        ctx.rebase_table(tab, base)
+        d_lo = ctx.device_alloc(lo.nbytes + 64)
+        ctx.h2d(d_lo, lo)
+        ctx.submit_raw(part[0], slot=0)
+        ctx.submit_raw_lz4(*packed[1], slot=1)
+        ctx.submit_lz4_mapped(buf, at[0], items[0].size, packed[2][1], slot=0, d_off=d_lo, n=250, rebase=(500, 0))
+        ctx.submit_raw_mapped(buf, at[1], items[1].size, slot=1, rebase=(750, 0))
+        ctx.submit_lz4_mapped(buf, at[2], items[2].size, packed[4][1], slot=0)
+        ctx.submit_raw(part[5], slot=1)
+        info = ctx.lz4_info()
+        blob5, d5 = packed[4]
+        assert info["batches"] == 3 and info["bad_blocks"] == 0 and info["first_bad"] is None
+        assert info["blocks"] == d5.shape[0] and info["stored_blocks"] == int(((d5[:, 0] & lz4.STORED) != 0).sum())
+        assert info["comp_bytes"] == blob5.size and info["raw_bytes"] == part[4].size
+        check_against(ctx, *exp)
+        bad_comp, bad_raw = malformed("offset 0")
+        ctx.submit_raw_lz4(bad_comp, [(len(bad_comp), bad_raw)], slot=1)   # launches nothing yet
+        with pytest.raises(YsbError) as e:
+            ctx.submit_raw(raw, slot=1)                                    # its slot's earlier batch first: dropped
+        assert e.value.code == -5 and "block 0" in str(e.value)
+        for call in (ctx.sync, ctx.stats):
+            with pytest.raises(YsbError) as e:
+                call()
+            assert e.value.code == -5 and "block 0" in str(e.value)
+        ctx.reset()
+        ctx.submit_raw(raw, slot=1)
+        check_against(ctx, *exp)
+        ctx.device_free(d_lo)
+
+
 # ---- 5. argument errors --------------------------------------------------------------------
 
 def test_argument_errors():
