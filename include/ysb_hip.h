@@ -587,6 +587,129 @@ typedef struct ysb_lz4_file_header {
 #define YSB_LZ4_FILE_LINE_ALIGNED 1u
 int         ysb_lz4_write_file(const char* path, const uint8_t* src, uint64_t nbytes, uint32_t block_bytes,
                                int line_aligned, int allow_stored, int threads);
+/* ---- standard LZ4 frames (additive within ABI 6) -----------------------------------------
+ * What `lz4 -B4`, liblz4's LZ4F_*, Python's lz4.frame and a Kafka LZ4 codec write: a frame
+ * records only each block's COMPRESSED size, so the directory above cannot be filled without a
+ * pass over the tokens.  Here the host reads one size word per block (ysb_lz4_frame_index) and
+ * the GPU finds the raw sizes (the measure pass) in front of the decode.
+ * ysb_lz4_frame_index walks bytes[0, nbytes), one or more concatenated frames and skippable
+ * frames (magic 0x184D2A50..5F), and fills one entry per data block: `offset` is the block's
+ * first data byte (behind its 4-byte size word), comp_bytes its size | YSB_LZ4_STORED.  Accepted:
+ * magic 04 22 4D 18, version 01, independent blocks, a block maximum of 64 KiB (BD id 4), an
+ * optional content size, block checksums and a content checksum (skipped and reported, never
+ * verified); the header checksum byte is verified.  YSB_ERR_FORMAT, the message naming the byte
+ * offset and the rule, for: another or the legacy magic, another version, reserved bits, a
+ * header checksum mismatch, linked blocks, a dictionary id, a block maximum above 64 KiB, a
+ * block size word above the maximum, a stored block of no bytes, and any truncation (no byte
+ * at or past nbytes is read).  YSB_ERR_CAPACITY with *n_blocks set when cap is short (blocks
+ * may be NULL with cap 0 to count).  info may be NULL.  No context: the message is the
+ * thread's (ysb_last_error(NULL)). */
+typedef struct ysb_lz4_frame_block {
+    uint64_t offset;       /* of the block's first data byte in the indexed buffer */
+    uint32_t comp_bytes;   /* its bytes there (| YSB_LZ4_STORED)                   */
+    uint32_t reserved;     /* 0                                                    */
+} ysb_lz4_frame_block;
+typedef struct ysb_lz4_frame_summary {
+    uint64_t frames;            /* LZ4 frames (skippable ones not counted)       */
+    uint64_t skippable_frames;
+    uint64_t blocks;            /* data blocks of all frames                     */
+    uint64_t stored_blocks;
+    uint64_t comp_bytes;        /* the sum of the blocks' sizes                  */
+    uint64_t content_bytes;     /* the sum of the content sizes that were stated */
+    uint32_t block_checksums;   /* frames with block checksums ...               */
+    uint32_t content_checksums; /* ... with a content checksum ...               */
+    uint32_t content_sizes;     /* ... with a content size                       */
+    uint32_t reserved;
+} ysb_lz4_frame_summary;
+int         ysb_lz4_frame_index(const uint8_t* bytes, uint64_t nbytes, ysb_lz4_frame_block* blocks, uint64_t cap,
+                                uint64_t* n_blocks, ysb_lz4_frame_summary* info);
+/* src[0, nbytes) as ONE standard frame any LZ4 tool reads: independent blocks, 64 KiB block
+ * maximum, no checksums, the content size set; blocks of block_bytes (1..65536; below 65536:
+ * short blocks, valid in a 64 KiB frame) from the library's greedy compressor, a block that did
+ * not shrink stored.  ysb_lz4_frame_pack writes into dst (dst_cap >= ysb_lz4_frame_bound(nbytes,
+ * block_bytes), else YSB_ERR_CAPACITY with *dst_bytes the bound); ysb_lz4_frame_write into a
+ * file.  threads > 1 compresses blocks in parallel (at most 16). */
+uint64_t    ysb_lz4_frame_bound(uint64_t nbytes, uint32_t block_bytes);
+int         ysb_lz4_frame_pack(const uint8_t* src, uint64_t nbytes, uint32_t block_bytes, int threads, uint8_t* dst,
+                               uint64_t dst_cap, uint64_t* dst_bytes);
+int         ysb_lz4_frame_write(const char* path, const uint8_t* src, uint64_t nbytes, uint32_t block_bytes,
+                                int threads);
+/* The host model of the measure pass: the raw size (1..65536) of one frame block src[0, comp)
+ * (comp_field: its index entry's comp_bytes, with the stored bit), found by a walk of its tokens
+ * alone.  YSB_ERR_FORMAT for a block that no raw size makes valid. */
+int         ysb_lz4_measure_block(const uint8_t* src, uint32_t comp_field, uint32_t* raw_bytes);
+/* The carry rule of a stream of frame batches, for a source that feeds decoded batches itself
+ * and for tests: of data[0, n) -- a batch's decoded bytes behind what the batch before left
+ * over -- how many bytes are whole lines; the rest is carried in front of the next batch.  The
+ * cut is behind the last '\n', or behind the last '\r' that is not the buffer's last byte (a
+ * '\r' there may be half of a "\r\n" whose '\n' opens the next batch: the whole last line is
+ * carried).  more == 0 (the stream's last batch): n, the tail is a line as in ysb_submit_raw. */
+uint64_t    ysb_lz4_frame_carry_cut(const uint8_t* data, uint64_t n, int more);
+/* The measure pass alone and measure + decode, device to device (synchronous; test support and
+ * the codec call of another GPU operator).  d_base (device, any alignment) is the buffer the
+ * index entries' offsets refer to; blocks is host memory.
+ * ysb_lz4_measure_device: raw_out[i] (host) <- block i's raw size, 0 for a bad block;
+ * *first_bad the first such block or 0xFFFFFFFF (then YSB_ERR_FORMAT is returned).
+ * ysb_lz4_decode_blocks_device: the blocks' bytes back to back into d_out; *raw_bytes the
+ * measured total (YSB_ERR_CAPACITY, nothing decoded, if above out_cap); a bad block's range --
+ * it has none: its measured size is 0 -- is skipped, the other blocks are decoded, and the call
+ * returns YSB_ERR_FORMAT with *first_bad set. */
+int         ysb_lz4_measure_device(ysb_ctx* ctx, const uint8_t* d_base, const ysb_lz4_frame_block* blocks,
+                                   uint32_t n_blocks, uint32_t* raw_out, uint32_t* first_bad);
+int         ysb_lz4_decode_blocks_device(ysb_ctx* ctx, const uint8_t* d_base, const ysb_lz4_frame_block* blocks,
+                                         uint32_t n_blocks, uint8_t* d_out, uint64_t out_cap, uint64_t* raw_bytes,
+                                         uint32_t* first_bad);
+/* A frame batch through a slot -- ysb_submit_raw_lz4 for a standard frame: blocks[0, n_blocks) is
+ * a run of consecutive entries of ysb_lz4_frame_index over `base` (host memory).  The span from
+ * the first block's data to the last block's end (size and checksum words between them included)
+ * goes through the slot's pinned buffer, or (_mapped) is read in place from a registered range
+ * (ysb_host_register; the span widened to 16-byte boundaries must lie inside one).  On the
+ * split's stream behind the slot's copy: the measure pass, the descriptors, the decode, the
+ * carry, the line split (its byte count read from device memory); the scan launches at the
+ * next call that orders work, as for every raw batch.  Frame blocks end mid-line: with
+ * YSB_LZ4F_MORE in flags the bytes behind the batch's last certain line terminator
+ * (ysb_lz4_frame_carry_cut's rule) are no line but are kept on the device (at most 64 KiB) and
+ * put in front of the next frame batch; without it the tail is a line, as in ysb_submit_raw.
+ * YSB_ERR_CAPACITY unless the span and (n_blocks + 1) x 65536 are both <= max_batch_bytes;
+ * YSB_ERR_ARG for entries that are not consecutive or not 1..65536 bytes, unknown flags, a span
+ * outside a registered range.  A batch with a bad block is dropped whole (sticky
+ * YSB_ERR_FORMAT naming the block), as is one that leaves more than 64 KiB behind its last
+ * terminator (sticky YSB_ERR_CAPACITY); the carry is emptied then and by ysb_reset.  While a
+ * carry is pending (the last frame batch queued had YSB_LZ4F_MORE) every other submit -- lines,
+ * compressed batches, device batches, column batches -- returns YSB_ERR_STATE.  The layout sample is block 0 decoded by the host model; counts never depend
+ * on it.  ysb_lz4_frame_info reports the last frame batch settled. */
+#define YSB_LZ4F_MORE 1u
+int         ysb_submit_lz4_blocks(ysb_ctx* ctx, int slot, const uint8_t* base, const ysb_lz4_frame_block* blocks,
+                                  uint32_t n_blocks, uint32_t flags);
+int         ysb_submit_lz4_blocks_mapped(ysb_ctx* ctx, int slot, const uint8_t* base,
+                                         const ysb_lz4_frame_block* blocks, uint32_t n_blocks, uint32_t flags);
+/* Which decode kernel the context's LZ4 calls launch: 0 by the batch's largest block (the
+ * default: one wave per block up to 16 KiB of raw bytes, the several-wave kernel above),
+ * 1 always the one-wave kernel, 2 always the several-wave kernel.  Results never depend on it;
+ * tests and tools/bench_lz4.py run both on every shape. */
+#define YSB_LZ4_DECODER_AUTO   0
+#define YSB_LZ4_DECODER_NARROW 1
+#define YSB_LZ4_DECODER_WIDE   2
+int         ysb_lz4_set_decoder(ysb_ctx* ctx, int decoder);
+/* The last synchronous call above, or the last frame batch settled (read-only measurement and
+ * test support).  Waits for everything submitted. */
+typedef struct ysb_lz4_frame_desc {
+    uint64_t blocks;
+    uint64_t stored_blocks;
+    uint64_t comp_bytes;
+    uint64_t raw_bytes;      /* the measured total                                  */
+    uint64_t bad_blocks;
+    uint64_t first_bad;      /* 0xFFFFFFFF: none                                    */
+    uint64_t decoder;        /* YSB_LZ4_DECODER_NARROW / _WIDE: which ran (0: none) */
+    uint64_t batches;        /* frame batches settled since ysb_open / ysb_reset    */
+    uint64_t carry_in;       /* a frame batch: bytes carried in front of it ...     */
+    uint64_t carry_out;      /* ... and behind its last certain line terminator     */
+    double   measure_ms;     /* YSB_F_TIMING: HIP events around the measure and
+                                descriptor kernels ...                              */
+    double   decode_ms;      /* ... and around the decode kernel                    */
+} ysb_lz4_frame_desc;
+int         ysb_lz4_frame_info(ysb_ctx* ctx, ysb_lz4_frame_desc* info);
+uint64_t    ysb_lz4_frame_desc_size(void);   /* sizeof(ysb_lz4_frame_desc) */
 /* Device-resident batch (HBM pointers, e.g. from ysb_device_alloc). Asynchronous.  The batch
  * must be complete when submitted, or its producer ordered before the compute stream
  * (hipStreamWaitEvent(ysb_stream(ctx), ...), or produced on that stream).  Unless

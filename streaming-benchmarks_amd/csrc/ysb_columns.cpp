@@ -175,6 +175,7 @@ static int enqueue_colcount(ysb_ctx* c, const u8* d_cols, const ysb_columns_layo
 
 int ysb_submit_columns_device(ysb_ctx* c, const uint8_t* d_cols, uint64_t batch_rows, uint64_t n_rows, uint32_t flags) {
     if (!c) return YSB_ERR_ARG;
+    if (int g = carry_guard(c)) return g;
     ysb_columns_layout lay;
     u64 total = 0;
     if (reinterpret_cast<uintptr_t>(d_cols) & 15) return fail(c, YSB_ERR_ARG, "d_cols must be 16-byte aligned");
@@ -189,6 +190,7 @@ int ysb_submit_columns(ysb_ctx* c, int slot, const uint8_t* image, uint64_t batc
                        uint32_t flags) {
     if (!c) return YSB_ERR_ARG;
     if (int rc = slot_arg(c, slot)) return rc;
+    if (int g = carry_guard(c)) return g;
     ysb_columns_layout lay;
     u64 total = 0;
     int rc = colcount_args(c, image, batch_rows, n_rows, flags, &lay, &total);

@@ -13,6 +13,8 @@
 //   ysb_lz4_api.cpp LZ4 batches: the directory's checks, the decode's staging, the host codec entries
 //   ysb_lz4.h       their format, its one sequence reader and the host model (no HIP:
 //                   tests/native/lz4_logic.cpp)
+//   ysb_lz4_frame.h standard LZ4 frames: the index, XXH32, the writer, the measure model and the carry
+//                   rule (no HIP: tests/native/lz4_frame_logic.cpp)
 //   ysb_group.cpp   multi-GPU: the RCCL / host-collective group and the keyBy exchange
 //   ysb_gen_api.cpp the synthetic generator (host and device) and its truth tables
 // Internal: nothing here is part of the ABI (the shared helpers have hidden visibility).
@@ -152,6 +154,10 @@ struct Lz4Staged {
     const u8* dsrc = nullptr;
     ysb_lz4_desc info{};
     u32 max_raw = 0;
+    u64 span = 0;                        // a frame batch's bytes: first block's data .. last block's end
+    u32 decoder = 0;                     // a frame batch: the decode kernel chosen when it was staged
+    bool frame = false;                  // a frame batch (ysb_submit_lz4_blocks): sizes measured on the device
+    bool more = false;                   // ... with YSB_LZ4F_MORE: its tail is carried
 };
 
 // A slot's batch between its submit and its launch one call later (ysb_raw.cpp).  Every submit
@@ -257,7 +263,22 @@ struct ysb_ctx {
     PinBuf<u32> h_lz4bad;
     ysb_lz4_desc lz4_last{};
     Event ev_lz4[2][2];
+    Event ev_lz4m[2];                           // a frame batch: in front of its measure pass (YSB_F_TIMING)
     DevBuf<u8> d_lz4desc_sync;                  // ysb_lz4_decode_device's descriptors
+    // standard frames (ysb_lz4_frame.h): the synchronous calls' device scratch -- {first bad, bad
+    // blocks, raw total (u64)}, the index entries, the measured sizes, the descriptors --, the
+    // last call's figures, and which decode kernel the context's LZ4 calls launch
+    DevBuf<u8> d_lz4f_sync;
+    ysb_lz4_frame_desc lz4f_last{};
+    u32 lz4_decoder = 0;                        // YSB_LZ4_DECODER_*
+    // frame batches through the slots (ysb_submit_lz4_blocks): per slot the descriptors and
+    // measured sizes (the index entries and the batch's Lz4FrameHead travel in d_lz4desc[slot]),
+    // the head read back to pinned memory behind the split (h_lz4f[slot]), the carry between
+    // batches (Lz4 CARRY_HEAD bytes of length, then the bytes) and whether one is pending
+    DevBuf<u8> d_lz4f[2];
+    PinBuf<Lz4FrameHead> h_lz4f;
+    DevBuf<u8> d_carry;
+    bool lz4f_more = false;
     // counts
     u32 c_pad = 0;                        // campaigns padded to the group size
     DevBuf<unsigned long long> d_counts;      // [c_pad][W]
@@ -465,6 +486,21 @@ YSB_INTERNAL int lz4_enqueue_decode(ysb_ctx* c, int slot, const Lz4Staged& b, hi
 // at the batch's launch (its decode is complete): lz4_last <- its figures; YSB_ERR_FORMAT, the
 // message naming the first bad block, if it had one
 YSB_INTERNAL int lz4_settle(ysb_ctx* c, int slot, const Lz4Staged& b);
+// a frame batch staged (ysb_submit_lz4_blocks): the span from the first block's data to the last
+// block's end into the slot's pinned buffer (dsrc: read in place), the rebased index entries and
+// the batch's head into the pinned descriptor buffer; batch->nbytes the bound (n_blocks + 1) x
+// 65536; *sample block 0 decoded by the host model, from behind its first terminator when a
+// carry is pending
+YSB_INTERNAL int lz4f_stage(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_block* blocks, uint32_t n_blocks,
+                            uint32_t flags, const uint8_t* dsrc, RawBatch* batch, std::vector<u8>* sample);
+// where the split reads a frame batch's byte count, and the head's read-back behind the split
+YSB_INTERNAL const u64* lz4f_nbytes(ysb_ctx* c, int slot);
+YSB_INTERNAL int lz4f_readback(ysb_ctx* c, int slot, hipStream_t s);
+// any submit that is not a frame batch while a carry is pending
+inline int carry_guard(ysb_ctx* c) {
+    return c->lz4f_more ? fail(c, YSB_ERR_STATE, "a frame batch left a carry (YSB_LZ4F_MORE): only ysb_submit_lz4_blocks "
+                                                 "may follow, until one without the flag or ysb_reset") : YSB_OK;
+}
 // ysb_group.cpp
 YSB_INTERNAL bool grouped(const ysb_ctx* c);
 YSB_INTERNAL int agree_ring(ysb_ctx* c);

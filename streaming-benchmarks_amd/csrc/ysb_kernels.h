@@ -213,8 +213,10 @@ void launch_h2d_copy(void* dst, const void* src, u64 bytes, int wgs, hipStream_t
 // the same from a device-visible host address at any byte alignment (reads up to 31 bytes
 // past src + bytes, from the 16-byte boundary below src)
 void launch_h2d_copy_unaligned(void* dst, const void* src, u64 bytes, int wgs, hipStream_t s);
+// (d_nbytes: the byte count in device memory -- nbytes is then the bound the grid is sized
+// for --, or NULL: nbytes itself, the path of every batch whose size the host knows)
 hipError_t launch_split_lines(const u8* b, u64 nbytes, u32* chunk, u32* off, u64 cap, unsigned long long* d_n,
-                              hipStream_t s);
+                              hipStream_t s, const u64* d_nbytes = nullptr);
 // The replay's event-time rebasing (ysb_split.hip, ysb_submit_raw_mapped): for the first
 // min(*d_n, tab_n, cap) lines of a split raw batch (starts off[0..cap)), the nine digits at line
 // start + (tab[i] & 0xFFFF) <- lead + (tab[i] >> 16), zero-padded; writes stay inside [0, nbytes).
@@ -376,8 +378,45 @@ struct Lz4Params {
     u32 max_raw;                // the largest raw of the batch (sizes the LDS window)
     u8* out;                    // block i's bytes go to out[desc[i].out_off, + raw)
     u32* bad;                   // [2]: {first bad block (LZ4_NO_BAD before), bad blocks (0 before)}
+    u32 decoder;                // YSB_LZ4_DECODER_*: 0 picks the kernel by max_raw (lz4_pick_decoder)
 };
 // Every block decoded (a bad block writes nothing and is recorded in bad[]).  Asynchronous on s.
+// One wave per block (lz4_decode_kernel) or four (lz4_decode_wide_kernel), by p.decoder.
 hipError_t launch_lz4_decode(const Lz4Params& p, hipStream_t s);
+
+// Standard frames (ysb_lz4_frame.h): the blocks' raw sizes are found on the GPU.  An index
+// entry as the kernels read it (ysb_lz4_frame_block's layout).
+struct Lz4FrameBlock {
+    u64 offset;
+    u32 comp, reserved;
+};
+// raw[i] <- block i's raw size by a walk of its tokens alone (no copies), 0 for a bad block.
+// One wave per block, four blocks per workgroup.  Asynchronous on s.
+hipError_t launch_lz4_measure(const u8* base, const Lz4FrameBlock* blocks, u32 n_blocks, u32* raw, hipStream_t s);
+// desc[i] <- {blocks[i].offset, carry + the raw sizes before it, blocks[i].comp, raw[i]};
+// *total <- the sum of the raw sizes.  One workgroup.  Asynchronous on s.
+// (d_carry: the carry length in device memory, or NULL: `carry`)
+hipError_t launch_lz4_frame_descs(const Lz4FrameBlock* blocks, const u32* raw, u32 n_blocks, u64 carry, Lz4Desc* desc,
+                                  u64* total, hipStream_t s, const u64* d_carry = nullptr);
+
+// A frame batch's device state (ysb_submit_lz4_blocks): what its kernels leave for the host,
+// read back in one copy behind the split.
+struct Lz4FrameHead {
+    u32 bad[2];        // first bad block (LZ4_NO_BAD), bad blocks
+    u64 raw_total;     // the measured sizes' sum
+    u64 nbytes;        // whole lines in the slot's buffer: carry in + raw_total - carry out (0: dropped)
+    u32 carry_in, carry_out;
+    u32 overflow;      // the bytes behind the last certain terminator exceed LZ4_CARRY_MAX
+    u32 pad;
+};
+constexpr u32 LZ4_CARRY_MAX = 65536;
+// The context's carry: a u64 length and 8 spare bytes in front of LZ4_CARRY_MAX bytes.
+constexpr u32 LZ4_CARRY_HEAD = 16;
+// Behind the decode of a frame batch into out (block 0 at the carry's length): the carry of the
+// batch before copied in front; with `more` the bytes behind the last certain line terminator
+// (ysb_lz4_frame.h lz4f_carry_cut's rule) moved to the carry, else the carry emptied; head's
+// nbytes / carry_in / carry_out / overflow written.  A batch with a bad block or an overflow is
+// dropped: nbytes 0, the carry emptied.  One workgroup.  Asynchronous on s.
+hipError_t launch_lz4_frame_carry(u8* out, u8* carry, Lz4FrameHead* head, u32 more, hipStream_t s);
 
 }  // namespace ysb

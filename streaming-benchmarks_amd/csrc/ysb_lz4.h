@@ -61,8 +61,11 @@ YSB_HD bool lz4_read_ext(In& in, u32& ip, u32 comp, u32& len, u32 cap) {
 // It reads input only and copies nothing, so a caller copies exactly what it returns.  Every
 // call consumes at least the token, so a walk over `comp` bytes ends.  In::byte(pos) is called
 // with pos < comp only.
+// measure (a frame's block, whose raw size nothing records: ysb_lz4_frame.h): `raw` is the cap
+// (LZ4_MAX_RAW), not the size, and the end rule is ip == comp alone -- LAST then tells that the
+// block decodes to op + lit_len bytes.  Every other rule is the same.
 template <class In>
-YSB_HD u32 lz4_read_seq(In& in, u32 ip, u32 comp, u32 op, u32 raw, Lz4Seq* s) {
+YSB_HD u32 lz4_read_seq(In& in, u32 ip, u32 comp, u32 op, u32 raw, Lz4Seq* s, bool measure = false) {
     if (ip >= comp) return LZ4_SEQ_BAD;
     const u32 tok = in.byte(ip++);
     u32 lit = tok >> 4;
@@ -74,7 +77,7 @@ YSB_HD u32 lz4_read_seq(In& in, u32 ip, u32 comp, u32 op, u32 raw, Lz4Seq* s) {
     op += lit;
     s->offset = s->match_len = 0;
     s->next = ip;
-    if (ip == comp) return op == raw ? LZ4_SEQ_LAST : LZ4_SEQ_BAD;
+    if (ip == comp) return (measure || op == raw) ? LZ4_SEQ_LAST : LZ4_SEQ_BAD;
     if (comp - ip < 2) return LZ4_SEQ_BAD;
     const u32 off = in.byte(ip) | (in.byte(ip + 1) << 8);
     ip += 2;
@@ -111,6 +114,24 @@ YSB_HD u32 lz4_window(u32 raw) { return raw + lz4_margin(raw); }
 // LDS bytes of a launch whose largest block decodes to max_raw bytes: 16 in front (the output
 // starts at its global address mod 16) and 16 behind (so does the input), a multiple of 16.
 YSB_HD u32 lz4_lds_bytes(u32 max_raw) { return (32 + lz4_window(max_raw) + 15) & ~15u; }
+
+// ---- the several-wave kernel's LDS geometry (lz4_decode_wide_kernel) ----------------------
+// The output block alone lies in LDS (16 bytes in front: it starts at its global address mod
+// 16; the compressed bytes are streamed from global memory), behind it three buffers of
+// LZ4W_BATCH sequence records (one is parsed while the one before has its literals copied and
+// the one before that its matches) and nine control words.
+constexpr u32 LZ4W_BATCH = 64;       // sequences per stage: one record per lane of a wave
+constexpr u32 LZ4W_FIELDS = 5;       // literal position, literal length, output position, offset, match length
+YSB_HD u32 lz4_wide_out_bytes(u32 max_raw) { return (32 + max_raw + 15) & ~15u; }
+YSB_HD u32 lz4_wide_lds_bytes(u32 max_raw) { return lz4_wide_out_bytes(max_raw) + 3 * LZ4W_FIELDS * LZ4W_BATCH * 4 + 48; }
+// launch_lz4_decode's choice when the context leaves it open (YSB_LZ4_DECODER_AUTO): the
+// several-wave kernel for a batch whose largest block is above this many raw bytes (measured:
+// DESIGN.md, LZ4 batches, "crossover").
+constexpr u32 LZ4_WIDE_ABOVE = 16384;
+YSB_HD u32 lz4_pick_decoder(u32 max_raw, u32 decoder) {
+    if (decoder == YSB_LZ4_DECODER_NARROW || decoder == YSB_LZ4_DECODER_WIDE) return decoder;
+    return max_raw > LZ4_WIDE_ABOVE ? (u32)YSB_LZ4_DECODER_WIDE : (u32)YSB_LZ4_DECODER_NARROW;
+}
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 

@@ -3,12 +3,16 @@
 // registered range, block descriptors in pinned memory, one copy each), the decode's one launch
 // and read-back (launch_decode), the synchronous decode alone, the last batch's figures, and the
 // host codec entries.  ysb_submit_raw_lz4 and ysb_submit_lz4_mapped sit beside ysb_submit_raw in
-// ysb_raw.cpp.
+// ysb_raw.cpp.  Standard frames (ysb_lz4_frame.h): the index, the writer and the host models as C
+// entries, and the synchronous measure and measure + decode.
 #include "ysb_ctx.h"
 #include "ysb_lz4.h"
+#include "ysb_lz4_frame.h"
 
 using namespace ysb;
 
+constexpr u64 LZ4F_HEAD = sizeof(Lz4FrameHead);   // a frame batch's head in front of its index entries
+static_assert(LZ4F_HEAD % 8 == 0, "the index entries behind the head hold 64-bit offsets");
 constexpr u64 LZ4_DESC_HEAD = 16;   // {first bad, bad blocks, 0, 0} in front of the descriptors
 
 // the directory as argument errors (the same for both entry points)
@@ -65,7 +69,7 @@ static int launch_decode(ysb_ctx* c, const u8* d_comp, u8* d_descs, u32 n_blocks
         HIPCHK(c, hipEventRecord(ev[0], s));
     }
     u32* bad = reinterpret_cast<u32*>(d_descs);
-    const Lz4Params lp{d_comp, reinterpret_cast<const Lz4Desc*>(d_descs + LZ4_DESC_HEAD), n_blocks, max_raw, d_out, bad};
+    const Lz4Params lp{d_comp, reinterpret_cast<const Lz4Desc*>(d_descs + LZ4_DESC_HEAD), n_blocks, max_raw, d_out, bad, c->lz4_decoder};
     HIPCHK(c, launch_lz4_decode(lp, s));
     if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
     HIPCHK(c, hipMemcpyAsync(h_bad, bad, 8, hipMemcpyDeviceToHost, s));
@@ -112,12 +116,166 @@ int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, c
 }
 
 void lz4_copies(ysb_ctx* c, int slot, const Lz4Staged& b, SlotCopy v[2]) {
+    if (b.frame) {
+        v[0] = {c->d_lz4[slot], b.dsrc, b.hsrc, b.span};
+        v[1] = {c->d_lz4desc[slot], c->hd_lz4desc[slot], c->h_lz4desc[slot], LZ4F_HEAD + b.info.blocks * sizeof(Lz4FrameBlock)};
+        return;
+    }
     v[0] = {c->d_lz4[slot], b.dsrc, b.hsrc, b.info.comp_bytes};
     v[1] = {c->d_lz4desc[slot], c->hd_lz4desc[slot], c->h_lz4desc[slot],
             b.info.blocks ? LZ4_DESC_HEAD + b.info.blocks * sizeof(Lz4Desc) : 0};
 }
 
+// The descriptors' pinned / device buffers of a slot grown to `need` bytes (outside steady
+// state: a batch with more blocks than any before).
+static int grow_descs(ysb_ctx* c, int slot, u64 need) {
+    if (need <= c->lz4desc_cap[slot]) return YSB_OK;
+    const u64 cap = std::max<u64>(need + need / 2, 64u << 10);
+    if (int rc = grow_device(c, c->d_lz4desc[slot], cap + 64, 0)) return rc;
+    HIPCHK(c, c->h_lz4desc[slot].alloc(cap + 64));
+    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hd_lz4desc[slot]), c->h_lz4desc[slot], 0));
+    c->lz4desc_cap[slot] = cap;
+    return YSB_OK;
+}
+
+// ---- frame batches through the slots (ysb_submit_lz4_blocks) ----------------------------------
+// d_lz4desc[slot]: the batch's Lz4FrameHead, then its index entries (offsets from the span's
+// start); d_lz4f[slot]: the descriptors, then the measured sizes.
+
+int lz4f_stage(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_block* blocks, uint32_t n, uint32_t flags,
+               const uint8_t* dsrc, RawBatch* batch, std::vector<u8>* sample) {
+    if (n && (!base || !blocks)) return fail(c, YSB_ERR_ARG, "NULL frame buffers");
+    if (flags & ~YSB_LZ4F_MORE) return fail(c, YSB_ERR_ARG, "unknown flags %#x", flags);
+    ysb_lz4_desc info{};
+    info.blocks = n;
+    info.first_bad = LZ4_NO_BAD;
+    for (u32 i = 0; i < n; ++i) {
+        const u32 comp = blocks[i].comp_bytes & ~LZ4_STORED;
+        if (comp < 1 || comp > LZ4F_BLOCK_MAX)
+            return fail(c, YSB_ERR_ARG, "frame block %u: %u bytes, not in 1..%u", i, comp, LZ4F_BLOCK_MAX);
+        if (i && blocks[i].offset < blocks[i - 1].offset + (blocks[i - 1].comp_bytes & ~LZ4_STORED) + 4)
+            return fail(c, YSB_ERR_ARG, "frame block %u does not lie behind block %u: a batch is a run of consecutive index entries", i, i - 1);
+        info.stored_blocks += (blocks[i].comp_bytes & LZ4_STORED) ? 1 : 0;
+        info.comp_bytes += comp;
+    }
+    const u64 first = n ? blocks[0].offset : 0;
+    const u64 span = n ? blocks[n - 1].offset + (blocks[n - 1].comp_bytes & ~LZ4_STORED) - first : 0;
+    const u64 bound = ((u64)n + 1) * LZ4_MAX_RAW;
+    if (span > c->cfg.max_batch_bytes || bound > c->cfg.max_batch_bytes)
+        return fail(c, YSB_ERR_CAPACITY, "frame batch of %u blocks (%llu B; up to %llu B decoded with the carry) exceeds max_batch_bytes",
+                    n, (unsigned long long)span, (unsigned long long)bound);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_lz4[slot]) HIPCHK(c, c->d_lz4[slot].alloc(c->cfg.max_batch_bytes + 64));
+    if (!c->h_lz4f) {
+        HIPCHK(c, c->h_lz4f.alloc(2 * LZ4F_HEAD));
+        std::memset(c->h_lz4f.get(), 0, 2 * LZ4F_HEAD);
+    }
+    if (!c->d_carry) {
+        HIPCHK(c, c->d_carry.alloc(LZ4_CARRY_HEAD + LZ4_CARRY_MAX));
+        HIPCHK(c, hipMemset(c->d_carry, 0, LZ4_CARRY_HEAD));
+    }
+    int rc = grow_descs(c, slot, LZ4F_HEAD + (u64)n * sizeof(Lz4FrameBlock));
+    if (!rc) rc = grow_device(c, c->d_lz4f[slot], (u64)n * (sizeof(Lz4Desc) + 4) + 64, 64u << 10);
+    if (rc) return rc;
+    const u8* src = n ? base + first : nullptr;
+    if (!dsrc && span && src != c->h_bytes[slot]) std::memcpy(c->h_bytes[slot], src, span);
+    Lz4FrameHead head{};
+    head.bad[0] = LZ4_NO_BAD;
+    std::memcpy(c->h_lz4desc[slot], &head, LZ4F_HEAD);
+    for (u32 i = 0; i < n; ++i) {
+        const Lz4FrameBlock e{blocks[i].offset - first, blocks[i].comp_bytes, 0};
+        std::memcpy(c->h_lz4desc[slot] + LZ4F_HEAD + (u64)i * sizeof e, &e, sizeof e);
+    }
+    batch->nbytes = bound;
+    Lz4Staged* out = &batch->lz4.emplace();
+    out->hsrc = dsrc ? src : c->h_bytes[slot].get();
+    out->dsrc = dsrc ? dsrc : c->hd_bytes[slot];
+    out->info = info;
+    out->max_raw = LZ4_MAX_RAW;
+    out->frame = true;
+    out->decoder = lz4_pick_decoder(LZ4_MAX_RAW, c->lz4_decoder);
+    out->span = span;
+    out->more = (flags & YSB_LZ4F_MORE) != 0;
+    // the layout sample: block 0 as the host model measures and decodes it, from behind its
+    // first terminator when the batch before left a carry (its head is the tail of a line)
+    sample->clear();
+    if (n) {
+        const u32 raw = lz4_measure_block(out->hsrc, blocks[0].comp_bytes);
+        sample->resize(raw);
+        if (raw && !lz4_decode_block(out->hsrc, ysb_lz4_block{blocks[0].comp_bytes, raw}, sample->data())) sample->clear();
+        if (c->lz4f_more && !sample->empty()) {
+            size_t k = 0;
+            while (k < sample->size() && (*sample)[k] != '\n' && (*sample)[k] != '\r') ++k;
+            sample->erase(sample->begin(), sample->begin() + std::min(sample->size(), k + 1));
+        }
+    }
+    return YSB_OK;
+}
+
+const u64* lz4f_nbytes(ysb_ctx* c, int slot) {
+    return &reinterpret_cast<const Lz4FrameHead*>(c->d_lz4desc[slot].get())->nbytes;
+}
+
+int lz4f_readback(ysb_ctx* c, int slot, hipStream_t s) {
+    HIPCHK(c, hipMemcpyAsync(c->h_lz4f + slot, c->d_lz4desc[slot], LZ4F_HEAD, hipMemcpyDeviceToHost, s));
+    return YSB_OK;
+}
+
+// measure, descriptors, decode behind the carry's length, carry in and out: on s behind the slot's copies
+static int lz4f_enqueue(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s) {
+    const u32 n = (u32)b.info.blocks;
+    Lz4FrameHead* head = reinterpret_cast<Lz4FrameHead*>(c->d_lz4desc[slot].get());
+    const Lz4FrameBlock* blocks = reinterpret_cast<const Lz4FrameBlock*>(c->d_lz4desc[slot] + LZ4F_HEAD);
+    Lz4Desc* desc = reinterpret_cast<Lz4Desc*>(c->d_lz4f[slot].get());
+    u32* raw = reinterpret_cast<u32*>(c->d_lz4f[slot] + (u64)n * sizeof(Lz4Desc));
+    Event* ev = (c->cfg.flags & YSB_F_TIMING) ? c->ev_lz4[slot] : nullptr;
+    if (ev) {   // three events: measure + descriptors between the first two, the decode between the last two
+        if (!c->ev_lz4m[slot]) HIPCHK(c, c->ev_lz4m[slot].create(hipEventDefault));
+        for (int k = 0; k < 2; ++k)
+            if (!ev[k]) HIPCHK(c, ev[k].create(hipEventDefault));
+        HIPCHK(c, hipEventRecord(c->ev_lz4m[slot], s));
+    }
+    HIPCHK(c, launch_lz4_measure(c->d_lz4[slot], blocks, n, raw, s));
+    HIPCHK(c, launch_lz4_frame_descs(blocks, raw, n, 0, desc, &head->raw_total, s, reinterpret_cast<const u64*>(c->d_carry.get())));
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], s));
+    const Lz4Params lp{c->d_lz4[slot], desc, n, LZ4_MAX_RAW, c->d_bytes[slot], head->bad, b.decoder};
+    HIPCHK(c, launch_lz4_decode(lp, s));
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, launch_lz4_frame_carry(c->d_bytes[slot], c->d_carry, head, b.more ? 1u : 0u, s));
+    return YSB_OK;
+}
+
+// at a frame batch's launch: lz4f_last <- its figures; a bad block or a carry above 64 KiB drops it
+static int lz4f_settle(ysb_ctx* c, int slot, const Lz4Staged& b) {
+    const Lz4FrameHead h = c->h_lz4f[slot];
+    ysb_lz4_frame_desc d{};
+    d.blocks = b.info.blocks;
+    d.stored_blocks = b.info.stored_blocks;
+    d.comp_bytes = b.info.comp_bytes;
+    d.raw_bytes = h.raw_total;
+    d.bad_blocks = h.bad[1];
+    d.first_bad = h.bad[0];
+    d.decoder = d.blocks ? b.decoder : 0;
+    d.carry_in = h.carry_in;
+    d.carry_out = h.carry_out;
+    d.batches = c->lz4f_last.batches + 1;
+    float ms = 0;
+    if (c->cfg.flags & YSB_F_TIMING) {
+        if (hipEventElapsedTime(&ms, c->ev_lz4m[slot], c->ev_lz4[slot][0]) == hipSuccess) d.measure_ms = ms;
+        if (hipEventElapsedTime(&ms, c->ev_lz4[slot][0], c->ev_lz4[slot][1]) == hipSuccess) d.decode_ms = ms;
+    }
+    c->lz4f_last = d;
+    if (h.bad[1])
+        return fail(c, YSB_ERR_FORMAT, "frame batch (slot %d): block %u of %llu breaks the block format (%u bad in all); "
+                    "the batch was dropped", slot, h.bad[0], (unsigned long long)d.blocks, h.bad[1]);
+    if (h.overflow)
+        return fail(c, YSB_ERR_CAPACITY, "frame batch (slot %d): more than %u bytes behind its last line terminator; "
+                    "the batch was dropped", slot, LZ4_CARRY_MAX);
+    return YSB_OK;
+}
+
 int lz4_enqueue_decode(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s) {
+    if (b.frame) return lz4f_enqueue(c, slot, b, s);
     c->h_lz4bad[2 * slot] = LZ4_NO_BAD;
     c->h_lz4bad[2 * slot + 1] = 0;
     if (!b.info.blocks) return YSB_OK;
@@ -127,6 +285,7 @@ int lz4_enqueue_decode(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s) 
 }
 
 int lz4_settle(ysb_ctx* c, int slot, const Lz4Staged& b) {
+    if (b.frame) return lz4f_settle(c, slot, b);
     ysb_lz4_desc d = b.info;
     d.batches = c->lz4_last.batches + 1;
     d.first_bad = c->h_lz4bad[2 * slot];
@@ -272,5 +431,215 @@ int ysb_lz4_write_file(const char* path, const uint8_t* src, uint64_t nbytes, ui
     ok = (std::fclose(f) == 0) && ok;
     return ok ? YSB_OK : fail(nullptr, YSB_ERR_ARG, "short write to %s", path);
 }
+
+// ---- standard frames ------------------------------------------------------------------------
+
+static_assert(sizeof(Lz4FrameBlock) == sizeof(ysb_lz4_frame_block) && offsetof(Lz4FrameBlock, comp) == offsetof(ysb_lz4_frame_block, comp_bytes),
+              "the kernels read the public index entry");
+
+int ysb_lz4_frame_index(const uint8_t* bytes, uint64_t nbytes, ysb_lz4_frame_block* blocks, uint64_t cap,
+                        uint64_t* n_blocks, ysb_lz4_frame_summary* info) {
+    if (nbytes && !bytes) return fail(nullptr, YSB_ERR_ARG, "ysb_lz4_frame_index: NULL buffer");
+    Lz4fError err;
+    const int rc = lz4f_index(bytes, nbytes, blocks, blocks ? cap : 0, n_blocks, info, &err);
+    return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
+}
+
+uint64_t ysb_lz4_frame_bound(uint64_t nbytes, uint32_t block_bytes) { return lz4f_bound(nbytes, block_bytes); }
+
+int ysb_lz4_frame_pack(const uint8_t* src, uint64_t nbytes, uint32_t block_bytes, int threads, uint8_t* dst,
+                       uint64_t dst_cap, uint64_t* dst_bytes) {
+    if ((nbytes && !src) || !dst_bytes || block_bytes < 1 || block_bytes > LZ4_MAX_RAW)
+        return fail(nullptr, YSB_ERR_ARG, "ysb_lz4_frame_pack: NULL argument or block_bytes not in 1..65536");
+    *dst_bytes = lz4f_bound(nbytes, block_bytes);
+    if (*dst_bytes > dst_cap || !dst)
+        return fail(nullptr, YSB_ERR_CAPACITY, "ysb_lz4_frame_pack: needs %llu bytes", (unsigned long long)*dst_bytes);
+    *dst_bytes = lz4f_pack(src, nbytes, block_bytes, threads, dst);
+    return YSB_OK;
+}
+
+int ysb_lz4_frame_write(const char* path, const uint8_t* src, uint64_t nbytes, uint32_t block_bytes, int threads) {
+    if (!path) return fail(nullptr, YSB_ERR_ARG, "ysb_lz4_frame_write: NULL path");
+    if ((nbytes && !src) || block_bytes < 1 || block_bytes > LZ4_MAX_RAW)
+        return fail(nullptr, YSB_ERR_ARG, "ysb_lz4_frame_write: NULL source or block_bytes not in 1..65536");
+    std::vector<u8> blob(lz4f_bound(nbytes, block_bytes));
+    const u64 n = lz4f_pack(src, nbytes, block_bytes, threads, blob.data());
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return fail(nullptr, YSB_ERR_ARG, "cannot write %s", path);
+    bool ok = std::fwrite(blob.data(), 1, n, f) == n;
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? YSB_OK : fail(nullptr, YSB_ERR_ARG, "short write to %s", path);
+}
+
+int ysb_lz4_measure_block(const uint8_t* src, uint32_t comp_field, uint32_t* raw_bytes) {
+    if (!src || !raw_bytes) return fail(nullptr, YSB_ERR_ARG, "ysb_lz4_measure_block: NULL argument");
+    *raw_bytes = lz4_measure_block(src, comp_field);
+    return *raw_bytes ? YSB_OK : fail(nullptr, YSB_ERR_FORMAT, "the block breaks the LZ4 block format");
+}
+
+uint64_t ysb_lz4_frame_carry_cut(const uint8_t* data, uint64_t n, int more) { return data ? lz4f_carry_cut(data, n, more != 0) : 0; }
+
+int ysb_lz4_set_decoder(ysb_ctx* c, int decoder) {
+    if (!c) return YSB_ERR_ARG;
+    if (decoder < YSB_LZ4_DECODER_AUTO || decoder > YSB_LZ4_DECODER_WIDE)
+        return fail(c, YSB_ERR_ARG, "decoder must be 0 (auto), 1 (one wave per block) or 2 (several waves)");
+    c->lz4_decoder = (u32)decoder;
+    return YSB_OK;
+}
+
+// The synchronous calls' device scratch (d_lz4f_sync): a 16-byte head {first bad, bad blocks,
+// raw total (u64)}, then the index entries, the descriptors and the measured sizes.
+struct FrameScratch {
+    u32* bad;
+    u64* total;
+    Lz4FrameBlock* blocks;
+    Lz4Desc* desc;
+    u32* raw;
+};
+// The synchronous calls copy to and from the caller's pageable memory and their own stack: no
+// return, an error's included, leaves such a copy pending.
+struct SyncOnExit {
+    hipStream_t s;
+    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+static int frame_scratch(ysb_ctx* c, const ysb_lz4_frame_block* blocks, u32 n, FrameScratch* fs) {
+    const u64 need = 16 + (u64)n * (sizeof(Lz4FrameBlock) + sizeof(Lz4Desc) + 4);
+    int rc = grow_device(c, c->d_lz4f_sync, need, 64u << 10);
+    if (rc) return rc;
+    u8* p = c->d_lz4f_sync;
+    fs->bad = reinterpret_cast<u32*>(p);
+    fs->total = reinterpret_cast<u64*>(p + 8);
+    fs->blocks = reinterpret_cast<Lz4FrameBlock*>(p + 16);
+    fs->desc = reinterpret_cast<Lz4Desc*>(p + 16 + (u64)n * sizeof(Lz4FrameBlock));
+    fs->raw = reinterpret_cast<u32*>(p + 16 + (u64)n * (sizeof(Lz4FrameBlock) + sizeof(Lz4Desc)));
+    static const u32 head[4] = {LZ4_NO_BAD, 0, 0, 0};   // (static: the copy is asynchronous)
+    HIPCHK(c, hipMemcpyAsync(p, head, 16, hipMemcpyHostToDevice, c->s_comp));
+    HIPCHK(c, hipMemcpyAsync(fs->blocks, blocks, (u64)n * sizeof(Lz4FrameBlock), hipMemcpyHostToDevice, c->s_comp));
+    return YSB_OK;
+}
+
+static int frame_args(ysb_ctx* c, const uint8_t* d_base, const ysb_lz4_frame_block* blocks, u32 n, ysb_lz4_frame_desc* info) {
+    if (n && (!d_base || !blocks)) return fail(c, YSB_ERR_ARG, "NULL frame buffers");
+    *info = ysb_lz4_frame_desc{};
+    info->blocks = n;
+    info->first_bad = LZ4_NO_BAD;
+    for (u32 i = 0; i < n; ++i) {
+        const u32 comp = blocks[i].comp_bytes & ~LZ4_STORED;
+        if (comp < 1 || comp > LZ4F_BLOCK_MAX)
+            return fail(c, YSB_ERR_ARG, "frame block %u: %u bytes, not in 1..%u", i, comp, LZ4F_BLOCK_MAX);
+        info->stored_blocks += (blocks[i].comp_bytes & LZ4_STORED) ? 1 : 0;
+        info->comp_bytes += comp;
+    }
+    return YSB_OK;
+}
+
+// measure + descriptors on s_comp, timed under YSB_F_TIMING
+static int frame_measure(ysb_ctx* c, const uint8_t* d_base, u32 n, const FrameScratch& fs, Event* ev) {
+    if (ev) {
+        for (int k = 0; k < 2; ++k) HIPCHK(c, ev[k].create(hipEventDefault));
+        HIPCHK(c, hipEventRecord(ev[0], c->s_comp));
+    }
+    HIPCHK(c, launch_lz4_measure(d_base, fs.blocks, n, fs.raw, c->s_comp));
+    HIPCHK(c, launch_lz4_frame_descs(fs.blocks, fs.raw, n, 0, fs.desc, fs.total, c->s_comp));
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->s_comp));
+    return YSB_OK;
+}
+
+int ysb_lz4_measure_device(ysb_ctx* c, const uint8_t* d_base, const ysb_lz4_frame_block* blocks, uint32_t n_blocks,
+                           uint32_t* raw_out, uint32_t* first_bad) {
+    if (!c) return YSB_ERR_ARG;
+    ysb_lz4_frame_desc info;
+    int rc = frame_args(c, d_base, blocks, n_blocks, &info);
+    if (rc) return rc;
+    if (n_blocks && !raw_out) return fail(c, YSB_ERR_ARG, "raw_out is NULL");
+    if (first_bad) *first_bad = LZ4_NO_BAD;
+    if ((rc = launch_pending_raw(c))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_blocks) {
+        FrameScratch fs;
+        const SyncOnExit settled{c->s_comp};
+        if ((rc = frame_scratch(c, blocks, n_blocks, &fs))) return rc;
+        const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
+        Event ev[2];
+        if ((rc = frame_measure(c, d_base, n_blocks, fs, timed ? ev : nullptr))) return rc;
+        HIPCHK(c, hipMemcpyAsync(raw_out, fs.raw, (u64)n_blocks * 4, hipMemcpyDeviceToHost, c->s_comp));
+        HIPCHK(c, hipMemcpyAsync(&info.raw_bytes, fs.total, 8, hipMemcpyDeviceToHost, c->s_comp));
+        HIPCHK(c, hipStreamSynchronize(c->s_comp));
+        float ms = 0;
+        if (timed && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) info.measure_ms = ms;
+        for (u32 i = 0; i < n_blocks; ++i)
+            if (!raw_out[i]) {
+                if (!info.bad_blocks) info.first_bad = i;
+                ++info.bad_blocks;
+            }
+    }
+    c->lz4f_last = info;
+    if (first_bad) *first_bad = (u32)info.first_bad;
+    if (info.bad_blocks)
+        return fail(c, YSB_ERR_FORMAT, "frame block %llu of %u breaks the block format (%llu bad in all)",
+                    (unsigned long long)info.first_bad, n_blocks, (unsigned long long)info.bad_blocks);
+    return YSB_OK;
+}
+
+int ysb_lz4_decode_blocks_device(ysb_ctx* c, const uint8_t* d_base, const ysb_lz4_frame_block* blocks, uint32_t n_blocks,
+                                 uint8_t* d_out, uint64_t out_cap, uint64_t* raw_bytes, uint32_t* first_bad) {
+    if (!c) return YSB_ERR_ARG;
+    ysb_lz4_frame_desc info;
+    int rc = frame_args(c, d_base, blocks, n_blocks, &info);
+    if (rc) return rc;
+    if (raw_bytes) *raw_bytes = 0;
+    if (first_bad) *first_bad = LZ4_NO_BAD;
+    if ((rc = launch_pending_raw(c))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_blocks) {
+        FrameScratch fs;
+        const SyncOnExit settled{c->s_comp};
+        if ((rc = frame_scratch(c, blocks, n_blocks, &fs))) return rc;
+        const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
+        Event evm[2], evd[2];
+        if ((rc = frame_measure(c, d_base, n_blocks, fs, timed ? evm : nullptr))) return rc;
+        // the measured total decides the capacity before a byte is decoded (this call is synchronous)
+        HIPCHK(c, hipMemcpyAsync(&info.raw_bytes, fs.total, 8, hipMemcpyDeviceToHost, c->s_comp));
+        HIPCHK(c, hipStreamSynchronize(c->s_comp));
+        if (raw_bytes) *raw_bytes = info.raw_bytes;
+        if (info.raw_bytes > out_cap)
+            return fail(c, YSB_ERR_CAPACITY, "%llu B decoded, cap %llu", (unsigned long long)info.raw_bytes,
+                        (unsigned long long)out_cap);
+        if (info.raw_bytes && !d_out) return fail(c, YSB_ERR_ARG, "NULL output buffer");
+        if (timed) {
+            for (int k = 0; k < 2; ++k) HIPCHK(c, evd[k].create(hipEventDefault));
+            HIPCHK(c, hipEventRecord(evd[0], c->s_comp));
+        }
+        // (a block measured bad has raw 0: the decode kernel records it in the bad pair)
+        const Lz4Params lp{d_base, fs.desc, n_blocks, LZ4_MAX_RAW, d_out, fs.bad, c->lz4_decoder};
+        HIPCHK(c, launch_lz4_decode(lp, c->s_comp));
+        if (timed) HIPCHK(c, hipEventRecord(evd[1], c->s_comp));
+        u32 bad[2] = {LZ4_NO_BAD, 0};
+        HIPCHK(c, hipMemcpyAsync(bad, fs.bad, 8, hipMemcpyDeviceToHost, c->s_comp));
+        HIPCHK(c, hipStreamSynchronize(c->s_comp));
+        float ms = 0;
+        if (timed && hipEventElapsedTime(&ms, evm[0], evm[1]) == hipSuccess) info.measure_ms = ms;
+        if (timed && hipEventElapsedTime(&ms, evd[0], evd[1]) == hipSuccess) info.decode_ms = ms;
+        info.first_bad = bad[0];
+        info.bad_blocks = bad[1];
+        info.decoder = lz4_pick_decoder(LZ4_MAX_RAW, c->lz4_decoder);
+    }
+    c->lz4f_last = info;
+    if (first_bad) *first_bad = (u32)info.first_bad;
+    if (info.bad_blocks)
+        return fail(c, YSB_ERR_FORMAT, "frame block %llu of %u breaks the block format (%llu bad in all)",
+                    (unsigned long long)info.first_bad, n_blocks, (unsigned long long)info.bad_blocks);
+    return YSB_OK;
+}
+
+int ysb_lz4_frame_info(ysb_ctx* c, ysb_lz4_frame_desc* info) {
+    if (!c || !info) return c ? fail(c, YSB_ERR_ARG, "info is NULL") : YSB_ERR_ARG;
+    const int rc = sync_streams(c);   // (a frame batch awaiting its launch settles here)
+    *info = c->lz4f_last;
+    return rc;
+}
+
+uint64_t ysb_lz4_frame_desc_size(void) { return sizeof(ysb_lz4_frame_desc); }
 
 }  // extern "C"

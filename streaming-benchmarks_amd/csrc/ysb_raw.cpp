@@ -59,7 +59,9 @@ int launch_pending_raw(ysb_ctx* c) {
                   "(max(max_batch_events, max_batch_bytes / 32))", slot, (unsigned long long)c->h_rawn[slot],
                   (unsigned long long)c->raw_lines_cap);
     } else {
-        const ysb_segment sg{c->d_bytes[slot], b.nbytes, b.off ? b.off : c->d_roff[slot].get(), c->h_rawn[slot]};
+        // (a frame batch's bytes were measured on the device: its count came back with the split's)
+        const u64 nbytes = b.lz4 && b.lz4->frame ? c->h_lz4f[slot].nbytes : b.nbytes;
+        const ysb_segment sg{c->d_bytes[slot], nbytes, b.off ? b.off : c->d_roff[slot].get(), c->h_rawn[slot]};
         rc = enqueue_scan(c, &sg, 1, b.lay);
     }
     // the slot's device buffers are free again once this launch (or nothing) has run
@@ -80,7 +82,7 @@ static int raw_args(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes)
         return fail(c, YSB_ERR_CAPACITY, "raw batch of %llu B exceeds max_batch_bytes", (unsigned long long)nbytes);
     if (nbytes && !bytes) return fail(c, YSB_ERR_ARG, "NULL batch buffer");
     if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
-    return YSB_OK;
+    return carry_guard(c);
 }
 
 // The slot made the caller's to refill, once the entry's arguments are checked: its own earlier
@@ -131,7 +133,8 @@ static int enqueue_deferred(ysb_ctx* c, int slot, RawBatch b, const SlotCopy* v,
     // empty batch) or the split's
     if (b.off || !b.nbytes) c->h_rawn[slot] = b.n_off;
     else HIPCHK(c, launch_split_lines(c->d_bytes[slot], b.nbytes, c->d_split_chunk, c->d_roff[slot], c->raw_lines_cap,
-                                      c->h_rawn + slot, s));
+                                      c->h_rawn + slot, s, b.lz4 && b.lz4->frame ? lz4f_nbytes(c, slot) : nullptr));
+    if (b.lz4 && b.lz4->frame && (rc = lz4f_readback(c, slot, s))) return rc;
     if (b.rebase && (b.off || b.nbytes) && (rc = rebase_lines(c, slot, b.nbytes, b.off, b.n_off, *b.rebase, s))) return rc;
     HIPCHK(c, hipEventRecord(c->ev_raw[slot], s));
     c->raw[slot] = b;
@@ -192,7 +195,48 @@ int ysb_submit_raw_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp
     if (!c) return YSB_ERR_ARG;
     if (int rc = slot_arg(c, slot)) return rc;
     if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
+    if (int rc = carry_guard(c)) return rc;
     return submit_lz4(c, slot, bytes, comp_bytes, dir, n_blocks, nullptr, nullptr, 0, nullptr);
+}
+
+// ---- standard-frame batches (ysb_lz4_api.cpp lz4f_stage; ysb_lz4_frame.h) ---------------------
+
+static int mapped_src(ysb_ctx* c, const uint8_t* bytes, u64 nbytes, const u8** dsrc);
+
+// Both frame submits: the slot claimed, the batch staged, enqueued like every deferred batch;
+// whether a carry is pending afterwards is the flag's.
+static int submit_frame(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_block* blocks, u32 n_blocks,
+                        u32 flags, bool mapped) {
+    if (!c) return YSB_ERR_ARG;
+    if (int rc = slot_arg(c, slot)) return rc;
+    if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
+    const u8* dsrc = nullptr;
+    if (mapped && n_blocks && base && blocks) {
+        const u64 first = blocks[0].offset, last = blocks[n_blocks - 1].offset + (blocks[n_blocks - 1].comp_bytes & 0x7FFFFFFFu);
+        if (last < first) return fail(c, YSB_ERR_ARG, "the frame blocks are not in order");
+        if (int rc = mapped_src(c, base + first, last - first, &dsrc)) return rc;
+    }
+    int rc = claim_slot(c, slot);
+    if (rc) return rc;
+    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));   // the slot's pinned buffers are rewritten
+    RawBatch b;
+    std::vector<u8> sample;
+    if ((rc = lz4f_stage(c, slot, base, blocks, n_blocks, flags, dsrc, &b, &sample))) return rc;
+    SlotCopy v[2];
+    lz4_copies(c, slot, *b.lz4, v);
+    rc = enqueue_deferred(c, slot, b, v, 2, sample.data(), sample.size());
+    if (c->raw_pend == slot) c->lz4f_more = (flags & YSB_LZ4F_MORE) != 0;   // only once the batch is on the device's queue
+    return rc;
+}
+
+int ysb_submit_lz4_blocks(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_block* blocks, uint32_t n_blocks,
+                          uint32_t flags) {
+    return submit_frame(c, slot, base, blocks, n_blocks, flags, false);
+}
+
+int ysb_submit_lz4_blocks_mapped(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_block* blocks,
+                                 uint32_t n_blocks, uint32_t flags) {
+    return submit_frame(c, slot, base, blocks, n_blocks, flags, true);
 }
 
 // ---- zero-copy raw batches from registered caller memory (ABI 5) ----------------------------
@@ -303,6 +347,7 @@ int ysb_submit_lz4_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t c
     if (!c) return YSB_ERR_ARG;
     if (int rc = slot_arg(c, slot)) return rc;
     if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
+    if (int g = carry_guard(c)) return g;
     if (comp_bytes && !bytes) return fail(c, YSB_ERR_ARG, "NULL batch buffer");
     if (!d_line_off && n) return fail(c, YSB_ERR_ARG, "n_events without line offsets (NULL d_line_off: the GPU split, n_events 0)");
     if (d_line_off && !n) return fail(c, YSB_ERR_ARG, "line offsets without n_events");

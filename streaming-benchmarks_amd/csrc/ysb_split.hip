@@ -198,9 +198,13 @@ __device__ __forceinline__ u32 start_mask16(const u8* b, u64 nbytes, u64 p) {
     return m;
 }
 
-__global__ __launch_bounds__(SPLIT_TPB) void split_count_kernel(const u8* b, u64 nbytes, u32* chunk_cnt) {
+// (d_nbytes, in all three kernels: the batch's byte count in device memory -- a frame batch's,
+// known only once its blocks are measured -- or NULL: nbytes itself.  With it nbytes is the bound
+// the grid was sized for, and chunks past the end count and write nothing.)
+__global__ __launch_bounds__(SPLIT_TPB) void split_count_kernel(const u8* b, u64 nbytes, const u64* d_nbytes, u32* chunk_cnt) {
     typedef hipcub::BlockReduce<u32, SPLIT_TPB> Reduce;
     __shared__ typename Reduce::TempStorage tmp;
+    if (d_nbytes) nbytes = *d_nbytes < nbytes ? *d_nbytes : nbytes;
     const u64 base = (u64)blockIdx.x * SPLIT_CHUNK;
     u32 cnt = 0;
 #pragma unroll 4
@@ -214,9 +218,10 @@ __global__ __launch_bounds__(SPLIT_TPB) void split_count_kernel(const u8* b, u64
 
 // chunk_cnt[0..nchunks) -> exclusive bases in place; *n = lines of the batch (0 when empty)
 __global__ __launch_bounds__(SPLIT_PREFIX_TPB) void split_prefix_kernel(u32* chunk, u64 nchunks, u64 nbytes,
-                                                                        unsigned long long* n) {
+                                                                        const u64* d_nbytes, unsigned long long* n) {
     typedef hipcub::BlockScan<unsigned long long, SPLIT_PREFIX_TPB> Scan;
     __shared__ typename Scan::TempStorage tmp;
+    if (d_nbytes) nbytes = *d_nbytes < nbytes ? *d_nbytes : nbytes;
     const u64 per = (nchunks + SPLIT_PREFIX_TPB - 1) / SPLIT_PREFIX_TPB;
     const u64 a = (u64)threadIdx.x * per, e = a + per < nchunks ? a + per : nchunks;
     unsigned long long s = 0;
@@ -231,13 +236,14 @@ __global__ __launch_bounds__(SPLIT_PREFIX_TPB) void split_prefix_kernel(u32* chu
     if (threadIdx.x == 0) *n = nbytes ? 1ull + total : 0ull;
 }
 
-__global__ __launch_bounds__(SPLIT_TPB) void split_write_kernel(const u8* b, u64 nbytes, const u32* chunk_base,
-                                                                u32* off, u64 cap) {
+__global__ __launch_bounds__(SPLIT_TPB) void split_write_kernel(const u8* b, u64 nbytes, const u64* d_nbytes,
+                                                                const u32* chunk_base, u32* off, u64 cap) {
     typedef hipcub::BlockScan<u32, SPLIT_TPB> Scan;
     __shared__ typename Scan::TempStorage tmp;
+    if (d_nbytes) nbytes = *d_nbytes < nbytes ? *d_nbytes : nbytes;
     const u64 base = (u64)blockIdx.x * SPLIT_CHUNK;
     u64 run = (u64)chunk_base[blockIdx.x] + 1;   // off index of the chunk's first start (off[0] = 0)
-    if (blockIdx.x == 0 && threadIdx.x == 0 && cap) off[0] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && cap && nbytes) off[0] = 0;
     for (int it = 0; it < SPLIT_STEPS; ++it) {
         const u64 p = base + ((u64)it * SPLIT_TPB + threadIdx.x) * 16;
         u32 m = p < nbytes ? start_mask16(b, nbytes, p) : 0u;
@@ -325,12 +331,12 @@ void launch_rebase(u8* b, u64 nbytes, const u32* off, u64 cap, const unsigned lo
 }
 
 hipError_t launch_split_lines(const u8* b, u64 nbytes, u32* chunk, u32* off, u64 cap, unsigned long long* d_n,
-                              hipStream_t s) {
+                              hipStream_t s, const u64* d_nbytes) {
     if (nbytes == 0) return hipMemsetAsync(d_n, 0, 8, s);
     const u64 nch = split_chunks(nbytes);
-    hipLaunchKernelGGL(split_count_kernel, dim3((unsigned)nch), dim3(SPLIT_TPB), 0, s, b, nbytes, chunk);
-    hipLaunchKernelGGL(split_prefix_kernel, dim3(1), dim3(SPLIT_PREFIX_TPB), 0, s, chunk, nch, nbytes, d_n);
-    hipLaunchKernelGGL(split_write_kernel, dim3((unsigned)nch), dim3(SPLIT_TPB), 0, s, b, nbytes, chunk, off, cap);
+    hipLaunchKernelGGL(split_count_kernel, dim3((unsigned)nch), dim3(SPLIT_TPB), 0, s, b, nbytes, d_nbytes, chunk);
+    hipLaunchKernelGGL(split_prefix_kernel, dim3(1), dim3(SPLIT_PREFIX_TPB), 0, s, chunk, nch, nbytes, d_nbytes, d_n);
+    hipLaunchKernelGGL(split_write_kernel, dim3((unsigned)nch), dim3(SPLIT_TPB), 0, s, b, nbytes, d_nbytes, chunk, off, cap);
     return hipGetLastError();
 }
 

@@ -434,6 +434,7 @@ int ysb_submit(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, cons
         return fail(c, YSB_ERR_CAPACITY, "batch (%llu B, %llu events) exceeds max_batch_bytes/max_batch_events",
                     (unsigned long long)nbytes, (unsigned long long)n);
     if ((nbytes && !bytes) || (n && !line_off)) return fail(c, YSB_ERR_ARG, "NULL batch buffers");
+    if (int g = carry_guard(c)) return g;
     int rc = launch_pending_raw(c);   // batches launch in submission order
     if (!rc) rc = ensure_slots(c);
     if (rc) return rc;
@@ -492,6 +493,7 @@ int ysb_submit_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const
     if (nbytes > (4ull << 30) - 64) return fail(c, YSB_ERR_CAPACITY, "device batch larger than 4 GiB (u32 offsets)");
     if ((nbytes && !d_bytes) || (n && !d_off)) return fail(c, YSB_ERR_ARG, "NULL batch buffers");
     if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(c, YSB_ERR_ARG, "d_bytes must be 16-byte aligned");
+    if (int g = carry_guard(c)) return g;
     HIPCHK(c, hipSetDevice(c->device));
     const ysb_segment sg{d_bytes, nbytes, d_off, n};
     return enqueue_device(c, &sg, 1);
@@ -510,6 +512,7 @@ int ysb_submit_device_segments(ysb_ctx* c, const ysb_segment* segs, uint32_t n_s
         if (reinterpret_cast<uintptr_t>(s.d_bytes) & 15)
             return fail(c, YSB_ERR_ARG, "segment %u: d_bytes must be 16-byte aligned", i);
     }
+    if (int g = carry_guard(c)) return g;
     HIPCHK(c, hipSetDevice(c->device));
     return enqueue_device(c, segs, n_segs);
 }

@@ -627,6 +627,28 @@ Lz4Container Lz4Container::parse(const uint8_t* file, uint64_t size, const std::
     return c;
 }
 
+void GpuAdCampaignOperator::submitLz4Blocks(const uint8_t* file, const ysb_lz4_frame_block* blocks, uint32_t nBlocks,
+                                            bool more, bool mapped) {
+    const uint32_t flags = more ? YSB_LZ4F_MORE : 0u;
+    if (mapped) {
+        check(ysb_submit_lz4_blocks_mapped(ctx_, cur_, file, blocks, nBlocks, flags), "ysb_submit_lz4_blocks_mapped");
+    } else {
+        // the span (first block's data .. last block's end) into the slot, the entries' offsets from its start
+        const uint64_t first = nBlocks ? blocks[0].offset : 0;
+        const uint64_t span = nBlocks ? blocks[nBlocks - 1].offset + (blocks[nBlocks - 1].comp_bytes & ~YSB_LZ4_STORED) - first : 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (span) std::memcpy(bytes_[cur_], file + first, span);   // (the slot is free: the last submit's ysb_wait)
+        std::vector<ysb_lz4_frame_block> rel(blocks, blocks + nBlocks);
+        for (ysb_lz4_frame_block& b : rel) b.offset -= first;
+        fillS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        check(ysb_submit_lz4_blocks(ctx_, cur_, bytes_[cur_], rel.data(), nBlocks, flags), "ysb_submit_lz4_blocks");
+    }
+    cur_ ^= 1;
+    const auto t1 = std::chrono::steady_clock::now();
+    check(ysb_wait(ctx_, cur_), "ysb_wait");   // the other slot is free again; at most two batches in flight
+    waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+}
+
 void GpuAdCampaignOperator::submitColumnsFile(const std::string& path, uint64_t rows) {
     ysb_columns_layout lay;
     uint64_t off[4], len[4];

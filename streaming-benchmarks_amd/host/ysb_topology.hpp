@@ -193,6 +193,10 @@ public:
     // the same read where the blocks lie, in the registered mapping of the container
     // (ysb_submit_lz4_mapped after registerSource): no copy into a slot
     void submitLz4Mapped(const uint8_t* blocks, uint64_t compBytes, const ysb_lz4_block* dir, uint32_t nBlocks);
+    // A run of a standard LZ4 frame's blocks (ysb_lz4_frame_index's entries over `file`) as one
+    // batch: through the slot, or (mapped) read where they lie in the registered mapping.  more:
+    // the batch's unfinished last line is carried in front of the next one (YSB_LZ4F_MORE).
+    void submitLz4Blocks(const uint8_t* file, const ysb_lz4_frame_block* blocks, uint32_t nBlocks, bool more, bool mapped);
     // One file image of WindowedArrowFormatBolter (<shared_file>_<k>, :303-317) of `rows` rows
     // counted from its columns (ysb_submit_columns, longs big-endian): only the ranges the count
     // reads are read from the file, straight into the open slot.  Throws, naming the file, if

@@ -18,7 +18,8 @@
 // splits the lines on the host instead (ysb_submit with offsets).  --repeat K reads the file
 // K times (a replay source; the counts are K times the file's).  --lz4 reads events_path as a
 // compressed replay file through the slots; --lz4 --io mapped maps it instead and hands runs of
-// its blocks over where they lie (ysb_submit_lz4_mapped).  The last stdout line is a JSON
+// its blocks over where they lie (ysb_submit_lz4_mapped); a standard LZ4 frame file (ysb_gen
+// --lz4-frame, lz4 -B4 -BI) is told by its magic and fed with ysb_submit_lz4_blocks(_mapped).  The last stdout line is a JSON
 // summary.
 #include <algorithm>
 #include <chrono>
@@ -404,21 +405,60 @@ int run(const Args& a) {
     // line-aligned flag makes every run a batch of whole lines
     // --lz4 --io mapped: the container is mapped (the source's mapping), not read, and every
     // run is read where it lies (ysb_submit_lz4_mapped)
+    // A standard LZ4 frame (lz4 -B4 -BI, ysb_gen --lz4-frame), told from the container by its
+    // magic: indexed on the host (one size word per block), fed in runs of blocks that fit a
+    // slot (the span and (blocks + 1) x 64 KiB), YSB_LZ4F_MORE on all batches but the last --
+    // frame blocks end mid-line, the device carries the unfinished line to the next batch.
     std::string lz4_file;
     Lz4Container lz4;
+    std::vector<ysb_lz4_frame_block> frame;
+    const uint8_t* frame_bytes = nullptr;
+    bool is_frame = false;
     if (a.lz4) {
-        if (lz4_mapped) {
+        if (!lz4_mapped) lz4_file = readFile(events);
+        const uint8_t* fb = lz4_mapped ? src.mapping() : reinterpret_cast<const uint8_t*>(lz4_file.data());
+        const uint64_t fn = lz4_mapped ? src.fileBytes() : lz4_file.size();
+        is_frame = fn >= 4 && fb[1] == (fb[0] == 0x04 ? 0x22 : 0x2A) && fb[2] == 0x4D && fb[3] == 0x18 &&
+                   (fb[0] == 0x04 || (fb[0] & 0xF0) == 0x50);
+        if (is_frame) {
+            uint64_t n = 0;
+            ysb_lz4_frame_summary sum{};
+            int rc = ysb_lz4_frame_index(fb, fn, nullptr, 0, &n, &sum);
+            if (rc && rc != YSB_ERR_CAPACITY) throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
+            frame.resize(n);
+            if (n && ysb_lz4_frame_index(fb, fn, frame.data(), n, &n, &sum))
+                throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
+            frame_bytes = fb;
+            lz4.rawBytes = sum.content_bytes;   // (what the frames state; 0 if none does)
+        } else if (lz4_mapped) {
             lz4 = Lz4Container::parse(src.mapping(), src.fileBytes(), events);
         } else {
-            lz4_file = readFile(events);
             lz4 = Lz4Container::parse(lz4_file, events);
         }
+    }
+    if (a.lz4 && !is_frame) {
         if (!lz4.lineAligned)
             throw std::runtime_error(events + ": its blocks are not line-aligned (ysb_gen --lz4 writes them so): "
                                      "a run of blocks would cut lines");
     }
     uint64_t lz4_comp = 0;
-    for (long long rep = 0; a.lz4 && rep < a.repeat; ++rep) {
+    for (long long rep = 0; is_frame && rep < a.repeat; ++rep) {
+        for (uint64_t b = 0; b < frame.size();) {
+            uint64_t e = b;
+            auto end_of = [&](uint64_t i) { return frame[i].offset + (frame[i].comp_bytes & ~YSB_LZ4_STORED); };
+            while (e < frame.size() && end_of(e) - frame[b].offset <= o.batchBytes && (e - b + 2) * 65536ull <= o.batchBytes) ++e;
+            if (e == b) throw std::runtime_error(events + ": block " + std::to_string(b) + " exceeds the slot (--batch-mb)");
+            op.submitLz4Blocks(frame_bytes, frame.data() + b, (uint32_t)(e - b), e < frame.size(), lz4_mapped);
+            lz4_comp += end_of(e - 1) - frame[b].offset;
+            b = e;
+            if (lookup) op.resolveParked(*lookup);
+            if (a.flush_ms > 0 && (now_s() - last_flush) * 1000.0 >= (double)a.flush_ms) {
+                flush();
+                last_flush = now_s();
+            }
+        }
+    }
+    for (long long rep = 0; a.lz4 && !is_frame && rep < a.repeat; ++rep) {
         for (uint64_t b = 0; b < lz4.nBlocks;) {
             uint64_t e = b, comp = 0, raw = 0;
             while (e < lz4.nBlocks && comp + (lz4.dir[e].comp_bytes & ~YSB_LZ4_STORED) <= o.batchBytes &&

@@ -3,7 +3,7 @@
 //
 //   ysb_gen -d DIR [-n EVENTS] [--seed S] [--campaigns C] [--ads-per-campaign A]
 //           [--rate EVENTS_PER_SEC] [--t0 MS] [--with-skew] [--users K]
-//           [--shards K] [--tbl] [--lz4 [--lz4-block N]]
+//           [--shards K] [--tbl] [--lz4 [--lz4-block N] | --lz4-frame]
 //
 // Writes campaign-ids.txt, ad-ids.txt, ad-to-campaign-ids.txt (JSON map lines),
 // ad-to-campaign.csv (the fork's CSV map) and kafka-json.txt into DIR; with --shards K
@@ -11,6 +11,8 @@
 // fork's pipe-delimited rows (conf/benchmarkConf.yaml:6); with --lz4 also kafka-json.txt.lz4
 // (and events.tbl.lz4): the same bytes as a compressed replay file of line-aligned LZ4 blocks
 // of N bytes (default 8192; include/ysb_hip.h ysb_lz4_file_header) for ysb_topology --lz4.
+// With --lz4-frame the .lz4 files are standard LZ4 frames instead (independent 64 KiB blocks,
+// content size set: any LZ4 tool reads them, and so does ysb_topology --lz4).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,7 +28,7 @@ int main(int argc, char** argv) {
     unsigned long long n = 10000000ULL;   // kafka-event-count (core.clj:17)
     const char* dir = nullptr;
     unsigned shards = 0;
-    bool tbl = false, lz4 = false;
+    bool tbl = false, lz4 = false, lz4_frame = false;
     unsigned lz4_block = 8192;
     for (int i = 1; i < argc; ++i) {
         auto val = [&]() -> const char* {
@@ -45,6 +47,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--shards")) shards = (unsigned)std::strtoul(val(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--tbl")) tbl = true;
         else if (!std::strcmp(argv[i], "--lz4")) lz4 = true;
+        else if (!std::strcmp(argv[i], "--lz4-frame")) lz4 = lz4_frame = true;
         else if (!std::strcmp(argv[i], "--lz4-block")) lz4_block = (unsigned)std::strtoul(val(), nullptr, 10);
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
@@ -68,7 +71,9 @@ int main(int argc, char** argv) {
             uint8_t buf[1 << 16];
             for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) data.insert(data.end(), buf, buf + k);
             std::fclose(f);
-            rc = ysb_lz4_write_file((path + ".lz4").c_str(), data.data(), data.size(), lz4_block, 1, 1, 16);
+            // --lz4-frame: one standard LZ4 frame of independent 64 KiB blocks (what lz4 -B4 -BI writes)
+            rc = lz4_frame ? ysb_lz4_frame_write((path + ".lz4").c_str(), data.data(), data.size(), 65536, 16)
+                           : ysb_lz4_write_file((path + ".lz4").c_str(), data.data(), data.size(), lz4_block, 1, 1, 16);
             if (rc) { std::fprintf(stderr, "ysb_gen: %s\n", ysb_last_error(nullptr)); return 1; }
         }
     }

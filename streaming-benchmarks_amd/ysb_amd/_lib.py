@@ -137,6 +137,22 @@ class YsbLz4Desc(C.Structure):
                                           "bad_blocks", "first_bad")] + [("decode_ms", C.c_double)]
 
 
+class YsbLz4FrameBlock(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("comp_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class YsbLz4FrameSummary(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("frames", "skippable_frames", "blocks", "stored_blocks", "comp_bytes",
+                                          "content_bytes")] + [
+                (n, C.c_uint32) for n in ("block_checksums", "content_checksums", "content_sizes", "reserved")]
+
+
+class YsbLz4FrameDesc(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("blocks", "stored_blocks", "comp_bytes", "raw_bytes", "bad_blocks",
+                                          "first_bad", "decoder", "batches", "carry_in", "carry_out")] + [
+                ("measure_ms", C.c_double), ("decode_ms", C.c_double)]
+
+
 class YsbGenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_campaigns", C.c_uint32), ("ads_per_campaign", C.c_uint32),
                 ("t0_ms", C.c_int64), ("events_per_sec", C.c_uint64), ("with_skew", C.c_uint32),
@@ -199,6 +215,19 @@ SIGNATURES = {
     "ysb_lz4_compress_block": (_I, [_PU8, _U32, _PU8, _U32, _I, C.POINTER(YsbLz4Block)]),
     "ysb_lz4_decompress_block": (_I, [_PU8, C.POINTER(YsbLz4Block), _PU8, _U32]),
     "ysb_lz4_write_file": (_I, [C.c_char_p, _PU8, _U64, _U32, _I, _I, _I]),
+    "ysb_lz4_frame_index": (_I, [_PU8, _U64, _P, _U64, C.POINTER(_U64), C.POINTER(YsbLz4FrameSummary)]),
+    "ysb_lz4_frame_bound": (_U64, [_U64, _U32]),
+    "ysb_lz4_frame_pack": (_I, [_PU8, _U64, _U32, _I, _PU8, _U64, C.POINTER(_U64)]),
+    "ysb_lz4_frame_write": (_I, [C.c_char_p, _PU8, _U64, _U32, _I]),
+    "ysb_lz4_measure_block": (_I, [_PU8, _U32, C.POINTER(_U32)]),
+    "ysb_lz4_frame_carry_cut": (_U64, [_PU8, _U64, _I]),
+    "ysb_lz4_measure_device": (_I, [_P, _PU8, _P, _U32, _PU32, C.POINTER(_U32)]),
+    "ysb_lz4_decode_blocks_device": (_I, [_P, _PU8, _P, _U32, _PU8, _U64, C.POINTER(_U64), C.POINTER(_U32)]),
+    "ysb_submit_lz4_blocks": (_I, [_P, _I, _PU8, _P, _U32, _U32]),
+    "ysb_submit_lz4_blocks_mapped": (_I, [_P, _I, _PU8, _P, _U32, _U32]),
+    "ysb_lz4_set_decoder": (_I, [_P, _I]),
+    "ysb_lz4_frame_info": (_I, [_P, C.POINTER(YsbLz4FrameDesc)]),
+    "ysb_lz4_frame_desc_size": (_U64, []),
     "ysb_lz4_pack": (_I, [_PU8, _U64, _U32, _I, _I, _I, _PU8, _U64, C.POINTER(_U64), _P, _U64, C.POINTER(_U64)]),
     "ysb_copy_time": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_U64), C.POINTER(_U64)]),
     "ysb_submit_device": (_I, [_P, _PU8, _U64, _PU32, _U64]),
@@ -296,7 +325,8 @@ def lib():
             raise ImportError("ysb_colcount_desc is %d bytes in the library, %d in this binding"
                               % (L.ysb_colcount_desc_size(), C.sizeof(YsbColcountDesc)))
         for fn, st in ((L.ysb_upsert_info_size, YsbUpsertInfo), (L.ysb_admap_desc_size, YsbAdmapDesc),
-                       (L.ysb_parked_info_size, YsbParkedDesc), (L.ysb_lz4_desc_size, YsbLz4Desc)):
+                       (L.ysb_parked_info_size, YsbParkedDesc), (L.ysb_lz4_desc_size, YsbLz4Desc),
+                       (L.ysb_lz4_frame_desc_size, YsbLz4FrameDesc)):
             if fn() != C.sizeof(st):
                 raise ImportError("%s is %d bytes in the library, %d in this binding"
                                   % (st.__name__, fn(), C.sizeof(st)))

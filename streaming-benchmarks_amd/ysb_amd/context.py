@@ -351,6 +351,60 @@ class YsbContext:
             out["first_bad"] = None
         return out
 
+    def submit_lz4_blocks(self, data, index, slot=0, more=False):
+        """ysb_submit_lz4_blocks: a run of consecutive entries of a standard frame's index
+        (ysb_amd.lz4.frame_index over `data`, bytes or a uint8 array) as one batch; the GPU
+        measures, decodes, splits and scans.  more=True: the bytes behind the batch's last certain
+        line terminator are carried in front of the next frame batch."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+        idx = np.ascontiguousarray(index)
+        self._c(lib().ysb_submit_lz4_blocks(self._h, slot, _ptr(buf), _ptr(idx), idx.size, 1 if more else 0))
+
+    def submit_lz4_blocks_mapped(self, arr, index, slot=0, more=False):
+        """ysb_submit_lz4_blocks_mapped: the same with the blocks read in place from a registered
+        array (host_register); the index's offsets refer to arr."""
+        idx = np.ascontiguousarray(index)
+        self._c(lib().ysb_submit_lz4_blocks_mapped(self._h, slot, C.c_void_p(arr.ctypes.data), _ptr(idx), idx.size,
+                                                   1 if more else 0))
+
+    def lz4_set_decoder(self, decoder):
+        """ysb_lz4_set_decoder: 0 by the batch's largest block, 1 always the one-wave kernel, 2
+        always the several-wave kernel."""
+        self._c(lib().ysb_lz4_set_decoder(self._h, decoder))
+
+    def lz4_measure_device(self, d_base, index):
+        """ysb_lz4_measure_device: the raw size of every block of a frame index (ysb_amd.lz4.
+        frame_index's) whose offsets refer to the device buffer d_base.  Returns (raw sizes as a
+        uint32 array with 0 for a bad block, first bad block or None); bad blocks do not raise."""
+        idx = np.ascontiguousarray(index)
+        raw, bad = np.zeros(max(idx.size, 1), dtype=np.uint32), C.c_uint32()
+        rc = lib().ysb_lz4_measure_device(self._h, C.c_void_p(d_base), _ptr(idx), idx.size, _ptr(raw), C.byref(bad))
+        if rc != -5 or bad.value == 0xFFFFFFFF:
+            self._c(rc)
+        return raw[:idx.size], (None if bad.value == 0xFFFFFFFF else bad.value)
+
+    def lz4_decode_blocks_device(self, d_base, index, d_out, out_cap):
+        """ysb_lz4_decode_blocks_device: measure + decode of a frame index's blocks, device to
+        device.  Returns (raw bytes, first bad block or None); a bad block does not raise."""
+        idx = np.ascontiguousarray(index)
+        raw, bad = C.c_uint64(), C.c_uint32()
+        rc = lib().ysb_lz4_decode_blocks_device(self._h, C.c_void_p(d_base), _ptr(idx), idx.size, C.c_void_p(d_out),
+                                                out_cap, C.byref(raw), C.byref(bad))
+        if rc != -5 or bad.value == 0xFFFFFFFF:
+            self._c(rc)
+        return raw.value, (None if bad.value == 0xFFFFFFFF else bad.value)
+
+    def lz4_frame_info(self):
+        """ysb_lz4_frame_info as a dict: the last measure / decode of frame blocks (blocks,
+        stored_blocks, comp_bytes, raw_bytes, bad_blocks, first_bad or None, decoder, and with
+        timing=True measure_ms and decode_ms)."""
+        d = _lib.YsbLz4FrameDesc()
+        self._c(lib().ysb_lz4_frame_info(self._h, C.byref(d)))
+        out = {n: getattr(d, n) for n, _ in d._fields_}
+        if out["first_bad"] == 0xFFFFFFFF:
+            out["first_bad"] = None
+        return out
+
     def copy_time(self):
         """(total ms, copies, bytes) of the slot H2D copies since the last call (timing=True)."""
         t, k, b = C.c_double(), C.c_uint64(), C.c_uint64()

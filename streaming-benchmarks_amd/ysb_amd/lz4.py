@@ -84,3 +84,63 @@ def read_file(path):
     if int((directory[:, 0] & 0x7FFFFFFF).sum()) != blocks.size or int(directory[:, 1].sum()) != raw:
         raise ValueError("%s: the directory does not match the file" % path)
     return flags, raw, blocks, directory
+
+
+# ---- standard LZ4 frames (csrc/ysb_lz4_frame.h) ------------------------------------------------
+
+FRAME_MAGIC = b"\x04\x22\x4d\x18"
+FRAME_BLOCK = np.dtype([("offset", "<u8"), ("comp_bytes", "<u4"), ("reserved", "<u4")])
+
+
+def is_frame(head):
+    """True when the bytes begin like a standard frame (or a skippable frame in front of one)."""
+    head = bytes(head[:4])
+    return head == FRAME_MAGIC or (len(head) == 4 and head[1:] == b"\x2a\x4d\x18" and 0x50 <= head[0] <= 0x5F)
+
+
+def frame_index(data):
+    """ysb_lz4_frame_index: (index, summary dict) of a buffer of concatenated standard frames.
+    index is a FRAME_BLOCK array: offset of each block's first data byte, comp_bytes | STORED.
+    Raises YsbError (YSB_ERR_FORMAT) naming the byte offset and the rule for a frame the library
+    does not take (linked blocks, a dictionary, a block maximum above 64 KiB, any truncation)."""
+    src = _u8(data)
+    n, info = C.c_uint64(), _lib.YsbLz4FrameSummary()
+    rc = lib().ysb_lz4_frame_index(src.ctypes.data, src.size, None, 0, C.byref(n), C.byref(info))
+    if rc not in (0, -4):
+        check(rc)
+    index = np.zeros(n.value, dtype=FRAME_BLOCK)
+    if n.value:
+        check(lib().ysb_lz4_frame_index(src.ctypes.data, src.size, index.ctypes.data, index.size, C.byref(n), C.byref(info)))
+    return index, {k: getattr(info, k) for k, _ in info._fields_ if k != "reserved"}
+
+
+def frame_pack(data, block_bytes=MAX_RAW, threads=1):
+    """ysb_lz4_frame_pack: data as one standard frame (independent blocks, 64 KiB maximum, no
+    checksums, content size set) that any LZ4 tool reads; a uint8 array."""
+    src = _u8(data)
+    dst = np.empty(lib().ysb_lz4_frame_bound(src.size, block_bytes), dtype=np.uint8)
+    n = C.c_uint64()
+    check(lib().ysb_lz4_frame_pack(src.ctypes.data, src.size, block_bytes, threads, dst.ctypes.data, dst.size, C.byref(n)))
+    return dst[:n.value]
+
+
+def frame_write(path, data, block_bytes=MAX_RAW, threads=1):
+    """ysb_lz4_frame_write: frame_pack into a file (what `lz4 -B4 -BI` would write)."""
+    src = _u8(data)
+    check(lib().ysb_lz4_frame_write(str(path).encode(), src.ctypes.data, src.size, block_bytes, threads))
+
+
+def measure_block(comp, comp_field=None):
+    """The host model of the measure pass: a frame block's raw size by its tokens alone;
+    raises YsbError (YSB_ERR_FORMAT) when no raw size makes the block valid."""
+    src = _u8(comp) if len(comp) else np.zeros(1, dtype=np.uint8)
+    raw = C.c_uint32()
+    check(lib().ysb_lz4_measure_block(src.ctypes.data, len(comp) if comp_field is None else comp_field, C.byref(raw)))
+    return raw.value
+
+
+def frame_carry_cut(data, more=True):
+    """ysb_lz4_frame_carry_cut: how many of data's bytes are whole lines when more batches
+    follow; the rest is carried in front of the next batch."""
+    src = _u8(data)
+    return lib().ysb_lz4_frame_carry_cut(src.ctypes.data if src.size else None, src.size, int(more))

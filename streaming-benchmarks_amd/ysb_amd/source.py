@@ -101,8 +101,9 @@ class FileBasedDataSource:
 
 
 class Lz4FileDataSource:
-    """A compressed replay file (ysb_gen --lz4, ysb_amd.lz4.write_file: header, directory,
-    blocks), mapped read-only: `runs(cap)` yields (offset into the mapping, compressed bytes,
+    """A compressed replay file -- the library's container (ysb_gen --lz4, ysb_amd.lz4.write_file:
+    header, directory, blocks) or a standard LZ4 frame (lz4 -B4 -BI, ysb_gen --lz4-frame), told
+    apart by magic --, mapped read-only: `runs(cap)` yields (offset into the mapping, compressed bytes,
     first block, blocks) of runs of whole blocks whose compressed and decoded sizes both fit
     cap; `run(ctx, cap)` registers the mapping and submits every run where it lies
     (ysb_submit_lz4_mapped: only compressed bytes cross PCIe, and none passes through a host
@@ -121,6 +122,16 @@ class Lz4FileDataSource:
             with open(self.path, "rb") as f:
                 self._mm = mmap.mmap(f.fileno(), 0, flags=mmap.MAP_SHARED, prot=mmap.PROT_READ)
             self.data = np.frombuffer(self._mm, dtype=np.uint8)
+        self.frame = lz4.is_frame(self.data[:4].tobytes())
+        self.comp_bytes = 0
+        self.batches = 0
+        if self.frame:
+            # a standard LZ4 frame (lz4 -B4 -BI, ysb_gen --lz4-frame, ysb_amd.lz4.frame_write),
+            # told from the container by its magic: indexed here, measured and decoded on the GPU
+            self.index, info = lz4.frame_index(self.data)
+            self.directory = np.zeros((0, 2), dtype=np.uint32)
+            self.raw_bytes = int(info["content_bytes"])   # (what the frames state; 0 if none does)
+            return
         if self.size < self.HEADER or self.data[:8].tobytes() != lz4.FILE_MAGIC:
             raise ValueError("%s: not a compressed replay file (ysb_gen --lz4 writes one)" % self.path)
         version, flags = (int(x) for x in self.data[8:16].view(np.uint32))
@@ -149,6 +160,19 @@ class Lz4FileDataSource:
     def runs(self, cap: int):
         if cap <= 0:
             raise ValueError("cap must be positive")
+        if self.frame:
+            # runs of consecutive blocks whose span and (blocks + 1) x 65536 both fit cap
+            n, b = self.index.size, 0
+            end = self.index["offset"].astype(np.int64) + (self.index["comp_bytes"] & 0x7FFFFFFF).astype(np.int64)
+            while b < n:
+                e, first = b, int(self.index[b]["offset"])
+                while e < n and int(end[e]) - first <= cap and (e - b + 2) * 65536 <= cap:
+                    e += 1
+                if e == b:
+                    raise ValueError("%s: block %d exceeds the slot" % (self.path, b))
+                yield first, int(end[e - 1]) - first, b, e - b
+                b = e
+            return
         n, b = self.directory.shape[0], 0
         while b < n:
             e, comp, raw = b, 0, 0
@@ -168,7 +192,10 @@ class Lz4FileDataSource:
         try:
             slot = 0
             for off, comp, b, k in self.runs(cap):
-                ctx.submit_lz4_mapped(self.data, off, comp, self.directory[b:b + k], slot=slot)
+                if self.frame:   # frame blocks end mid-line: every batch but the last leaves its tail to the next
+                    ctx.submit_lz4_blocks_mapped(self.data, self.index[b:b + k], slot=slot, more=b + k < self.index.size)
+                else:
+                    ctx.submit_lz4_mapped(self.data, off, comp, self.directory[b:b + k], slot=slot)
                 slot ^= 1
                 ctx.wait(slot)
                 self.comp_bytes += comp

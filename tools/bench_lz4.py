@@ -8,7 +8,13 @@ path, the yardstick), the other the same batches compressed on the host by block
 same batches in place from one registered array each, without the pinned slots: `mapped` the
 compressed ones (ysb_submit_lz4_mapped) and `raw_mapped` the raw lines (ysb_submit_raw_mapped).
 The legs alternate --repeats times in one process.  Plus the decode alone (ysb_lz4_decode_device) at several
-block sizes.
+block sizes, and a standard frame of 64 KiB blocks through the measure pass and the decode
+(ysb_lz4_decode_blocks_device).  --decoder picks the decode kernel; --decoder both runs the
+one-wave and the several-wave kernel at every block size, alternated --repeats times -- the
+crossover table of DESIGN.md §6 -- and writes it with the frame table to
+profiles/lz4_frame_bench.json; --decode-only skips the chain legs.
+--legs picks the chain legs; `frame` submits each batch as one standard frame of 64 KiB blocks
+(ysb_submit_lz4_blocks): `--legs raw,lz4,frame` is the run of profiles/lz4_frame_chain.json.
 
 Per leg: events/s, the H2D rate (bytes copied / copy time, HIP events on the copy stream), the
 copy queue's busy share; for the compressed leg the compression ratio and the decode's rate in
@@ -48,6 +54,15 @@ def main():
     ap.add_argument("--block", type=int, default=None, help="LZ4 block size of the chain legs (default: the tools')")
     ap.add_argument("--decode-blocks", default="4096,8192,16384,65536")
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--decoder", default="auto", choices=["auto", "narrow", "wide", "both"],
+                    help="the decode kernel (ysb_lz4_set_decoder); both: the decode-alone table runs the one-wave and "
+                         "the several-wave kernel at every block size, alternated --repeats times (the crossover)")
+    ap.add_argument("--legs", default="raw,lz4,raw_mapped,mapped",
+                    help="the chain legs, alternated; `frame`: the batches as standard frames of 64 KiB blocks "
+                         "(ysb_submit_lz4_blocks); with another set than the default the summary is the legs' medians")
+    ap.add_argument("--decode-only", action="store_true", help="skip the chain legs: the decode-alone and frame tables only")
+    ap.add_argument("--frame-out", default=os.path.join(ROOT, "profiles", "lz4_frame_bench.json"),
+                    help="where --decoder both / --decode-only write their tables")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lz4_bench.json"))
     a = ap.parse_args()
 
@@ -62,6 +77,8 @@ def main():
     with YsbContext(device=a.device, n_campaigns=100, window_ring=1024, timing=True, max_batch_bytes=a.slot_mb << 20,
                     max_batch_events=per, ring_base_bucket=g.c.t0_ms // 10000 - 8) as ctx:
         ctx.load_ad_map(aids, g.ad_campaign_index())
+        DEC = {"auto": 0, "narrow": 1, "wide": 2}
+        ctx.lz4_set_decoder(DEC.get(a.decoder, 0))
         raw = []
         for s in (0, 1):   # two distinct batches, generated on the device, kept on the host
             cap = per * g.max_line_bytes()
@@ -99,11 +116,22 @@ def main():
         reg_comp, at_comp = registered([b for b, _ in comp])
         reg_raw, at_raw = registered(raw)
 
+        legs = [k for k in a.legs.split(",") if k]
+        frames = []
+        if "frame" in legs and not a.decode_only:   # each batch as one standard frame; its span starts at the first block's data
+            for r in raw:
+                f = lz4.frame_pack(r, 65536, threads=threads)
+                idx, _ = lz4.frame_index(f)
+                first = int(idx[0]["offset"])
+                frames.append((f[first:], np.ascontiguousarray(idx), first))
+            res["frame"] = {"ratio": round(raw_bytes / sum(f.size + fst for f, _, fst in frames), 4),
+                            "blocks": [int(i.size) for _, i, _ in frames]}
+
         def leg(kind):
             for s in (0, 1):   # staged once per leg: the slot's pinned buffer holds what crosses PCIe
                 ctx.wait(s)
-                if kind in ("raw", "lz4"):
-                    src = raw[s] if kind == "raw" else comp[s][0]
+                if kind in ("raw", "lz4", "frame"):
+                    src = raw[s] if kind == "raw" else comp[s][0] if kind == "lz4" else frames[s][0]
                     slot[s][:src.size] = src
 
             def submit(s):
@@ -111,6 +139,9 @@ def main():
                     check(lib().ysb_submit_raw(ctx._h, s, C.c_void_p(slot[s].ctypes.data), raw[s].size), ctx._h)
                 elif kind == "raw_mapped":
                     ctx.submit_raw_mapped(reg_raw, at_raw[s], raw[s].size, slot=s)
+                elif kind == "frame":   # (base: where the frame's byte 0 would lie in front of the slot's span)
+                    check(lib().ysb_submit_lz4_blocks(ctx._h, s, C.c_void_p(slot[s].ctypes.data - frames[s][2]),
+                                                      C.c_void_p(frames[s][1].ctypes.data), frames[s][1].size, 0), ctx._h)
                 elif kind == "mapped":
                     ctx.submit_lz4_mapped(reg_comp, at_comp[s], comp[s][0].size, dirs[s], slot=s)
                 else:
@@ -131,7 +162,7 @@ def main():
             kms, launches = ctx.kernel_time()
             cms, copies, cbytes = ctx.copy_time()
             st = ctx.stats()
-            info = ctx.lz4_info() if kind in ("lz4", "mapped") else None
+            info = ctx.lz4_info() if kind in ("lz4", "mapped") else ctx.lz4_frame_info() if kind == "frame" else None
             for i in range(nsub):
                 ctx.truth_accumulate(g, (i & 1) * per, per)
             mism, truth, counted = ctx.truth_compare()
@@ -149,8 +180,8 @@ def main():
             log(json.dumps(out))
             return out
 
-        for _ in range(a.repeats):
-            for kind in ("raw", "lz4", "raw_mapped", "mapped"):
+        for _ in range(0 if a.decode_only else a.repeats):
+            for kind in legs:
                 res["legs"].append(leg(kind))
         ctx.sync()
         ctx.host_unregister(reg_comp)
@@ -159,28 +190,91 @@ def main():
         # the decode alone, device to device, at several block sizes
         res["decode_alone"] = []
         d_out = ctx.device_alloc(raw[0].size + 64)
-        for bb in [int(x) for x in a.decode_blocks.split(",") if x]:
-            blob, d = (comp[0] if bb == block else lz4.pack(raw[0], bb, line_aligned=True, threads=threads))
-            d_in = ctx.device_alloc(blob.size + 64)
-            ctx.h2d(d_in, blob)
+
+        def timed_decode(d_in, blob, d):
             ms = []
             for _ in range(7):
                 got, bad = ctx.lz4_decode_device(d_in, blob.size, d, d_out, raw[0].size)
                 assert got == raw[0].size and bad is None
                 ms.append(ctx.lz4_info()["decode_ms"])
             same = bool((ctx.d2h(np.empty(raw[0].size, dtype=np.uint8), d_out) == raw[0]).all())
-            ctx.device_free(d_in)
             med = statistics.median(ms[2:])
-            res["decode_alone"].append({"block_bytes": bb, "blocks": int(d.shape[0]), "ratio": round(raw[0].size / blob.size, 4),
-                                        "ms": [round(x, 4) for x in ms], "median_ms": round(med, 4),
-                                        "GBs_out": round(raw[0].size / (med * 1e-3) / 1e9, 2),
-                                        "GBs_in": round(blob.size / (med * 1e-3) / 1e9, 2), "output_equal": same})
-            log(json.dumps(res["decode_alone"][-1]))
+            return {"ms": [round(x, 4) for x in ms], "median_ms": round(med, 4),
+                    "GBs_out": round(raw[0].size / (med * 1e-3) / 1e9, 2),
+                    "GBs_in": round(blob.size / (med * 1e-3) / 1e9, 2), "output_equal": same}
+
+        for bb in [int(x) for x in a.decode_blocks.split(",") if x]:
+            blob, d = (comp[0] if bb == block else lz4.pack(raw[0], bb, line_aligned=True, threads=threads))
+            d_in = ctx.device_alloc(blob.size + 64)
+            ctx.h2d(d_in, blob)
+            head = {"block_bytes": bb, "blocks": int(d.shape[0]), "ratio": round(raw[0].size / blob.size, 4)}
+            if a.decoder == "both":   # the two kernels alternated: the crossover table
+                for rep in range(a.repeats):
+                    for name in ("narrow", "wide"):
+                        ctx.lz4_set_decoder(DEC[name])
+                        res["decode_alone"].append(dict(head, decoder=name, round=rep, **timed_decode(d_in, blob, d)))
+                        log(json.dumps(res["decode_alone"][-1]))
+                ctx.lz4_set_decoder(0)
+            else:
+                res["decode_alone"].append(dict(head, decoder=a.decoder, **timed_decode(d_in, blob, d)))
+                log(json.dumps(res["decode_alone"][-1]))
+            ctx.device_free(d_in)
+
+        # a standard frame of 64 KiB blocks (what lz4 -B4 -BI writes): the measure pass, the
+        # descriptors and the decode, device to device (ysb_lz4_decode_blocks_device)
+        res["frame_alone"] = []
+        frame = lz4.frame_pack(raw[0], 65536, threads=threads)
+        index, finfo = lz4.frame_index(frame)
+        d_in = ctx.device_alloc(frame.size + 64)
+        ctx.h2d(d_in, frame)
+        for rep in range(a.repeats if a.decoder == "both" else 1):
+            for name in (("narrow", "wide") if a.decoder == "both" else (a.decoder,)):
+                ctx.lz4_set_decoder(DEC[name])
+                mm, dm = [], []
+                for _ in range(7):
+                    got, bad = ctx.lz4_decode_blocks_device(d_in, index, d_out, raw[0].size)
+                    assert got == raw[0].size and bad is None
+                    fi = ctx.lz4_frame_info()
+                    mm.append(fi["measure_ms"])
+                    dm.append(fi["decode_ms"])
+                same = bool((ctx.d2h(np.empty(raw[0].size, dtype=np.uint8), d_out) == raw[0]).all())
+                m, dd = statistics.median(mm[2:]), statistics.median(dm[2:])
+                res["frame_alone"].append({"decoder": name, "round": rep, "blocks": int(index.size),
+                                           "ratio": round(raw[0].size / frame.size, 4),
+                                           "measure_ms": round(m, 4), "decode_ms": round(dd, 4),
+                                           "measure_GBs_in": round(frame.size / (m * 1e-3) / 1e9, 2),
+                                           "GBs_out": round(raw[0].size / ((m + dd) * 1e-3) / 1e9, 2),
+                                           "decoder_ran": fi["decoder"], "output_equal": same})
+                log(json.dumps(res["frame_alone"][-1]))
+        ctx.lz4_set_decoder(DEC.get(a.decoder, 0))
+        ctx.device_free(d_in)
         ctx.device_free(d_out)
+
+    if a.decode_only or a.decoder == "both":
+        os.makedirs(os.path.dirname(a.frame_out), exist_ok=True)
+        with open(a.frame_out, "w") as f:
+            json.dump({k: res[k] for k in ("events_per_batch", "slot_MB", "compress", "decode_alone", "frame_alone")}, f, indent=1)
+            f.write("\n")
+        if a.decode_only:
+            print(json.dumps({"decode_alone": len(res["decode_alone"]), "frame_alone": len(res["frame_alone"])}), flush=True)
+            return
 
     def summary(kind):
         v = [l["events_per_s"] for l in res["legs"] if l["leg"] == kind]
         return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    if legs != ["raw", "lz4", "raw_mapped", "mapped"]:
+        res["summary"] = {k + "_events_per_s": summary(k) for k in legs}
+        res["summary"]["all_checks_exact"] = all(l["check"]["truth_mismatched_cells"] == 0 and
+                                                 l["check"]["truth_views"] == l["check"]["counted_views"] for l in res["legs"])
+        if "frame" in legs and "raw" in legs:
+            res["summary"]["frame_over_raw_median"] = round(summary("frame")["median"] / summary("raw")["median"], 4)
+            res["summary"]["frame_median_above_raw_max"] = summary("frame")["median"] > summary("raw")["max"]
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps(res["summary"]), flush=True)
+        return
     r, z, rm, zm = summary("raw"), summary("lz4"), summary("raw_mapped"), summary("mapped")
     h2d = statistics.median(l["h2d_GBs"] for l in res["legs"] if l["leg"] == "raw")
     dec = next((x["GBs_out"] for x in res["decode_alone"] if x["block_bytes"] == block), None)
