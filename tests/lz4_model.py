@@ -10,7 +10,9 @@ the format's description, not from csrc/ysb_lz4.h:
     extensions; the block's last sequence ends after its literals;
   * a block is invalid when its input runs out inside a token, an extension, the literals or
     the offset; when an offset is 0 or reaches before the block's first byte; when literals or a
-    match run past raw_bytes; when the block ends with fewer or more than raw_bytes bytes.
+    match run past raw_bytes; when the block ends with fewer or more than raw_bytes bytes;
+  * a block whose raw size nothing records (a standard frame's) is measured by its tokens alone
+    (measure_block): the same rules, 65536 as the cap, the end where the input ends.
 
 Also here: the corpora that the CPU tests (tests/test_lz4_logic.py) and the GPU tests
 (tests/test_gpu_lz4.py) share: hand-assembled blocks, the malformed corpus, periodic and random
@@ -80,6 +82,44 @@ def decode_block(src, raw_bytes):
             raise Bad("the match runs past raw_bytes")
         for _ in range(ml):          # byte by byte: an overlapping match replicates
             out.append(out[-off])
+
+
+def measure_block(src):
+    """The raw size of a compressed block that records none (a frame's block), by its tokens
+    alone: the literal and match lengths add up, no more than MAX_RAW; the block ends where its
+    input does, behind a sequence's literals; Bad for anything else the format forbids."""
+    src = bytes(src)
+    ip = op = 0
+    while True:
+        if ip >= len(src):
+            raise Bad("input exhausted where a token should be")
+        tok = src[ip]
+        ip += 1
+        lit = tok >> 4
+        if lit == 15:
+            ip, lit = _ext(src, ip, lit)
+        if ip + lit > len(src):
+            raise Bad("input exhausted inside the literals")
+        ip += lit
+        op += lit
+        if op > MAX_RAW:
+            raise Bad("literals run past the largest block")
+        if ip == len(src):
+            if op == 0:
+                raise Bad("a block of no bytes")
+            return op
+        if ip + 2 > len(src):
+            raise Bad("input exhausted inside the offset")
+        off = src[ip] | (src[ip + 1] << 8)
+        ip += 2
+        if off == 0 or off > op:
+            raise Bad("offset 0 or before the block's start")
+        ml = tok & 15
+        if ml == 15:
+            ip, ml = _ext(src, ip, ml)
+        op += ml + 4
+        if op > MAX_RAW:
+            raise Bad("a match runs past the largest block")
 
 
 def decode_entry(src, comp_field, raw_bytes):

@@ -62,13 +62,15 @@ def model_raw(comp, field):
     if field & M.STORED:
         return len(comp) if 1 <= len(comp) <= M.MAX_RAW else 0
     try:
-        raw = lz4.measure_block(comp, field)     # the host model (checked against lz4_model on the CPU) ...
+        want = M.measure_block(comp)             # the Python model's walk, written from the format
+    except M.Bad:
+        want = 0
+    try:
+        raw = lz4.measure_block(comp, field)     # the host model (the walk the kernel instantiates) ...
     except YsbError:
-        # (the kernel instantiates the same walk, so "bad" is cross-checked here too: the Python
-        # model accepts the block with none of the sizes a short block could have)
-        assert not any(M.is_valid(comp, r) for r in range(1, min(4 * len(comp) + 20, M.MAX_RAW) + 1, 1 if len(comp) < 64 else 97))
-        return 0
-    assert M.is_valid(comp, raw)                 # ... and the Python model agrees here too
+        raw = 0
+    assert raw == want                           # ... and the Python model agree, on "bad" too
+    assert raw == 0 or M.is_valid(comp, raw)
     return raw
 
 
