@@ -921,6 +921,180 @@ int         ysb_columns_launch_info(ysb_ctx* ctx, ysb_colcount_desc* out);
 /* sizeof(ysb_colcount_desc) as this library writes it. */
 uint64_t    ysb_colcount_desc_size(void);
 
+/* ---- Arrow record batches -----------------------------------------------------------------
+ * The same chain on an Apache Arrow record batch: three columns named ad_id, event_type and
+ * event_time among a struct's children, as the Arrow C data interface hands them over
+ * (pyarrow's _export_to_c / __arrow_c_array__, Arrow Java's Data.exportVectorSchemaRoot).
+ * Additive (the ABI version stays 6).  The two structs below are the specification's own,
+ * under its own guard: a caller that includes Arrow's header first compiles.
+ *
+ * Accepted formats: ad_id `u` / `z`; event_type `u` / `z`, or dictionary-encoded with `i`
+ * (int32) indices and a `u` / `z` dictionary; event_time `u` / `z` (a decimal string, as the
+ * JSON carries it), `l` or `tsm:*` (int64).  Everything else is YSB_ERR_FORMAT, the message
+ * naming the field, its format and the way out.  Every array may be a slice (a nonzero
+ * offset): row i of the batch is element batch.offset + child.offset + i of the child.  A
+ * validity bitmap may be absent (all valid); bit k is bit k % 8 of byte k / 8, at the element
+ * index.  The row rule -- stated once in csrc/ysb_arrow.h, which also holds its host model --
+ * per row, in order: events += 1; a row with a zero validity bit at struct level or in any of
+ * the three columns, a dictionary index outside [0, dict_len), a null dictionary value, or
+ * offsets that break data_first <= off[k] <= off[k+1] <= data_bytes adds 1 to parse_errors and
+ * nothing else (YSB_ERR_DATA at ysb_sync under YSB_F_STRICT); the row is a view iff its
+ * event_type value is exactly the four bytes `view`; the key is the ad_id value's bytes (above
+ * 56 bytes: a join miss; 36 bytes: the cuckoo table, then the general table where that is
+ * partial; other lengths: the general table; a miss is join_misses, foreign_shard on a sharded
+ * context, or with parking the view is parked); joined += 1; an int64 time is taken as it is, a
+ * string time is Long.parseLong's ([+-]?[0-9]+ within int64, at any length), a rejected one
+ * adds 1 to time_errors and counts nothing; bucket = time / time_divisor_ms in Java long
+ * division, counted as the columnar count counts a joined view.  deferred never changes; each
+ * submit adds 1 to batches; n_rows = 0 counts nothing.  The calls never run in record mode,
+ * leave the layout sampling's state alone, and are part of ysb_kernel_time / ysb_path_time
+ * under YSB_F_TIMING.  No byte outside the stated buffers is read, except that an access is
+ * made in whole aligned 32-bit words: the up to three bytes that share a word with a buffer's
+ * first or last byte may be loaded (never used). */
+#ifndef ARROW_C_DATA_INTERFACE
+#define ARROW_C_DATA_INTERFACE
+#define ARROW_FLAG_DICTIONARY_ORDERED 1
+#define ARROW_FLAG_NULLABLE 2
+#define ARROW_FLAG_MAP_KEYS_SORTED 4
+struct ArrowSchema {
+    const char* format;
+    const char* name;
+    const char* metadata;
+    int64_t flags;
+    int64_t n_children;
+    struct ArrowSchema** children;
+    struct ArrowSchema* dictionary;
+    void (*release)(struct ArrowSchema*);
+    void* private_data;
+};
+struct ArrowArray {
+    int64_t length;
+    int64_t null_count;
+    int64_t offset;
+    int64_t n_buffers;
+    int64_t n_children;
+    const void** buffers;
+    struct ArrowArray** children;
+    struct ArrowArray* dictionary;
+    void (*release)(struct ArrowArray*);
+    void* private_data;
+};
+#endif
+
+#define YSB_ARROW_STRING 1u   /* `u` / `z`: int32 offsets and bytes             */
+#define YSB_ARROW_INT64  2u   /* `l` / `tsm:*`: int64 values (event_time)       */
+#define YSB_ARROW_DICT   3u   /* int32 indices into a string dictionary (event_type) */
+
+/* Where the three columns are in a struct schema, and how each is stored. */
+typedef struct ysb_arrow_binding {
+    int64_t  n_children;     /* of the schema bound                              */
+    int64_t  child[3];       /* ad_id, event_type, event_time                    */
+    uint32_t kind[3];        /* YSB_ARROW_*                                      */
+    uint32_t reserved;
+} ysb_arrow_binding;
+/* Host, no context (messages: ysb_last_error(NULL), the thread's).  Finds the three fields by
+ * name among the children of a struct schema (`+s`), checks their formats, records the child
+ * indices and kinds.  Never calls release.  YSB_ERR_FORMAT as above, YSB_ERR_ARG for NULL. */
+int         ysb_arrow_bind(const struct ArrowSchema* schema, ysb_arrow_binding* out);
+uint64_t    ysb_arrow_binding_size(void);
+
+/* One column as the count reads it.  Strings: int32 `offsets` (element k's bytes are
+ * [off[k], off[k+1])) and `data`, which holds the bytes from offset data_first on (so byte x is
+ * data[x - data_first]; 0 for a whole buffer) up to data_bytes, the buffer's stated end:
+ * offsets outside [data_first, data_bytes] make their row invalid and are never followed.
+ * YSB_ARROW_INT64 / _DICT: `data` holds the int64 values / int32 indices, data_bytes their
+ * stated size (at least (offset + n_rows) elements).  validity: the bitmap or NULL.  offset:
+ * the element of row 0 in offsets / values, validity_offset: its bit in the bitmap (for an
+ * Arrow child both are batch.offset + child.offset; the host form's packed copy keeps only
+ * the rows' elements and the bitmap bytes that cover them, so there they differ). */
+typedef struct ysb_arrow_col {
+    uint32_t kind;           /* YSB_ARROW_*                                      */
+    uint32_t data_first;
+    const uint8_t* validity;
+    const uint8_t* offsets;
+    const uint8_t* data;
+    uint64_t data_bytes;
+    uint64_t offset;
+    uint64_t validity_offset;
+} ysb_arrow_col;
+typedef struct ysb_arrow_cols {
+    uint64_t n_rows;
+    const uint8_t* validity; /* struct level, or NULL                            */
+    uint64_t offset;         /* ... its element of row 0 (batch.offset)          */
+    ysb_arrow_col col[3];    /* ad_id, event_type, event_time                    */
+    ysb_arrow_col dict;      /* event_type's dictionary (kind[1] == YSB_ARROW_DICT): a string
+                                column whose element `offset + index` is the value */
+    uint64_t dict_len;
+} ysb_arrow_cols;
+uint64_t    ysb_arrow_cols_size(void);
+
+/* The host form, double-buffered like ysb_submit_columns.  Only what the rows need is copied
+ * into the slot's pinned buffer, each range at a 16-byte boundary: offsets [o, o + n] of each
+ * string column, the data bytes between the first and last of those offsets, the bitmap bytes
+ * that cover the rows, the int64 times or the indices of the rows, the dictionary's offsets and
+ * bytes (the plan: csrc/ysb_arrow.h arrow_plan).  The Arrow C data interface states no data
+ * size, so a string column's bounds are its first and last offset.  The bytes go to the device
+ * by the context's H2D path and the count launches behind the copy on the compute stream.
+ * Never calls release; the caller keeps the batch alive until ysb_wait(ctx, slot).
+ * YSB_ERR_CAPACITY if the planned bytes exceed max_batch_bytes; YSB_ERR_ARG for a NULL offsets
+ * or data buffer on a non-empty column, n_children not matching the binding, a negative length
+ * or offset, length > 2^31 - 1, a child shorter than the batch, a last offset below the first;
+ * YSB_ERR_STATE without an ad map or while a frame carry is pending. */
+int         ysb_submit_arrow(ysb_ctx* ctx, int slot, const ysb_arrow_binding* binding,
+                             const struct ArrowArray* batch);
+/* The device form: every pointer is device memory at any alignment.  Asynchronous on the
+ * compute stream, behind everything submitted, like ysb_submit_columns_device.  YSB_ERR_ARG
+ * for unknown kinds, a NULL buffer on a non-empty column, n_rows > 2^31 - 1, data_first >
+ * data_bytes, string data above 2^31 bytes, fixed-width data shorter than its rows;
+ * YSB_ERR_CAPACITY for a dictionary above 2^30 - 2 values; YSB_ERR_STATE as above. */
+int         ysb_submit_arrow_device(ysb_ctx* ctx, const ysb_arrow_cols* cols);
+/* The host form's copy plan (host, no context; csrc/ysb_arrow.h arrow_plan): the only bytes of
+ * a batch that ysb_submit_arrow touches, as ranges {src, bytes, dst} -- dst the range's place in
+ * the packed image, a multiple of 16 --, col 0..2 the column, 3 the dictionary, 4 the struct's
+ * bitmap, what 0 a bitmap, 1 offsets, 2 data / values.  *n <- their number, *total <- the packed
+ * image's bytes; YSB_ERR_CAPACITY if cap (in ranges) is short.  ysb_arrow_pack makes the packed
+ * image in host memory (cap bytes; YSB_ERR_CAPACITY with too few) and *packed the batch as it
+ * lies there; ysb_arrow_view is the whole batch in place (nothing copied; a string column's
+ * data ends at its array's last offset).  Errors as ysb_submit_arrow's argument errors. */
+typedef struct ysb_arrow_range {
+    const uint8_t* src;
+    uint64_t bytes;
+    uint64_t dst;
+    uint32_t col;
+    uint32_t what;
+} ysb_arrow_range;
+int         ysb_arrow_plan(const ysb_arrow_binding* binding, const struct ArrowArray* batch,
+                           ysb_arrow_range* ranges, uint64_t cap, uint64_t* n, uint64_t* total);
+int         ysb_arrow_pack(const ysb_arrow_binding* binding, const struct ArrowArray* batch,
+                           uint8_t* image, uint64_t cap, ysb_arrow_cols* packed);
+int         ysb_arrow_view(const ysb_arrow_binding* binding, const struct ArrowArray* batch,
+                           ysb_arrow_cols* out);
+/* The host model of the row rule over host buffers (csrc/ysb_arrow.h arrow_count_rows): no
+ * context, no GPU.  The map: n_keys keys, key i the bytes keys[key_off[i], key_off[i + 1]) with
+ * campaign[i] (later entries win).  stats[8] <- events, views, joined, join_misses,
+ * parse_errors, time_errors, foreign_shard, 0; invalid[3] <- invalid rows by cause (null,
+ * offsets, dictionary index); cells <- up to cap triples {campaign, bucket, count}, *n_cells
+ * their number (YSB_ERR_CAPACITY if cap is short). */
+int         ysb_arrow_count_host(const ysb_arrow_cols* cols, const uint8_t* keys, const uint32_t* key_off,
+                                 const uint32_t* campaign, uint64_t n_keys, int64_t divisor,
+                                 uint32_t shard_rank, uint32_t shard_n, uint64_t stats[8],
+                                 uint64_t invalid[3], int64_t* cells, uint64_t cap, uint64_t* n_cells);
+/* The last Arrow launch (n_rows > 0); waits for it.  resident_grid: the largest grid a launch
+ * takes (a batch of more than 64 * resident_grid rows makes workgroups take several tiles);
+ * per_lane_tiles: tiles that did not go through the staged path. */
+typedef struct ysb_arrow_desc {
+    uint64_t rows, tiles;
+    uint32_t grid, resident_grid;
+    uint64_t per_lane_tiles;
+    uint64_t invalid_null, invalid_offsets, invalid_dict;
+    uint32_t kind[3];
+    uint32_t lds_counters;
+    uint32_t hbm_table;
+    uint32_t reserved;
+} ysb_arrow_desc;
+int         ysb_arrow_launch_info(ysb_ctx* ctx, ysb_arrow_desc* out);
+uint64_t    ysb_arrow_desc_size(void);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* With YSB_F_TIMING: total device time of the scan kernel launches (HIP events on
  * the compute stream) and the number of launches since the last call (resets). */

@@ -405,6 +405,11 @@ struct ysb_ctx {
     // columnar count (ysb_columns.cpp): the last columnar launch (ysb_columns_launch_info)
     ysb_colcount_desc last_col{};
     bool col_launched = false;
+    // Arrow count (ysb_arrow_api.cpp): the last Arrow launch (ysb_arrow_launch_info) and its device
+    // counters {per-lane tiles, rows invalid by null / offsets / dictionary index}
+    ysb_arrow_desc last_arrow{};
+    bool arrow_launched = false;
+    DevBuf<unsigned long long> d_arrow_info;
 };
 
 // One host -> device copy of a slot: the source's device address (the copy kernel) and its

@@ -293,6 +293,36 @@ void launch_colcount_level(const ColCountParams& p, hipStream_t s);
 // Sets ring[0..1] from the batch's first 256 rows if ring[1] == 0 (launch_ring_autobase's rule).
 void launch_colcount_autobase(const ColCountParams& p, hipStream_t s);
 
+// Arrow count (ysb_count_arrow.h, ysb_submit_arrow*; the row rule: ysb_arrow.h): rows
+// [0, n_rows) of a batch of three Arrow columns through filter, join and window count.  Column
+// c is 0 ad_id, 1 event_type, 2 event_time, 3 event_type's dictionary; every pointer is device
+// memory at any alignment.  sp as for ColCountParams.  info[4] (zero before the launch) +=
+// tiles on the per-lane path, rows invalid by null / offsets / dictionary index.
+struct ArrowCountParams {
+    ScanParams sp;
+    u64 n_rows;
+    u64 n_tiles;                // ceil(n_rows / TILE_LINES)
+    const u8* sval;             // the struct's bitmap (or null) ...
+    u64 sval_off;               // ... and row 0's bit in it
+    const u8* val[4];           // the column's bitmap (or null) ...
+    u64 val_off[4];             // ... and row 0's (dictionary: value 0's) bit in it
+    const u8* offs[4];          // a string column's int32 offsets ...
+    u64 elem[4];                // ... and row 0's (value 0's) element in them / in the values
+    const u8* data[4];          // a string column's bytes from offset first[c] on; the int64 times; the int32 indices
+    u32 first[4], end[4];       // string data: the offsets a value may have, [first, end]
+    u32 type_dict;              // 1: event_type is dictionary-encoded
+    u32 time_i64;               // 1: event_time is int64
+    u32 dict_len;
+    unsigned long long* info;
+};
+void launch_arrowcount(const ArrowCountParams& p, int cus, hipStream_t s, const ParkParams* park = nullptr);
+// Right behind it: *sp.used_out <- the out-of-ring map's fill level (nothing if used_out is null).
+void launch_arrowcount_level(const ArrowCountParams& p, hipStream_t s);
+// Sets ring[0..1] from the batch's first 256 rows if ring[1] == 0 (launch_ring_autobase's rule).
+void launch_arrowcount_autobase(const ArrowCountParams& p, hipStream_t s);
+// the largest grid launch_arrowcount takes on a device of `cus` compute units
+u32 arrowcount_resident_grid(int cus);
+
 // Generator kernels (ysb_gen.hip).
 hipError_t gen_events_device(const GenSpec& spec, u64 first, u64 n, u8* d_out, u64 cap,
                              u32* d_off, u64* nbytes, hipStream_t s);

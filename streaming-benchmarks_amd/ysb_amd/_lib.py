@@ -287,6 +287,68 @@ SIGNATURES = {
     "ysb_gen_dump_shards": (_I, [C.POINTER(YsbGenParams), _U64, C.c_char_p, _U32]),
 }
 
+
+
+class ArrowSchema(C.Structure):
+    """struct ArrowSchema of the Arrow C data interface."""
+
+
+ArrowSchema._fields_ = [("format", C.c_char_p), ("name", C.c_char_p), ("metadata", C.c_char_p), ("flags", C.c_int64),
+                        ("n_children", C.c_int64), ("children", C.POINTER(C.POINTER(ArrowSchema))),
+                        ("dictionary", C.POINTER(ArrowSchema)), ("release", C.c_void_p), ("private_data", C.c_void_p)]
+
+
+class ArrowArray(C.Structure):
+    """struct ArrowArray of the Arrow C data interface."""
+
+
+ArrowArray._fields_ = [("length", C.c_int64), ("null_count", C.c_int64), ("offset", C.c_int64), ("n_buffers", C.c_int64),
+                       ("n_children", C.c_int64), ("buffers", C.POINTER(C.c_void_p)),
+                       ("children", C.POINTER(C.POINTER(ArrowArray))), ("dictionary", C.POINTER(ArrowArray)),
+                       ("release", C.c_void_p), ("private_data", C.c_void_p)]
+
+
+class YsbArrowBinding(C.Structure):
+    _fields_ = [("n_children", C.c_int64), ("child", C.c_int64 * 3), ("kind", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
+class YsbArrowCol(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("data_first", C.c_uint32), ("validity", C.c_void_p), ("offsets", C.c_void_p),
+                ("data", C.c_void_p), ("data_bytes", C.c_uint64), ("offset", C.c_uint64), ("validity_offset", C.c_uint64)]
+
+
+class YsbArrowCols(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("validity", C.c_void_p), ("offset", C.c_uint64), ("col", YsbArrowCol * 3),
+                ("dict", YsbArrowCol), ("dict_len", C.c_uint64)]
+
+
+class YsbArrowRange(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("bytes", C.c_uint64), ("dst", C.c_uint64), ("col", C.c_uint32), ("what", C.c_uint32)]
+
+
+class YsbArrowDesc(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("tiles", C.c_uint64), ("grid", C.c_uint32), ("resident_grid", C.c_uint32),
+                ("per_lane_tiles", C.c_uint64), ("invalid_null", C.c_uint64), ("invalid_offsets", C.c_uint64),
+                ("invalid_dict", C.c_uint64), ("kind", C.c_uint32 * 3), ("lds_counters", C.c_uint32),
+                ("hbm_table", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SIGNATURES.update({
+    "ysb_arrow_bind": (_I, [C.POINTER(ArrowSchema), C.POINTER(YsbArrowBinding)]),
+    "ysb_arrow_binding_size": (_U64, []),
+    "ysb_arrow_cols_size": (_U64, []),
+    "ysb_arrow_desc_size": (_U64, []),
+    "ysb_arrow_plan": (_I, [C.POINTER(YsbArrowBinding), C.POINTER(ArrowArray), C.POINTER(YsbArrowRange), _U64,
+                            C.POINTER(_U64), C.POINTER(_U64)]),
+    "ysb_arrow_pack": (_I, [C.POINTER(YsbArrowBinding), C.POINTER(ArrowArray), C.c_void_p, _U64, C.POINTER(YsbArrowCols)]),
+    "ysb_arrow_view": (_I, [C.POINTER(YsbArrowBinding), C.POINTER(ArrowArray), C.POINTER(YsbArrowCols)]),
+    "ysb_arrow_count_host": (_I, [C.POINTER(YsbArrowCols), C.c_void_p, C.c_void_p, C.c_void_p, _U64, _I64, _U32, _U32,
+                                  C.POINTER(_U64), C.POINTER(_U64), C.c_void_p, _U64, C.POINTER(_U64)]),
+    "ysb_submit_arrow": (_I, [_P, _I, C.POINTER(YsbArrowBinding), C.POINTER(ArrowArray)]),
+    "ysb_submit_arrow_device": (_I, [_P, C.POINTER(YsbArrowCols)]),
+    "ysb_arrow_launch_info": (_I, [_P, C.POINTER(YsbArrowDesc)]),
+})
+
 ABI_VERSION = 6   # include/ysb_hip.h YSB_ABI_VERSION this binding is written against
 
 _lib = None
@@ -326,7 +388,8 @@ def lib():
                               % (L.ysb_colcount_desc_size(), C.sizeof(YsbColcountDesc)))
         for fn, st in ((L.ysb_upsert_info_size, YsbUpsertInfo), (L.ysb_admap_desc_size, YsbAdmapDesc),
                        (L.ysb_parked_info_size, YsbParkedDesc), (L.ysb_lz4_desc_size, YsbLz4Desc),
-                       (L.ysb_lz4_frame_desc_size, YsbLz4FrameDesc)):
+                       (L.ysb_lz4_frame_desc_size, YsbLz4FrameDesc), (L.ysb_arrow_binding_size, YsbArrowBinding),
+                       (L.ysb_arrow_cols_size, YsbArrowCols), (L.ysb_arrow_desc_size, YsbArrowDesc)):
             if fn() != C.sizeof(st):
                 raise ImportError("%s is %d bytes in the library, %d in this binding"
                                   % (st.__name__, fn(), C.sizeof(st)))

@@ -488,6 +488,38 @@ class YsbContext:
         self._c(lib().ysb_columns_launch_info(self._h, C.byref(d)))
         return {n: getattr(d, n) for n, _ in _lib.YsbColcountDesc._fields_}
 
+    # -- Arrow record batches ------------------------------------------------------------
+    def submit_arrow(self, batch, slot=0, binding=None):
+        """ysb_submit_arrow: the host form.  batch: an object with __arrow_c_array__ (the
+        PyCapsule protocol), a pyarrow RecordBatch (_export_to_c), or ysb_amd.arrow.batch()'s
+        output.  Only the rows' bytes are copied.  The batch is kept alive until wait(slot) or
+        the slot's next submit_arrow; returns the binding (pass it back for the next batch of
+        the same schema)."""
+        from . import arrow
+        ex = arrow.export(batch)
+        if binding is None:
+            binding = arrow.bind(ex.schema)
+        self._c(lib().ysb_submit_arrow(self._h, slot, C.byref(binding), C.byref(ex.array)))
+        if not hasattr(self, "_arrow_live"):
+            self._arrow_live = {}
+        self._arrow_live[slot] = ex
+        return binding
+
+    def submit_arrow_device(self, cols):
+        """ysb_submit_arrow_device: a ysb_arrow_cols (ysb_amd.arrow.cols) of device pointers at any
+        alignment.  Asynchronous on the compute stream."""
+        self._c(lib().ysb_submit_arrow_device(self._h, C.byref(cols)))
+
+    def arrow_launch_info(self):
+        """The last Arrow launch (ysb_arrow_launch_info; waits for it): rows, tiles, grid,
+        resident_grid, per_lane_tiles, invalid_null / _offsets / _dict, kind, lds_counters,
+        hbm_table.  Raises YSB_ERR_STATE before the first one."""
+        d = _lib.YsbArrowDesc()
+        self._c(lib().ysb_arrow_launch_info(self._h, C.byref(d)))
+        out = {n: getattr(d, n) for n, _ in _lib.YsbArrowDesc._fields_ if n != "reserved"}
+        out["kind"] = tuple(d.kind)
+        return out
+
     # -- results -----------------------------------------------------------------------
     def drain(self, bucket_lo=INT64_MIN, bucket_hi=(1 << 63) - 1, clear=False):
         """Returns {(campaign, window_ms): count} for buckets in [bucket_lo, bucket_hi)."""
