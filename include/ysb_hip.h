@@ -921,6 +921,80 @@ int         ysb_columns_launch_info(ysb_ctx* ctx, ysb_colcount_desc* out);
 /* sizeof(ysb_colcount_desc) as this library writes it. */
 uint64_t    ysb_colcount_desc_size(void);
 
+/* ---- joined views ------------------------------------------------------------------------
+ * The third boundary inside the chain DeserializeBolt -> EventFilterBolt -> project ->
+ * RedisJoinBolt -> keyBy -> CampaignProcessor (AdvertisingTopologyNative.java:111-119): after
+ * the join.  RedisJoinBolt.flatMap (:460-474) emits a Tuple3(campaign_id, ad_id, event_time) for
+ * every view whose ad is in the map; ysb_join_device gives that stream for one device batch, in
+ * HBM and in stream order, as columns -- what a caller's own keyed operator consumes (another
+ * window size, a session window, a per-ad count, a sink of joined tuples).  Additive: nothing of
+ * the counting path is touched and the ABI version stays 6.
+ *
+ * Row i of the batch yields an output row iff the reference would not throw on it before the
+ * join (the counting path's rule: the line parses and getString of the required keys succeeds,
+ * YSB_F_REQUIRE_IP honoured; .tbl rows: the row split's rule), its event_type is exactly "view"
+ * after unescaping, and its decoded ad_id is in the context's device tables as they are at the
+ * call -- earlier ysb_ad_map_upsert calls apply; every table layout is covered (cache-resident
+ * cuckoo slots, the HBM bucket table, the general table for ids that are not 36 bytes, sharded
+ * loads).  Output rows are in ascending source row; nothing else is emitted.  A joined view
+ * whose event_time Long.parseLong rejects is still emitted, as the reference parses the time only
+ * after the join (CampaignProcessorCommon.java:58): time_ok = 0, event_time = 0, one time_error.
+ *
+ * The columns of a buffer for cap_rows rows (host function, no context), each starting on a
+ * 4096-byte page like the columnar decode's: 0 campaign (u32, the campaign index), 1 row (u32,
+ * the line's index in the batch), 2 event_time (int64, little-endian), 3 time_ok (u8) and, with
+ * YSB_JOIN_KEYS, 4 key (56-byte stride: the decoded ad_id in the join tables' own key form,
+ * zero-padded, as ysb_parked_keys returns it) and 5 key_len (u8).  start[j] is column j's byte
+ * offset, start[6] the whole size; a column the flags leave out has width 0 and starts where
+ * the next one does.  cap_rows = 0 is legal (an empty buffer).  YSB_ERR_ARG for unknown flags
+ * or cap_rows above 2^32 - 1. */
+#define YSB_JOIN_KEYS 0x1u       /* also the key and key_len columns */
+typedef struct ysb_joined_layout {
+    uint64_t cap_rows;
+    uint64_t start[7];
+    uint32_t width[6];      /* 4,4,8,1,56,1 (0 for a column the flags leave out)     */
+    uint32_t flags;
+    uint32_t n_cols;        /* 4, or 6 with YSB_JOIN_KEYS                            */
+} ysb_joined_layout;
+int         ysb_joined_layout_of(uint64_t cap_rows, uint32_t flags, ysb_joined_layout* out);
+
+/* By definition events .. foreign_shard equal the change in ysb_stats that ysb_submit_device of
+ * the same batch would have made (on a context that does not park). */
+typedef struct ysb_join_info {
+    uint64_t events, views, joined, join_misses, parse_errors, time_errors, foreign_shard;
+    uint64_t rows_written;  /* min(joined, cap_rows)                                 */
+    uint64_t fast_rows;     /* lines the kernel's fast tier took                     */
+    uint64_t tiles;         /* 64-line tiles of the batch                            */
+    uint32_t grid;          /* workgroups of the join kernel in this call ...        */
+    uint32_t max_grid;      /* ... and the most it launches on this device: each
+                               workgroup takes tiles grid apart                      */
+    double   join_ms, prefix_ms, pack_ms;   /* the three kernels (HIP event pairs)   */
+} ysb_join_info;
+/* One device batch (as for ysb_submit_device: d_bytes 16-byte aligned, < 4 GiB, n_events u32
+ * line offsets; the context's YSB_F_FORMAT_TBL decides the format) through filter and join into
+ * d_out, a 16-byte aligned HBM buffer of ysb_joined_layout_of(cap_rows, flags).start[6] bytes.
+ * Only rows < joined of each column are written; the rest of d_out keeps what it held.  If
+ * joined > cap_rows the first cap_rows rows are written, info is complete and the call returns
+ * YSB_ERR_CAPACITY; cap_rows = n_events always suffices.  n_events = 0 is legal and writes
+ * nothing.
+ *   Runs on the compute stream behind everything submitted, then waits.  It leaves the ring, the
+ * side list, ysb_stats, the parked log and the layout sampling's state alone, and it never
+ * parks: a miss is a miss, or foreign_shard on a sharded context.
+ *   Three kernels, none waiting for another's workgroups: the join writes each 64-line tile's
+ * joined rows to a context-owned scratch area, a prefix over the tiles' counts places them, a
+ * pack moves them into the columns.  The scratch area is allocated on first use, reused and
+ * freed with the context: at most 16 bytes per line of the batch (rounded up to whole tiles)
+ * without YSB_JOIN_KEYS, at most 80 with it.
+ *   YSB_ERR_ARG for unknown flags, NULL buffers, a misaligned d_bytes or d_out; YSB_ERR_CAPACITY
+ * for a batch above 4 GiB or n_events above max_batch_events; YSB_ERR_STATE without an ad map
+ * and after ysb_group_init.  info may be NULL. */
+int         ysb_join_device(ysb_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes,
+                            const uint32_t* d_line_off, uint64_t n_events,
+                            uint8_t* d_out, uint64_t cap_rows, uint32_t flags,
+                            ysb_join_info* info);
+/* sizeof(ysb_join_info) as this library writes it. */
+size_t      ysb_join_info_size(void);
+
 /* ---- Arrow record batches -----------------------------------------------------------------
  * The same chain on an Apache Arrow record batch: three columns named ad_id, event_type and
  * event_time among a struct's children, as the Arrow C data interface hands them over

@@ -4,6 +4,8 @@
 //   ysb_submit.cpp  segments into launches: slots, device batches, the layout samples, the scan launch
 //   ysb_raw.cpp     batches that cross PCIe into a slot and launch a call later (raw, mapped, LZ4)
 //   ysb_columns.cpp the columnar decode and the columnar count's submits
+//   ysb_join_api.cpp the join's output as ordered columns (its layout, scratch format and plan:
+//                   ysb_join.h, no HIP: tests/native/join_logic.cpp)
 //   ysb_layout.h    the layout sampling's rules (no HIP: tests/native/layout_logic.cpp)
 //   ysb_admap.h     the join tables as host data and the live map's rules (no HIP:
 //                   tests/native/admap_logic.cpp, upsert_logic.cpp)
@@ -402,6 +404,12 @@ struct ysb_ctx {
     // columnar decode (ysb_columns.cpp): {valid rows, fast-tier rows} of a call, its event pair
     DevBuf<unsigned long long> d_colinfo;
     Event ev_col[2];
+    // joined views (ysb_join_api.cpp; ysb_join.h): the scratch area between the three launches --
+    // the tiles' blocks, their counts, the prefix; grown on first use --, a call's tallies (the
+    // scan's ST_COUNT_ u64, then the fast tier's rows) and the events around its kernels
+    DevBuf<u8> d_join_scratch;
+    DevBuf<unsigned long long> d_join_info;
+    Event ev_join[4];
     // columnar count (ysb_columns.cpp): the last columnar launch (ysb_columns_launch_info)
     ysb_colcount_desc last_col{};
     bool col_launched = false;

@@ -293,6 +293,29 @@ void launch_colcount_level(const ColCountParams& p, hipStream_t s);
 // Sets ring[0..1] from the batch's first 256 rows if ring[1] == 0 (launch_ring_autobase's rule).
 void launch_colcount_autobase(const ColCountParams& p, hipStream_t s);
 
+// Joined views as ordered columns (ysb_scan_join.h, ysb_join_device; the layout, the scratch
+// format and the plan: ysb_join.h).  b: the batch as a columnar decode gets it, out the joined
+// layout's buffer, start[0..5] its columns; sp: the context's join tables, with stats pointing
+// at the call's own tallies (ST_COUNT_ u64 as the scan fills them, then the fast tier's rows).
+// Three launches on s: the tiles' joined rows into scratch, the prefix over their counts, the
+// rows into out.  Only rows < min(joined, cap_rows) of each column are written.
+struct JoinParams {
+    ScanParams sp;
+    ColParams b;
+    u8* scratch;                // join_scratch_bytes(b.n, flags) bytes, 16-byte aligned
+    u32* tile_count;            // [b.n_tiles] inside scratch
+    u32* prefix;                // [b.n_tiles] behind them
+    u64 cap_rows;
+    u32 keys;                   // 1: YSB_JOIN_KEYS
+};
+void launch_join(const JoinParams& p, int cus, hipStream_t s);
+void launch_join_prefix(const JoinParams& p, hipStream_t s);
+void launch_join_pack(const JoinParams& p, int cus, hipStream_t s);
+// join_kernel's workgroups for a batch of n_tiles tiles, and the most it launches on a device of
+// `cus` compute units (each workgroup walks tiles blockIdx.x + k * grid)
+u32 join_grid(u64 n_tiles, int cus, bool tbl);
+u32 join_max_grid(int cus, bool tbl);
+
 // Arrow count (ysb_count_arrow.h, ysb_submit_arrow*; the row rule: ysb_arrow.h): rows
 // [0, n_rows) of a batch of three Arrow columns through filter, join and window count.  Column
 // c is 0 ad_id, 1 event_type, 2 event_time, 3 event_type's dictionary; every pointer is device

@@ -1312,3 +1312,4 @@ int scan_lds_bytes() { return LDS_BYTES; }
 #include "ysb_scan_columns.h"
 #include "ysb_count_columns.h"
 #include "ysb_count_arrow.h"
+#include "ysb_scan_join.h"

@@ -3,9 +3,9 @@
 The compute path is libysb_hip.so (HIP kernels for gfx950, C ABI in include/ysb_hip.h);
 this package only binds it.  There is no CPU fallback.
 """
-from ._lib import LIB_PATH, YSB_COL_JAVA_ORDER, YSB_COL_VALIDITY, YsbError, lib  # noqa: F401
+from ._lib import LIB_PATH, YSB_COL_JAVA_ORDER, YSB_COL_VALIDITY, YSB_JOIN_KEYS, YsbError, lib  # noqa: F401
 from .admap import AdCampaignMap  # noqa: F401
-from .context import YsbContext, columns_layout, columns_read_ranges, device_count, device_sync, rank_device  # noqa: F401
+from .context import YsbContext, columns_layout, columns_read_ranges, device_count, device_sync, joined_columns, joined_layout, rank_device  # noqa: F401
 from . import lz4  # noqa: F401
 from .source import FileBasedDataSource, Lz4FileDataSource  # noqa: F401
 from .generator import (AD_TYPES, EVENT_TYPES, GEN_COMPACT, GEN_MIXED, GEN_MIXED_BLOCKS, GEN_MORE_AD_TYPES, GEN_RANDOM_IP, GEN_REORDER,  # noqa: F401

@@ -111,6 +111,21 @@ class YsbColcountDesc(C.Structure):
                 ("java_order", C.c_uint32), ("validity", C.c_uint32)]
 
 
+YSB_JOIN_KEYS = 0x1
+
+
+class YsbJoinedLayout(C.Structure):
+    _fields_ = [("cap_rows", C.c_uint64), ("start", C.c_uint64 * 7), ("width", C.c_uint32 * 6),
+                ("flags", C.c_uint32), ("n_cols", C.c_uint32)]
+
+
+class YsbJoinInfo(C.Structure):
+    _fields_ = ([(n, C.c_uint64) for n in ("events", "views", "joined", "join_misses", "parse_errors", "time_errors",
+                                           "foreign_shard", "rows_written", "fast_rows", "tiles")]
+                + [("grid", C.c_uint32), ("max_grid", C.c_uint32)]
+                + [(n, C.c_double) for n in ("join_ms", "prefix_ms", "pack_ms")])
+
+
 class YsbUpsertInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("entries", "foreign", "duplicates", "updated", "inserted", "cuckoo_first",
                                           "cuckoo_second", "cuckoo_moved", "cuckoo_left_out")] + [
@@ -240,6 +255,9 @@ SIGNATURES = {
     "ysb_submit_columns": (_I, [_P, _I, _PU8, _U64, _U64, _U32]),
     "ysb_columns_launch_info": (_I, [_P, C.POINTER(YsbColcountDesc)]),
     "ysb_colcount_desc_size": (_U64, []),
+    "ysb_joined_layout_of": (_I, [_U64, _U32, C.POINTER(YsbJoinedLayout)]),
+    "ysb_join_device": (_I, [_P, _PU8, _U64, _PU32, _U64, _PU8, _U64, _U32, C.POINTER(YsbJoinInfo)]),
+    "ysb_join_info_size": (C.c_size_t, []),
     "ysb_sync": (_I, [_P]),
     "ysb_drain": (_I, [_P, _I64, _I64, _I, C.POINTER(YsbCount), _U64, C.POINTER(_U64)]),
     "ysb_stats_get": (_I, [_P, C.POINTER(YsbStats)]),
@@ -389,7 +407,8 @@ def lib():
         for fn, st in ((L.ysb_upsert_info_size, YsbUpsertInfo), (L.ysb_admap_desc_size, YsbAdmapDesc),
                        (L.ysb_parked_info_size, YsbParkedDesc), (L.ysb_lz4_desc_size, YsbLz4Desc),
                        (L.ysb_lz4_frame_desc_size, YsbLz4FrameDesc), (L.ysb_arrow_binding_size, YsbArrowBinding),
-                       (L.ysb_arrow_cols_size, YsbArrowCols), (L.ysb_arrow_desc_size, YsbArrowDesc)):
+                       (L.ysb_arrow_cols_size, YsbArrowCols), (L.ysb_arrow_desc_size, YsbArrowDesc),
+                       (L.ysb_join_info_size, YsbJoinInfo)):
             if fn() != C.sizeof(st):
                 raise ImportError("%s is %d bytes in the library, %d in this binding"
                                   % (st.__name__, fn(), C.sizeof(st)))

@@ -54,6 +54,30 @@ def columns_read_ranges(rows, n_rows, flags=0):
     return [(int(off[i]), int(nb[i])) for i in range(n.value)]
 
 
+def joined_layout(cap_rows, flags=0):
+    """ysb_joined_layout_of: the columns ysb_join_device writes for cap_rows rows, as a dict:
+    cap_rows, start (7 byte offsets: campaign, row, event_time, time_ok, key, key_len, [6] the
+    total), width (6; 0 for a column the flags leave out), flags, n_cols."""
+    lay = _lib.YsbJoinedLayout()
+    check(lib().ysb_joined_layout_of(int(cap_rows), int(flags), C.byref(lay)), None)
+    return {"cap_rows": lay.cap_rows, "start": [int(v) for v in lay.start], "width": [int(v) for v in lay.width],
+            "flags": lay.flags, "n_cols": lay.n_cols}
+
+
+def joined_columns(image, lay, rows):
+    """Rows [0, rows) of the columns of a joined_layout buffer copied to host memory (a uint8
+    array), as a dict of numpy arrays."""
+    st = lay["start"]
+    out = {"campaign": image[st[0]:st[0] + 4 * rows].view("<u4").copy(),
+           "row": image[st[1]:st[1] + 4 * rows].view("<u4").copy(),
+           "event_time": image[st[2]:st[2] + 8 * rows].view("<i8").copy(),
+           "time_ok": image[st[3]:st[3] + rows].copy()}
+    if lay["flags"] & _lib.YSB_JOIN_KEYS:
+        out["key"] = image[st[4]:st[4] + 56 * rows].reshape(rows, 56).copy()
+        out["key_len"] = image[st[5]:st[5] + rows].copy()
+    return out
+
+
 def rank_device(local_rank, n_visible):
     """The device a rank uses (one context per GPU): its LOCAL_RANK, unless the launcher left
     each process fewer visible devices (e.g. one per rank through HIP_VISIBLE_DEVICES): then
@@ -461,6 +485,54 @@ class YsbContext:
         words = image[columns_layout(rows)["start"][7]:][:8 * ((n + 63) // 64)].view("<u8")
         valid = ((words[np.arange(n) // 64] >> (np.arange(n) % 64).astype(np.uint64)) & np.uint64(1)).astype(np.bool_)
         return image, valid, info
+
+    # -- joined views ------------------------------------------------------------------
+    def join_device(self, d_bytes, nbytes, d_off, n, d_out, cap_rows, flags=0):
+        """ysb_join_device: the joined views of lines [0, n) of a device batch -- RedisJoinBolt's
+        Tuple3 stream (AdvertisingTopologyNative.java:460-474) -- in source order as the columns
+        of d_out (joined_layout(cap_rows, flags)["start"][6] bytes of HBM).  Returns the info as
+        a dict: events, views, joined, join_misses, parse_errors, time_errors, foreign_shard,
+        rows_written, fast_rows, tiles, grid, max_grid, join_ms, prefix_ms, pack_ms.  With more
+        joined views than cap_rows the first cap_rows rows are written and the YsbError
+        (YSB_ERR_CAPACITY) raised carries the complete dict as its `info`."""
+        info = _lib.YsbJoinInfo()
+        rc = lib().ysb_join_device(self._h, C.c_void_p(d_bytes), nbytes, C.c_void_p(d_off), n, C.c_void_p(d_out),
+                                   int(cap_rows), int(flags), C.byref(info))
+        out = {k: getattr(info, k) for k, _ in _lib.YsbJoinInfo._fields_}
+        try:
+            self._c(rc)
+        except _lib.YsbError as e:
+            if e.code == -4 and out["joined"] > int(cap_rows):
+                e.info = out
+            raise
+        return out
+
+    def join(self, data, offsets, keys=False, cap_rows=None):
+        """Host batch (bytes / uint8 array + uint32 line offsets) joined on the device: allocates,
+        copies, joins and returns (columns, info), columns a dict of numpy arrays of info["joined"]
+        rows each: campaign uint32, row uint32, event_time int64, time_ok uint8 and, with keys,
+        key uint8[rows, 56] and key_len uint8.  cap_rows defaults to the number of lines, which
+        always suffices."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        n = off.size
+        cap = n if cap_rows is None else int(cap_rows)
+        flags = _lib.YSB_JOIN_KEYS if keys else 0
+        lay = joined_layout(cap, flags)
+        image = np.zeros(max(lay["start"][6], 16), dtype=np.uint8)
+        d_b, d_o, d_out = self.device_alloc(max(buf.size, 16)), self.device_alloc(max(4 * n, 16)), self.device_alloc(image.size)
+        try:
+            if buf.size:
+                self.h2d(d_b, buf)
+            if n:
+                self.h2d(d_o, off)
+            self.h2d(d_out, image)
+            info = self.join_device(d_b, buf.size, d_o, n, d_out, cap, flags)
+            self.d2h(image, d_out)
+        finally:
+            for p in (d_b, d_o, d_out):
+                self.device_free(p)
+        return joined_columns(image, lay, info["rows_written"]), info
 
     # -- columnar count ----------------------------------------------------------------
     def submit_columns_device(self, d_cols, batch_rows, n_rows, flags=0):
