@@ -710,6 +710,157 @@ typedef struct ysb_lz4_frame_desc {
 } ysb_lz4_frame_desc;
 int         ysb_lz4_frame_info(ysb_ctx* ctx, ysb_lz4_frame_desc* info);
 uint64_t    ysb_lz4_frame_desc_size(void);   /* sizeof(ysb_lz4_frame_desc) */
+/* ---- Kafka record batches (additive within ABI 6) ----------------------------------------
+ * What a Kafka consumer holds -- the reference's ingest: the ad-events topic, KafkaSpout
+ * (AdvertisingTopology.java), the fork's FlinkKafkaConsumer -- is a fetch response: a run of
+ * record batches (message format v2, Kafka >= 0.11; a partition's .log segment is the same bytes).
+ * The event values lie between varint-framed record headers, so they are neither newline-
+ * separated nor back to back.  Here the framed bytes cross PCIe as they are: the host reads one
+ * 61-byte header per batch (ysb_kafka_index), the GPU walks the records, finds the values and
+ * gathers them back to back with their offsets in front of the unchanged scan.
+ * ysb_kafka_index walks bytes[0, nbytes) and fills one entry per data batch.  A last batch that
+ * is not whole is normal in a fetch response and no error: info->consumed stops in front of it,
+ * so the caller keeps the tail.  Control batches are skipped and counted.  YSB_ERR_FORMAT, the
+ * message naming the byte offset, the field, its value and the rule, for: a magic other than 2
+ * (message formats v0 / v1), a codec other than 0 (compressed batches), batchLength < 49, a
+ * negative recordsCount and, with YSB_KAFKA_CHECK_CRC, a CRC-32C mismatch (verified on the host,
+ * in software: a pass over the bytes, so off by default).  YSB_ERR_CAPACITY with info complete
+ * when cap is short (batches may be NULL with cap 0 to count).  No context: the message is the
+ * thread's (ysb_last_error(NULL)). */
+typedef struct ysb_kafka_batch {
+    uint64_t records_off;     /* of the batch's first record byte in the indexed buffer      */
+    uint32_t records_bytes;   /* its records' bytes: batchLength - 49                        */
+    uint32_t n_records;       /* recordsCount                                                */
+    uint64_t first_record;    /* the records of the entries before it: the running sum       */
+    int64_t  base_offset;     /* baseOffset                                                  */
+    uint32_t control_before;  /* control batches skipped between the entry before and this   */
+    uint32_t reserved;        /* 0                                                           */
+} ysb_kafka_batch;
+typedef struct ysb_kafka_summary {
+    uint64_t n_batches;       /* data batches                                   */
+    uint64_t n_records;
+    uint64_t consumed;        /* bytes of whole batches: the rest is the tail   */
+    uint64_t control_batches; /* skipped                                        */
+    uint64_t crc_checked;     /* batches whose CRC-32C was verified             */
+} ysb_kafka_summary;
+#define YSB_KAFKA_CHECK_CRC 1u
+int         ysb_kafka_index(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, ysb_kafka_batch* batches,
+                            uint64_t cap, ysb_kafka_summary* info);
+uint32_t    ysb_kafka_crc32c(const uint8_t* bytes, uint64_t nbytes);   /* "123456789" -> 0xE3069283 */
+/* Why a batch is bad: a record of it breaks a rule.  rule: 1 a varint runs past its limit (5
+ * bytes; timestampDelta 10) or its extent, 2 length < 6, 3 the record runs past the batch, 4 the
+ * key runs past the record (or its length is below -1), 5 the same for the value, 6 the headers
+ * do not end exactly at the record's end (or a negative count / header key length), 7 the walk
+ * does not yield exactly recordsCount records ending exactly at the batch's end (record: where
+ * it stopped).  The verdict names the smallest bad batch and its smallest bad record. */
+typedef struct ysb_kafka_verdict {
+    uint32_t bad_batches;
+    uint32_t first_bad;       /* index entry; 0xFFFFFFFF: none */
+    uint32_t record;          /* within that batch             */
+    uint32_t rule;
+} ysb_kafka_verdict;
+typedef struct ysb_kafka_counters {
+    uint64_t records;
+    uint64_t null_values;     /* valueLength -1 (an empty value is not counted)  */
+    uint64_t keyed;           /* records with a key (an empty one included)      */
+    uint64_t headers;         /* record headers in all                           */
+    uint64_t value_bytes;
+} ysb_kafka_counters;
+/* The host model of the GPU's unframing (csrc/ysb_kafka.h): the values of every record of the
+ * indexed batches back to back into out, line_off[0 .. n] their offsets (line_off[n]: the
+ * total; off_cap >= n + 1), the counters.  A null value and an empty value are both a line of no
+ * bytes.  out / line_off NULL: sizes and counters only.  YSB_ERR_FORMAT with *verdict set for a
+ * bad batch (nothing of a bad batch is written); YSB_ERR_ARG for an index entry outside the
+ * buffer or with a wrong running sum; YSB_ERR_CAPACITY when out or line_off is short or the
+ * values pass 4 GiB (u32 offsets). */
+int         ysb_kafka_unframe_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                   uint64_t n_batches, uint8_t* out, uint64_t out_cap, uint32_t* line_off,
+                                   uint64_t off_cap, uint64_t* n_lines, uint64_t* out_bytes,
+                                   ysb_kafka_counters* counters, ysb_kafka_verdict* verdict);
+/* The packer (a test's, a tool's or a source's stand-in for a producer): lines
+ * [line_off[i], line_off[i + 1]) of src (the last one ends at nbytes) as record batches.  A batch
+ * is closed before the record that would take it past batch_bytes bytes (header included; a
+ * batch holds one record at least) or past batch_records records (0: no such limit).  Record i
+ * gets offset base_offset + i; keys are null (key_off NULL) or key i is keys[key_off[i],
+ * key_off[i + 1]); ts_delta NULL: 0; the n_headers headers (a value length of -1: null) go on
+ * every record.  baseOffset, offsetDelta, lastOffsetDelta, maxTimestamp and the CRC-32C are
+ * what a consumer checks.  dst_cap >= ysb_kafka_bound(...), else YSB_ERR_CAPACITY with
+ * *dst_bytes the bound. */
+typedef struct ysb_kafka_pack_opts {
+    uint32_t        batch_bytes;
+    uint32_t        batch_records;
+    int64_t         base_offset;
+    int64_t         base_timestamp;
+    const uint32_t* key_off;         /* n_lines + 1 offsets into keys, or NULL */
+    const uint8_t*  keys;
+    const int64_t*  ts_delta;        /* n_lines, or NULL                       */
+    uint32_t        n_headers;
+    uint32_t        reserved;
+    const char* const*    header_keys;      /* NUL-terminated                  */
+    const uint8_t* const* header_vals;
+    const int32_t*        header_val_len;   /* -1: a null value                */
+} ysb_kafka_pack_opts;
+uint64_t    ysb_kafka_bound(uint64_t nbytes, uint64_t n_lines, const ysb_kafka_pack_opts* opts);
+int         ysb_kafka_pack(const uint8_t* src, uint64_t nbytes, const uint32_t* line_off, uint64_t n_lines,
+                           const ysb_kafka_pack_opts* opts, uint8_t* dst, uint64_t dst_cap, uint64_t* dst_bytes,
+                           uint64_t* n_batches);
+int         ysb_kafka_write_file(const char* path, const uint8_t* src, uint64_t nbytes, const uint32_t* line_off,
+                                 uint64_t n_lines, const ysb_kafka_pack_opts* opts);
+/* The unframing alone, device to device (synchronous, like ysb_lz4_decode_device): d_bytes
+ * (device, any alignment; the 16-byte vectors that hold its first and last byte are read whole)
+ * holds the framed bytes that `batches` (host memory) indexes; d_out (out_cap bytes) receives the
+ * values back to back, d_line_off (off_cap >= records + 1 entries) their offsets and the total.
+ * Three launches: a walk (one wave per Kafka batch), a scan of the batches' totals, a gather.
+ * Returns as ysb_kafka_unframe_host does; with a bad batch nothing is written to d_out or
+ * d_line_off. */
+int         ysb_kafka_unframe_device(ysb_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes,
+                                     const ysb_kafka_batch* batches, uint64_t n_batches, uint8_t* d_out,
+                                     uint64_t out_cap, uint32_t* d_line_off, uint64_t off_cap, uint64_t* n_lines,
+                                     uint64_t* out_bytes);
+/* A run of whole Kafka batches through a slot -- what replaces the consumer's per-record
+ * deserialisation loop in front of the first operator: bytes[0, nbytes) is (part of) the buffer
+ * that `batches` indexes (records_off relative to `bytes`; first_record running from 0).  The
+ * framed bytes and the index are what crosses PCIe, into a device staging buffer that is not
+ * the slot's device buffer: through the slot's pinned buffer, or (_mapped) read in place from a
+ * registered range (ysb_host_register) at any byte address, the span widened to 16-byte
+ * boundaries inside one range.  On the split's stream behind the slot's copy the three kernels
+ * leave the values, their offsets and the count in the slot's device buffers; no line split
+ * runs; the scan launches at the next call that orders work, as for every raw batch.
+ * YSB_ERR_CAPACITY at the call for nbytes above max_batch_bytes or more records than the
+ * slot's line capacity (ysb_submit_raw's).  A bad Kafka batch drops the whole slot batch: a
+ * sticky YSB_ERR_FORMAT naming the Kafka batch, its baseOffset, the record and the rule, from
+ * the call that would have launched it and every later one that orders work, until ysb_reset.
+ * The layout sample is the first batch's first values as the host model unframes them; counts
+ * never depend on it.  No rebase; YSB_ERR_STATE while a frame batch's carry is pending. */
+int         ysb_submit_kafka(ysb_ctx* ctx, int slot, const uint8_t* bytes, uint64_t nbytes,
+                             const ysb_kafka_batch* batches, uint64_t n_batches);
+int         ysb_submit_kafka_mapped(ysb_ctx* ctx, int slot, const uint8_t* bytes, uint64_t nbytes,
+                                    const ysb_kafka_batch* batches, uint64_t n_batches);
+/* The last Kafka call settled (a slot batch: at its launch; ysb_kafka_unframe_device: at once).
+ * Read-only measurement and test support.  Waits for everything submitted. */
+typedef struct ysb_kafka_desc {
+    uint64_t calls;            /* Kafka submits and unframe calls since ysb_open / ysb_reset */
+    uint64_t batches;          /* the last call: its Kafka batches ...                       */
+    uint64_t records;
+    uint64_t null_values;
+    uint64_t keyed;
+    uint64_t headers;
+    uint64_t control_skipped;  /* control batches the index skipped among them               */
+    uint64_t framed_bytes;
+    uint64_t value_bytes;
+    uint64_t window_bytes;     /* the walk kernel's window                                   */
+    ysb_kafka_verdict verdict;
+    double   walk_ms;          /* YSB_F_TIMING: HIP events around each kernel                */
+    double   base_ms;
+    double   gather_ms;
+} ysb_kafka_desc;
+int         ysb_kafka_info(ysb_ctx* ctx, ysb_kafka_desc* info);
+uint64_t    ysb_kafka_batch_size(void);      /* sizeof(ysb_kafka_batch)     */
+uint64_t    ysb_kafka_summary_size(void);
+uint64_t    ysb_kafka_verdict_size(void);
+uint64_t    ysb_kafka_counters_size(void);
+uint64_t    ysb_kafka_pack_opts_size(void);
+uint64_t    ysb_kafka_desc_size(void);
 /* Device-resident batch (HBM pointers, e.g. from ysb_device_alloc). Asynchronous.  The batch
  * must be complete when submitted, or its producer ordered before the compute stream
  * (hipStreamWaitEvent(ysb_stream(ctx), ...), or produced on that stream).  Unless

@@ -2,7 +2,7 @@
 // library's host translation units:
 //   ysb_capi.cpp    context lifecycle, the ad -> campaign tables, sync / drain / ring / stats
 //   ysb_submit.cpp  segments into launches: slots, device batches, the layout samples, the scan launch
-//   ysb_raw.cpp     batches that cross PCIe into a slot and launch a call later (raw, mapped, LZ4)
+//   ysb_raw.cpp     batches that cross PCIe into a slot and launch a call later (raw, mapped, LZ4, Kafka)
 //   ysb_columns.cpp the columnar decode and the columnar count's submits
 //   ysb_join_api.cpp the join's output as ordered columns (its layout, scratch format and plan:
 //                   ysb_join.h, no HIP: tests/native/join_logic.cpp)
@@ -17,6 +17,9 @@
 //                   tests/native/lz4_logic.cpp)
 //   ysb_lz4_frame.h standard LZ4 frames: the index, XXH32, the writer, the measure model and the carry
 //                   rule (no HIP: tests/native/lz4_frame_logic.cpp)
+//   ysb_kafka_api.cpp Kafka record batches: the index's checks, a slot batch's staging, the three launches
+//   ysb_kafka.h     their format, the one record reader, the host model and the packer (no HIP:
+//                   tests/native/kafka_logic.cpp)
 //   ysb_group.cpp   multi-GPU: the RCCL / host-collective group and the keyBy exchange
 //   ysb_gen_api.cpp the synthetic generator (host and device) and its truth tables
 // Internal: nothing here is part of the ABI (the shared helpers have hidden visibility).
@@ -162,6 +165,12 @@ struct Lz4Staged {
     bool more = false;                   // ... with YSB_LZ4F_MORE: its tail is carried
 };
 
+// A Kafka batch as kafka_stage leaves it: what its settling reports (the index stays in the
+// slot's pinned buffer until the slot is claimed again, which launches this batch first).
+struct KafkaStaged {
+    u64 n_batches = 0, n_records = 0, framed_bytes = 0, control_skipped = 0;
+};
+
 // A slot's batch between its submit and its launch one call later (ysb_raw.cpp).  Every submit
 // assigns the whole record and launch_pending_raw resets it whole.
 struct RawBatch {
@@ -171,6 +180,7 @@ struct RawBatch {
     u64 n_off = 0;                       //   split's, in d_roff[slot]
     std::optional<ysb_rebase> rebase;    // its lines' event times rebased before the scan
     std::optional<Lz4Staged> lz4;        // a decode precedes the split
+    std::optional<KafkaStaged> kafka;    // the Kafka kernels produce the bytes and `off` (the slot's d_roff); no split
 };
 
 struct ysb_ctx {
@@ -281,6 +291,21 @@ struct ysb_ctx {
     PinBuf<Lz4FrameHead> h_lz4f;
     DevBuf<u8> d_carry;
     bool lz4f_more = false;
+    // Kafka record batches (ysb_kafka_api.cpp; ysb_kafka.h).  The framed bytes of a slot's batch
+    // go to d_lz4[slot] (the compressed-bytes staging: a slot holds one batch, of either kind,
+    // from its copy until its kernels on the split's stream are done).  Per slot one pinned /
+    // device buffer pair, {KafkaHead, the index entries} -- one copy --, and behind them on the
+    // device the kernels' scratch (kafka_layout); the head read back to pinned memory behind the
+    // gather (h_kafka_head[slot]); the synchronous call's buffer; the last call settled;
+    // YSB_F_TIMING's events around the three kernels
+    PinBuf<u8> h_kafka[2];
+    u8* hd_kafka[2] = {nullptr, nullptr};
+    DevBuf<u8> d_kafka[2];
+    u64 kafka_cap[2] = {0, 0}, kafka_hcap[2] = {0, 0};   // device bytes; pinned bytes (head and index only)
+    PinBuf<KafkaHead> h_kafka_head;
+    DevBuf<u8> d_kafka_sync;
+    ysb_kafka_desc kafka_last{};
+    Event ev_kafka[2][4];
     // counts
     u32 c_pad = 0;                        // campaigns padded to the group size
     DevBuf<unsigned long long> d_counts;      // [c_pad][W]
@@ -509,6 +534,20 @@ YSB_INTERNAL int lz4f_stage(ysb_ctx* c, int slot, const uint8_t* base, const ysb
 // where the split reads a frame batch's byte count, and the head's read-back behind the split
 YSB_INTERNAL const u64* lz4f_nbytes(ysb_ctx* c, int slot);
 YSB_INTERNAL int lz4f_readback(ysb_ctx* c, int slot, hipStream_t s);
+// ysb_kafka_api.cpp
+// A Kafka batch's index checked against the slot's capacities and placed, with the bytes (dsrc
+// NULL: into the slot's pinned buffer; else they stay in their registered range), for the
+// slot's copies v[2]; batch->kafka the staged batch, *sample its first values as the host model
+// unframes them, a line each (the layout sample).  The caller has waited for the slot's
+// previous copy.
+YSB_INTERNAL int kafka_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                             uint64_t n_batches, const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample);
+// the three kernels on s behind the slot's copies: d_bytes[slot], d_roff[slot]; the head's read-back
+YSB_INTERNAL int kafka_enqueue(ysb_ctx* c, int slot, const KafkaStaged& b, hipStream_t s);
+// at the batch's launch: kafka_last <- its figures; YSB_ERR_FORMAT naming the bad Kafka batch
+YSB_INTERNAL int kafka_settle(ysb_ctx* c, int slot, const KafkaStaged& b);
+// the value bytes the kernels left in d_bytes[slot] (read at the launch)
+YSB_INTERNAL u64 kafka_out_bytes(const ysb_ctx* c, int slot);
 // any submit that is not a frame batch while a carry is pending
 inline int carry_guard(ysb_ctx* c) {
     return c->lz4f_more ? fail(c, YSB_ERR_STATE, "a frame batch left a carry (YSB_LZ4F_MORE): only ysb_submit_lz4_blocks "

@@ -1,0 +1,314 @@
+// ysb_kafka_api.cpp -- Kafka record batches above the kernels (ysb_kafka.hip; the rules:
+// ysb_kafka.h): the index, the host model and the packer as C entries, a slot batch's staging
+// (the framed bytes in the slot's pinned buffer or left in place in a registered range, the
+// index in pinned memory, one copy each), the three launches and the verdict's read-back, the
+// synchronous unframing alone and the last call's figures.  ysb_submit_kafka and
+// ysb_submit_kafka_mapped sit beside ysb_submit_raw in ysb_raw.cpp.
+#include "ysb_ctx.h"
+#include "ysb_kafka.h"
+
+using namespace ysb;
+
+static_assert(sizeof(KafkaHead) == 64 && sizeof(KafkaBatchOut) == 32 && sizeof(ysb_kafka_batch) == 40,
+              "the device layout below counts on these sizes");
+
+// A call's device buffer: the head and the index entries (what one copy carries), then the
+// kernels' scratch.
+struct KafkaLayout {
+    u64 batches, meta, bout, base, total;
+};
+static KafkaLayout kafka_layout(u64 nb, u64 nrec) {
+    KafkaLayout l;
+    l.batches = sizeof(KafkaHead);
+    l.meta = (l.batches + nb * sizeof(ysb_kafka_batch) + 15) & ~15ull;
+    l.bout = l.meta + nrec * 16;
+    l.base = l.bout + nb * sizeof(KafkaBatchOut);
+    l.total = l.base + nb * 8;
+    return l;
+}
+static KafkaParams kafka_params(u8* d, const KafkaLayout& l, const u8* d_bytes, u64 nb, u64 nrec, u8* out, u64 out_cap,
+                                u32* line_off) {
+    KafkaParams p{};
+    p.bytes = d_bytes;
+    p.batches = reinterpret_cast<const ysb_kafka_batch*>(d + l.batches);
+    p.n_batches = (u32)nb;
+    p.n_records = nrec;
+    p.meta = reinterpret_cast<uint4*>(d + l.meta);
+    p.bout = reinterpret_cast<KafkaBatchOut*>(d + l.bout);
+    p.base = reinterpret_cast<u64*>(d + l.base);
+    p.head = reinterpret_cast<KafkaHead*>(d);
+    p.out = out;
+    p.out_cap = out_cap;
+    p.line_off = line_off;
+    return p;
+}
+
+// the index as argument errors (the same for every entry that takes one): *n_records its records
+static int index_args(ysb_ctx* c, const uint8_t* bytes, u64 nbytes, const ysb_kafka_batch* batches, u64 nb, u64* n_records,
+                      u64* control) {
+    if ((nbytes && !bytes) || (nb && !batches)) return fail(c, YSB_ERR_ARG, "NULL Kafka buffers");
+    if (nb > 0x7FFFFFFFull) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 Kafka batches per call");
+    u64 first = 0, ctl = 0;
+    for (u64 k = 0; k < nb; ++k) {
+        if (!kafka_entry_ok(batches[k], nbytes, first))
+            return fail(c, YSB_ERR_ARG, "Kafka index entry %llu does not lie in the %llu bytes given or breaks the running "
+                        "record count (first_record %llu, expected %llu)", (unsigned long long)k, (unsigned long long)nbytes,
+                        (unsigned long long)batches[k].first_record, (unsigned long long)first);
+        first += batches[k].n_records;
+        ctl += batches[k].control_before;
+    }
+    *n_records = first;
+    if (control) *control = ctl;
+    return YSB_OK;
+}
+
+// walk, base, gather on s (ev: YSB_F_TIMING's four events, created on demand, or NULL)
+static int launch_unframe(ysb_ctx* c, const KafkaParams& p, hipStream_t s, Event* ev) {
+    if (ev)
+        for (int k = 0; k < 4; ++k)
+            if (!ev[k]) HIPCHK(c, ev[k].create(hipEventDefault));
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], s));
+    if (p.n_batches) HIPCHK(c, launch_kafka_walk(p, s));
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, launch_kafka_base(p, s));
+    if (ev) HIPCHK(c, hipEventRecord(ev[2], s));
+    HIPCHK(c, launch_kafka_gather(p, s));
+    if (ev) HIPCHK(c, hipEventRecord(ev[3], s));
+    return YSB_OK;
+}
+
+// kafka_last <- a call's figures; the error its verdict asks for
+static int settle(ysb_ctx* c, const KafkaHead& h, u64 nb, u64 framed, u64 control, const ysb_kafka_batch* batches,
+                  Event* ev, const char* what) {
+    ysb_kafka_desc d{};
+    d.calls = c->kafka_last.calls + 1;
+    d.batches = nb;
+    d.records = h.n_lines;
+    d.null_values = h.nulls;
+    d.keyed = h.keyed;
+    d.headers = h.headers;
+    d.control_skipped = control;
+    d.framed_bytes = framed;
+    d.value_bytes = h.out_bytes;
+    d.window_bytes = KAFKA_WIN;
+    d.verdict = ysb_kafka_verdict{h.bad_batches, h.bad_batches ? h.first_bad : KAFKA_NONE, h.bad_rec, h.rule};
+    if (ev) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) d.walk_ms = ms;
+        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) d.base_ms = ms;
+        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) d.gather_ms = ms;
+    }
+    c->kafka_last = d;
+    if (h.bad_batches)
+        return fail(c, YSB_ERR_FORMAT, "%s: Kafka batch %u (baseOffset %lld), record %u: %s (%u bad batches in all); "
+                    "nothing of the call was counted", what, h.first_bad,
+                    h.first_bad < nb ? (long long)batches[h.first_bad].base_offset : -1LL, h.bad_rec, kafka_rule_name(h.rule),
+                    h.bad_batches);
+    if (h.overflow)
+        return fail(c, YSB_ERR_CAPACITY, "%s: %llu value bytes do not fit the output", what, (unsigned long long)h.out_bytes);
+    return YSB_OK;
+}
+
+extern "C" {
+
+// ---- a Kafka batch through a slot (ysb_raw.cpp submit_kafka) ----------------------------------
+
+int kafka_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                uint64_t nb, const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample) {
+    u64 nrec = 0, control = 0;
+    int rc = index_args(c, bytes, nbytes, batches, nb, &nrec, &control);
+    if (rc) return rc;
+    if (nrec + 1 > c->raw_lines_cap)
+        return fail(c, YSB_ERR_CAPACITY, "Kafka batch of %llu records, more than the %llu lines its slot holds "
+                    "(max(max_batch_events, max_batch_bytes / 32))", (unsigned long long)nrec,
+                    (unsigned long long)(c->raw_lines_cap - 1));
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_lz4[slot]) HIPCHK(c, c->d_lz4[slot].alloc(c->cfg.max_batch_bytes + 64));
+    if (!c->h_kafka_head) {
+        HIPCHK(c, c->h_kafka_head.alloc(2 * sizeof(KafkaHead)));
+        std::memset(c->h_kafka_head.get(), 0, 2 * sizeof(KafkaHead));
+    }
+    const KafkaLayout l = kafka_layout(nb, nrec);
+    if (l.total > c->kafka_cap[slot]) {   // (outside steady state: more batches or records than any call before)
+        const u64 cap = std::max<u64>(l.total + l.total / 2, 256u << 10);
+        if ((rc = grow_device(c, c->d_kafka[slot], cap + 64, 0))) return rc;
+        c->kafka_cap[slot] = cap;
+    }
+    if (l.meta > c->kafka_hcap[slot]) {
+        const u64 cap = std::max<u64>(l.meta + l.meta / 2, 64u << 10);
+        c->kafka_hcap[slot] = 0;
+        HIPCHK(c, c->h_kafka[slot].alloc(cap + 64));
+        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hd_kafka[slot]), c->h_kafka[slot], 0));
+        c->kafka_hcap[slot] = cap;
+    }
+    KafkaHead head{};
+    head.first_bad = KAFKA_NONE;
+    std::memcpy(c->h_kafka[slot], &head, sizeof head);
+    if (nb) std::memcpy(c->h_kafka[slot] + l.batches, batches, nb * sizeof(ysb_kafka_batch));
+    if (!dsrc && nbytes && bytes != c->h_bytes[slot]) std::memcpy(c->h_bytes[slot], bytes, nbytes);
+    v[0] = {c->d_lz4[slot], dsrc ? dsrc : c->hd_bytes[slot], dsrc ? bytes : c->h_bytes[slot].get(), nbytes};
+    v[1] = {c->d_kafka[slot], c->hd_kafka[slot], c->h_kafka[slot], l.batches + nb * sizeof(ysb_kafka_batch)};
+    batch->nbytes = nbytes;
+    batch->off = c->d_roff[slot];
+    batch->n_off = nrec;
+    batch->kafka = KafkaStaged{nb, nrec, nbytes, control};
+    // the layout sample: the first batch's first values as the host model's reader finds them,
+    // a line each (nothing from a record the reader refuses -- the device decides that for the batch)
+    sample->clear();
+    if (nb) {
+        const ysb_kafka_batch& b = batches[0];
+        KafkaHostIn in{bytes + b.records_off};
+        u32 pos = 0;
+        for (u32 i = 0; i < b.n_records && i < SAMPLE_LINES && pos < b.records_bytes; ++i) {
+            u32 body = 0, end = 0;
+            KafkaRec r{};
+            if (kafka_read_len(in, pos, b.records_bytes, &body, &end) || kafka_read_body(in, body, end, &r)) break;
+            sample->insert(sample->end(), in.p + r.val_pos, in.p + r.val_pos + r.val_len);
+            if (sample->empty() || sample->back() != '\n') sample->push_back('\n');
+            pos = end;
+        }
+    }
+    return YSB_OK;
+}
+
+int kafka_enqueue(ysb_ctx* c, int slot, const KafkaStaged& b, hipStream_t s) {
+    const KafkaLayout l = kafka_layout(b.n_batches, b.n_records);
+    const KafkaParams p = kafka_params(c->d_kafka[slot], l, c->d_lz4[slot], b.n_batches, b.n_records, c->d_bytes[slot],
+                                       c->cfg.max_batch_bytes, c->d_roff[slot]);
+    if (int rc = launch_unframe(c, p, s, (c->cfg.flags & YSB_F_TIMING) ? c->ev_kafka[slot] : nullptr)) return rc;
+    // the verdict comes back through pinned memory with the line count: no host wait here
+    HIPCHK(c, hipMemcpyAsync(c->h_kafka_head + slot, p.head, sizeof(KafkaHead), hipMemcpyDeviceToHost, s));
+    return YSB_OK;
+}
+
+int kafka_settle(ysb_ctx* c, int slot, const KafkaStaged& b) {
+    char what[48];
+    std::snprintf(what, sizeof what, "Kafka batch (slot %d)", slot);
+    return settle(c, c->h_kafka_head[slot], b.n_batches, b.framed_bytes, b.control_skipped,
+                  reinterpret_cast<const ysb_kafka_batch*>(c->h_kafka[slot] + sizeof(KafkaHead)),
+                  (c->cfg.flags & YSB_F_TIMING) ? c->ev_kafka[slot] : nullptr, what);
+}
+
+u64 kafka_out_bytes(const ysb_ctx* c, int slot) { return c->h_kafka_head[slot].out_bytes; }
+
+// ---- the unframing alone ----------------------------------------------------------------------
+
+int ysb_kafka_unframe_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                             uint64_t nb, uint8_t* d_out, uint64_t out_cap, uint32_t* d_line_off, uint64_t off_cap,
+                             uint64_t* n_lines, uint64_t* out_bytes) {
+    if (!c) return YSB_ERR_ARG;
+    u64 nrec = 0, control = 0;
+    int rc = index_args(c, d_bytes, nbytes, batches, nb, &nrec, &control);
+    if (rc) return rc;
+    if (n_lines) *n_lines = nrec;
+    if (out_bytes) *out_bytes = 0;
+    if (!d_line_off || nrec + 1 > off_cap)
+        return fail(c, YSB_ERR_CAPACITY, "%llu records, room for %llu offsets (one more than the records is needed)",
+                    (unsigned long long)nrec, (unsigned long long)(d_line_off ? off_cap : 0));
+    if (out_cap && !d_out) return fail(c, YSB_ERR_ARG, "NULL output buffer");
+    if ((rc = launch_pending_raw(c))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const KafkaLayout l = kafka_layout(nb, nrec);
+    if ((rc = grow_device(c, c->d_kafka_sync, l.total + 64, 256u << 10))) return rc;
+    const KafkaParams p = kafka_params(c->d_kafka_sync, l, d_bytes, nb, nrec, d_out, d_out ? out_cap : 0, d_line_off);
+    // (the index is the caller's pageable memory, the head this frame's: nothing is left pending)
+    struct SyncOnExit {
+        hipStream_t s;
+        ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+    } const settled{c->s_comp};
+    if (nb) HIPCHK(c, hipMemcpyAsync(c->d_kafka_sync + l.batches, batches, nb * sizeof(ysb_kafka_batch), hipMemcpyHostToDevice, c->s_comp));
+    const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
+    Event ev[4];
+    if ((rc = launch_unframe(c, p, c->s_comp, timed ? ev : nullptr))) return rc;
+    KafkaHead h{};
+    HIPCHK(c, hipMemcpyAsync(&h, p.head, sizeof h, hipMemcpyDeviceToHost, c->s_comp));
+    HIPCHK(c, hipStreamSynchronize(c->s_comp));
+    if (out_bytes) *out_bytes = h.out_bytes;
+    return settle(c, h, nb, nbytes, control, batches, timed ? ev : nullptr, "ysb_kafka_unframe_device");
+}
+
+int ysb_kafka_info(ysb_ctx* c, ysb_kafka_desc* info) {
+    if (!c || !info) return c ? fail(c, YSB_ERR_ARG, "info is NULL") : YSB_ERR_ARG;
+    const int rc = sync_streams(c);   // (a Kafka batch awaiting its launch settles here)
+    *info = c->kafka_last;
+    info->window_bytes = KAFKA_WIN;
+    return rc;
+}
+
+// ---- the host entries: index, model, packer ---------------------------------------------------
+
+int ysb_kafka_index(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, ysb_kafka_batch* batches, uint64_t cap,
+                    ysb_kafka_summary* info) {
+    if (nbytes && !bytes) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index: NULL buffer");
+    if (flags & ~YSB_KAFKA_CHECK_CRC) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index: unknown flags %#x", flags);
+    KafkaError err;
+    const int rc = kafka_index(bytes, nbytes, flags, batches, batches ? cap : 0, info, &err);
+    return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
+}
+
+uint32_t ysb_kafka_crc32c(const uint8_t* bytes, uint64_t nbytes) { return bytes || !nbytes ? kafka_crc32c(bytes, nbytes) : 0; }
+
+int ysb_kafka_unframe_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, uint64_t n_batches,
+                           uint8_t* out, uint64_t out_cap, uint32_t* line_off, uint64_t off_cap, uint64_t* n_lines,
+                           uint64_t* out_bytes, ysb_kafka_counters* counters, ysb_kafka_verdict* verdict) {
+    if ((nbytes && !bytes) || (n_batches && !batches)) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_unframe_host: NULL buffers");
+    KafkaError err;
+    const int rc = kafka_unframe(bytes, nbytes, batches, n_batches, out, out_cap, line_off, off_cap, n_lines, out_bytes,
+                                 counters, verdict, &err);
+    return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
+}
+
+static const ysb_kafka_pack_opts KAFKA_DEFAULT_OPTS{};
+
+uint64_t ysb_kafka_bound(uint64_t nbytes, uint64_t n_lines, const ysb_kafka_pack_opts* opts) {
+    return kafka_bound(nbytes, n_lines, opts ? *opts : KAFKA_DEFAULT_OPTS);
+}
+
+static int pack_args(const uint8_t* src, uint64_t nbytes, const uint32_t* line_off, uint64_t n_lines, const ysb_kafka_pack_opts& o) {
+    if ((nbytes && !src) || (n_lines && !line_off)) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: NULL buffers");
+    for (u64 i = 0; i < n_lines; ++i)
+        if (line_off[i] > nbytes || (i && line_off[i] < line_off[i - 1]))
+            return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: line offset %llu is out of order or past the bytes", (unsigned long long)i);
+    if (o.key_off && !o.keys && o.key_off[n_lines]) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: key offsets without keys");
+    if (o.n_headers && (!o.header_keys || !o.header_vals || !o.header_val_len))
+        return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: headers without their arrays");
+    return YSB_OK;
+}
+
+int ysb_kafka_pack(const uint8_t* src, uint64_t nbytes, const uint32_t* line_off, uint64_t n_lines,
+                   const ysb_kafka_pack_opts* opts, uint8_t* dst, uint64_t dst_cap, uint64_t* dst_bytes, uint64_t* n_batches) {
+    const ysb_kafka_pack_opts& o = opts ? *opts : KAFKA_DEFAULT_OPTS;
+    if (!dst_bytes) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: dst_bytes is NULL");
+    if (int rc = pack_args(src, nbytes, line_off, n_lines, o)) return rc;
+    *dst_bytes = kafka_bound(nbytes, n_lines, o);
+    if (*dst_bytes > dst_cap || (!dst && *dst_bytes))
+        return fail(nullptr, YSB_ERR_CAPACITY, "ysb_kafka_pack: needs %llu bytes", (unsigned long long)*dst_bytes);
+    u64 nb = 0;
+    *dst_bytes = kafka_pack(src, nbytes, line_off, n_lines, o, dst, &nb);
+    if (n_batches) *n_batches = nb;
+    return YSB_OK;
+}
+
+int ysb_kafka_write_file(const char* path, const uint8_t* src, uint64_t nbytes, const uint32_t* line_off, uint64_t n_lines,
+                         const ysb_kafka_pack_opts* opts) {
+    if (!path) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_write_file: NULL path");
+    const ysb_kafka_pack_opts& o = opts ? *opts : KAFKA_DEFAULT_OPTS;
+    if (int rc = pack_args(src, nbytes, line_off, n_lines, o)) return rc;
+    std::vector<u8> blob(kafka_bound(nbytes, n_lines, o) + 1);
+    u64 nb = 0;
+    const u64 n = kafka_pack(src, nbytes, line_off, n_lines, o, blob.data(), &nb);
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return fail(nullptr, YSB_ERR_ARG, "cannot write %s", path);
+    bool ok = !n || std::fwrite(blob.data(), 1, n, f) == n;
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? YSB_OK : fail(nullptr, YSB_ERR_ARG, "short write to %s", path);
+}
+
+uint64_t ysb_kafka_batch_size(void) { return sizeof(ysb_kafka_batch); }
+uint64_t ysb_kafka_summary_size(void) { return sizeof(ysb_kafka_summary); }
+uint64_t ysb_kafka_verdict_size(void) { return sizeof(ysb_kafka_verdict); }
+uint64_t ysb_kafka_counters_size(void) { return sizeof(ysb_kafka_counters); }
+uint64_t ysb_kafka_pack_opts_size(void) { return sizeof(ysb_kafka_pack_opts); }
+uint64_t ysb_kafka_desc_size(void) { return sizeof(ysb_kafka_desc); }
+
+}  // extern "C"

@@ -2,8 +2,9 @@
 // gfx950 kernels (ysb_scan.hip, ysb_gen.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/ysb_hip.h"   // ysb_kafka_batch: the index entry the Kafka kernels read
 #include "ysb_common.h"
-#include "ysb_parked.h"    // the parked views' record format and counters
+#include "ysb_parked.h"   // the parked views' record format and counters
 #include "ysb_recplan.h"   // TILE_LINES, MAX_TILES_PER_BLOCK and record mode's REC_* constants
 
 namespace ysb {
@@ -471,5 +472,42 @@ constexpr u32 LZ4_CARRY_HEAD = 16;
 // nbytes / carry_in / carry_out / overflow written.  A batch with a bad block or an overflow is
 // dropped: nbytes 0, the carry emptied.  One workgroup.  Asynchronous on s.
 hipError_t launch_lz4_frame_carry(u8* out, u8* carry, Lz4FrameHead* head, u32 more, hipStream_t s);
+
+// Kafka record batches (ysb_kafka.hip; the format's rules: ysb_kafka.h).  Three launches between
+// the framed bytes and the scan's input.  What the walk leaves per Kafka batch:
+struct KafkaBatchOut {
+    u64 total;                  // its values' bytes
+    u32 bad_rec, rule;          // its smallest bad record and that record's rule (rule 0: a good batch)
+    u32 nulls, keyed, headers, pad;
+};
+// ... and the call's result, which the base kernel writes and the host reads back.
+struct KafkaHead {
+    u64 out_bytes, n_lines;
+    u32 bad_batches, first_bad, bad_rec, rule;   // first_bad KAFKA_NONE: none
+    u64 nulls, keyed, headers;
+    u32 overflow, pad;          // the values exceed out_cap or 4 GiB: nothing is gathered
+};
+struct KafkaParams {
+    const u8* bytes;            // the framed bytes, any alignment
+    const ysb_kafka_batch* batches;
+    u32 n_batches;
+    u64 n_records;              // the batches' records in all
+    uint4* meta;                // [n_records] {value position in its batch, output offset in its batch, length, batch}
+    KafkaBatchOut* bout;        // [n_batches]
+    u64* base;                  // [n_batches] where a batch's values start in out
+    KafkaHead* head;
+    u8* out;
+    u64 out_cap;
+    u32* line_off;              // [n_records + 1]
+};
+// One wave per Kafka batch: the serial chain of record lengths, 64 record bodies parsed at a
+// time, meta and bout written.  Nothing outside the 16-byte vectors that hold
+// [records_off, records_off + records_bytes) is read.  Asynchronous on s; n_batches >= 1.
+hipError_t launch_kafka_walk(const KafkaParams& p, hipStream_t s);
+// One workgroup: base <- the exclusive scan of the good batches' totals, *head <- the result.
+hipError_t launch_kafka_base(const KafkaParams& p, hipStream_t s);
+// Each value copied to out + base[batch] + its offset, line_off written (line_off[n_records]:
+// the total); nothing at all when head says a batch is bad or the values do not fit.
+hipError_t launch_kafka_gather(const KafkaParams& p, hipStream_t s);
 
 }  // namespace ysb

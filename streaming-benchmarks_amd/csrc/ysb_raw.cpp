@@ -1,7 +1,8 @@
 // ysb_raw.cpp -- every batch that crosses PCIe into a slot and may launch a call later: raw
 // lines split on the GPU (ysb_submit_raw), read in place from registered caller memory
 // (ysb_submit_raw_mapped, ysb_submit_mapped; host registration, the rebase table), LZ4 batches
-// decoded in front of the split (ysb_submit_raw_lz4, ysb_submit_lz4_mapped).  A deferred batch is
+// decoded in front of the split (ysb_submit_raw_lz4, ysb_submit_lz4_mapped), Kafka record batches
+// unframed in its place (ysb_submit_kafka, ysb_submit_kafka_mapped).  A deferred batch is
 // one RawBatch per slot (ysb_ctx.h): enqueue_deferred states its order once, launch_pending_raw
 // launches it at the next call.  The launch (enqueue_scan) and the slot copies: ysb_submit.cpp.
 #include "ysb_ctx.h"
@@ -51,6 +52,8 @@ int launch_pending_raw(ysb_ctx* c) {
         rc = fail(c, YSB_ERR_HIP, "raw batch (slot %d): waiting for its line split failed", slot);
     } else if (b.lz4 && (rc = lz4_settle(c, slot, *b.lz4))) {
         // a compressed batch with a bad block: dropped whole (YSB_ERR_FORMAT, the message lz4_settle's)
+    } else if (b.kafka && (rc = kafka_settle(c, slot, *b.kafka))) {
+        // a Kafka batch with a bad record: dropped whole (YSB_ERR_FORMAT, the message kafka_settle's)
     } else if (b.rebase && c->h_rawn[slot] > c->rebase_n - b.rebase->first_line) {
         rc = fail(c, YSB_ERR_ARG, "raw batch (slot %d): %llu lines, more than the rebase table holds from line %llu",
                   slot, (unsigned long long)c->h_rawn[slot], (unsigned long long)b.rebase->first_line);
@@ -60,7 +63,8 @@ int launch_pending_raw(ysb_ctx* c) {
                   (unsigned long long)c->raw_lines_cap);
     } else {
         // (a frame batch's bytes were measured on the device: its count came back with the split's)
-        const u64 nbytes = b.lz4 && b.lz4->frame ? c->h_lz4f[slot].nbytes : b.nbytes;
+        // (a Kafka batch's value bytes were counted there too: they came back with its verdict)
+        const u64 nbytes = b.lz4 && b.lz4->frame ? c->h_lz4f[slot].nbytes : b.kafka ? kafka_out_bytes(c, slot) : b.nbytes;
         const ysb_segment sg{c->d_bytes[slot], nbytes, b.off ? b.off : c->d_roff[slot].get(), c->h_rawn[slot]};
         rc = enqueue_scan(c, &sg, 1, b.lay);
     }
@@ -129,6 +133,9 @@ static int enqueue_deferred(ysb_ctx* c, int slot, RawBatch b, const SlotCopy* v,
     hipStream_t s = c->s_split;
     HIPCHK(c, hipStreamWaitEvent(s, c->ev_h2d[slot], 0));
     if (b.lz4 && (rc = lz4_enqueue_decode(c, slot, *b.lz4, s))) return rc;
+    // a Kafka batch's kernels leave the values in the slot's device buffer and their offsets in
+    // d_roff[slot], which is b.off: no split
+    if (b.kafka && (rc = kafka_enqueue(c, slot, *b.kafka, s))) return rc;
     // the line count goes straight to pinned memory (read at the launch): the caller's (0: an
     // empty batch) or the split's
     if (b.off || !b.nbytes) c->h_rawn[slot] = b.n_off;
@@ -237,6 +244,37 @@ int ysb_submit_lz4_blocks(ysb_ctx* c, int slot, const uint8_t* base, const ysb_l
 int ysb_submit_lz4_blocks_mapped(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_block* blocks,
                                  uint32_t n_blocks, uint32_t flags) {
     return submit_frame(c, slot, base, blocks, n_blocks, flags, true);
+}
+
+// ---- Kafka record batches (ysb_kafka_api.cpp kafka_stage; ysb_kafka.h) ------------------------
+
+// Both Kafka submits: the slot claimed, the batch staged -- the framed bytes (through the slot's
+// pinned buffer or in place from a registered range) and the index are what crosses PCIe --,
+// enqueued like every deferred batch.
+static int submit_kafka(ysb_ctx* c, int slot, const uint8_t* bytes, u64 nbytes, const ysb_kafka_batch* batches, u64 n_batches,
+                        bool mapped) {
+    if (!c) return YSB_ERR_ARG;
+    int rc = raw_args(c, slot, bytes, nbytes);
+    const u8* dsrc = nullptr;
+    if (!rc && mapped) rc = mapped_src(c, bytes, nbytes, &dsrc);
+    if (!rc) rc = claim_slot(c, slot);
+    if (rc) return rc;
+    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));   // the slot's pinned buffers are rewritten
+    RawBatch b;
+    SlotCopy v[2];
+    std::vector<u8> sample;
+    if ((rc = kafka_stage(c, slot, bytes, nbytes, batches, n_batches, dsrc, &b, v, &sample))) return rc;
+    return enqueue_deferred(c, slot, b, v, 2, sample.data(), sample.size());
+}
+
+int ysb_submit_kafka(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                     uint64_t n_batches) {
+    return submit_kafka(c, slot, bytes, nbytes, batches, n_batches, false);
+}
+
+int ysb_submit_kafka_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                            uint64_t n_batches) {
+    return submit_kafka(c, slot, bytes, nbytes, batches, n_batches, true);
 }
 
 // ---- zero-copy raw batches from registered caller memory (ABI 5) ----------------------------

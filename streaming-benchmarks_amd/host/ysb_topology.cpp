@@ -600,6 +600,22 @@ void GpuAdCampaignOperator::submitLz4Mapped(const uint8_t* blocks, uint64_t comp
     waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 }
 
+void GpuAdCampaignOperator::submitKafka(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, uint64_t nBatches,
+                                        bool mapped) {
+    if (mapped) {
+        check(ysb_submit_kafka_mapped(ctx_, cur_, bytes, nbytes, batches, nBatches), "ysb_submit_kafka_mapped");
+    } else {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (nbytes) std::memcpy(bytes_[cur_], bytes, nbytes);   // (the slot is free: the last submit's ysb_wait)
+        fillS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        check(ysb_submit_kafka(ctx_, cur_, bytes_[cur_], nbytes, batches, nBatches), "ysb_submit_kafka");
+    }
+    cur_ ^= 1;
+    const auto t1 = std::chrono::steady_clock::now();
+    check(ysb_wait(ctx_, cur_), "ysb_wait");   // at most two batches in flight
+    waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+}
+
 Lz4Container Lz4Container::parse(const uint8_t* file, uint64_t size, const std::string& name) {
     ysb_lz4_file_header h;
     if (size < sizeof h) throw std::runtime_error(name + ": not a compressed replay file (too short)");

@@ -197,6 +197,10 @@ public:
     // batch: through the slot, or (mapped) read where they lie in the registered mapping.  more:
     // the batch's unfinished last line is carried in front of the next one (YSB_LZ4F_MORE).
     void submitLz4Blocks(const uint8_t* file, const ysb_lz4_frame_block* blocks, uint32_t nBlocks, bool more, bool mapped);
+    // A run of whole Kafka record batches (ysb_kafka_index's entries, records_off relative to
+    // `bytes`, first_record running from 0) as one batch: through the slot, or (mapped) read where
+    // it lies in the registered mapping.
+    void submitKafka(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, uint64_t nBatches, bool mapped);
     // One file image of WindowedArrowFormatBolter (<shared_file>_<k>, :303-317) of `rows` rows
     // counted from its columns (ysb_submit_columns, longs big-endian): only the ranges the count
     // reads are read from the file, straight into the open slot.  Throws, naming the file, if

@@ -61,6 +61,9 @@ struct Args {
     // --lz4: events_path is a compressed replay file (ysb_gen --lz4): runs of whole LZ4 blocks go
     // over PCIe as they are and are decoded on the GPU (ysb_submit_raw_lz4)
     bool lz4 = false;
+    // --kafka: events_path is a partition's log segment (ysb_gen --kafka): runs of whole record
+    // batches go over PCIe framed and are unframed on the GPU (ysb_submit_kafka)
+    bool kafka = false;
     // streaming mode (configs[4]): --stream plus its options (ysb_stream.hpp)
     bool stream = false;
     StreamOptions so;
@@ -78,7 +81,7 @@ void usage() {
                  "       [--format json|tbl] [--flush-ms MS] [--batch-mb MB | --batch-bytes B] [--batch-events N]\n"
                  "       [--window-ring W] [--require-ip] [--dry-run] [--print-config] [--replay-rows CSV]\n"
                  "       [--host-split] [--repeat K] [--io-threads T] [--io auto|mapped|mmap|pread]\n"
-                 "       [--h2d-sdma] [--join-redis [--park-capacity N]] [--lz4]\n"
+                 "       [--h2d-sdma] [--join-redis [--park-capacity N]] [--lz4] [--kafka]\n"
                  "   or: ysb_topology --confPath PATH --columns [--device N] [--format json|tbl] [--require-ip]\n"
                  "       [--batch-mb MB | --batch-bytes B]   (window.size rows per <shared_file>_<k>)\n"
                  "   or: ysb_topology --confPath PATH --from-columns [--device N] [--sink none|csv:FILE|redis[:HOST[:PORT]]]\n"
@@ -126,6 +129,7 @@ Args parse(int argc, char** argv) {
         else if (k == "--join-redis") a.join_redis = true;
         else if (k == "--park-capacity") a.park_capacity = std::max(1ll, std::atoll(val().c_str()));
         else if (k == "--lz4") a.lz4 = true;
+        else if (k == "--kafka") a.kafka = true;
         else if (k == "--columns") a.columns = true;
         else if (k == "--from-columns") a.from_columns = true;
         else if (k == "--stream") a.stream = true;
@@ -177,6 +181,11 @@ Args parse(int argc, char** argv) {
     if (a.so.streamLz4 && a.so.replay == StreamOptions::COPY) {
         std::fprintf(stderr, "--stream-lz4 is read in place from the registered cycle: not with --replay copy "
                              "(--replay mapped or mapped-raw)\n");
+        std::exit(2);
+    }
+    if (a.kafka && (a.stream || a.columns || a.from_columns || a.lz4 || a.host_split)) {
+        std::fprintf(stderr, "--kafka reads events_path as a log segment of record batches in batch mode: not with --stream, "
+                             "--columns, --from-columns, --lz4 or --host-split\n");
         std::exit(2);
     }
     if (a.lz4 && a.stream) {
@@ -305,7 +314,7 @@ int run(const Args& a) {
     o.requireIp = a.require_ip;
     o.gpuSplit = !a.host_split;
     o.h2dSdma = a.h2d_sdma;
-    o.mappedIo = !a.lz4 && (a.io == "mapped" || (a.io == "auto" && o.gpuSplit && !o.h2dSdma));
+    o.mappedIo = !a.lz4 && !a.kafka && (a.io == "mapped" || (a.io == "auto" && o.gpuSplit && !o.h2dSdma));
     o.parkCapacity = lookup ? (uint64_t)a.park_capacity : 0;
     if (a.io == "mapped" && !o.gpuSplit) {
         std::fprintf(stderr, "--io mapped reads raw lines in place: not with --host-split\n");
@@ -442,6 +451,60 @@ int run(const Args& a) {
                                      "a run of blocks would cut lines");
     }
     uint64_t lz4_comp = 0;
+    // --kafka: the segment's index (one 61-byte header per batch) and runs of whole batches that
+    // fit a slot's bytes and lines; --io mapped: read where they lie in the registered mapping
+    bool kafka_mapped = a.kafka && a.io == "mapped";
+    uint64_t kafka_framed = 0, kafka_records = 0, kafka_batches = 0;
+    if (kafka_mapped) {
+        try {
+            op.registerSource(src);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "note: the segment's mapping cannot be read in place (%s): slot copies\n", e.what());
+            kafka_mapped = false;
+        }
+    }
+    if (a.kafka) {
+        std::string file;
+        if (!kafka_mapped) file = readFile(events);
+        const uint8_t* fb = kafka_mapped ? src.mapping() : reinterpret_cast<const uint8_t*>(file.data());
+        const uint64_t fn = kafka_mapped ? src.fileBytes() : file.size();
+        ysb_kafka_summary sum{};
+        int rc = ysb_kafka_index(fb, fn, 0, nullptr, 0, &sum);
+        if (rc && rc != YSB_ERR_CAPACITY) throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
+        std::vector<ysb_kafka_batch> idx(sum.n_batches);
+        if (sum.n_batches && ysb_kafka_index(fb, fn, 0, idx.data(), idx.size(), &sum))
+            throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
+        if (sum.consumed != fn)
+            std::fprintf(stderr, "note: %llu bytes behind the segment's last whole batch are left alone\n",
+                         (unsigned long long)(fn - sum.consumed));
+        const uint64_t max_lines = std::max<uint64_t>(o.batchEvents, o.batchBytes / 32);
+        std::vector<ysb_kafka_batch> rel;
+        for (long long rep = 0; rep < a.repeat; ++rep) {
+            for (uint64_t b = 0; b < idx.size();) {
+                const uint64_t start = idx[b].records_off - 61;
+                uint64_t e = b, recs = 0;
+                while (e < idx.size() && idx[e].records_off + idx[e].records_bytes - start <= o.batchBytes &&
+                       recs + idx[e].n_records <= max_lines) recs += idx[e++].n_records;
+                if (e == b) throw std::runtime_error(events + ": batch " + std::to_string(b) + " exceeds the slot (--batch-mb)");
+                const uint64_t span = idx[e - 1].records_off + idx[e - 1].records_bytes - start;
+                rel.assign(idx.begin() + (ptrdiff_t)b, idx.begin() + (ptrdiff_t)e);
+                for (ysb_kafka_batch& k : rel) {
+                    k.records_off -= start;
+                    k.first_record -= idx[b].first_record;
+                }
+                op.submitKafka(fb + start, span, rel.data(), rel.size(), kafka_mapped);
+                kafka_framed += span;
+                kafka_records += recs;
+                kafka_batches += e - b;
+                b = e;
+                if (lookup) op.resolveParked(*lookup);
+                if (a.flush_ms > 0 && (now_s() - last_flush) * 1000.0 >= (double)a.flush_ms) {
+                    flush();
+                    last_flush = now_s();
+                }
+            }
+        }
+    }
     for (long long rep = 0; is_frame && rep < a.repeat; ++rep) {
         for (uint64_t b = 0; b < frame.size();) {
             uint64_t e = b;
@@ -479,7 +542,7 @@ int run(const Args& a) {
             }
         }
     }
-    for (long long rep = 0; !a.lz4 && rep < a.repeat; ++rep) {
+    for (long long rep = 0; !a.lz4 && !a.kafka && rep < a.repeat; ++rep) {
         if (rep) src.rewind();
         while (o.mappedIo ? op.submitMapped(src) > 0 : (o.gpuSplit ? op.fillFromRaw(src) : op.fillFrom(src)) > 0) {
             if (!o.mappedIo) op.submit();
@@ -509,7 +572,9 @@ int run(const Args& a) {
                 "\"format\": \"%s\", \"sink\": %s, \"h2d\": \"%s\", \"copy_GBs\": %.2f, \"copy_busy_frac\": %.4f, "
                 "\"fill_s\": %.3f, \"slot_wait_s\": %.3f, \"join_redis\": %s, \"parked_keys\": %llu, "
                 "\"parked_found\": %llu, \"parked_joined\": %llu, \"parked_missed\": %llu, \"join_round_trips\": %llu, "
-                "\"lz4\": %s, \"lz4_comp_bytes\": %llu, \"lz4_raw_bytes\": %llu, \"lz4_io\": \"%s\"}\n",
+                "\"lz4\": %s, \"lz4_comp_bytes\": %llu, \"lz4_raw_bytes\": %llu, \"lz4_io\": \"%s\", "
+                "\"kafka\": %s, \"kafka_framed_bytes\": %llu, \"kafka_records\": %llu, \"kafka_batches\": %llu, "
+                "\"kafka_io\": \"%s\"}\n",
                 (unsigned long long)s.events, (unsigned long long)s.views, (unsigned long long)s.joined,
                 (unsigned long long)s.join_misses, (unsigned long long)s.parse_errors,
                 (unsigned long long)s.time_errors, (unsigned long long)s.out_of_ring,
@@ -526,7 +591,9 @@ int run(const Args& a) {
                 (unsigned long long)op.parkedTotals().missed, (unsigned long long)(lookup ? lookup->roundTrips() : 0),
                 a.lz4 ? "true" : "false", (unsigned long long)lz4_comp,
                 (unsigned long long)(a.lz4 ? lz4.rawBytes * (uint64_t)a.repeat : 0),
-                !a.lz4 ? "" : lz4_mapped ? "mapped" : "slot");
+                !a.lz4 ? "" : lz4_mapped ? "mapped" : "slot", a.kafka ? "true" : "false",
+                (unsigned long long)kafka_framed, (unsigned long long)kafka_records, (unsigned long long)kafka_batches,
+                !a.kafka ? "" : kafka_mapped ? "mapped" : "slot");
     return s.overflow_dropped ? 3 : 0;
 }
 

@@ -3,7 +3,7 @@
 //
 //   ysb_gen -d DIR [-n EVENTS] [--seed S] [--campaigns C] [--ads-per-campaign A]
 //           [--rate EVENTS_PER_SEC] [--t0 MS] [--with-skew] [--users K]
-//           [--shards K] [--tbl] [--lz4 [--lz4-block N] | --lz4-frame]
+//           [--shards K] [--tbl] [--lz4 [--lz4-block N] | --lz4-frame] [--kafka [--kafka-batch BYTES]]
 //
 // Writes campaign-ids.txt, ad-ids.txt, ad-to-campaign-ids.txt (JSON map lines),
 // ad-to-campaign.csv (the fork's CSV map) and kafka-json.txt into DIR; with --shards K
@@ -13,6 +13,10 @@
 // of N bytes (default 8192; include/ysb_hip.h ysb_lz4_file_header) for ysb_topology --lz4.
 // With --lz4-frame the .lz4 files are standard LZ4 frames instead (independent 64 KiB blocks,
 // content size set: any LZ4 tool reads them, and so does ysb_topology --lz4).
+// With --kafka also kafka-json.log: the same events as a partition's log segment -- Kafka record
+// batches (message format v2) of at most BYTES bytes (default 16384, a producer's batch.size),
+// each event one record's value without its line terminator, as write-to-kafka (core.clj:61-98)
+// sends it -- for ysb_topology --kafka.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +34,8 @@ int main(int argc, char** argv) {
     unsigned shards = 0;
     bool tbl = false, lz4 = false, lz4_frame = false;
     unsigned lz4_block = 8192;
+    bool kafka = false;
+    unsigned kafka_batch = 16384;
     for (int i = 1; i < argc; ++i) {
         auto val = [&]() -> const char* {
             if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", argv[i]); std::exit(2); }
@@ -49,6 +55,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--lz4")) lz4 = true;
         else if (!std::strcmp(argv[i], "--lz4-frame")) lz4 = lz4_frame = true;
         else if (!std::strcmp(argv[i], "--lz4-block")) lz4_block = (unsigned)std::strtoul(val(), nullptr, 10);
+        else if (!std::strcmp(argv[i], "--kafka")) kafka = true;
+        else if (!std::strcmp(argv[i], "--kafka-batch")) kafka_batch = (unsigned)std::strtoul(val(), nullptr, 10);
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (!dir) { std::fprintf(stderr, "usage: ysb_gen -d DIR [-n EVENTS] [options]\n"); return 2; }
@@ -76,6 +84,33 @@ int main(int argc, char** argv) {
                            : ysb_lz4_write_file((path + ".lz4").c_str(), data.data(), data.size(), lz4_block, 1, 1, 16);
             if (rc) { std::fprintf(stderr, "ysb_gen: %s\n", ysb_last_error(nullptr)); return 1; }
         }
+    }
+    if (kafka) {
+        if (shards > 1) { std::fprintf(stderr, "ysb_gen: --kafka frames kafka-json.txt: not with --shards\n"); return 2; }
+        const std::string path = std::string(dir) + "/kafka-json.txt";
+        FILE* f = std::fopen(path.c_str(), "rb");
+        if (!f) { std::fprintf(stderr, "ysb_gen: cannot read %s\n", path.c_str()); return 1; }
+        // the values back to back: every line without its terminator
+        std::vector<uint8_t> data;
+        std::vector<uint32_t> off;
+        uint8_t buf[1 << 16];
+        bool at_start = true;
+        for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;)
+            for (size_t j = 0; j < k; ++j) {
+                if (buf[j] == '\n') { at_start = true; continue; }
+                if (at_start) {
+                    if (data.size() > 0xFFFFFFFFull) { std::fprintf(stderr, "ysb_gen: --kafka takes up to 4 GiB of values\n"); return 1; }
+                    off.push_back((uint32_t)data.size());
+                    at_start = false;
+                }
+                data.push_back(buf[j]);
+            }
+        std::fclose(f);
+        ysb_kafka_pack_opts o{};
+        o.batch_bytes = kafka_batch;
+        o.base_timestamp = p.t0_ms;
+        rc = ysb_kafka_write_file((std::string(dir) + "/kafka-json.log").c_str(), data.data(), data.size(), off.data(), off.size(), &o);
+        if (rc) { std::fprintf(stderr, "ysb_gen: %s\n", ysb_last_error(nullptr)); return 1; }
     }
     return 0;
 }

@@ -168,6 +168,37 @@ class YsbLz4FrameDesc(C.Structure):
                 ("measure_ms", C.c_double), ("decode_ms", C.c_double)]
 
 
+class YsbKafkaBatch(C.Structure):
+    _fields_ = [("records_off", C.c_uint64), ("records_bytes", C.c_uint32), ("n_records", C.c_uint32),
+                ("first_record", C.c_uint64), ("base_offset", C.c_int64), ("control_before", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class YsbKafkaSummary(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_batches", "n_records", "consumed", "control_batches", "crc_checked")]
+
+
+class YsbKafkaVerdict(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("bad_batches", "first_bad", "record", "rule")]
+
+
+class YsbKafkaCounters(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("records", "null_values", "keyed", "headers", "value_bytes")]
+
+
+class YsbKafkaPackOpts(C.Structure):
+    _fields_ = [("batch_bytes", C.c_uint32), ("batch_records", C.c_uint32), ("base_offset", C.c_int64),
+                ("base_timestamp", C.c_int64), ("key_off", C.c_void_p), ("keys", C.c_void_p), ("ts_delta", C.c_void_p),
+                ("n_headers", C.c_uint32), ("reserved", C.c_uint32), ("header_keys", C.POINTER(C.c_char_p)),
+                ("header_vals", C.POINTER(C.c_char_p)), ("header_val_len", C.POINTER(C.c_int32))]
+
+
+class YsbKafkaDesc(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "batches", "records", "null_values", "keyed", "headers",
+                                          "control_skipped", "framed_bytes", "value_bytes", "window_bytes")] + [
+                ("verdict", YsbKafkaVerdict), ("walk_ms", C.c_double), ("base_ms", C.c_double), ("gather_ms", C.c_double)]
+
+
 class YsbGenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_campaigns", C.c_uint32), ("ads_per_campaign", C.c_uint32),
                 ("t0_ms", C.c_int64), ("events_per_sec", C.c_uint64), ("with_skew", C.c_uint32),
@@ -243,6 +274,25 @@ SIGNATURES = {
     "ysb_lz4_set_decoder": (_I, [_P, _I]),
     "ysb_lz4_frame_info": (_I, [_P, C.POINTER(YsbLz4FrameDesc)]),
     "ysb_lz4_frame_desc_size": (_U64, []),
+    "ysb_kafka_index": (_I, [_PU8, _U64, _U32, _P, _U64, C.POINTER(YsbKafkaSummary)]),
+    "ysb_kafka_crc32c": (_U32, [_PU8, _U64]),
+    "ysb_kafka_unframe_host": (_I, [_PU8, _U64, _P, _U64, _PU8, _U64, _PU32, _U64, C.POINTER(_U64), C.POINTER(_U64),
+                                    C.POINTER(YsbKafkaCounters), C.POINTER(YsbKafkaVerdict)]),
+    "ysb_kafka_bound": (_U64, [_U64, _U64, C.POINTER(YsbKafkaPackOpts)]),
+    "ysb_kafka_pack": (_I, [_PU8, _U64, _PU32, _U64, C.POINTER(YsbKafkaPackOpts), _PU8, _U64, C.POINTER(_U64),
+                            C.POINTER(_U64)]),
+    "ysb_kafka_write_file": (_I, [C.c_char_p, _PU8, _U64, _PU32, _U64, C.POINTER(YsbKafkaPackOpts)]),
+    "ysb_kafka_unframe_device": (_I, [_P, _PU8, _U64, _P, _U64, _PU8, _U64, _PU32, _U64, C.POINTER(_U64),
+                                      C.POINTER(_U64)]),
+    "ysb_submit_kafka": (_I, [_P, _I, _PU8, _U64, _P, _U64]),
+    "ysb_submit_kafka_mapped": (_I, [_P, _I, _PU8, _U64, _P, _U64]),
+    "ysb_kafka_info": (_I, [_P, C.POINTER(YsbKafkaDesc)]),
+    "ysb_kafka_batch_size": (_U64, []),
+    "ysb_kafka_summary_size": (_U64, []),
+    "ysb_kafka_verdict_size": (_U64, []),
+    "ysb_kafka_counters_size": (_U64, []),
+    "ysb_kafka_pack_opts_size": (_U64, []),
+    "ysb_kafka_desc_size": (_U64, []),
     "ysb_lz4_pack": (_I, [_PU8, _U64, _U32, _I, _I, _I, _PU8, _U64, C.POINTER(_U64), _P, _U64, C.POINTER(_U64)]),
     "ysb_copy_time": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_U64), C.POINTER(_U64)]),
     "ysb_submit_device": (_I, [_P, _PU8, _U64, _PU32, _U64]),
@@ -408,7 +458,10 @@ def lib():
                        (L.ysb_parked_info_size, YsbParkedDesc), (L.ysb_lz4_desc_size, YsbLz4Desc),
                        (L.ysb_lz4_frame_desc_size, YsbLz4FrameDesc), (L.ysb_arrow_binding_size, YsbArrowBinding),
                        (L.ysb_arrow_cols_size, YsbArrowCols), (L.ysb_arrow_desc_size, YsbArrowDesc),
-                       (L.ysb_join_info_size, YsbJoinInfo)):
+                       (L.ysb_join_info_size, YsbJoinInfo), (L.ysb_kafka_batch_size, YsbKafkaBatch),
+                       (L.ysb_kafka_summary_size, YsbKafkaSummary), (L.ysb_kafka_verdict_size, YsbKafkaVerdict),
+                       (L.ysb_kafka_counters_size, YsbKafkaCounters), (L.ysb_kafka_pack_opts_size, YsbKafkaPackOpts),
+                       (L.ysb_kafka_desc_size, YsbKafkaDesc)):
             if fn() != C.sizeof(st):
                 raise ImportError("%s is %d bytes in the library, %d in this binding"
                                   % (st.__name__, fn(), C.sizeof(st)))

@@ -429,6 +429,49 @@ class YsbContext:
             out["first_bad"] = None
         return out
 
+    def submit_kafka(self, data, index, slot=0):
+        """ysb_submit_kafka: whole Kafka record batches (bytes / a uint8 array) with their index
+        (ysb_amd.kafka.index over `data`); the framed bytes cross PCIe, the GPU finds the values,
+        gathers them and scans them.  A bad Kafka batch drops the slot batch (YSB_ERR_FORMAT at
+        the call that would have launched it)."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+        idx = np.ascontiguousarray(index)
+        self._c(lib().ysb_submit_kafka(self._h, slot, _ptr(buf), buf.size, _ptr(idx), idx.size))
+
+    def submit_kafka_mapped(self, arr, offset, nbytes, index, slot=0):
+        """ysb_submit_kafka_mapped: arr[offset:offset + nbytes] of a registered array, read in
+        place by the device; the index's offsets are relative to that range's start."""
+        idx = np.ascontiguousarray(index)
+        self._c(lib().ysb_submit_kafka_mapped(self._h, slot, C.c_void_p(arr.ctypes.data + offset), nbytes, _ptr(idx),
+                                              idx.size))
+
+    def kafka_unframe_device(self, d_bytes, nbytes, index, d_out, out_cap, d_line_off, off_cap):
+        """ysb_kafka_unframe_device: the unframing alone, device to device.  Returns (records,
+        value bytes); raises YsbError (YSB_ERR_FORMAT) for a bad batch -- kafka_info()["verdict"]
+        then names it."""
+        idx = np.ascontiguousarray(index)
+        n, nb = C.c_uint64(), C.c_uint64()
+        self._c(lib().ysb_kafka_unframe_device(self._h, C.c_void_p(d_bytes), nbytes, _ptr(idx), idx.size,
+                                               C.c_void_p(d_out), out_cap, C.c_void_p(d_line_off), off_cap,
+                                               C.byref(n), C.byref(nb)))
+        return n.value, nb.value
+
+    def kafka_info(self, check=True):
+        """ysb_kafka_info as a dict: the last Kafka call settled (calls, batches, records,
+        null_values, keyed, headers, control_skipped, framed_bytes, value_bytes, window_bytes, the
+        verdict as a dict with first_bad None for a good call, and with timing=True walk_ms,
+        base_ms, gather_ms).  check=False: a sticky error of an earlier batch does not raise."""
+        d = _lib.YsbKafkaDesc()
+        rc = lib().ysb_kafka_info(self._h, C.byref(d))
+        if check:
+            self._c(rc)
+        out = {n: getattr(d, n) for n, _ in d._fields_ if n != "verdict"}
+        v = {n: getattr(d.verdict, n) for n, _ in d.verdict._fields_}
+        if v["first_bad"] == 0xFFFFFFFF:
+            v["first_bad"] = None
+        out["verdict"] = v
+        return out
+
     def copy_time(self):
         """(total ms, copies, bytes) of the slot H2D copies since the last call (timing=True)."""
         t, k, b = C.c_double(), C.c_uint64(), C.c_uint64()

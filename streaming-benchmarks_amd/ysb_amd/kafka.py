@@ -1,0 +1,148 @@
+"""Kafka record batches on the host side (csrc/ysb_kafka.h through the C ABI): the index of a
+fetch response or a .log segment, the host model of the GPU's unframing, and a packer for
+sources, tools and tests that have no Kafka client of their own.
+
+YsbContext.submit_kafka takes the bytes and the index that `index` returns.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, lib
+
+CHECK_CRC = 1
+BATCH = np.dtype([("records_off", "<u8"), ("records_bytes", "<u4"), ("n_records", "<u4"), ("first_record", "<u8"),
+                  ("base_offset", "<i8"), ("control_before", "<u4"), ("reserved", "<u4")])
+RULES = {0: "none", 1: "varint", 2: "length", 3: "past_batch", 4: "key", 5: "value", 6: "headers", 7: "count"}
+DEFAULT_BATCH = 16384   # a producer's default batch.size
+
+
+def _u8(data):
+    return np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) \
+        else np.ascontiguousarray(data, dtype=np.uint8)
+
+
+def crc32c(data):
+    """CRC-32C (Castagnoli) as the batch header carries it."""
+    src = _u8(data)
+    return lib().ysb_kafka_crc32c(src.ctypes.data if src.size else None, src.size)
+
+
+def index(data, check_crc=False):
+    """ysb_kafka_index: (index, summary dict) of a buffer of record batches.  index is a BATCH
+    array with one entry per data batch; summary["consumed"] stops in front of a last batch that
+    is not whole.  Raises YsbError (YSB_ERR_FORMAT) naming the byte offset, the field and the rule
+    for a batch the library does not take (magic other than 2, a codec, batchLength < 49, a negative
+    recordsCount, with check_crc a CRC-32C mismatch)."""
+    src = _u8(data)
+    flags = CHECK_CRC if check_crc else 0
+    info = _lib.YsbKafkaSummary()
+    p = src.ctypes.data if src.size else None
+    rc = lib().ysb_kafka_index(p, src.size, flags, None, 0, C.byref(info))
+    if rc not in (0, -4):
+        check(rc)
+    idx = np.zeros(info.n_batches, dtype=BATCH)
+    if info.n_batches:
+        check(lib().ysb_kafka_index(p, src.size, flags, idx.ctypes.data, idx.size, C.byref(info)))
+    return idx, {k: getattr(info, k) for k, _ in info._fields_}
+
+
+def unframe_host(data, idx, sizes_only=False):
+    """ysb_kafka_unframe_host, the model of the GPU's unframing: (values back to back as a uint8
+    array, line offsets with the total as the last entry, counters dict).  Raises YsbError
+    (YSB_ERR_FORMAT) for a bad batch; `verdict(data, idx)` returns it without raising."""
+    out, off, ct, vd, rc = _unframe(data, idx, sizes_only)
+    check(rc)
+    return out, off, ct
+
+
+def verdict(data, idx):
+    """The model's verdict as a dict: bad_batches, first_bad (None: none), record, rule."""
+    vd = _unframe(data, idx, True)[3]
+    return vd
+
+
+def _unframe(data, idx, sizes_only):
+    src = _u8(data)
+    idx = np.ascontiguousarray(idx, dtype=BATCH)
+    n, nb = C.c_uint64(), C.c_uint64()
+    ct, vd = _lib.YsbKafkaCounters(), _lib.YsbKafkaVerdict()
+    p = src.ctypes.data if src.size else None
+    ip = idx.ctypes.data if idx.size else None
+    rc = lib().ysb_kafka_unframe_host(p, src.size, ip, idx.size, None, 0, None, 0, C.byref(n), C.byref(nb), C.byref(ct),
+                                      C.byref(vd))
+    out = np.zeros(0, dtype=np.uint8)
+    off = np.zeros(0, dtype=np.uint32)
+    if rc == 0 and not sizes_only:
+        out = np.empty(max(nb.value, 1), dtype=np.uint8)
+        off = np.empty(n.value + 1, dtype=np.uint32)
+        rc = lib().ysb_kafka_unframe_host(p, src.size, ip, idx.size, out.ctypes.data, out.size, off.ctypes.data, off.size,
+                                          C.byref(n), C.byref(nb), C.byref(ct), C.byref(vd))
+        out = out[:nb.value]
+    v = {k: getattr(vd, k) for k, _ in vd._fields_}
+    if v["first_bad"] == 0xFFFFFFFF:
+        v["first_bad"] = None
+    return out, off, {k: getattr(ct, k) for k, _ in ct._fields_}, v, rc
+
+
+class _Opts:
+    """ysb_kafka_pack_opts with the arrays it points to kept alive."""
+
+    def __init__(self, n_lines, batch_bytes, batch_records, base_offset, base_timestamp, keys, ts_delta, headers):
+        o = self.o = _lib.YsbKafkaPackOpts()
+        o.batch_bytes, o.batch_records = int(batch_bytes or 0), int(batch_records or 0)
+        o.base_offset, o.base_timestamp = int(base_offset), int(base_timestamp)
+        self.keep = []
+        if keys is not None:
+            if len(keys) != n_lines:
+                raise ValueError("one key per line")
+            koff = np.zeros(n_lines + 1, dtype=np.uint32)
+            koff[1:] = np.cumsum([len(k) for k in keys])
+            kb = np.frombuffer(b"".join(bytes(k) for k in keys) + b"\0", dtype=np.uint8)
+            self.keep += [koff, kb]
+            o.key_off, o.keys = koff.ctypes.data, kb.ctypes.data
+        if ts_delta is not None:
+            ts = np.ascontiguousarray(ts_delta, dtype=np.int64)
+            if ts.size != n_lines:
+                raise ValueError("one timestamp delta per line")
+            self.keep.append(ts)
+            o.ts_delta = ts.ctypes.data
+        if headers:
+            n = len(headers)
+            hk = (C.c_char_p * n)(*[bytes(k) for k, _ in headers])
+            hv = (C.c_char_p * n)(*[None if v is None else bytes(v) for _, v in headers])
+            hl = (C.c_int32 * n)(*[-1 if v is None else len(v) for _, v in headers])
+            self.keep += [hk, hv, hl]
+            o.n_headers, o.header_keys, o.header_vals, o.header_val_len = n, hk, hv, hl
+
+
+def _lines(data, offsets):
+    return _u8(data), np.ascontiguousarray(offsets, dtype=np.uint32)
+
+
+def pack(data, offsets, batch_bytes=DEFAULT_BATCH, batch_records=0, base_offset=0, base_timestamp=0, keys=None,
+         ts_delta=None, headers=None):
+    """ysb_kafka_pack: the lines data[offsets[i]:offsets[i + 1]] (the last one ends at len(data))
+    as record batches of at most batch_bytes bytes or batch_records records; a uint8 array.
+    keys: None (null keys) or one bytes per line; ts_delta: None or one int per line; headers: a
+    list of (key bytes, value bytes or None) put on every record."""
+    src, off = _lines(data, offsets)
+    o = _Opts(off.size, batch_bytes, batch_records, base_offset, base_timestamp, keys, ts_delta, headers)
+    dst = np.empty(max(lib().ysb_kafka_bound(src.size, off.size, C.byref(o.o)), 1), dtype=np.uint8)
+    n, nb = C.c_uint64(), C.c_uint64()
+    check(lib().ysb_kafka_pack(src.ctypes.data if src.size else None, src.size, off.ctypes.data if off.size else None,
+                               off.size, C.byref(o.o), dst.ctypes.data, dst.size, C.byref(n), C.byref(nb)))
+    return dst[:n.value]
+
+
+def write_file(path, data, offsets, **kw):
+    """ysb_kafka_write_file: `pack` into a file -- a partition's .log segment (what ysb_gen
+    --kafka writes and ysb_topology --kafka reads)."""
+    src, off = _lines(data, offsets)
+    o = _Opts(off.size, kw.pop("batch_bytes", DEFAULT_BATCH), kw.pop("batch_records", 0), kw.pop("base_offset", 0),
+              kw.pop("base_timestamp", 0), kw.pop("keys", None), kw.pop("ts_delta", None), kw.pop("headers", None))
+    if kw:
+        raise TypeError("unknown options %s" % sorted(kw))
+    check(lib().ysb_kafka_write_file(str(path).encode(), src.ctypes.data if src.size else None, src.size,
+                                     off.ctypes.data if off.size else None, off.size, C.byref(o.o)))

@@ -220,3 +220,85 @@ class Lz4FileDataSource:
 
     def __exit__(self, *a):
         self.close()
+
+
+class KafkaLogDataSource:
+    """A partition's .log segment (or a saved fetch response) -- Kafka record batches, message
+    format v2, back to back (ysb_gen --kafka, ysb_amd.kafka.write_file) --, mapped read-only:
+    `runs(cap, max_records)` yields (offset into the mapping, bytes, first batch, batches) of
+    runs of whole batches that fit a slot; `run(ctx, cap)` registers the mapping and submits
+    every run where it lies (ysb_submit_kafka_mapped: the framed bytes cross PCIe once, the host
+    reads one 61-byte header per batch).  A tail that is not a whole batch is left alone."""
+
+    def __init__(self, path: str, check_crc: bool = False):
+        from . import kafka
+        self.path = str(path)
+        self.size = os.path.getsize(self.path)
+        self._mm = None
+        self.data = np.zeros(0, dtype=np.uint8)
+        if self.size:
+            with open(self.path, "rb") as f:
+                self._mm = mmap.mmap(f.fileno(), 0, flags=mmap.MAP_SHARED, prot=mmap.PROT_READ)
+            self.data = np.frombuffer(self._mm, dtype=np.uint8)
+        self.index, self.summary = kafka.index(self.data, check_crc=check_crc)
+        self.framed_bytes = 0
+        self.batches = 0
+
+    @property
+    def mapping_bytes(self) -> int:
+        return (self.size + PAGE - 1) // PAGE * PAGE
+
+    def runs(self, cap: int, max_records: int):
+        if cap <= 0 or max_records <= 0:
+            raise ValueError("cap and max_records must be positive")
+        n, b = self.index.size, 0
+        start = self.index["records_off"].astype(np.int64) - 61
+        end = self.index["records_off"].astype(np.int64) + self.index["records_bytes"].astype(np.int64)
+        while b < n:
+            e, recs = b, 0
+            while e < n and int(end[e]) - int(start[b]) <= cap and recs + int(self.index[e]["n_records"]) <= max_records:
+                recs += int(self.index[e]["n_records"])
+                e += 1
+            if e == b:
+                raise ValueError("%s: batch %d exceeds the slot" % (self.path, b))
+            yield int(start[b]), int(end[e - 1]) - int(start[b]), b, e - b
+            b = e
+
+    def run(self, ctx, cap: int):
+        """Every run of the segment through ctx (a YsbContext), in place; returns the framed
+        bytes submitted.  At most two batches in flight."""
+        max_bytes, max_events = ctx.slot_capacity()
+        max_records = max(max_events, max_bytes // 32)
+        if self.size:
+            ctx.host_register(self.data, self.mapping_bytes)
+        try:
+            slot = 0
+            for off, nbytes, b, k in self.runs(min(cap, max_bytes), max_records):
+                idx = self.index[b:b + k].copy()
+                idx["records_off"] -= off
+                idx["first_record"] -= idx["first_record"][0]
+                ctx.submit_kafka_mapped(self.data, off, nbytes, idx, slot=slot)
+                slot ^= 1
+                ctx.wait(slot)
+                self.framed_bytes += nbytes
+                self.batches += 1
+            ctx.sync()
+        finally:
+            if self.size:
+                ctx.host_unregister(self.data)
+        return self.framed_bytes
+
+    def close(self):
+        self.data = np.zeros(0, dtype=np.uint8)
+        if self._mm is not None:
+            try:
+                self._mm.close()
+            except BufferError:   # a caller still holds a view of the mapping: it stays until freed
+                pass
+            self._mm = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
