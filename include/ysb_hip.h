@@ -752,7 +752,8 @@ uint32_t    ysb_kafka_crc32c(const uint8_t* bytes, uint64_t nbytes);   /* "12345
  * key runs past the record (or its length is below -1), 5 the same for the value, 6 the headers
  * do not end exactly at the record's end (or a negative count / header key length), 7 the walk
  * does not yield exactly recordsCount records ending exactly at the batch's end (record: where
- * it stopped).  The verdict names the smallest bad batch and its smallest bad record. */
+ * it stopped), 8 (compressed batches only, below) a block of the batch's LZ4 frame does not
+ * decode (record: the block).  The verdict names the smallest bad batch and its smallest bad record. */
 typedef struct ysb_kafka_verdict {
     uint32_t bad_batches;
     uint32_t first_bad;       /* index entry; 0xFFFFFFFF: none */
@@ -795,7 +796,10 @@ typedef struct ysb_kafka_pack_opts {
     const uint8_t*  keys;
     const int64_t*  ts_delta;        /* n_lines, or NULL                       */
     uint32_t        n_headers;
-    uint32_t        reserved;
+    uint32_t        codec;           /* 0: uncompressed; YSB_KAFKA_CODEC_LZ4: each batch's records as one
+                                        standard LZ4 frame (64 KiB independent blocks, a block that does not
+                                        shrink stored), attributes = 3, the CRC over the wire bytes; any
+                                        other value: YSB_ERR_ARG                                            */
     const char* const*    header_keys;      /* NUL-terminated                  */
     const uint8_t* const* header_vals;
     const int32_t*        header_val_len;   /* -1: a null value                */
@@ -861,6 +865,105 @@ uint64_t    ysb_kafka_verdict_size(void);
 uint64_t    ysb_kafka_counters_size(void);
 uint64_t    ysb_kafka_pack_opts_size(void);
 uint64_t    ysb_kafka_desc_size(void);
+/* ---- LZ4-compressed Kafka record batches (additive within ABI 6) ---------------------------
+ * A topic whose producers set compression.type=lz4: in message format v2 the 61-byte batch header
+ * stays as it is and the records section is ONE standard LZ4 frame (attributes codec 3).  The
+ * Java client writes FLG 0x60 / BD 0x40 and an EndMark, librdkafka LZ4F_blockIndependent with the
+ * default block size: independent blocks of at most 64 KiB, which is what ysb_lz4_frame_index
+ * accepts.  Everything here is opt-in: ysb_kafka_index and the submits above keep refusing any
+ * codec.  The wire bytes and three index arrays cross PCIe; the GPU measures the blocks, plans
+ * the inflated layout (the walk's index is made on the device: the host never learns a batch's
+ * raw size), decodes, then walks, scans and gathers as above.
+ * ysb_kafka_index_lz4 is ysb_kafka_index for codec 0 and codec 3: batches[k] as above
+ * (records_off / records_bytes: the wire bytes, for codec 3 the frame; n_records, first_record
+ * and base_offset from the header), frames[k] the blocks of entry k, blocks[] every block's
+ * place in the indexed buffer.  A codec-0 batch's records become stored blocks of at most 64 KiB,
+ * so a mixed fetch response takes one path.  YSB_ERR_FORMAT naming the Kafka batch, its byte, and
+ * the frame's byte and rule (with the way out where ysb_lz4_frame_index gives one: linked blocks,
+ * a block maximum above 64 KiB) for every frame refusal, truncation inside the records and bytes
+ * behind the last frame included; codecs 1, 2 and 4 are refused by name (gzip, snappy, zstd:
+ * have the producer write lz4 or none).  cap counts batches and frames, block_cap blocks;
+ * YSB_ERR_CAPACITY with info complete when either is short (NULL arrays with 0 caps count). */
+#define YSB_KAFKA_CODEC_LZ4 3u
+typedef struct ysb_kafka_frame {
+    uint64_t first_block;     /* the blocks of the entries before it: the running sum */
+    uint32_t n_blocks;        /* at most 32767                                        */
+    uint32_t codec;           /* 0 (stored blocks over the records) or 3              */
+} ysb_kafka_frame;
+typedef struct ysb_kafka_lz4_summary {
+    uint64_t n_batches;       /* as ysb_kafka_summary ...                        */
+    uint64_t n_records;
+    uint64_t consumed;
+    uint64_t control_batches;
+    uint64_t crc_checked;
+    uint64_t compressed_batches; /* ... and: data batches with codec 3           */
+    uint64_t blocks;          /* entries of blocks[]                             */
+    uint64_t stored_blocks;   /* a frame's stored blocks and the codec-0 batches' */
+    uint64_t comp_bytes;      /* the sum of the blocks' sizes on the wire        */
+} ysb_kafka_lz4_summary;
+int         ysb_kafka_index_lz4(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, ysb_kafka_batch* batches,
+                                ysb_kafka_frame* frames, uint64_t cap, ysb_lz4_frame_block* blocks, uint64_t block_cap,
+                                ysb_kafka_lz4_summary* info);
+/* The host model (csrc/ysb_kafka_lz4.h): each batch's blocks decoded by the host block decoder,
+ * then ysb_kafka_unframe_host's walk over the result.  verdict->rule 8: a block of the batch's
+ * frame does not decode (the measure walk or the decoder refuses it); `record` is then the
+ * smallest such block within the batch.  The verdict is the smallest bad batch, whichever kind
+ * of fault it has; bad_batches counts both kinds.  *inflated (may be NULL): the good batches'
+ * decoded bytes.  YSB_ERR_ARG for entries that break their rules (a frame entry's running block
+ * sum, a block outside its batch's wire bytes or not 1..65536 bytes). */
+int         ysb_kafka_unframe_lz4_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                       const ysb_kafka_frame* frames, uint64_t n_batches,
+                                       const ysb_lz4_frame_block* blocks, uint64_t n_blocks, uint8_t* out,
+                                       uint64_t out_cap, uint32_t* line_off, uint64_t off_cap, uint64_t* n_lines,
+                                       uint64_t* out_bytes, uint64_t* inflated, ysb_kafka_counters* counters,
+                                       ysb_kafka_verdict* verdict);
+/* The inflate and the unframing alone, device to device (synchronous): as
+ * ysb_kafka_unframe_device, with the chain measure, plan, decode, walk, codec verdict, base,
+ * gather on one stream.  The inflated bytes go to a buffer of the context's own (n_blocks x 64
+ * KiB, grown on demand).  Same outputs and returns; rule 8 in ysb_kafka_info's verdict. */
+int         ysb_kafka_unframe_lz4_device(ysb_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes,
+                                         const ysb_kafka_batch* batches, const ysb_kafka_frame* frames,
+                                         uint64_t n_batches, const ysb_lz4_frame_block* blocks, uint64_t n_blocks,
+                                         uint8_t* d_out, uint64_t out_cap, uint32_t* d_line_off, uint64_t off_cap,
+                                         uint64_t* n_lines, uint64_t* out_bytes);
+/* ysb_submit_kafka / _mapped for batches indexed by ysb_kafka_index_lz4 (offsets relative to
+ * `bytes`).  The host cannot know raw sizes, so the capacity rule is the guaranteed bound:
+ * YSB_ERR_CAPACITY at the call unless nbytes <= max_batch_bytes and n_blocks x 65536 <=
+ * max_batch_bytes (and the record-count rule above).  The inflated buffer, max_batch_bytes + 64
+ * per slot, is allocated at a slot's first compressed submit: a context that never calls these
+ * pays nothing.  A batch with a bad block or a bad record drops the whole slot batch (sticky
+ * YSB_ERR_FORMAT until ysb_reset, the message naming the batch and the block or record).
+ * YSB_ERR_STATE while a frame batch's carry is pending. */
+int         ysb_submit_kafka_lz4(ysb_ctx* ctx, int slot, const uint8_t* bytes, uint64_t nbytes,
+                                 const ysb_kafka_batch* batches, const ysb_kafka_frame* frames, uint64_t n_batches,
+                                 const ysb_lz4_frame_block* blocks, uint64_t n_blocks);
+int         ysb_submit_kafka_lz4_mapped(ysb_ctx* ctx, int slot, const uint8_t* bytes, uint64_t nbytes,
+                                        const ysb_kafka_batch* batches, const ysb_kafka_frame* frames,
+                                        uint64_t n_batches, const ysb_lz4_frame_block* blocks, uint64_t n_blocks);
+/* The inflate half of the last compressed Kafka call settled (ysb_kafka_info keeps reporting its
+ * walk, base and gather).  Waits for everything submitted. */
+typedef struct ysb_kafka_lz4_desc {
+    uint64_t calls;              /* compressed Kafka calls since ysb_open / ysb_reset      */
+    uint64_t blocks;
+    uint64_t stored_blocks;
+    uint64_t compressed_batches;
+    uint64_t wire_bytes;
+    uint64_t inflated_bytes;     /* the measured total                                     */
+    uint64_t bad_blocks;         /* refused by the measure pass or by the decoder          */
+    uint64_t decoder;            /* YSB_LZ4_DECODER_NARROW / _WIDE: which ran (0: none); 3:
+                                    both, each on its size class (blocks of up to 16 KiB of
+                                    raw bytes the one-wave kernel: _AUTO, where only the
+                                    device knows the sizes)                                */
+    uint64_t inflated_buffer_bytes; /* the context's inflated buffers in all (0: none yet) */
+    uint64_t inflated_total;     /* inflated_bytes of every call since ysb_open / ysb_reset */
+    double   measure_ms;         /* YSB_F_TIMING: HIP events around each kernel            */
+    double   plan_ms;
+    double   decode_ms;
+} ysb_kafka_lz4_desc;
+int         ysb_kafka_lz4_info(ysb_ctx* ctx, ysb_kafka_lz4_desc* info);
+uint64_t    ysb_kafka_frame_size(void);
+uint64_t    ysb_kafka_lz4_summary_size(void);
+uint64_t    ysb_kafka_lz4_desc_size(void);
 /* Device-resident batch (HBM pointers, e.g. from ysb_device_alloc). Asynchronous.  The batch
  * must be complete when submitted, or its producer ordered before the compute stream
  * (hipStreamWaitEvent(ysb_stream(ctx), ...), or produced on that stream).  Unless

@@ -855,6 +855,7 @@ int ysb_reset(ysb_ctx* c) {
     c->lz4f_last = ysb_lz4_frame_desc{};
     c->lz4f_more = false;
     c->kafka_last = ysb_kafka_desc{};
+    c->kafka_lz4_last = ysb_kafka_lz4_desc{};
     if (c->d_carry) HIPCHK(c, hipMemset(c->d_carry, 0, LZ4_CARRY_HEAD));   // the carry is cleared
     return YSB_OK;
 }

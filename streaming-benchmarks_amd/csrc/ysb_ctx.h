@@ -169,6 +169,10 @@ struct Lz4Staged {
 // slot's pinned buffer until the slot is claimed again, which launches this batch first).
 struct KafkaStaged {
     u64 n_batches = 0, n_records = 0, framed_bytes = 0, control_skipped = 0;
+    // a compressed batch (ysb_submit_kafka_lz4): the inflate chain runs in front of the walk
+    bool lz4 = false;
+    u64 n_blocks = 0, stored_blocks = 0, compressed_batches = 0;
+    u32 decoder = 0;                     // the decode kernel chosen when it was staged
 };
 
 // A slot's batch between its submit and its launch one call later (ysb_raw.cpp).  Every submit
@@ -306,6 +310,16 @@ struct ysb_ctx {
     DevBuf<u8> d_kafka_sync;
     ysb_kafka_desc kafka_last{};
     Event ev_kafka[2][4];
+    // LZ4-compressed Kafka batches (ysb_kafka_lz4.h): per slot the inflated records (max_batch_bytes
+    // + 64, allocated at the slot's first compressed submit: a context that never sees one pays
+    // nothing) -- the decode's output and the walk's input --; the synchronous call's inflated
+    // buffer and scratch; the plan's head read back beside the verdict; the last call settled;
+    // YSB_F_TIMING's events around measure, plan and decode
+    DevBuf<u8> d_kafka_infl[2];
+    DevBuf<u8> d_kafka_infl_sync, d_kafka_lz4_sync;
+    PinBuf<KafkaPlanHead> h_kafka_plan;
+    ysb_kafka_lz4_desc kafka_lz4_last{};
+    Event ev_kafka_lz4[2][4];
     // counts
     u32 c_pad = 0;                        // campaigns padded to the group size
     DevBuf<unsigned long long> d_counts;      // [c_pad][W]
@@ -542,7 +556,12 @@ YSB_INTERNAL int lz4f_readback(ysb_ctx* c, int slot, hipStream_t s);
 // previous copy.
 YSB_INTERNAL int kafka_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
                              uint64_t n_batches, const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample);
+// ... of a compressed one (index, frames and blocks in the slot's pinned buffer, one copy)
+YSB_INTERNAL int kafka_lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                 const ysb_kafka_frame* frames, uint64_t nb, const ysb_lz4_frame_block* blocks,
+                                 uint64_t n_blocks, const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample);
 // the three kernels on s behind the slot's copies: d_bytes[slot], d_roff[slot]; the head's read-back
+// (a compressed batch: measure, plan, decode in front of them, the codec verdict behind the walk)
 YSB_INTERNAL int kafka_enqueue(ysb_ctx* c, int slot, const KafkaStaged& b, hipStream_t s);
 // at the batch's launch: kafka_last <- its figures; YSB_ERR_FORMAT naming the bad Kafka batch
 YSB_INTERNAL int kafka_settle(ysb_ctx* c, int slot, const KafkaStaged& b);

@@ -52,7 +52,9 @@ enum : u32 {
     KAFKA_R_VALUE = 5,     // the same for the value
     KAFKA_R_HEADERS = 6,   // a negative count or header key length, a header past the record, or the
                            //   headers not ending exactly at the record's end
-    KAFKA_R_COUNT = 7      // the batch ends in front of record recordsCount, or bytes are left behind it
+    KAFKA_R_COUNT = 7,     // the batch ends in front of record recordsCount, or bytes are left behind it
+    KAFKA_R_CODEC = 8      // a block of the batch's LZ4 frame does not decode (`record`: the smallest such block
+                           //   of the batch; ysb_kafka_lz4.h)
 };
 YSB_HD const char* kafka_rule_name(u32 r) {
     return r == KAFKA_R_VARINT ? "a varint runs past its limit or its extent"
@@ -61,7 +63,8 @@ YSB_HD const char* kafka_rule_name(u32 r) {
          : r == KAFKA_R_KEY ? "the key runs past the record"
          : r == KAFKA_R_VALUE ? "the value runs past the record"
          : r == KAFKA_R_HEADERS ? "the headers do not end at the record's end"
-         : r == KAFKA_R_COUNT ? "the records do not end at the batch's end" : "none";
+         : r == KAFKA_R_COUNT ? "the records do not end at the batch's end"
+         : r == KAFKA_R_CODEC ? "a block of the batch's LZ4 frame does not decode" : "none";
 }
 
 YSB_HD int32_t kafka_unzigzag32(u32 v) { return (int32_t)(v >> 1) ^ -(int32_t)(v & 1); }
@@ -187,7 +190,7 @@ inline void kafka_put_be(u8* p, int n, u64 v) {
 }
 
 struct KafkaError {
-    char msg[320];
+    char msg[512];
 };
 
 // ---- the index: the headers alone -------------------------------------------------------------
@@ -376,9 +379,12 @@ inline u64 kafka_headers_bytes(const ysb_kafka_pack_opts& o) {
 }
 
 // What kafka_pack may write for n_lines lines of nbytes bytes (each record in a batch of its own).
+// With o.codec 3 (kafka_pack_lz4, ysb_kafka_lz4.h) a batch's records are a frame: 19 bytes of
+// header and EndMark per batch and a size word per 64 KiB block (a block is never above its raw size).
 inline u64 kafka_bound(u64 nbytes, u64 n_lines, const ysb_kafka_pack_opts& o) {
     const u64 keys = o.key_off ? o.key_off[n_lines] : 0;
-    return nbytes + keys + n_lines * (KAFKA_HEADER + 40 + kafka_headers_bytes(o));
+    const u64 plain = nbytes + keys + n_lines * (KAFKA_HEADER + 40 + kafka_headers_bytes(o));
+    return o.codec ? plain + n_lines * 23 + 4 * (plain / 65536 + 1) : plain;
 }
 
 // Lines [line_off[i], line_off[i + 1]) (the last one ends at nbytes) as record batches: a batch

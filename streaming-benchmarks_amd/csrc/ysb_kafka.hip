@@ -26,8 +26,23 @@
 // buffer), every read of the parser is bounded by the reader's checks against the record's
 // extent inside it, and every step of the chain moves on by at least 7 bytes.  The gather runs
 // only on a call whose every batch the reader accepted.
+//
+// LZ4-compressed batches (ysb_kafka_lz4.h; ysb_submit_kafka_lz4) put four launches in front of
+// the walk and one behind it, on the same stream:
+//   lz4_measure_kernel         (ysb_lz4.hip, unchanged) each block's raw size, 0 for a bad block
+//   kafka_inflate_plan_kernel  one workgroup: the decode's descriptors and the walk's index
+//   lz4_decode_kernel / _wide  (ysb_lz4.hip) into the context's inflated buffer
+//   kafka_walk_kernel          P.bytes the inflated buffer, P.batches the planned index
+//   kafka_codec_kernel         the batches with a bad block become rule 8 in bout, whatever the
+//                              walk made of their undecoded bytes; then base and gather as above.
+// The inflated extents lie at any byte alignment and the walk loads whole 16-byte vectors around
+// an extent.  That is safe: the inflated buffer is 256-byte aligned with 64 bytes of slack
+// behind the last extent, and the decode is complete before the walk (the same stream).  A batch
+// the decode left unwritten is walked over whatever the buffer held; the reader's bounds hold
+// for any bytes, and its verdict is replaced.
 #include "ysb_kernels.h"
 #include "ysb_kafka.h"
+#include "ysb_lz4.h"
 
 namespace ysb {
 
@@ -275,6 +290,119 @@ __global__ __launch_bounds__(KAFKA_G_TPB) void kafka_gather_kernel(const KafkaPa
         for (u32 v = z + tid; v < c1; v += KAFKA_G_TPB) gbase[v] = buf[v - c0];
         __syncthreads();
     }
+}
+
+// ---- compressed batches: the plan between the measure pass and the decode ---------------------
+// Phase 1, KAFKA_PLAN_STEP blocks per step: a wave-shuffle inclusive scan of (raw size, measured
+// 0) inside each wave, the four waves' totals through LDS, two running prefixes carried from
+// step to step.  desc[i].out_off is block i's place in the inflated buffer.  Phase 2, a thread
+// per Kafka batch: its extent is [out_off of its first block, out_off + raw of its last); a
+// batch whose zero count moves is bad -- its smallest such block is the verdict and its blocks'
+// descriptors get raw 0, so the decode writes nothing of it.  Every index read is bounded by
+// the host's checks (kafka_lz4_entries); all values leave through ordinary vector stores.
+static_assert(KAFKA_PLAN_STEP == 256, "four waves per step");
+
+__global__ __launch_bounds__(KAFKA_PLAN_STEP) void kafka_inflate_plan_kernel(const KafkaPlanParams P) {
+    __shared__ u32 w_raw[4], w_zero[4];
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    u64 run = 0;
+    u32 zrun = 0;
+    for (u32 at = 0; at < P.n_blocks; at += KAFKA_PLAN_STEP) {
+        const u32 i = at + tid;
+        const u32 r = i < P.n_blocks ? P.raw[i] : 0u;
+        const u32 z = (i < P.n_blocks && r == 0u) ? 1u : 0u;
+        u32 ir = r, iz = z;
+        for (int d = 1; d < 64; d <<= 1) {
+            const u32 ur = (u32)__shfl_up((int)ir, d), uz = (u32)__shfl_up((int)iz, d);
+            if ((int)lane >= d) {
+                ir += ur;
+                iz += uz;
+            }
+        }
+        if (lane == 63) {
+            w_raw[wave] = ir;
+            w_zero[wave] = iz;
+        }
+        __syncthreads();
+        u32 pr = 0, pz = 0, tr = 0, tz = 0;
+        for (u32 w = 0; w < 4; ++w) {
+            if (w < wave) {
+                pr += w_raw[w];
+                pz += w_zero[w];
+            }
+            tr += w_raw[w];
+            tz += w_zero[w];
+        }
+        if (i < P.n_blocks) {
+            const Lz4FrameBlock b = P.blocks[i];
+            P.desc[i] = Lz4Desc{b.offset, run + (pr + ir - r), b.comp, r};
+            P.zeros[i] = zrun + (pz + iz - z);
+            P.block_bad[i] = 0u;
+        }
+        run += tr;
+        zrun += tz;
+        __syncthreads();   // the waves' totals are rewritten by the next step
+    }
+    if (tid == 0) {
+        P.zeros[P.n_blocks] = zrun;
+        *P.head = KafkaPlanHead{{LZ4_NO_BAD, 0u}, zrun, 0u, run};
+    }
+    __threadfence();
+    __syncthreads();   // phase 2 reads desc[] and zeros[] that other threads of this workgroup wrote
+    for (u32 k = tid; k < P.n_batches; k += KAFKA_PLAN_STEP) {
+        const ysb_kafka_frame f = P.frames[k];
+        ysb_kafka_batch b = P.batches[k];
+        u64 off = 0;
+        u32 bytes = 0, bad = KAFKA_NONE;
+        if (f.n_blocks) {
+            const u64 first = f.first_block, last = first + f.n_blocks - 1;
+            off = P.desc[first].out_off;
+            bytes = (u32)(P.desc[last].out_off + P.raw[last] - off);
+            if (P.zeros[last + 1] != P.zeros[first]) {
+                for (u32 j = 0; j < f.n_blocks; ++j)
+                    if (P.raw[first + j] == 0u) {
+                        bad = j;
+                        break;
+                    }
+                for (u32 j = 0; j < f.n_blocks; ++j) P.desc[first + j].raw = 0u;
+                bytes = 0;
+            }
+        }
+        b.records_off = off;
+        b.records_bytes = bytes;
+        P.planned[k] = b;
+        P.codec_bad[k] = bad;
+    }
+}
+
+// The codec verdict, a thread per Kafka batch: the plan's bad block, else (only when the decode
+// recorded a bad block at all) the smallest block of the batch that the decoder flagged.
+__global__ __launch_bounds__(256) void kafka_codec_kernel(const KafkaPlanParams P, KafkaBatchOut* bout) {
+    const u32 k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= P.n_batches) return;
+    u32 j = P.codec_bad[k];
+    if (j == KAFKA_NONE && P.head->bad[1] != 0u) {
+        const ysb_kafka_frame f = P.frames[k];
+        u32 n = 0;
+        for (u32 i = 0; i < f.n_blocks; ++i)
+            if (P.block_bad[f.first_block + i]) {
+                if (j == KAFKA_NONE) j = i;
+                ++n;
+            }
+        if (n) atomicAdd(&P.head->decoder_bad, n);
+    }
+    if (j != KAFKA_NONE) bout[k] = KafkaBatchOut{0, j, KAFKA_R_CODEC, 0, 0, 0, 0};
+}
+
+hipError_t launch_kafka_plan(const KafkaPlanParams& p, hipStream_t s) {
+    hipLaunchKernelGGL(kafka_inflate_plan_kernel, dim3(1), dim3(KAFKA_PLAN_STEP), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_kafka_codec(const KafkaPlanParams& p, KafkaBatchOut* bout, hipStream_t s) {
+    if (!p.n_batches) return hipSuccess;
+    hipLaunchKernelGGL(kafka_codec_kernel, dim3((p.n_batches + 255) / 256), dim3(256), 0, s, p, bout);
+    return hipGetLastError();
 }
 
 hipError_t launch_kafka_walk(const KafkaParams& p, hipStream_t s) {

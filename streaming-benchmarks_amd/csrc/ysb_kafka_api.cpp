@@ -6,6 +6,7 @@
 // ysb_submit_kafka_mapped sit beside ysb_submit_raw in ysb_raw.cpp.
 #include "ysb_ctx.h"
 #include "ysb_kafka.h"
+#include "ysb_kafka_lz4.h"
 
 using namespace ysb;
 
@@ -62,13 +63,15 @@ static int index_args(ysb_ctx* c, const uint8_t* bytes, u64 nbytes, const ysb_ka
     return YSB_OK;
 }
 
-// walk, base, gather on s (ev: YSB_F_TIMING's four events, created on demand, or NULL)
-static int launch_unframe(ysb_ctx* c, const KafkaParams& p, hipStream_t s, Event* ev) {
+// walk, base, gather on s (ev: YSB_F_TIMING's four events, created on demand, or NULL; codec: a
+// compressed call's plan, whose bad batches become rule 8 behind the walk, or NULL)
+static int launch_unframe(ysb_ctx* c, const KafkaParams& p, hipStream_t s, Event* ev, const KafkaPlanParams* codec = nullptr) {
     if (ev)
         for (int k = 0; k < 4; ++k)
             if (!ev[k]) HIPCHK(c, ev[k].create(hipEventDefault));
     if (ev) HIPCHK(c, hipEventRecord(ev[0], s));
     if (p.n_batches) HIPCHK(c, launch_kafka_walk(p, s));
+    if (codec) HIPCHK(c, launch_kafka_codec(*codec, p.bout, s));
     if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
     HIPCHK(c, launch_kafka_base(p, s));
     if (ev) HIPCHK(c, hipEventRecord(ev[2], s));
@@ -100,13 +103,120 @@ static int settle(ysb_ctx* c, const KafkaHead& h, u64 nb, u64 framed, u64 contro
     }
     c->kafka_last = d;
     if (h.bad_batches)
-        return fail(c, YSB_ERR_FORMAT, "%s: Kafka batch %u (baseOffset %lld), record %u: %s (%u bad batches in all); "
+        return fail(c, YSB_ERR_FORMAT, "%s: Kafka batch %u (baseOffset %lld), %s %u: %s (%u bad batches in all); "
                     "nothing of the call was counted", what, h.first_bad,
-                    h.first_bad < nb ? (long long)batches[h.first_bad].base_offset : -1LL, h.bad_rec, kafka_rule_name(h.rule),
-                    h.bad_batches);
+                    h.first_bad < nb ? (long long)batches[h.first_bad].base_offset : -1LL,
+                    h.rule == KAFKA_R_CODEC ? "block" : "record", h.bad_rec, kafka_rule_name(h.rule), h.bad_batches);
     if (h.overflow)
         return fail(c, YSB_ERR_CAPACITY, "%s: %llu value bytes do not fit the output", what, (unsigned long long)h.out_bytes);
     return YSB_OK;
+}
+
+
+// ---- LZ4-compressed batches (ysb_kafka_lz4.h) ---------------------------------------------------
+static_assert(sizeof(ysb_kafka_frame) == 16 && sizeof(ysb_lz4_frame_block) == sizeof(Lz4FrameBlock) && sizeof(Lz4Desc) == 24 &&
+              sizeof(KafkaPlanHead) == 24, "the device layout below counts on these sizes");
+
+// A compressed call's device buffer: the head and the three index arrays (what one copy
+// carries), the plan's outputs and the measured sizes, then the Kafka kernels' scratch as
+// kafka_layout has it (its own index area stays unused: the walk reads the planned one).
+struct KafkaLz4Layout {
+    u64 batches, frames, blocks, copied;
+    u64 planned, desc, phead, raw, zeros, bbad, cbad, kafka, total;
+    KafkaLayout kl;
+};
+static KafkaLz4Layout kafka_lz4_layout(u64 nb, u64 nblk, u64 nrec) {
+    KafkaLz4Layout l;
+    l.batches = sizeof(KafkaHead);
+    l.frames = l.batches + nb * sizeof(ysb_kafka_batch);
+    l.blocks = l.frames + nb * sizeof(ysb_kafka_frame);
+    l.copied = l.blocks + nblk * sizeof(ysb_lz4_frame_block);
+    l.planned = (l.copied + 15) & ~15ull;
+    l.desc = l.planned + nb * sizeof(ysb_kafka_batch);
+    l.phead = l.desc + nblk * sizeof(Lz4Desc);
+    l.raw = l.phead + sizeof(KafkaPlanHead);
+    l.zeros = l.raw + nblk * 4;
+    l.bbad = l.zeros + (nblk + 1) * 4;
+    l.cbad = l.bbad + nblk * 4;
+    l.kafka = (l.cbad + nb * 4 + 15) & ~15ull;
+    l.kl = kafka_layout(nb, nrec);
+    l.total = l.kafka + l.kl.total;
+    return l;
+}
+static KafkaPlanParams kafka_plan_params(u8* d, const KafkaLz4Layout& l, u64 nb, u64 nblk) {
+    KafkaPlanParams p{};
+    p.blocks = reinterpret_cast<const Lz4FrameBlock*>(d + l.blocks);
+    p.raw = reinterpret_cast<const u32*>(d + l.raw);
+    p.n_blocks = (u32)nblk;
+    p.frames = reinterpret_cast<const ysb_kafka_frame*>(d + l.frames);
+    p.batches = reinterpret_cast<const ysb_kafka_batch*>(d + l.batches);
+    p.n_batches = (u32)nb;
+    p.desc = reinterpret_cast<Lz4Desc*>(d + l.desc);
+    p.zeros = reinterpret_cast<u32*>(d + l.zeros);
+    p.block_bad = reinterpret_cast<u32*>(d + l.bbad);
+    p.planned = reinterpret_cast<ysb_kafka_batch*>(d + l.planned);
+    p.codec_bad = reinterpret_cast<u32*>(d + l.cbad);
+    p.head = reinterpret_cast<KafkaPlanHead*>(d + l.phead);
+    return p;
+}
+
+// The whole chain on s: measure, plan, decode (d_wire -> d_infl), then walk, codec verdict, base,
+// gather with P.bytes the inflated buffer and P.batches the planned index.  *head_out / *plan_out:
+// where the two heads lie on the device.  ev / kev: YSB_F_TIMING's events or NULL.
+static int launch_inflate_unframe(ysb_ctx* c, u8* d, const KafkaLz4Layout& l, const u8* d_wire, u8* d_infl, u64 nb, u64 nblk,
+                                  u64 nrec, u32 decoder, u8* out, u64 out_cap, u32* line_off, hipStream_t s, Event* ev,
+                                  Event* kev, const KafkaHead** head_out, const KafkaPlanHead** plan_out) {
+    const KafkaPlanParams pp = kafka_plan_params(d, l, nb, nblk);
+    KafkaParams p = kafka_params(d + l.kafka, l.kl, d_infl, nb, nrec, out, out_cap, line_off);
+    p.batches = pp.planned;
+    if (ev)
+        for (int k = 0; k < 4; ++k)
+            if (!ev[k]) HIPCHK(c, ev[k].create(hipEventDefault));
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], s));
+    HIPCHK(c, launch_lz4_measure(d_wire, pp.blocks, pp.n_blocks, const_cast<u32*>(pp.raw), s));
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, launch_kafka_plan(pp, s));
+    if (ev) HIPCHK(c, hipEventRecord(ev[2], s));
+    if (decoder == YSB_LZ4_DECODER_AUTO) {
+        // only the device knows the sizes: each kernel takes its size class (lz4_pick_decoder's
+        // threshold), the one-wave kernel with the small window that keeps many waves per CU
+        const Lz4Params small{d_wire, pp.desc, pp.n_blocks, LZ4_WIDE_ABOVE, d_infl, pp.head->bad, YSB_LZ4_DECODER_NARROW,
+                              pp.block_bad, LZ4_WIDE_ABOVE, 0};
+        const Lz4Params large{d_wire, pp.desc, pp.n_blocks, LZ4_MAX_RAW, d_infl, pp.head->bad, YSB_LZ4_DECODER_WIDE,
+                              pp.block_bad, 0, LZ4_WIDE_ABOVE};
+        HIPCHK(c, launch_lz4_decode(small, s));
+        HIPCHK(c, launch_lz4_decode(large, s));
+    } else {
+        const Lz4Params lp{d_wire, pp.desc, pp.n_blocks, LZ4_MAX_RAW, d_infl, pp.head->bad, decoder, pp.block_bad, 0, 0};
+        HIPCHK(c, launch_lz4_decode(lp, s));
+    }
+    if (ev) HIPCHK(c, hipEventRecord(ev[3], s));
+    if (int rc = launch_unframe(c, p, s, kev, &pp)) return rc;
+    *head_out = p.head;
+    *plan_out = pp.head;
+    return YSB_OK;
+}
+
+// kafka_lz4_last <- the inflate half of a call's figures
+static void settle_lz4(ysb_ctx* c, const KafkaPlanHead& h, u64 nblk, u64 stored, u64 compressed, u64 wire, u32 decoder,
+                       Event* ev) {
+    ysb_kafka_lz4_desc d{};
+    d.calls = c->kafka_lz4_last.calls + 1;
+    d.blocks = nblk;
+    d.stored_blocks = stored;
+    d.compressed_batches = compressed;
+    d.wire_bytes = wire;
+    d.inflated_bytes = h.inflated;
+    d.inflated_total = c->kafka_lz4_last.inflated_total + h.inflated;
+    d.bad_blocks = (u64)h.zero_blocks + h.decoder_bad;
+    d.decoder = !nblk ? 0 : decoder == YSB_LZ4_DECODER_AUTO ? 3 : decoder;
+    if (ev) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) d.measure_ms = ms;
+        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) d.plan_ms = ms;
+        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) d.decode_ms = ms;
+    }
+    c->kafka_lz4_last = d;
 }
 
 extern "C" {
@@ -171,7 +281,106 @@ int kafka_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, con
     return YSB_OK;
 }
 
+// ---- a compressed Kafka batch through a slot (ysb_raw.cpp submit_kafka_lz4) ---------------------
+
+int kafka_lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                    const ysb_kafka_frame* frames, uint64_t nb, const ysb_lz4_frame_block* blocks, uint64_t nblk,
+                    const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample) {
+    if ((nbytes && !bytes) || (nb && (!batches || !frames)) || (nblk && !blocks)) return fail(c, YSB_ERR_ARG, "NULL Kafka buffers");
+    if (nb > 0x7FFFFFFFull || nblk > 0x7FFFFFFFull) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 Kafka batches and blocks per call");
+    u64 nrec = 0, control = 0, compressed = 0, stored = 0;
+    KafkaError err;
+    int rc = kafka_lz4_entries(batches, frames, nb, blocks, nblk, nbytes, &nrec, &control, &compressed, &stored, &err);
+    if (rc) return fail(c, rc, "%s", err.msg);
+    if (nrec + 1 > c->raw_lines_cap)
+        return fail(c, YSB_ERR_CAPACITY, "Kafka batch of %llu records, more than the %llu lines its slot holds "
+                    "(max(max_batch_events, max_batch_bytes / 32))", (unsigned long long)nrec,
+                    (unsigned long long)(c->raw_lines_cap - 1));
+    // the host cannot know the raw sizes: the guaranteed bound, 64 KiB per block
+    if (nblk * (u64)LZ4_MAX_RAW > c->cfg.max_batch_bytes)
+        return fail(c, YSB_ERR_CAPACITY, "compressed Kafka batch of %llu blocks: %llu x 65536 B may not fit max_batch_bytes "
+                    "(%llu); submit fewer Kafka batches per call", (unsigned long long)nblk, (unsigned long long)nblk,
+                    (unsigned long long)c->cfg.max_batch_bytes);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_lz4[slot]) HIPCHK(c, c->d_lz4[slot].alloc(c->cfg.max_batch_bytes + 64));
+    if (!c->d_kafka_infl[slot]) HIPCHK(c, c->d_kafka_infl[slot].alloc(c->cfg.max_batch_bytes + 64));
+    if (!c->h_kafka_head) {
+        HIPCHK(c, c->h_kafka_head.alloc(2 * sizeof(KafkaHead)));
+        std::memset(c->h_kafka_head.get(), 0, 2 * sizeof(KafkaHead));
+    }
+    if (!c->h_kafka_plan) {
+        HIPCHK(c, c->h_kafka_plan.alloc(2 * sizeof(KafkaPlanHead)));
+        std::memset(c->h_kafka_plan.get(), 0, 2 * sizeof(KafkaPlanHead));
+    }
+    const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec);
+    if (l.total > c->kafka_cap[slot]) {
+        const u64 cap = std::max<u64>(l.total + l.total / 2, 256u << 10);
+        if ((rc = grow_device(c, c->d_kafka[slot], cap + 64, 0))) return rc;
+        c->kafka_cap[slot] = cap;
+    }
+    if (l.copied > c->kafka_hcap[slot]) {
+        const u64 cap = std::max<u64>(l.copied + l.copied / 2, 64u << 10);
+        c->kafka_hcap[slot] = 0;
+        HIPCHK(c, c->h_kafka[slot].alloc(cap + 64));
+        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hd_kafka[slot]), c->h_kafka[slot], 0));
+        c->kafka_hcap[slot] = cap;
+    }
+    KafkaHead head{};
+    head.first_bad = KAFKA_NONE;
+    u8* hp = c->h_kafka[slot];
+    std::memcpy(hp, &head, sizeof head);
+    if (nb) std::memcpy(hp + l.batches, batches, nb * sizeof(ysb_kafka_batch));
+    if (nb) std::memcpy(hp + l.frames, frames, nb * sizeof(ysb_kafka_frame));
+    if (nblk) std::memcpy(hp + l.blocks, blocks, nblk * sizeof(ysb_lz4_frame_block));
+    if (!dsrc && nbytes && bytes != c->h_bytes[slot]) std::memcpy(c->h_bytes[slot], bytes, nbytes);
+    v[0] = {c->d_lz4[slot], dsrc ? dsrc : c->hd_bytes[slot], dsrc ? bytes : c->h_bytes[slot].get(), nbytes};
+    v[1] = {c->d_kafka[slot], c->hd_kafka[slot], c->h_kafka[slot], l.copied};
+    batch->nbytes = nbytes;
+    batch->off = c->d_roff[slot];
+    batch->n_off = nrec;
+    KafkaStaged st{nb, nrec, nbytes, control};
+    st.lz4 = true;
+    st.n_blocks = nblk;
+    st.stored_blocks = stored;
+    st.compressed_batches = compressed;
+    st.decoder = c->lz4_decoder;
+    batch->kafka = st;
+    // the layout sample: the first batch inflated and read by the host model
+    sample->clear();
+    if (nb) {
+        std::vector<u8> infl((u64)frames[0].n_blocks * LZ4_MAX_RAW + 1);
+        u64 total = 0;
+        if (kafka_inflate_batch(bytes, frames[0], blocks, infl.data(), &total) == KAFKA_NONE) {
+            KafkaHostIn in{infl.data()};
+            u32 pos = 0;
+            for (u32 i = 0; i < batches[0].n_records && i < SAMPLE_LINES && pos < total; ++i) {
+                u32 body = 0, end = 0;
+                KafkaRec r{};
+                if (kafka_read_len(in, pos, (u32)total, &body, &end) || kafka_read_body(in, body, end, &r)) break;
+                sample->insert(sample->end(), in.p + r.val_pos, in.p + r.val_pos + r.val_len);
+                if (sample->empty() || sample->back() != '\n') sample->push_back('\n');
+                pos = end;
+            }
+        }
+    }
+    return YSB_OK;
+}
+
 int kafka_enqueue(ysb_ctx* c, int slot, const KafkaStaged& b, hipStream_t s) {
+    if (b.lz4) {
+        const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
+        const KafkaLz4Layout l = kafka_lz4_layout(b.n_batches, b.n_blocks, b.n_records);
+        const KafkaHead* head = nullptr;
+        const KafkaPlanHead* plan = nullptr;
+        if (int rc = launch_inflate_unframe(c, c->d_kafka[slot], l, c->d_lz4[slot], c->d_kafka_infl[slot], b.n_batches, b.n_blocks,
+                                            b.n_records, b.decoder, c->d_bytes[slot], c->cfg.max_batch_bytes, c->d_roff[slot], s,
+                                            timed ? c->ev_kafka_lz4[slot] : nullptr, timed ? c->ev_kafka[slot] : nullptr, &head,
+                                            &plan))
+            return rc;
+        HIPCHK(c, hipMemcpyAsync(c->h_kafka_head + slot, head, sizeof(KafkaHead), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(c->h_kafka_plan + slot, plan, sizeof(KafkaPlanHead), hipMemcpyDeviceToHost, s));
+        return YSB_OK;
+    }
     const KafkaLayout l = kafka_layout(b.n_batches, b.n_records);
     const KafkaParams p = kafka_params(c->d_kafka[slot], l, c->d_lz4[slot], b.n_batches, b.n_records, c->d_bytes[slot],
                                        c->cfg.max_batch_bytes, c->d_roff[slot]);
@@ -182,6 +391,9 @@ int kafka_enqueue(ysb_ctx* c, int slot, const KafkaStaged& b, hipStream_t s) {
 }
 
 int kafka_settle(ysb_ctx* c, int slot, const KafkaStaged& b) {
+    if (b.lz4)
+        settle_lz4(c, c->h_kafka_plan[slot], b.n_blocks, b.stored_blocks, b.compressed_batches, b.framed_bytes, b.decoder,
+                   (c->cfg.flags & YSB_F_TIMING) ? c->ev_kafka_lz4[slot] : nullptr);
     char what[48];
     std::snprintf(what, sizeof what, "Kafka batch (slot %d)", slot);
     return settle(c, c->h_kafka_head[slot], b.n_batches, b.framed_bytes, b.control_skipped,
@@ -227,6 +439,64 @@ int ysb_kafka_unframe_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes
     return settle(c, h, nb, nbytes, control, batches, timed ? ev : nullptr, "ysb_kafka_unframe_device");
 }
 
+// ---- the inflate and the unframing alone ---------------------------------------------------------
+
+int ysb_kafka_unframe_lz4_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                 const ysb_kafka_frame* frames, uint64_t nb, const ysb_lz4_frame_block* blocks, uint64_t nblk,
+                                 uint8_t* d_out, uint64_t out_cap, uint32_t* d_line_off, uint64_t off_cap, uint64_t* n_lines,
+                                 uint64_t* out_bytes) {
+    if (!c) return YSB_ERR_ARG;
+    if ((nbytes && !d_bytes) || (nb && (!batches || !frames)) || (nblk && !blocks)) return fail(c, YSB_ERR_ARG, "NULL Kafka buffers");
+    if (nb > 0x7FFFFFFFull || nblk > 0x7FFFFFFFull) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 Kafka batches and blocks per call");
+    u64 nrec = 0, control = 0, compressed = 0, stored = 0;
+    KafkaError err;
+    int rc = kafka_lz4_entries(batches, frames, nb, blocks, nblk, nbytes, &nrec, &control, &compressed, &stored, &err);
+    if (rc) return fail(c, rc, "%s", err.msg);
+    if (n_lines) *n_lines = nrec;
+    if (out_bytes) *out_bytes = 0;
+    if (!d_line_off || nrec + 1 > off_cap)
+        return fail(c, YSB_ERR_CAPACITY, "%llu records, room for %llu offsets (one more than the records is needed)",
+                    (unsigned long long)nrec, (unsigned long long)(d_line_off ? off_cap : 0));
+    if (out_cap && !d_out) return fail(c, YSB_ERR_ARG, "NULL output buffer");
+    if ((rc = launch_pending_raw(c))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec);
+    if ((rc = grow_device(c, c->d_kafka_lz4_sync, l.total + 64, 256u << 10))) return rc;
+    if ((rc = grow_device(c, c->d_kafka_infl_sync, nblk * (u64)LZ4_MAX_RAW + 64, 1u << 20))) return rc;
+    u8* d = c->d_kafka_lz4_sync;
+    struct SyncOnExit {
+        hipStream_t s;
+        ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+    } const settled{c->s_comp};
+    hipStream_t s = c->s_comp;
+    if (nb) HIPCHK(c, hipMemcpyAsync(d + l.batches, batches, nb * sizeof(ysb_kafka_batch), hipMemcpyHostToDevice, s));
+    if (nb) HIPCHK(c, hipMemcpyAsync(d + l.frames, frames, nb * sizeof(ysb_kafka_frame), hipMemcpyHostToDevice, s));
+    if (nblk) HIPCHK(c, hipMemcpyAsync(d + l.blocks, blocks, nblk * sizeof(ysb_lz4_frame_block), hipMemcpyHostToDevice, s));
+    const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
+    Event ev[4], kev[4];
+    const KafkaHead* dh = nullptr;
+    const KafkaPlanHead* dp = nullptr;
+    if ((rc = launch_inflate_unframe(c, d, l, d_bytes, c->d_kafka_infl_sync, nb, nblk, nrec, c->lz4_decoder, d_out,
+                                     d_out ? out_cap : 0, d_line_off, s, timed ? ev : nullptr, timed ? kev : nullptr, &dh, &dp)))
+        return rc;
+    KafkaHead h{};
+    KafkaPlanHead ph{};
+    HIPCHK(c, hipMemcpyAsync(&h, dh, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&ph, dp, sizeof ph, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (out_bytes) *out_bytes = h.out_bytes;
+    settle_lz4(c, ph, nblk, stored, compressed, nbytes, c->lz4_decoder, timed ? ev : nullptr);
+    return settle(c, h, nb, nbytes, control, batches, timed ? kev : nullptr, "ysb_kafka_unframe_lz4_device");
+}
+
+int ysb_kafka_lz4_info(ysb_ctx* c, ysb_kafka_lz4_desc* info) {
+    if (!c || !info) return c ? fail(c, YSB_ERR_ARG, "info is NULL") : YSB_ERR_ARG;
+    const int rc = sync_streams(c);   // (a Kafka batch awaiting its launch settles here)
+    *info = c->kafka_lz4_last;
+    info->inflated_buffer_bytes = c->d_kafka_infl[0].bytes() + c->d_kafka_infl[1].bytes() + c->d_kafka_infl_sync.bytes();
+    return rc;
+}
+
 int ysb_kafka_info(ysb_ctx* c, ysb_kafka_desc* info) {
     if (!c || !info) return c ? fail(c, YSB_ERR_ARG, "info is NULL") : YSB_ERR_ARG;
     const int rc = sync_streams(c);   // (a Kafka batch awaiting its launch settles here)
@@ -258,6 +528,28 @@ int ysb_kafka_unframe_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafk
     return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
 }
 
+int ysb_kafka_index_lz4(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, ysb_kafka_batch* batches, ysb_kafka_frame* frames,
+                        uint64_t cap, ysb_lz4_frame_block* blocks, uint64_t block_cap, ysb_kafka_lz4_summary* info) {
+    if (nbytes && !bytes) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: NULL buffer");
+    if (flags & ~YSB_KAFKA_CHECK_CRC) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: unknown flags %#x", flags);
+    if (!batches != !frames) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: batches and frames go together");
+    KafkaError err;
+    const int rc = kafka_index_lz4(bytes, nbytes, flags, batches, frames, batches ? cap : 0, blocks, blocks ? block_cap : 0, info, &err);
+    return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
+}
+
+int ysb_kafka_unframe_lz4_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, const ysb_kafka_frame* frames,
+                               uint64_t n_batches, const ysb_lz4_frame_block* blocks, uint64_t n_blocks, uint8_t* out,
+                               uint64_t out_cap, uint32_t* line_off, uint64_t off_cap, uint64_t* n_lines, uint64_t* out_bytes,
+                               uint64_t* inflated, ysb_kafka_counters* counters, ysb_kafka_verdict* verdict) {
+    if ((nbytes && !bytes) || (n_batches && (!batches || !frames)) || (n_blocks && !blocks))
+        return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_unframe_lz4_host: NULL buffers");
+    KafkaError err;
+    const int rc = kafka_unframe_lz4(bytes, nbytes, batches, frames, n_batches, blocks, n_blocks, out, out_cap, line_off, off_cap,
+                                     n_lines, out_bytes, inflated, counters, verdict, &err);
+    return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
+}
+
 static const ysb_kafka_pack_opts KAFKA_DEFAULT_OPTS{};
 
 uint64_t ysb_kafka_bound(uint64_t nbytes, uint64_t n_lines, const ysb_kafka_pack_opts* opts) {
@@ -272,6 +564,8 @@ static int pack_args(const uint8_t* src, uint64_t nbytes, const uint32_t* line_o
     if (o.key_off && !o.keys && o.key_off[n_lines]) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: key offsets without keys");
     if (o.n_headers && (!o.header_keys || !o.header_vals || !o.header_val_len))
         return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: headers without their arrays");
+    if (o.codec != 0 && o.codec != YSB_KAFKA_CODEC_LZ4)
+        return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: codec %u: 0 (none) and 3 (lz4) are written", o.codec);
     return YSB_OK;
 }
 
@@ -284,7 +578,8 @@ int ysb_kafka_pack(const uint8_t* src, uint64_t nbytes, const uint32_t* line_off
     if (*dst_bytes > dst_cap || (!dst && *dst_bytes))
         return fail(nullptr, YSB_ERR_CAPACITY, "ysb_kafka_pack: needs %llu bytes", (unsigned long long)*dst_bytes);
     u64 nb = 0;
-    *dst_bytes = kafka_pack(src, nbytes, line_off, n_lines, o, dst, &nb);
+    *dst_bytes = o.codec ? kafka_pack_lz4(src, nbytes, line_off, n_lines, o, dst, &nb)
+                         : kafka_pack(src, nbytes, line_off, n_lines, o, dst, &nb);
     if (n_batches) *n_batches = nb;
     return YSB_OK;
 }
@@ -296,7 +591,8 @@ int ysb_kafka_write_file(const char* path, const uint8_t* src, uint64_t nbytes, 
     if (int rc = pack_args(src, nbytes, line_off, n_lines, o)) return rc;
     std::vector<u8> blob(kafka_bound(nbytes, n_lines, o) + 1);
     u64 nb = 0;
-    const u64 n = kafka_pack(src, nbytes, line_off, n_lines, o, blob.data(), &nb);
+    const u64 n = o.codec ? kafka_pack_lz4(src, nbytes, line_off, n_lines, o, blob.data(), &nb)
+                          : kafka_pack(src, nbytes, line_off, n_lines, o, blob.data(), &nb);
     FILE* f = std::fopen(path, "wb");
     if (!f) return fail(nullptr, YSB_ERR_ARG, "cannot write %s", path);
     bool ok = !n || std::fwrite(blob.data(), 1, n, f) == n;
@@ -310,5 +606,8 @@ uint64_t ysb_kafka_verdict_size(void) { return sizeof(ysb_kafka_verdict); }
 uint64_t ysb_kafka_counters_size(void) { return sizeof(ysb_kafka_counters); }
 uint64_t ysb_kafka_pack_opts_size(void) { return sizeof(ysb_kafka_pack_opts); }
 uint64_t ysb_kafka_desc_size(void) { return sizeof(ysb_kafka_desc); }
+uint64_t ysb_kafka_frame_size(void) { return sizeof(ysb_kafka_frame); }
+uint64_t ysb_kafka_lz4_summary_size(void) { return sizeof(ysb_kafka_lz4_summary); }
+uint64_t ysb_kafka_lz4_desc_size(void) { return sizeof(ysb_kafka_lz4_desc); }
 
 }  // extern "C"

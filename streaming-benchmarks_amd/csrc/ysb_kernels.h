@@ -433,6 +433,12 @@ struct Lz4Params {
     u8* out;                    // block i's bytes go to out[desc[i].out_off, + raw)
     u32* bad;                   // [2]: {first bad block (LZ4_NO_BAD before), bad blocks (0 before)}
     u32 decoder;                // YSB_LZ4_DECODER_*: 0 picks the kernel by max_raw (lz4_pick_decoder)
+    u32* block_bad;             // NULL, or [n_blocks] (0 before): 1 for every block recorded in bad[]
+    // 0, or a launch that takes one size class of the blocks and leaves the others alone (neither
+    // decoded nor bad): the one-wave kernel skips blocks of more than skip_above raw bytes, the
+    // several-wave kernel blocks of skip_upto or fewer.  A compressed Kafka call, whose sizes only
+    // the device knows, launches both (ysb_kafka_api.cpp).
+    u32 skip_above, skip_upto;
 };
 // Every block decoded (a bad block writes nothing and is recorded in bad[]).  Asynchronous on s.
 // One wave per block (lz4_decode_kernel) or four (lz4_decode_wide_kernel), by p.decoder.
@@ -509,5 +515,36 @@ hipError_t launch_kafka_base(const KafkaParams& p, hipStream_t s);
 // Each value copied to out + base[batch] + its offset, line_off written (line_off[n_records]:
 // the total); nothing at all when head says a batch is bad or the values do not fit.
 hipError_t launch_kafka_gather(const KafkaParams& p, hipStream_t s);
+
+
+// LZ4-compressed Kafka batches (ysb_kafka_lz4.h): between the measure pass and the decode, one
+// launch turns the measured sizes into the decode's descriptors AND the walk's index.
+struct KafkaPlanHead {
+    u32 bad[2];                 // the decode's Lz4Params::bad (the plan sets LZ4_NO_BAD, 0)
+    u32 zero_blocks;            // blocks the measure pass refused
+    u32 decoder_bad;            // blocks only the decoder refused (kafka_codec_kernel)
+    u64 inflated;               // the measured sizes' sum
+};
+struct KafkaPlanParams {
+    const Lz4FrameBlock* blocks;     // [n_blocks] offsets into the wire bytes
+    const u32* raw;                  // [n_blocks] the measured sizes, 0: a bad block
+    u32 n_blocks;
+    const ysb_kafka_frame* frames;   // [n_batches]: first_block + n_blocks <= n_blocks, the host checked
+    const ysb_kafka_batch* batches;  // [n_batches] the host's index (never written)
+    u32 n_batches;
+    Lz4Desc* desc;                   // [n_blocks] out: out_off the inflated offset; raw 0 for every block of a bad batch
+    u32* zeros;                      // [n_blocks + 1] out: the bad blocks in front of block i
+    u32* block_bad;                  // [n_blocks] out: zeroed (the decode's per-block flags)
+    ysb_kafka_batch* planned;        // [n_batches] out: records_off / records_bytes in the inflated buffer, the rest copied
+    u32* codec_bad;                  // [n_batches] out: the smallest block measured 0, or KAFKA_NONE
+    KafkaPlanHead* head;
+};
+// One workgroup: a pass over the blocks with two running prefixes (raw bytes, blocks measured
+// 0), KAFKA_PLAN_STEP blocks per step, then one thread per Kafka batch.  Asynchronous on s.
+constexpr u32 KAFKA_PLAN_STEP = 256;
+hipError_t launch_kafka_plan(const KafkaPlanParams& p, hipStream_t s);
+// Behind the walk, in front of the base kernel: bout[k] <- {rule 8, the smallest bad block} for
+// every batch with a block the plan (codec_bad) or the decoder (block_bad) refused.
+hipError_t launch_kafka_codec(const KafkaPlanParams& p, KafkaBatchOut* bout, hipStream_t s);
 
 }  // namespace ysb

@@ -91,6 +91,7 @@ __global__ __launch_bounds__(LZ4_TPB) void lz4_decode_kernel(const Lz4Params P) 
     const u32 comp = lz4_entry_comp(e), raw = d.raw;
     const u8* gin = P.in + d.in_off;
     u8* gout = P.out + d.out_off;
+    if (P.skip_above && raw > P.skip_above) return;   // (the whole workgroup: the other launch's block)
     // (the host has checked every entry: lz4_check_dir; a launch sized for max_raw must not
     // meet a larger block all the same)
     bool bad = !lz4_entry_ok(e) || raw > P.max_raw;
@@ -162,6 +163,7 @@ __global__ __launch_bounds__(LZ4_TPB) void lz4_decode_kernel(const Lz4Params P) 
     if (bad && lane == 0) {
         atomicMin(&P.bad[0], blockIdx.x);
         atomicAdd(&P.bad[1], 1u);
+        if (P.block_bad) P.block_bad[blockIdx.x] = 1u;
     }
 }
 
@@ -245,6 +247,7 @@ __global__ __launch_bounds__(LZ4W_TPB) void lz4_decode_wide_kernel(const Lz4Para
     const u32 comp = lz4_entry_comp(e), raw = d.raw;
     const u8* gin = P.in + d.in_off;
     u8* gout = P.out + d.out_off;
+    if (P.skip_upto && raw <= P.skip_upto) return;   // (the whole workgroup: the other launch's block)
     bool bad = !lz4_entry_ok(e) || raw > P.max_raw;
     if (!bad && (d.comp & LZ4_STORED)) {
         bad = !lz4_stored_ok(e);
@@ -360,6 +363,7 @@ __global__ __launch_bounds__(LZ4W_TPB) void lz4_decode_wide_kernel(const Lz4Para
     if (bad && tid == 0) {
         atomicMin(&P.bad[0], blockIdx.x);
         atomicAdd(&P.bad[1], 1u);
+        if (P.block_bad) P.block_bad[blockIdx.x] = 1u;
     }
 }
 

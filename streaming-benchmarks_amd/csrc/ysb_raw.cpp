@@ -277,6 +277,38 @@ int ysb_submit_kafka_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t
     return submit_kafka(c, slot, bytes, nbytes, batches, n_batches, true);
 }
 
+// Both compressed Kafka submits (ysb_kafka_api.cpp kafka_lz4_stage; ysb_kafka_lz4.h): as
+// submit_kafka, with the frames and the blocks beside the index; the inflate chain runs in
+// enqueue_deferred's Kafka step (kafka_enqueue).
+static int submit_kafka_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, u64 nbytes, const ysb_kafka_batch* batches,
+                            const ysb_kafka_frame* frames, u64 n_batches, const ysb_lz4_frame_block* blocks, u64 n_blocks,
+                            bool mapped) {
+    if (!c) return YSB_ERR_ARG;
+    int rc = raw_args(c, slot, bytes, nbytes);
+    const u8* dsrc = nullptr;
+    if (!rc && mapped) rc = mapped_src(c, bytes, nbytes, &dsrc);
+    if (!rc) rc = claim_slot(c, slot);
+    if (rc) return rc;
+    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));   // the slot's pinned buffers are rewritten
+    RawBatch b;
+    SlotCopy v[2];
+    std::vector<u8> sample;
+    if ((rc = kafka_lz4_stage(c, slot, bytes, nbytes, batches, frames, n_batches, blocks, n_blocks, dsrc, &b, v, &sample))) return rc;
+    return enqueue_deferred(c, slot, b, v, 2, sample.data(), sample.size());
+}
+
+int ysb_submit_kafka_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                         const ysb_kafka_frame* frames, uint64_t n_batches, const ysb_lz4_frame_block* blocks,
+                         uint64_t n_blocks) {
+    return submit_kafka_lz4(c, slot, bytes, nbytes, batches, frames, n_batches, blocks, n_blocks, false);
+}
+
+int ysb_submit_kafka_lz4_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                const ysb_kafka_frame* frames, uint64_t n_batches, const ysb_lz4_frame_block* blocks,
+                                uint64_t n_blocks) {
+    return submit_kafka_lz4(c, slot, bytes, nbytes, batches, frames, n_batches, blocks, n_blocks, true);
+}
+
 // ---- zero-copy raw batches from registered caller memory (ABI 5) ----------------------------
 
 int ysb_host_register(ysb_ctx* c, void* host, uint64_t bytes) {

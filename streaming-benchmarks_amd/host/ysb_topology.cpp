@@ -600,6 +600,31 @@ void GpuAdCampaignOperator::submitLz4Mapped(const uint8_t* blocks, uint64_t comp
     waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 }
 
+void GpuAdCampaignOperator::submitKafkaLz4(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                           const ysb_kafka_frame* frames, uint64_t nBatches, const ysb_lz4_frame_block* blocks,
+                                           uint64_t nBlocks, bool mapped) {
+    if (mapped) {
+        check(ysb_submit_kafka_lz4_mapped(ctx_, cur_, bytes, nbytes, batches, frames, nBatches, blocks, nBlocks),
+              "ysb_submit_kafka_lz4_mapped");
+    } else {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (nbytes) std::memcpy(bytes_[cur_], bytes, nbytes);   // (the slot is free: the last submit's ysb_wait)
+        fillS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        check(ysb_submit_kafka_lz4(ctx_, cur_, bytes_[cur_], nbytes, batches, frames, nBatches, blocks, nBlocks),
+              "ysb_submit_kafka_lz4");
+    }
+    cur_ ^= 1;
+    const auto t1 = std::chrono::steady_clock::now();
+    check(ysb_wait(ctx_, cur_), "ysb_wait");   // at most two batches in flight
+    waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+}
+
+ysb_kafka_lz4_desc GpuAdCampaignOperator::kafkaLz4Info() {
+    ysb_kafka_lz4_desc d{};
+    check(ysb_kafka_lz4_info(ctx_, &d), "ysb_kafka_lz4_info");
+    return d;
+}
+
 void GpuAdCampaignOperator::submitKafka(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, uint64_t nBatches,
                                         bool mapped) {
     if (mapped) {

@@ -201,6 +201,12 @@ public:
     // `bytes`, first_record running from 0) as one batch: through the slot, or (mapped) read where
     // it lies in the registered mapping.
     void submitKafka(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, uint64_t nBatches, bool mapped);
+    // The same for batches that may be LZ4-compressed (ysb_kafka_index_lz4's three arrays, offsets
+    // relative to `bytes`): inflated on the GPU in front of the unframing (ysb_submit_kafka_lz4).
+    void submitKafkaLz4(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, const ysb_kafka_frame* frames,
+                        uint64_t nBatches, const ysb_lz4_frame_block* blocks, uint64_t nBlocks, bool mapped);
+    // ysb_kafka_lz4_info: the last compressed call and the inflated bytes of all (waits for everything)
+    ysb_kafka_lz4_desc kafkaLz4Info();
     // One file image of WindowedArrowFormatBolter (<shared_file>_<k>, :303-317) of `rows` rows
     // counted from its columns (ysb_submit_columns, longs big-endian): only the ranges the count
     // reads are read from the file, straight into the open slot.  Throws, naming the file, if

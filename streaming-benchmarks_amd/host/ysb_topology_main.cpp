@@ -64,6 +64,10 @@ struct Args {
     // --kafka: events_path is a partition's log segment (ysb_gen --kafka): runs of whole record
     // batches go over PCIe framed and are unframed on the GPU (ysb_submit_kafka)
     bool kafka = false;
+    // --kafka-codec lz4: the segment's batches may be LZ4-compressed (attributes codec 3; ysb_gen
+    // --kafka --kafka-codec lz4): inflated on the GPU in front of the unframing (ysb_submit_kafka_lz4).
+    // Without it a compressed segment is refused, as before.
+    std::string kafka_codec;
     // streaming mode (configs[4]): --stream plus its options (ysb_stream.hpp)
     bool stream = false;
     StreamOptions so;
@@ -81,7 +85,7 @@ void usage() {
                  "       [--format json|tbl] [--flush-ms MS] [--batch-mb MB | --batch-bytes B] [--batch-events N]\n"
                  "       [--window-ring W] [--require-ip] [--dry-run] [--print-config] [--replay-rows CSV]\n"
                  "       [--host-split] [--repeat K] [--io-threads T] [--io auto|mapped|mmap|pread]\n"
-                 "       [--h2d-sdma] [--join-redis [--park-capacity N]] [--lz4] [--kafka]\n"
+                 "       [--h2d-sdma] [--join-redis [--park-capacity N]] [--lz4] [--kafka [--kafka-codec lz4]]\n"
                  "   or: ysb_topology --confPath PATH --columns [--device N] [--format json|tbl] [--require-ip]\n"
                  "       [--batch-mb MB | --batch-bytes B]   (window.size rows per <shared_file>_<k>)\n"
                  "   or: ysb_topology --confPath PATH --from-columns [--device N] [--sink none|csv:FILE|redis[:HOST[:PORT]]]\n"
@@ -130,6 +134,14 @@ Args parse(int argc, char** argv) {
         else if (k == "--park-capacity") a.park_capacity = std::max(1ll, std::atoll(val().c_str()));
         else if (k == "--lz4") a.lz4 = true;
         else if (k == "--kafka") a.kafka = true;
+        else if (k == "--kafka-codec") {
+            a.kafka_codec = val();
+            if (a.kafka_codec != "lz4") {
+                std::fprintf(stderr, "--kafka-codec %s: lz4 is the codec that is read (gzip, snappy and zstd are not)\n",
+                             a.kafka_codec.c_str());
+                std::exit(2);
+            }
+        }
         else if (k == "--columns") a.columns = true;
         else if (k == "--from-columns") a.from_columns = true;
         else if (k == "--stream") a.stream = true;
@@ -186,6 +198,10 @@ Args parse(int argc, char** argv) {
     if (a.kafka && (a.stream || a.columns || a.from_columns || a.lz4 || a.host_split)) {
         std::fprintf(stderr, "--kafka reads events_path as a log segment of record batches in batch mode: not with --stream, "
                              "--columns, --from-columns, --lz4 or --host-split\n");
+        std::exit(2);
+    }
+    if (!a.kafka_codec.empty() && !a.kafka) {
+        std::fprintf(stderr, "--kafka-codec names the codec of a log segment's batches: only with --kafka\n");
         std::exit(2);
     }
     if (a.lz4 && a.stream) {
@@ -463,7 +479,69 @@ int run(const Args& a) {
             kafka_mapped = false;
         }
     }
-    if (a.kafka) {
+    uint64_t kafka_compressed = 0, kafka_inflated = 0;
+    if (a.kafka && !a.kafka_codec.empty()) {
+        // the three arrays of ysb_kafka_index_lz4; runs of whole batches by the slot's bytes and lines
+        // and by the guaranteed bound on what they inflate to: 64 KiB per block
+        std::string file;
+        if (!kafka_mapped) file = readFile(events);
+        const uint8_t* fb = kafka_mapped ? src.mapping() : reinterpret_cast<const uint8_t*>(file.data());
+        const uint64_t fn = kafka_mapped ? src.fileBytes() : file.size();
+        ysb_kafka_lz4_summary sum{};
+        int rc = ysb_kafka_index_lz4(fb, fn, 0, nullptr, nullptr, 0, nullptr, 0, &sum);
+        if (rc && rc != YSB_ERR_CAPACITY) throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
+        std::vector<ysb_kafka_batch> idx(sum.n_batches);
+        std::vector<ysb_kafka_frame> frames(sum.n_batches);
+        std::vector<ysb_lz4_frame_block> blocks(sum.blocks);
+        if (sum.n_batches && ysb_kafka_index_lz4(fb, fn, 0, idx.data(), frames.data(), idx.size(), blocks.data(), blocks.size(), &sum))
+            throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
+        if (sum.consumed != fn)
+            std::fprintf(stderr, "note: %llu bytes behind the segment's last whole batch are left alone\n",
+                         (unsigned long long)(fn - sum.consumed));
+        const uint64_t max_lines = std::max<uint64_t>(o.batchEvents, o.batchBytes / 32);
+        std::vector<ysb_kafka_batch> rel;
+        std::vector<ysb_kafka_frame> relf;
+        std::vector<ysb_lz4_frame_block> relb;
+        for (long long rep = 0; rep < a.repeat; ++rep) {
+            for (uint64_t b = 0; b < idx.size();) {
+                const uint64_t start = idx[b].records_off - 61;
+                uint64_t e = b, recs = 0, nblk = 0;
+                while (e < idx.size() && idx[e].records_off + idx[e].records_bytes - start <= o.batchBytes &&
+                       recs + idx[e].n_records <= max_lines && (nblk + frames[e].n_blocks) * 65536ull <= o.batchBytes) {
+                    recs += idx[e].n_records;
+                    nblk += frames[e].n_blocks;
+                    ++e;
+                }
+                if (e == b) throw std::runtime_error(events + ": batch " + std::to_string(b) + " exceeds the slot (--batch-mb; "
+                                                     "a compressed batch needs 65536 bytes per block)");
+                const uint64_t span = idx[e - 1].records_off + idx[e - 1].records_bytes - start;
+                rel.assign(idx.begin() + (ptrdiff_t)b, idx.begin() + (ptrdiff_t)e);
+                relf.assign(frames.begin() + (ptrdiff_t)b, frames.begin() + (ptrdiff_t)e);
+                const uint64_t fb0 = frames[b].first_block;
+                relb.assign(blocks.begin() + (ptrdiff_t)fb0, blocks.begin() + (ptrdiff_t)(fb0 + nblk));
+                for (ysb_kafka_batch& k : rel) {
+                    k.records_off -= start;
+                    k.first_record -= idx[b].first_record;
+                }
+                for (ysb_kafka_frame& f : relf) {
+                    f.first_block -= fb0;
+                    kafka_compressed += f.codec ? 1 : 0;
+                }
+                for (ysb_lz4_frame_block& k : relb) k.offset -= start;
+                op.submitKafkaLz4(fb + start, span, rel.data(), relf.data(), rel.size(), relb.data(), relb.size(), kafka_mapped);
+                kafka_framed += span;
+                kafka_records += recs;
+                kafka_batches += e - b;
+                b = e;
+                if (lookup) op.resolveParked(*lookup);
+                if (a.flush_ms > 0 && (now_s() - last_flush) * 1000.0 >= (double)a.flush_ms) {
+                    flush();
+                    last_flush = now_s();
+                }
+            }
+        }
+        kafka_inflated = op.kafkaLz4Info().inflated_total;
+    } else if (a.kafka) {
         std::string file;
         if (!kafka_mapped) file = readFile(events);
         const uint8_t* fb = kafka_mapped ? src.mapping() : reinterpret_cast<const uint8_t*>(file.data());
@@ -574,7 +652,8 @@ int run(const Args& a) {
                 "\"parked_found\": %llu, \"parked_joined\": %llu, \"parked_missed\": %llu, \"join_round_trips\": %llu, "
                 "\"lz4\": %s, \"lz4_comp_bytes\": %llu, \"lz4_raw_bytes\": %llu, \"lz4_io\": \"%s\", "
                 "\"kafka\": %s, \"kafka_framed_bytes\": %llu, \"kafka_records\": %llu, \"kafka_batches\": %llu, "
-                "\"kafka_io\": \"%s\"}\n",
+                "\"kafka_io\": \"%s\", \"kafka_codec\": \"%s\", \"kafka_compressed_batches\": %llu, "
+                "\"kafka_inflated_bytes\": %llu}\n",
                 (unsigned long long)s.events, (unsigned long long)s.views, (unsigned long long)s.joined,
                 (unsigned long long)s.join_misses, (unsigned long long)s.parse_errors,
                 (unsigned long long)s.time_errors, (unsigned long long)s.out_of_ring,
@@ -593,7 +672,8 @@ int run(const Args& a) {
                 (unsigned long long)(a.lz4 ? lz4.rawBytes * (uint64_t)a.repeat : 0),
                 !a.lz4 ? "" : lz4_mapped ? "mapped" : "slot", a.kafka ? "true" : "false",
                 (unsigned long long)kafka_framed, (unsigned long long)kafka_records, (unsigned long long)kafka_batches,
-                !a.kafka ? "" : kafka_mapped ? "mapped" : "slot");
+                !a.kafka ? "" : kafka_mapped ? "mapped" : "slot", a.kafka_codec.c_str(),
+                (unsigned long long)kafka_compressed, (unsigned long long)kafka_inflated);
     return s.overflow_dropped ? 3 : 0;
 }
 

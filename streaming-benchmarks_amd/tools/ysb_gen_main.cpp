@@ -3,7 +3,7 @@
 //
 //   ysb_gen -d DIR [-n EVENTS] [--seed S] [--campaigns C] [--ads-per-campaign A]
 //           [--rate EVENTS_PER_SEC] [--t0 MS] [--with-skew] [--users K]
-//           [--shards K] [--tbl] [--lz4 [--lz4-block N] | --lz4-frame] [--kafka [--kafka-batch BYTES]]
+//           [--shards K] [--tbl] [--lz4 [--lz4-block N] | --lz4-frame] [--kafka [--kafka-batch BYTES] [--kafka-codec lz4]]
 //
 // Writes campaign-ids.txt, ad-ids.txt, ad-to-campaign-ids.txt (JSON map lines),
 // ad-to-campaign.csv (the fork's CSV map) and kafka-json.txt into DIR; with --shards K
@@ -16,7 +16,9 @@
 // With --kafka also kafka-json.log: the same events as a partition's log segment -- Kafka record
 // batches (message format v2) of at most BYTES bytes (default 16384, a producer's batch.size),
 // each event one record's value without its line terminator, as write-to-kafka (core.clj:61-98)
-// sends it -- for ysb_topology --kafka.
+// sends it -- for ysb_topology --kafka.  With --kafka-codec lz4 each batch's records are one
+// standard LZ4 frame (attributes codec 3, what compression.type=lz4 puts on the wire), for
+// ysb_topology --kafka --kafka-codec lz4.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -36,6 +38,7 @@ int main(int argc, char** argv) {
     unsigned lz4_block = 8192;
     bool kafka = false;
     unsigned kafka_batch = 16384;
+    unsigned kafka_codec = 0;     // --kafka-codec lz4: each batch's records as one LZ4 frame (attributes codec 3)
     for (int i = 1; i < argc; ++i) {
         auto val = [&]() -> const char* {
             if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", argv[i]); std::exit(2); }
@@ -57,6 +60,11 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--lz4-block")) lz4_block = (unsigned)std::strtoul(val(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--kafka")) kafka = true;
         else if (!std::strcmp(argv[i], "--kafka-batch")) kafka_batch = (unsigned)std::strtoul(val(), nullptr, 10);
+        else if (!std::strcmp(argv[i], "--kafka-codec")) {
+            const char* v = val();
+            if (std::strcmp(v, "lz4")) { std::fprintf(stderr, "ysb_gen: --kafka-codec %s: lz4 is the codec that is written\n", v); return 2; }
+            kafka_codec = YSB_KAFKA_CODEC_LZ4;
+        }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (!dir) { std::fprintf(stderr, "usage: ysb_gen -d DIR [-n EVENTS] [options]\n"); return 2; }
@@ -108,6 +116,7 @@ int main(int argc, char** argv) {
         std::fclose(f);
         ysb_kafka_pack_opts o{};
         o.batch_bytes = kafka_batch;
+        o.codec = kafka_codec;
         o.base_timestamp = p.t0_ms;
         rc = ysb_kafka_write_file((std::string(dir) + "/kafka-json.log").c_str(), data.data(), data.size(), off.data(), off.size(), &o);
         if (rc) { std::fprintf(stderr, "ysb_gen: %s\n", ysb_last_error(nullptr)); return 1; }

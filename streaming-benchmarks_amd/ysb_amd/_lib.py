@@ -189,7 +189,7 @@ class YsbKafkaCounters(C.Structure):
 class YsbKafkaPackOpts(C.Structure):
     _fields_ = [("batch_bytes", C.c_uint32), ("batch_records", C.c_uint32), ("base_offset", C.c_int64),
                 ("base_timestamp", C.c_int64), ("key_off", C.c_void_p), ("keys", C.c_void_p), ("ts_delta", C.c_void_p),
-                ("n_headers", C.c_uint32), ("reserved", C.c_uint32), ("header_keys", C.POINTER(C.c_char_p)),
+                ("n_headers", C.c_uint32), ("codec", C.c_uint32), ("header_keys", C.POINTER(C.c_char_p)),
                 ("header_vals", C.POINTER(C.c_char_p)), ("header_val_len", C.POINTER(C.c_int32))]
 
 
@@ -197,6 +197,22 @@ class YsbKafkaDesc(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("calls", "batches", "records", "null_values", "keyed", "headers",
                                           "control_skipped", "framed_bytes", "value_bytes", "window_bytes")] + [
                 ("verdict", YsbKafkaVerdict), ("walk_ms", C.c_double), ("base_ms", C.c_double), ("gather_ms", C.c_double)]
+
+
+class YsbKafkaFrame(C.Structure):
+    _fields_ = [("first_block", C.c_uint64), ("n_blocks", C.c_uint32), ("codec", C.c_uint32)]
+
+
+class YsbKafkaLz4Summary(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_batches", "n_records", "consumed", "control_batches", "crc_checked",
+                                          "compressed_batches", "blocks", "stored_blocks", "comp_bytes")]
+
+
+class YsbKafkaLz4Desc(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "blocks", "stored_blocks", "compressed_batches", "wire_bytes",
+                                          "inflated_bytes", "bad_blocks", "decoder", "inflated_buffer_bytes",
+                                          "inflated_total")] + [
+                ("measure_ms", C.c_double), ("plan_ms", C.c_double), ("decode_ms", C.c_double)]
 
 
 class YsbGenParams(C.Structure):
@@ -287,6 +303,18 @@ SIGNATURES = {
     "ysb_submit_kafka": (_I, [_P, _I, _PU8, _U64, _P, _U64]),
     "ysb_submit_kafka_mapped": (_I, [_P, _I, _PU8, _U64, _P, _U64]),
     "ysb_kafka_info": (_I, [_P, C.POINTER(YsbKafkaDesc)]),
+    "ysb_kafka_index_lz4": (_I, [_PU8, _U64, _U32, _P, _P, _U64, _P, _U64, C.POINTER(YsbKafkaLz4Summary)]),
+    "ysb_kafka_unframe_lz4_host": (_I, [_PU8, _U64, _P, _P, _U64, _P, _U64, _PU8, _U64, _PU32, _U64, C.POINTER(_U64),
+                                        C.POINTER(_U64), C.POINTER(_U64), C.POINTER(YsbKafkaCounters),
+                                        C.POINTER(YsbKafkaVerdict)]),
+    "ysb_kafka_unframe_lz4_device": (_I, [_P, _PU8, _U64, _P, _P, _U64, _P, _U64, _PU8, _U64, _PU32, _U64,
+                                          C.POINTER(_U64), C.POINTER(_U64)]),
+    "ysb_submit_kafka_lz4": (_I, [_P, _I, _PU8, _U64, _P, _P, _U64, _P, _U64]),
+    "ysb_submit_kafka_lz4_mapped": (_I, [_P, _I, _PU8, _U64, _P, _P, _U64, _P, _U64]),
+    "ysb_kafka_lz4_info": (_I, [_P, C.POINTER(YsbKafkaLz4Desc)]),
+    "ysb_kafka_frame_size": (_U64, []),
+    "ysb_kafka_lz4_summary_size": (_U64, []),
+    "ysb_kafka_lz4_desc_size": (_U64, []),
     "ysb_kafka_batch_size": (_U64, []),
     "ysb_kafka_summary_size": (_U64, []),
     "ysb_kafka_verdict_size": (_U64, []),
@@ -461,7 +489,8 @@ def lib():
                        (L.ysb_join_info_size, YsbJoinInfo), (L.ysb_kafka_batch_size, YsbKafkaBatch),
                        (L.ysb_kafka_summary_size, YsbKafkaSummary), (L.ysb_kafka_verdict_size, YsbKafkaVerdict),
                        (L.ysb_kafka_counters_size, YsbKafkaCounters), (L.ysb_kafka_pack_opts_size, YsbKafkaPackOpts),
-                       (L.ysb_kafka_desc_size, YsbKafkaDesc)):
+                       (L.ysb_kafka_desc_size, YsbKafkaDesc), (L.ysb_kafka_frame_size, YsbKafkaFrame),
+                       (L.ysb_kafka_lz4_summary_size, YsbKafkaLz4Summary), (L.ysb_kafka_lz4_desc_size, YsbKafkaLz4Desc)):
             if fn() != C.sizeof(st):
                 raise ImportError("%s is %d bytes in the library, %d in this binding"
                                   % (st.__name__, fn(), C.sizeof(st)))

@@ -14,7 +14,11 @@ from ._lib import check, lib
 CHECK_CRC = 1
 BATCH = np.dtype([("records_off", "<u8"), ("records_bytes", "<u4"), ("n_records", "<u4"), ("first_record", "<u8"),
                   ("base_offset", "<i8"), ("control_before", "<u4"), ("reserved", "<u4")])
-RULES = {0: "none", 1: "varint", 2: "length", 3: "past_batch", 4: "key", 5: "value", 6: "headers", 7: "count"}
+FRAME = np.dtype([("first_block", "<u8"), ("n_blocks", "<u4"), ("codec", "<u4")])
+BLOCK = np.dtype([("offset", "<u8"), ("comp_bytes", "<u4"), ("reserved", "<u4")])   # ysb_lz4_frame_block
+CODEC_LZ4 = 3
+RULES = {0: "none", 1: "varint", 2: "length", 3: "past_batch", 4: "key", 5: "value", 6: "headers", 7: "count",
+         8: "codec"}
 DEFAULT_BATCH = 16384   # a producer's default batch.size
 
 
@@ -46,6 +50,74 @@ def index(data, check_crc=False):
     if info.n_batches:
         check(lib().ysb_kafka_index(p, src.size, flags, idx.ctypes.data, idx.size, C.byref(info)))
     return idx, {k: getattr(info, k) for k, _ in info._fields_}
+
+
+def index_lz4(data, check_crc=False):
+    """ysb_kafka_index_lz4: (batches, frames, blocks, summary dict) of a buffer whose record
+    batches are uncompressed (codec 0) or LZ4-compressed (codec 3).  batches is a BATCH array
+    (records_off / records_bytes: the wire bytes), frames a FRAME array with one entry per batch,
+    blocks a BLOCK array with every block's place in `data`.  Raises YsbError (YSB_ERR_FORMAT) for
+    what `index` refuses, for gzip, snappy and zstd by name, and for a frame the LZ4 frame index
+    refuses (naming the Kafka batch, its byte, and the frame's byte and rule)."""
+    src = _u8(data)
+    flags = CHECK_CRC if check_crc else 0
+    info = _lib.YsbKafkaLz4Summary()
+    p = src.ctypes.data if src.size else None
+    rc = lib().ysb_kafka_index_lz4(p, src.size, flags, None, None, 0, None, 0, C.byref(info))
+    if rc not in (0, -4):
+        check(rc)
+    idx = np.zeros(info.n_batches, dtype=BATCH)
+    frames = np.zeros(info.n_batches, dtype=FRAME)
+    blocks = np.zeros(info.blocks, dtype=BLOCK)
+    if info.n_batches:
+        check(lib().ysb_kafka_index_lz4(p, src.size, flags, idx.ctypes.data, frames.ctypes.data, idx.size,
+                                        blocks.ctypes.data if blocks.size else None, blocks.size, C.byref(info)))
+    return idx, frames, blocks, {k: getattr(info, k) for k, _ in info._fields_}
+
+
+def unframe_lz4_host(data, idx, frames, blocks, sizes_only=False):
+    """ysb_kafka_unframe_lz4_host, the model of the GPU's inflate and unframing: (values, line
+    offsets, counters dict with "inflated_bytes").  Raises YsbError (YSB_ERR_FORMAT) for a bad
+    batch; `verdict_lz4` returns the verdict (rule 8: a block does not decode) without raising."""
+    out, off, ct, vd, rc = _unframe_lz4(data, idx, frames, blocks, sizes_only)
+    check(rc)
+    return out, off, ct
+
+
+def verdict_lz4(data, idx, frames, blocks):
+    """The compressed model's verdict as a dict: bad_batches, first_bad (None: none), record, rule."""
+    return _unframe_lz4(data, idx, frames, blocks, True)[3]
+
+
+def _unframe_lz4(data, idx, frames, blocks, sizes_only):
+    src = _u8(data)
+    idx = np.ascontiguousarray(idx, dtype=BATCH)
+    frames = np.ascontiguousarray(frames, dtype=FRAME)
+    blocks = np.ascontiguousarray(blocks, dtype=BLOCK)
+    n, nb, infl = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    ct, vd = _lib.YsbKafkaCounters(), _lib.YsbKafkaVerdict()
+    p = src.ctypes.data if src.size else None
+    ip = idx.ctypes.data if idx.size else None
+    fp = frames.ctypes.data if frames.size else None
+    bp = blocks.ctypes.data if blocks.size else None
+
+    def call(o, ocap, lo, locap):
+        return lib().ysb_kafka_unframe_lz4_host(p, src.size, ip, fp, idx.size, bp, blocks.size, o, ocap, lo, locap,
+                                                C.byref(n), C.byref(nb), C.byref(infl), C.byref(ct), C.byref(vd))
+    rc = call(None, 0, None, 0)
+    out = np.zeros(0, dtype=np.uint8)
+    off = np.zeros(0, dtype=np.uint32)
+    if rc == 0 and not sizes_only:
+        out = np.empty(max(nb.value, 1), dtype=np.uint8)
+        off = np.empty(n.value + 1, dtype=np.uint32)
+        rc = call(out.ctypes.data, out.size, off.ctypes.data, off.size)
+        out = out[:nb.value]
+    v = {k: getattr(vd, k) for k, _ in vd._fields_}
+    if v["first_bad"] == 0xFFFFFFFF:
+        v["first_bad"] = None
+    c = {k: getattr(ct, k) for k, _ in ct._fields_}
+    c["inflated_bytes"] = infl.value
+    return out, off, c, v, rc
 
 
 def unframe_host(data, idx, sizes_only=False):
@@ -89,8 +161,12 @@ def _unframe(data, idx, sizes_only):
 class _Opts:
     """ysb_kafka_pack_opts with the arrays it points to kept alive."""
 
-    def __init__(self, n_lines, batch_bytes, batch_records, base_offset, base_timestamp, keys, ts_delta, headers):
+    def __init__(self, n_lines, batch_bytes, batch_records, base_offset, base_timestamp, keys, ts_delta, headers,
+                 codec=None):
         o = self.o = _lib.YsbKafkaPackOpts()
+        if codec not in (None, "none", "lz4"):
+            raise ValueError("codec %r: None or \"lz4\"" % (codec,))
+        o.codec = CODEC_LZ4 if codec == "lz4" else 0
         o.batch_bytes, o.batch_records = int(batch_bytes or 0), int(batch_records or 0)
         o.base_offset, o.base_timestamp = int(base_offset), int(base_timestamp)
         self.keep = []
@@ -122,13 +198,14 @@ def _lines(data, offsets):
 
 
 def pack(data, offsets, batch_bytes=DEFAULT_BATCH, batch_records=0, base_offset=0, base_timestamp=0, keys=None,
-         ts_delta=None, headers=None):
+         ts_delta=None, headers=None, codec=None):
     """ysb_kafka_pack: the lines data[offsets[i]:offsets[i + 1]] (the last one ends at len(data))
-    as record batches of at most batch_bytes bytes or batch_records records; a uint8 array.
+    as record batches of at most batch_bytes bytes (uncompressed) or batch_records records; a
+    uint8 array.  codec="lz4": each batch's records as one standard LZ4 frame (attributes 3).
     keys: None (null keys) or one bytes per line; ts_delta: None or one int per line; headers: a
     list of (key bytes, value bytes or None) put on every record."""
     src, off = _lines(data, offsets)
-    o = _Opts(off.size, batch_bytes, batch_records, base_offset, base_timestamp, keys, ts_delta, headers)
+    o = _Opts(off.size, batch_bytes, batch_records, base_offset, base_timestamp, keys, ts_delta, headers, codec)
     dst = np.empty(max(lib().ysb_kafka_bound(src.size, off.size, C.byref(o.o)), 1), dtype=np.uint8)
     n, nb = C.c_uint64(), C.c_uint64()
     check(lib().ysb_kafka_pack(src.ctypes.data if src.size else None, src.size, off.ctypes.data if off.size else None,
@@ -141,7 +218,8 @@ def write_file(path, data, offsets, **kw):
     --kafka writes and ysb_topology --kafka reads)."""
     src, off = _lines(data, offsets)
     o = _Opts(off.size, kw.pop("batch_bytes", DEFAULT_BATCH), kw.pop("batch_records", 0), kw.pop("base_offset", 0),
-              kw.pop("base_timestamp", 0), kw.pop("keys", None), kw.pop("ts_delta", None), kw.pop("headers", None))
+              kw.pop("base_timestamp", 0), kw.pop("keys", None), kw.pop("ts_delta", None), kw.pop("headers", None),
+              kw.pop("codec", None))
     if kw:
         raise TypeError("unknown options %s" % sorted(kw))
     check(lib().ysb_kafka_write_file(str(path).encode(), src.ctypes.data if src.size else None, src.size,

@@ -228,9 +228,12 @@ class KafkaLogDataSource:
     `runs(cap, max_records)` yields (offset into the mapping, bytes, first batch, batches) of
     runs of whole batches that fit a slot; `run(ctx, cap)` registers the mapping and submits
     every run where it lies (ysb_submit_kafka_mapped: the framed bytes cross PCIe once, the host
-    reads one 61-byte header per batch).  A tail that is not a whole batch is left alone."""
+    reads one 61-byte header per batch).  A tail that is not a whole batch is left alone.
+    codecs=("lz4",): the segment's batches may be LZ4-compressed (ysb_gen --kafka --kafka-codec lz4);
+    runs are then also cut by the guaranteed bound on what they inflate to, 65536 bytes per block,
+    and submitted with ysb_submit_kafka_lz4_mapped.  Without it a compressed batch is refused."""
 
-    def __init__(self, path: str, check_crc: bool = False):
+    def __init__(self, path: str, check_crc: bool = False, codecs=()):
         from . import kafka
         self.path = str(path)
         self.size = os.path.getsize(self.path)
@@ -240,7 +243,15 @@ class KafkaLogDataSource:
             with open(self.path, "rb") as f:
                 self._mm = mmap.mmap(f.fileno(), 0, flags=mmap.MAP_SHARED, prot=mmap.PROT_READ)
             self.data = np.frombuffer(self._mm, dtype=np.uint8)
-        self.index, self.summary = kafka.index(self.data, check_crc=check_crc)
+        codecs = tuple(codecs or ())
+        if any(c != "lz4" for c in codecs):
+            raise ValueError("codecs %r: \"lz4\" is the codec that is read" % (codecs,))
+        self.lz4 = "lz4" in codecs
+        self.frames = self.blocks = None
+        if self.lz4:
+            self.index, self.frames, self.blocks, self.summary = kafka.index_lz4(self.data, check_crc=check_crc)
+        else:
+            self.index, self.summary = kafka.index(self.data, check_crc=check_crc)
         self.framed_bytes = 0
         self.batches = 0
 
@@ -254,10 +265,13 @@ class KafkaLogDataSource:
         n, b = self.index.size, 0
         start = self.index["records_off"].astype(np.int64) - 61
         end = self.index["records_off"].astype(np.int64) + self.index["records_bytes"].astype(np.int64)
+        nblk = self.frames["n_blocks"].astype(np.int64) if self.lz4 else np.zeros(n, dtype=np.int64)
         while b < n:
-            e, recs = b, 0
-            while e < n and int(end[e]) - int(start[b]) <= cap and recs + int(self.index[e]["n_records"]) <= max_records:
+            e, recs, blocks = b, 0, 0
+            while e < n and int(end[e]) - int(start[b]) <= cap and recs + int(self.index[e]["n_records"]) <= max_records \
+                    and (blocks + int(nblk[e])) * 65536 <= cap:
                 recs += int(self.index[e]["n_records"])
+                blocks += int(nblk[e])
                 e += 1
             if e == b:
                 raise ValueError("%s: batch %d exceeds the slot" % (self.path, b))
@@ -277,7 +291,15 @@ class KafkaLogDataSource:
                 idx = self.index[b:b + k].copy()
                 idx["records_off"] -= off
                 idx["first_record"] -= idx["first_record"][0]
-                ctx.submit_kafka_mapped(self.data, off, nbytes, idx, slot=slot)
+                if self.lz4:
+                    fr = self.frames[b:b + k].copy()
+                    f0 = int(fr["first_block"][0])
+                    bl = self.blocks[f0:f0 + int(fr["n_blocks"].sum())].copy()
+                    fr["first_block"] -= f0
+                    bl["offset"] -= off
+                    ctx.submit_kafka_lz4_mapped(self.data, off, nbytes, idx, fr, bl, slot=slot)
+                else:
+                    ctx.submit_kafka_mapped(self.data, off, nbytes, idx, slot=slot)
                 slot ^= 1
                 ctx.wait(slot)
                 self.framed_bytes += nbytes

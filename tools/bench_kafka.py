@@ -12,6 +12,15 @@ chain legs.
 
 Per leg: events/s, bytes over PCIe per event, the copy queue's busy share.  Everything goes to
 profiles/kafka_bench.json and, as one JSON line, to stdout.
+
+With --lz4 the same batches also go LZ4-compressed (attributes codec 3, ysb_submit_kafka_lz4 and
+_mapped), alternating with the three legs above in the same process.  The capacity rule of the
+compressed submits is 65536 bytes per block, so a slot batch holds slot / 65536 blocks: the
+compressed legs submit the first Kafka batches of each staged batch that fit, and say how many.
+Per compressed leg also the wire bytes per event, the measured compression ratio, the Kafka batches
+per slot batch and which stage bounds it; plus the six kernels alone (measure, plan, decode, walk,
+base, gather by HIP events, the median of five after two warm-ups).  Those figures go to
+profiles/kafka_lz4_bench.json.
 """
 from __future__ import annotations
 
@@ -47,6 +56,8 @@ def main():
     ap.add_argument("--batch-sizes", default="16384,65536,1048576")
     ap.add_argument("--unframe-only", action="store_true", help="skip the chain legs: the three kernels alone")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kafka_bench.json"))
+    ap.add_argument("--lz4", action="store_true", help="add the LZ4-compressed legs (profiles/kafka_lz4_bench.json)")
+    ap.add_argument("--lz4-out", default=os.path.join(ROOT, "profiles", "kafka_lz4_bench.json"))
     a = ap.parse_args()
 
     from ysb_amd import GenParams, YsbContext, kafka
@@ -58,6 +69,8 @@ def main():
     per = int(slot_bytes // (g.max_line_bytes() + 16))   # (the framing's few bytes per record fit the slot too)
     res = {"events_per_batch": per, "slot_MB": a.slot_mb, "repeats": a.repeats, "batch_sizes": sizes, "legs": [],
            "unframe_alone": []}
+    zres = {"events_per_raw_batch": per, "slot_MB": a.slot_mb, "repeats": a.repeats, "batch_sizes": sizes,
+            "blocks_per_slot_batch_cap": slot_bytes // 65536, "legs": [], "kernels_alone": []}
     with YsbContext(device=a.device, n_campaigns=100, window_ring=1024, timing=True, max_batch_bytes=slot_bytes,
                     max_batch_events=per, ring_base_bucket=g.c.t0_ms // 10000 - 8) as ctx:
         ctx.load_ad_map(aids, g.ad_campaign_index())
@@ -121,6 +134,108 @@ def main():
             log(json.dumps(out))
             return out
 
+        def leg_lz4(kind, z, reg, at):
+            """A compressed leg: z holds per staged batch the wire bytes, the three index arrays and
+            the events of the Kafka batches that fit a slot batch by the capacity rule."""
+            for s in (0, 1):
+                ctx.wait(s)
+                if kind == "kafka_lz4":
+                    slot[s][:z["blobs"][s].size] = z["blobs"][s]
+
+            def submit(s):
+                b, i, f, k = z["blobs"][s], z["idx"][s], z["frames"][s], z["blocks"][s]
+                if kind == "kafka_lz4":
+                    check(lib().ysb_submit_kafka_lz4(ctx._h, s, C.c_void_p(slot[s].ctypes.data), b.size, C.c_void_p(i.ctypes.data),
+                                                     C.c_void_p(f.ctypes.data), i.size, C.c_void_p(k.ctypes.data), k.size), ctx._h)
+                else:
+                    ctx.submit_kafka_lz4_mapped(reg, at[s], b.size, i, f, k, slot=s)
+            for s in (0, 1, 0, 1):   # warmup
+                submit(s)
+            ctx.sync()
+            ctx.kernel_time()
+            ctx.copy_time()
+            ctx.reset()
+            ev = z["events"]
+            nsub = max(2, -(-a.events // min(ev)))
+            t = time.perf_counter()
+            for i in range(nsub):
+                submit(i & 1)
+            ctx.sync()
+            el = time.perf_counter() - t
+            kms, launches = ctx.kernel_time()
+            cms, copies, cbytes = ctx.copy_time()
+            st = ctx.stats()
+            info, li = ctx.kafka_info(), ctx.kafka_lz4_info()
+            for i in range(nsub):
+                ctx.truth_accumulate(g, (i & 1) * per, ev[i & 1])
+            mism, truth, counted = ctx.truth_compare()
+            n = sum(ev[i & 1] for i in range(nsub))
+            stages = {k: round(v, 4) for k, v in (("measure", li["measure_ms"]), ("plan", li["plan_ms"]), ("decode", li["decode_ms"]),
+                                                   ("walk", info["walk_ms"]), ("base", info["base_ms"]), ("gather", info["gather_ms"]))}
+            chain_ms = sum(stages.values())
+            busy = cms * 1e-3 / el
+            chain_share = chain_ms * 1e-3 * nsub / el     # (the last batch's kernels, taken for every batch)
+            bound = "the copy queue" if busy >= 0.9 else \
+                ("the %s kernel (the chain's kernels take %.0f%% of the leg)" % (max(stages, key=stages.get), 100 * chain_share)
+                 if chain_share >= 0.6 else "the host's submit path (copy queue %.0f%% busy, chain kernels %.0f%%)" % (100 * busy, 100 * chain_share))
+            out = {"leg": kind, "events": n, "batches": nsub, "seconds": round(el, 4), "events_per_s": round(n / el, 1),
+                   "h2d_bytes": cbytes, "wire_bytes_per_event": round(cbytes / n, 2),
+                   "h2d_GBs": round(cbytes / (cms * 1e-3) / 1e9, 2) if cms else 0.0, "copy_busy_frac": round(busy, 4),
+                   "scan_ms_per_batch": round(kms / max(launches, 1), 4), "stage_ms_last_batch": stages,
+                   "chain_ms_last_batch": round(chain_ms, 4), "bound": bound, "kafka_batches_per_slot_batch": int(z["idx"][0].size),
+                   "blocks_last_batch": li["blocks"], "inflated_bytes_last_batch": li["inflated_bytes"],
+                   "compression_ratio": round(li["inflated_bytes"] / max(li["wire_bytes"], 1), 4), "decoder": li["decoder"],
+                   "bad_batches": info["verdict"]["bad_batches"],
+                   "check": {"truth_mismatched_cells": mism, "truth_views": truth, "counted_views": counted,
+                             "events": st["events"], "parse_errors": st["parse_errors"]}}
+            log(json.dumps(out))
+            return out
+
+        def lz4_staging(size):
+            """The staged batches compressed, cut to the Kafka batches a slot batch may hold."""
+            z = {"blobs": [], "idx": [], "frames": [], "blocks": [], "events": [], "batch_bytes": size}
+            t0 = time.perf_counter()
+            for r, o in zip(raw, offs):
+                blob = kafka.pack(r, o, batch_bytes=size, codec="lz4")
+                idx, fr, bl, _ = kafka.index_lz4(blob)
+                keep = int(np.searchsorted(np.cumsum(fr["n_blocks"]), slot_bytes // 65536, side="right"))
+                keep = min(keep, idx.size)
+                nblk = int(fr["n_blocks"][:keep].sum())
+                end = int(idx[keep - 1]["records_off"]) + int(idx[keep - 1]["records_bytes"])
+                z["blobs"].append(np.ascontiguousarray(blob[:end]))
+                z["idx"].append(np.ascontiguousarray(idx[:keep]))
+                z["frames"].append(np.ascontiguousarray(fr[:keep]))
+                z["blocks"].append(np.ascontiguousarray(bl[:nblk]))
+                z["events"].append(int(idx["n_records"][:keep].sum()))
+            z["pack_seconds"] = round(time.perf_counter() - t0, 3)
+            return z
+
+        def lz4_kernels_alone(z):
+            """measure, plan, decode, walk, base, gather of the first staged batch, device to device."""
+            b, i, f, k, n = z["blobs"][0], z["idx"][0], z["frames"][0], z["blocks"][0], z["events"][0]
+            nval = int(offs[0][n]) if n < per else raw[0].size
+            d_in = ctx.device_alloc(b.size)
+            ctx.h2d(d_in, b)
+            rows = []
+            for _ in range(7):
+                got = ctx.kafka_unframe_lz4_device(d_in, b.size, i, f, k, d_out, raw[0].size, d_off, per + 1)
+                assert got == (n, nval), (got, n, nval)
+                ki, li = ctx.kafka_info(), ctx.kafka_lz4_info()
+                rows.append((li["measure_ms"], li["plan_ms"], li["decode_ms"], ki["walk_ms"], ki["base_ms"], ki["gather_ms"]))
+            same = bool((ctx.d2h(np.empty(nval, dtype=np.uint8), d_out) == raw[0][:nval]).all()) and \
+                bool((ctx.d2h(np.empty(n, dtype=np.uint32), d_off) == offs[0][:n]).all())
+            med = [statistics.median(r[c] for r in rows[2:]) for c in range(6)]
+            out = {"batch_bytes": z["batch_bytes"], "kafka_batches": int(i.size), "blocks": int(k.size), "events": n,
+                   "wire_bytes": int(b.size), "inflated_bytes": li["inflated_bytes"], "value_bytes": nval,
+                   "compression_ratio": round(li["inflated_bytes"] / b.size, 4), "decoder": li["decoder"],
+                   "output_equal": same}
+            out.update({nm + "_ms": round(v, 4) for nm, v in zip(("measure", "plan", "decode", "walk", "base", "gather"), med)})
+            out["decode_GBs_out"] = round(li["inflated_bytes"] / (med[2] * 1e-3) / 1e9, 2) if med[2] else 0.0
+            out["chain_GBs_out"] = round(li["inflated_bytes"] / (sum(med) * 1e-3) / 1e9, 2) if sum(med) else 0.0
+            ctx.device_free(d_in)
+            log(json.dumps(out))
+            return out
+
         d_out = ctx.device_alloc(raw[0].size + 64)
         d_off = ctx.device_alloc(4 * (per + 1) + 64)
         for size in sizes:
@@ -164,11 +279,30 @@ def main():
             for o, p in zip(at, blobs):
                 reg[o:o + p.size] = p
             ctx.host_register(reg)
+            z = zreg = zat = None
+            if a.lz4:   # the compressed staging, its kernels alone, its registered copy (the second batch at an odd address)
+                z = lz4_staging(size)
+                zres["kernels_alone"].append(lz4_kernels_alone(z))
+                zat, zpos = [], 0
+                for p in z["blobs"]:
+                    zat.append(zpos)
+                    zpos += (p.size + 63) // 64 * 64 + 64 + 1
+                zreg = np.empty(zpos + 8192, dtype=np.uint8)
+                zreg = zreg[(-zreg.ctypes.data) % 4096:][:(zpos + 4095) // 4096 * 4096]
+                for o, p in zip(zat, z["blobs"]):
+                    zreg[o:o + p.size] = p
+                ctx.host_register(zreg)
             for rep in range(a.repeats):
                 for kind in ("raw", "kafka", "kafka_mapped"):
                     res["legs"].append(dict(leg(kind, blobs, idxs, reg, at), batch_bytes=size, round=rep))
+                    if z and kind == "raw":
+                        zres["legs"].append(dict(res["legs"][-1]))
+                for kind in (("kafka_lz4", "kafka_lz4_mapped") if z else ()):
+                    zres["legs"].append(dict(leg_lz4(kind, z, zreg, zat), batch_bytes=size, round=rep))
             ctx.sync()
             ctx.host_unregister(reg)
+            if z:
+                ctx.host_unregister(zreg)
         ctx.device_free(d_out)
         ctx.device_free(d_off)
 
@@ -195,6 +329,32 @@ def main():
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
+    if a.lz4 and not a.unframe_only:
+        zs = {"kernels_alone": zres["kernels_alone"], "all_inflated_equal": all(u["output_equal"] for u in zres["kernels_alone"])}
+        for size in sizes:
+            def of(kind):
+                return [l for l in zres["legs"] if l["leg"] == kind and l["batch_bytes"] == size]
+            rawm = statistics.median(l["events_per_s"] for l in of("raw"))
+            zs[str(size)] = {"raw_median_events_per_s": rawm}
+            for kind in ("kafka_lz4", "kafka_lz4_mapped"):
+                v = of(kind)
+                e = [l["events_per_s"] for l in v]
+                zs[str(size)][kind] = {
+                    "M_events_per_s": {"min": round(min(e) / 1e6, 2), "median": round(statistics.median(e) / 1e6, 2),
+                                       "max": round(max(e) / 1e6, 2)},
+                    "over_raw_median": round(statistics.median(e) / rawm, 4),
+                    "wire_bytes_per_event": statistics.median(l["wire_bytes_per_event"] for l in v),
+                    "compression_ratio": statistics.median(l["compression_ratio"] for l in v),
+                    "copy_busy_frac": statistics.median(l["copy_busy_frac"] for l in v),
+                    "kafka_batches_per_slot_batch": v[0]["kafka_batches_per_slot_batch"],
+                    "events_per_slot_batch": v[0]["events"] // v[0]["batches"], "bound": v[-1]["bound"]}
+        zs["all_checks_exact"] = all(l["check"]["truth_mismatched_cells"] == 0 and l["check"]["truth_views"] == l["check"]["counted_views"]
+                                     and l["check"]["events"] == l["events"] and l.get("bad_batches", 0) == 0 for l in zres["legs"])
+        zres["summary"] = zs
+        with open(a.lz4_out, "w") as f:
+            json.dump(zres, f, indent=1)
+            f.write("\n")
+        print(json.dumps(zs), flush=True)
     print(json.dumps(res["summary"]), flush=True)
 
 
