@@ -269,6 +269,17 @@ def verdict(buf, idx):
     return None
 
 
+def verdict_all(buf, idx):
+    """Every batch walked on its own, as the library reports a call: None, or (bad_batches,
+    first_bad, record, rule number) with the record and rule of the first bad batch."""
+    bad = []
+    for k, b in enumerate(idx):
+        v = verdict(buf, [b])
+        if v is not None:
+            bad.append((k,) + v[1:])
+    return ((len(bad),) + bad[0]) if bad else None
+
+
 def malformed_corpus():
     """One case per rule: [(name, rule, records_count, record bytes)], a good record in front of
     the broken one.  Byte for byte the corpus of tests/native/kafka_logic.cpp (test_kafka_logic.py

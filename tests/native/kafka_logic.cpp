@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 #include "ysb_kafka.h"
+#include "kafka_walk.h"
 
 using namespace ysb;
 typedef std::vector<u8> Bytes;
@@ -46,33 +47,7 @@ static Bytes vlong(i64 v) {
 }
 static Bytes str(const char* s) { return Bytes(s, s + std::strlen(s)); }
 
-// The kernel's walk on the host: the chain of lengths for up to 64 records, then their bodies;
-// the smallest bad record wins.  Must equal the serial model's verdict.
-static u32 walk_like_kernel(const u8* rec, u32 n, u32 nrec, u32* bad_rec, u64* total) {
-    KafkaHostIn in{rec};
-    u32 pos = 0, done = 0;
-    *total = 0;
-    while (done < nrec) {
-        const u32 want = std::min(nrec - done, KAFKA_GROUP);
-        u32 m = 0, body[KAFKA_GROUP], end[KAFKA_GROUP], chain = KAFKA_OK;
-        while (m < want) {
-            if (pos >= n) { chain = KAFKA_R_COUNT; break; }
-            chain = kafka_read_len(in, pos, n, &body[m], &end[m]);
-            if (chain) break;
-            pos = end[m++];
-        }
-        for (u32 j = 0; j < m; ++j) {
-            KafkaRec r{};
-            const u32 rule = kafka_read_body(in, body[j], end[j], &r);
-            if (rule) { *bad_rec = done + j; return rule; }
-            *total += r.val_len;
-        }
-        if (chain) { *bad_rec = done + m; return chain; }
-        done += m;
-    }
-    *bad_rec = nrec;
-    return pos == n ? KAFKA_OK : KAFKA_R_COUNT;
-}
+// (the kernel's walk on the host, walk_like_kernel: kafka_walk.h)
 
 // records `rec` with recordsCount `count` through the model and the kernel's order, in an exact-size buffer
 static u32 verdict_of(const Bytes& rec, u32 count, u32* bad_rec) {

@@ -25,7 +25,8 @@ def ctx():
 
 def unframe_device(c, blob, idx, out_shift=3, nval=None):
     """blob in a device allocation of its exact size (so the last batch ends at the allocation's
-    last byte), unframed to an output that starts at an odd address: (values, offsets, info)."""
+    last byte), unframed to an output that starts at an odd address: (values, offsets, info).
+    The bytes in front of the output and the spare byte behind it are pre-filled and must stay."""
     blob = np.frombuffer(bytes(blob), dtype=np.uint8)
     nrec = int(idx["n_records"].sum()) if idx.size else 0
     if nval is None:
@@ -36,9 +37,13 @@ def unframe_device(c, blob, idx, out_shift=3, nval=None):
     try:
         if blob.size:
             c.h2d(d_in, blob)
+        c.h2d(d_out, np.full(nval + out_shift + 1, 0xA5, dtype=np.uint8))
         n, nb = c.kafka_unframe_device(d_in, blob.size, idx, d_out + out_shift, nval, d_off, nrec + 1)
         assert (n, nb) == (nrec, nval)
-        out = c.d2h(np.empty(nval + out_shift + 1, dtype=np.uint8), d_out)[out_shift:out_shift + nval]
+        whole = c.d2h(np.empty(nval + out_shift + 1, dtype=np.uint8), d_out)
+        assert (whole[:out_shift] == 0xA5).all(), "bytes in front of the output were written"
+        assert whole[out_shift + nval] == 0xA5, "the byte behind the output was written"
+        out = whole[out_shift:out_shift + nval]
         off = c.d2h(np.empty(nrec + 1, dtype=np.uint32), d_off)
         return out, off, c.kafka_info()
     finally:
