@@ -151,21 +151,17 @@ struct Layout {
     LearnDesc learn{};
 };
 
-// A compressed batch as lz4_stage leaves it: its source as host and device address (the slot's
-// pinned buffer, or the bytes where they lie in a registered range), its figures until its
-// launch settles them into lz4_last, and its largest block (the decode's LDS window).
+// A compressed batch as lz4_stage / lz4f_stage leaves it: its figures until its launch settles
+// them into lz4_last / lz4f_last, and its largest block (the decode's LDS window).
 struct Lz4Staged {
-    const u8* hsrc = nullptr;
-    const u8* dsrc = nullptr;
     ysb_lz4_desc info{};
     u32 max_raw = 0;
-    u64 span = 0;                        // a frame batch's bytes: first block's data .. last block's end
     u32 decoder = 0;                     // a frame batch: the decode kernel chosen when it was staged
     bool frame = false;                  // a frame batch (ysb_submit_lz4_blocks): sizes measured on the device
     bool more = false;                   // ... with YSB_LZ4F_MORE: its tail is carried
 };
 
-// A Kafka batch as kafka_stage leaves it: what its settling reports (the index stays in the
+// A Kafka batch as kafka_stage / kafka_lz4_stage leaves it: what its settling reports (the index stays in the
 // slot's pinned buffer until the slot is claimed again, which launches this batch first).
 struct KafkaStaged {
     u64 n_batches = 0, n_records = 0, framed_bytes = 0, control_skipped = 0;
@@ -178,7 +174,8 @@ struct KafkaStaged {
 // A slot's batch between its submit and its launch one call later (ysb_raw.cpp).  Every submit
 // assigns the whole record and launch_pending_raw resets it whole.
 struct RawBatch {
-    u64 nbytes = 0;                      // decoded bytes in d_bytes[slot]
+    u64 nbytes = 0;                      // decoded bytes in d_bytes[slot]; a bound where only the device knows them
+                                         //   (a frame or Kafka batch: its settle step reports the count)
     Layout lay;                          // its first lines' layout (sampled on the host)
     const u32* off = nullptr;            // the caller's n_off device line offsets; NULL: the GPU
     u64 n_off = 0;                       //   split's, in d_roff[slot]
@@ -265,21 +262,24 @@ struct ysb_ctx {
     Event ev_park[2];
     u64 park_resolved_total = 0;
     ysb_parked_desc park_last{};
-    // LZ4 batches (ysb_lz4_api.cpp; ysb_lz4.h): per slot the compressed bytes in HBM (the
-    // slot's pinned buffer carries them over PCIe, or they are read in place from a registered
-    // range: Lz4Staged; d_bytes[slot] receives the decode) and the
-    // block descriptors -- pinned and device, LZ4_DESC_HEAD bytes of {first bad, bad blocks}
-    // in front, initialised by the same copy --; the pair read back to pinned memory behind the
-    // decode (h_lz4bad[2 * slot]); the last settled batch's figures; YSB_F_TIMING's event pair
-    DevBuf<u8> d_lz4[2];
+    // The wire buffer: per slot a batch's bytes as they crossed PCIe, compressed (LZ4 batches) or
+    // framed (Kafka batches) -- through the slot's pinned buffer, or read in place from a
+    // registered range (stage_wire).  A slot holds one batch, of any kind, from its copy until
+    // its kernels on the split's stream are done; they leave the lines in d_bytes[slot].
+    // max_batch_bytes + 64, allocated at the slot's first such batch (ensure_wire).
+    DevBuf<u8> d_wire[2];
+    // LZ4 batches (ysb_lz4_api.cpp; ysb_lz4.h): per slot the block descriptors -- pinned and
+    // device, LZ4_DESC_HEAD bytes of {first bad, bad blocks} in front, initialised by the same
+    // copy --; the pair read back to pinned memory behind the decode (h_lz4bad[2 * slot]); the
+    // last settled batch's figures; YSB_F_TIMING's marks per slot: around the decode kernel, a
+    // frame batch's in front of its measure pass, between it and the decode, behind the decode
     PinBuf<u8> h_lz4desc[2];
     u8* hd_lz4desc[2] = {nullptr, nullptr};
     DevBuf<u8> d_lz4desc[2];
     u64 lz4desc_cap[2] = {0, 0};
     PinBuf<u32> h_lz4bad;
     ysb_lz4_desc lz4_last{};
-    Event ev_lz4[2][2];
-    Event ev_lz4m[2];                           // a frame batch: in front of its measure pass (YSB_F_TIMING)
+    Event ev_lz4[2][3];
     DevBuf<u8> d_lz4desc_sync;                  // ysb_lz4_decode_device's descriptors
     // standard frames (ysb_lz4_frame.h): the synchronous calls' device scratch -- {first bad, bad
     // blocks, raw total (u64)}, the index entries, the measured sizes, the descriptors --, the
@@ -295,17 +295,16 @@ struct ysb_ctx {
     PinBuf<Lz4FrameHead> h_lz4f;
     DevBuf<u8> d_carry;
     bool lz4f_more = false;
-    // Kafka record batches (ysb_kafka_api.cpp; ysb_kafka.h).  The framed bytes of a slot's batch
-    // go to d_lz4[slot] (the compressed-bytes staging: a slot holds one batch, of either kind,
-    // from its copy until its kernels on the split's stream are done).  Per slot one pinned /
-    // device buffer pair, {KafkaHead, the index entries} -- one copy --, and behind them on the
-    // device the kernels' scratch (kafka_layout); the head read back to pinned memory behind the
-    // gather (h_kafka_head[slot]); the synchronous call's buffer; the last call settled;
-    // YSB_F_TIMING's events around the three kernels
+    // Kafka record batches (ysb_kafka_api.cpp; ysb_kafka.h): per slot one pinned / device buffer
+    // pair, {KafkaHead, the index entries} -- one copy --, and behind them on the device the
+    // kernels' scratch (kafka_layout; a compressed batch's: kafka_lz4_layout, its three index
+    // arrays in the one copy); the head read back to pinned memory behind the gather
+    // (h_kafka_head[slot]); the synchronous call's buffer; the last call settled;
+    // YSB_F_TIMING's marks around the three kernels
     PinBuf<u8> h_kafka[2];
     u8* hd_kafka[2] = {nullptr, nullptr};
     DevBuf<u8> d_kafka[2];
-    u64 kafka_cap[2] = {0, 0}, kafka_hcap[2] = {0, 0};   // device bytes; pinned bytes (head and index only)
+    u64 kafka_cap[2] = {0, 0}, kafka_hcap[2] = {0, 0};   // device bytes; pinned bytes (what the one copy carries)
     PinBuf<KafkaHead> h_kafka_head;
     DevBuf<u8> d_kafka_sync;
     ysb_kafka_desc kafka_last{};
@@ -314,7 +313,7 @@ struct ysb_ctx {
     // + 64, allocated at the slot's first compressed submit: a context that never sees one pays
     // nothing) -- the decode's output and the walk's input --; the synchronous call's inflated
     // buffer and scratch; the plan's head read back beside the verdict; the last call settled;
-    // YSB_F_TIMING's events around measure, plan and decode
+    // YSB_F_TIMING's marks around measure, plan and decode
     DevBuf<u8> d_kafka_infl[2];
     DevBuf<u8> d_kafka_infl_sync, d_kafka_lz4_sync;
     PinBuf<KafkaPlanHead> h_kafka_plan;
@@ -495,6 +494,44 @@ extern thread_local std::string g_open_err;
 inline bool is_pow2(u64 x) { return x && !(x & (x - 1)); }   // (log2u: ysb_recplan.h)
 inline int slot_arg(ysb_ctx* c, int slot) { return slot < 0 || slot > 1 ? fail(c, YSB_ERR_ARG, "slot must be 0 or 1") : YSB_OK; }
 
+// The synchronous calls copy to and from the caller's pageable memory and their own stack: no
+// return, an error's included, leaves such a copy pending.
+struct SyncOnExit {
+    hipStream_t s;
+    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+// YSB_F_TIMING's marks around a call's kernels.  Mark k of ev recorded on s, the event created on
+// demand; ev NULL (the call is not timed): nothing.
+inline hipError_t mark(Event* ev, int k, hipStream_t s) {
+    if (!ev) return hipSuccess;
+    if (!ev[k]) {
+        const hipError_t e = ev[k].create(hipEventDefault);
+        if (e != hipSuccess) return e;
+    }
+    return hipEventRecord(ev[k], s);
+}
+// The milliseconds between marks a and b added to *figure, if both are readable (complete: the
+// caller has waited for what follows them); ev NULL: nothing.
+inline void add_span(const Event* ev, int a, int b, double* figure) {
+    float ms = 0;
+    if (ev && hipEventElapsedTime(&ms, ev[a], ev[b]) == hipSuccess) *figure += ms;
+}
+
+// The slot's wire buffer (d_wire), allocated at its first use.
+inline int ensure_wire(ysb_ctx* c, int slot) {
+    if (!c->d_wire[slot]) HIPCHK(c, c->d_wire[slot].alloc(c->cfg.max_batch_bytes + 64));
+    return YSB_OK;
+}
+// The slot's copy of a batch's wire bytes.  dsrc NULL: through the slot's pinned buffer, into
+// which they are copied now (the caller has waited for the slot's previous copy); else they
+// stay where they lie, in a registered range whose device alias of `bytes` dsrc is.
+inline SlotCopy stage_wire(ysb_ctx* c, int slot, const u8* bytes, u64 nbytes, const u8* dsrc) {
+    if (dsrc) return {c->d_wire[slot], dsrc, bytes, nbytes};
+    if (nbytes && bytes != c->h_bytes[slot]) std::memcpy(c->h_bytes[slot], bytes, nbytes);
+    return {c->d_wire[slot], c->hd_bytes[slot], c->h_bytes[slot].get(), nbytes};
+}
+
 extern "C" {
 // ysb_capi.cpp
 YSB_INTERNAL int sync_streams(ysb_ctx* c);       // every queued launch / copy / exchange done
@@ -524,36 +561,31 @@ YSB_INTERNAL bool park_params(const ysb_ctx* c, ParkParams* out);
 YSB_INTERNAL int park_counters(ysb_ctx* c);
 YSB_INTERNAL int park_reset(ysb_ctx* c);         // ysb_reset's part: the log emptied, the counters zero
 // ysb_lz4_api.cpp
-// A compressed batch's directory checked and its bytes and descriptors placed in the slot's
-// pinned memory (the caller has waited for the slot's previous copy): batch->lz4 the staged
-// batch, batch->nbytes its raw size, *sample its block 0 decoded on the host (the layout sample;
-// empty if there is none or it is bad).  dsrc != NULL: the bytes stay where they are, in a
-// registered range whose device alias of `bytes` it is, and only the descriptors are placed.
+// A compressed batch's directory checked and its descriptors placed in the slot's pinned memory,
+// with its bytes (stage_wire), for the slot's copies v[2] (the caller has waited for the slot's
+// previous copy): batch->lz4 the staged batch, batch->nbytes its raw size, *sample its block 0
+// decoded on the host (the layout sample; empty if there is none or it is bad).
 YSB_INTERNAL int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
-                           uint32_t n_blocks, const uint8_t* dsrc, RawBatch* batch, std::vector<u8>* sample);
-// the staged batch's two copies (compressed bytes, descriptors) as copy_slot_ranges takes them
-YSB_INTERNAL void lz4_copies(ysb_ctx* c, int slot, const Lz4Staged& b, SlotCopy v[2]);
-// the staged batch decoded into d_bytes[slot] on s, and its {first bad, bad blocks} read back
-YSB_INTERNAL int lz4_enqueue_decode(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s);
-// at the batch's launch (its decode is complete): lz4_last <- its figures; YSB_ERR_FORMAT, the
-// message naming the first bad block, if it had one
-YSB_INTERNAL int lz4_settle(ysb_ctx* c, int slot, const Lz4Staged& b);
+                           uint32_t n_blocks, const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample);
 // a frame batch staged (ysb_submit_lz4_blocks): the span from the first block's data to the last
-// block's end into the slot's pinned buffer (dsrc: read in place), the rebased index entries and
-// the batch's head into the pinned descriptor buffer; batch->nbytes the bound (n_blocks + 1) x
-// 65536; *sample block 0 decoded by the host model, from behind its first terminator when a
-// carry is pending
+// block's end as the wire bytes, the rebased index entries and the batch's head into the pinned
+// descriptor buffer; batch->nbytes the bound (n_blocks + 1) x 65536; *sample block 0 decoded by
+// the host model, from behind its first terminator when a carry is pending
 YSB_INTERNAL int lz4f_stage(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_block* blocks, uint32_t n_blocks,
-                            uint32_t flags, const uint8_t* dsrc, RawBatch* batch, std::vector<u8>* sample);
-// where the split reads a frame batch's byte count, and the head's read-back behind the split
-YSB_INTERNAL const u64* lz4f_nbytes(ysb_ctx* c, int slot);
+                            uint32_t flags, const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample);
+// the staged batch decoded into d_bytes[slot] on s, and its {first bad, bad blocks} read back;
+// *d_nbytes: where on the device the split reads a frame batch's measured byte count (else untouched)
+YSB_INTERNAL int lz4_enqueue_decode(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s, const u64** d_nbytes);
+// a frame batch's head read back to pinned memory behind the split
 YSB_INTERNAL int lz4f_readback(ysb_ctx* c, int slot, hipStream_t s);
+// at the batch's launch (its decode is complete): lz4_last / lz4f_last <- its figures, *nbytes
+// its decoded bytes; YSB_ERR_FORMAT, the message naming the first bad block, if it had one
+YSB_INTERNAL int lz4_settle(ysb_ctx* c, int slot, const Lz4Staged& b, u64* nbytes);
 // ysb_kafka_api.cpp
-// A Kafka batch's index checked against the slot's capacities and placed, with the bytes (dsrc
-// NULL: into the slot's pinned buffer; else they stay in their registered range), for the
-// slot's copies v[2]; batch->kafka the staged batch, *sample its first values as the host model
-// unframes them, a line each (the layout sample).  The caller has waited for the slot's
-// previous copy.
+// A Kafka batch's index checked against the slot's capacities and placed, with the bytes
+// (stage_wire), for the slot's copies v[2]; batch->kafka the staged batch, *sample its first
+// values as the host model unframes them, a line each (the layout sample).  The caller has
+// waited for the slot's previous copy.
 YSB_INTERNAL int kafka_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
                              uint64_t n_batches, const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample);
 // ... of a compressed one (index, frames and blocks in the slot's pinned buffer, one copy)
@@ -563,10 +595,9 @@ YSB_INTERNAL int kafka_lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uin
 // the three kernels on s behind the slot's copies: d_bytes[slot], d_roff[slot]; the head's read-back
 // (a compressed batch: measure, plan, decode in front of them, the codec verdict behind the walk)
 YSB_INTERNAL int kafka_enqueue(ysb_ctx* c, int slot, const KafkaStaged& b, hipStream_t s);
-// at the batch's launch: kafka_last <- its figures; YSB_ERR_FORMAT naming the bad Kafka batch
-YSB_INTERNAL int kafka_settle(ysb_ctx* c, int slot, const KafkaStaged& b);
-// the value bytes the kernels left in d_bytes[slot] (read at the launch)
-YSB_INTERNAL u64 kafka_out_bytes(const ysb_ctx* c, int slot);
+// at the batch's launch: kafka_last <- its figures, *nbytes the value bytes the kernels left in
+// d_bytes[slot]; YSB_ERR_FORMAT naming the bad Kafka batch
+YSB_INTERNAL int kafka_settle(ysb_ctx* c, int slot, const KafkaStaged& b, u64* nbytes);
 // any submit that is not a frame batch while a carry is pending
 inline int carry_guard(ysb_ctx* c) {
     return c->lz4f_more ? fail(c, YSB_ERR_STATE, "a frame batch left a carry (YSB_LZ4F_MORE): only ysb_submit_lz4_blocks "

@@ -160,23 +160,15 @@ static KafkaPlanParams kafka_plan_params(u8* d, const KafkaLz4Layout& l, u64 nb,
     return p;
 }
 
-// The whole chain on s: measure, plan, decode (d_wire -> d_infl), then walk, codec verdict, base,
-// gather with P.bytes the inflated buffer and P.batches the planned index.  *head_out / *plan_out:
-// where the two heads lie on the device.  ev / kev: YSB_F_TIMING's events or NULL.
-static int launch_inflate_unframe(ysb_ctx* c, u8* d, const KafkaLz4Layout& l, const u8* d_wire, u8* d_infl, u64 nb, u64 nblk,
-                                  u64 nrec, u32 decoder, u8* out, u64 out_cap, u32* line_off, hipStream_t s, Event* ev,
-                                  Event* kev, const KafkaHead** head_out, const KafkaPlanHead** plan_out) {
-    const KafkaPlanParams pp = kafka_plan_params(d, l, nb, nblk);
-    KafkaParams p = kafka_params(d + l.kafka, l.kl, d_infl, nb, nrec, out, out_cap, line_off);
-    p.batches = pp.planned;
-    if (ev)
-        for (int k = 0; k < 4; ++k)
-            if (!ev[k]) HIPCHK(c, ev[k].create(hipEventDefault));
-    if (ev) HIPCHK(c, hipEventRecord(ev[0], s));
+// The inflate chain on s: measure, plan, decode of the wire bytes into d_infl by pp's arrays (ev:
+// YSB_F_TIMING's four marks, or NULL).
+static int launch_inflate(ysb_ctx* c, const KafkaPlanParams& pp, const u8* d_wire, u8* d_infl, u32 decoder, hipStream_t s,
+                          Event* ev) {
+    HIPCHK(c, mark(ev, 0, s));
     HIPCHK(c, launch_lz4_measure(d_wire, pp.blocks, pp.n_blocks, const_cast<u32*>(pp.raw), s));
-    if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, mark(ev, 1, s));
     HIPCHK(c, launch_kafka_plan(pp, s));
-    if (ev) HIPCHK(c, hipEventRecord(ev[2], s));
+    HIPCHK(c, mark(ev, 2, s));
     if (decoder == YSB_LZ4_DECODER_AUTO) {
         // only the device knows the sizes: each kernel takes its size class (lz4_pick_decoder's
         // threshold), the one-wave kernel with the small window that keeps many waves per CU
@@ -190,11 +182,33 @@ static int launch_inflate_unframe(ysb_ctx* c, u8* d, const KafkaLz4Layout& l, co
         const Lz4Params lp{d_wire, pp.desc, pp.n_blocks, LZ4_MAX_RAW, d_infl, pp.head->bad, decoder, pp.block_bad, 0, 0};
         HIPCHK(c, launch_lz4_decode(lp, s));
     }
-    if (ev) HIPCHK(c, hipEventRecord(ev[3], s));
-    if (int rc = launch_unframe(c, p, s, kev, &pp)) return rc;
-    *head_out = p.head;
-    *plan_out = pp.head;
+    HIPCHK(c, mark(ev, 3, s));
     return YSB_OK;
+}
+
+// A call's kernels on s behind the copy of its index into d, the wire bytes in d_wire: walk, base,
+// gather into out and line_off.  d_infl set: a compressed call (index, frames and blocks in d as
+// kafka_lz4_layout has them) -- the inflate chain in front, the walk over the inflated bytes by
+// the planned index, the codec verdict behind it.  *head / *plan: where the two heads lie on the
+// device (*plan NULL: not compressed).  zev / kev: YSB_F_TIMING's marks around the inflate chain's
+// and the unframing's kernels, or NULL.
+static int launch_call(ysb_ctx* c, u8* d, const u8* d_wire, u8* d_infl, u64 nb, u64 nblk, u64 nrec, u32 decoder, u8* out,
+                       u64 out_cap, u32* line_off, hipStream_t s, Event* zev, Event* kev, const KafkaHead** head,
+                       const KafkaPlanHead** plan) {
+    KafkaParams p;
+    KafkaPlanParams pp{};
+    if (d_infl) {
+        const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec);
+        pp = kafka_plan_params(d, l, nb, nblk);
+        p = kafka_params(d + l.kafka, l.kl, d_infl, nb, nrec, out, out_cap, line_off);
+        p.batches = pp.planned;
+        if (int rc = launch_inflate(c, pp, d_wire, d_infl, decoder, s, zev)) return rc;
+    } else {
+        p = kafka_params(d, kafka_layout(nb, nrec), d_wire, nb, nrec, out, out_cap, line_off);
+    }
+    *head = p.head;
+    *plan = d_infl ? pp.head : nullptr;
+    return launch_unframe(c, p, s, kev, d_infl ? &pp : nullptr);
 }
 
 // kafka_lz4_last <- the inflate half of a call's figures
@@ -210,12 +224,9 @@ static void settle_lz4(ysb_ctx* c, const KafkaPlanHead& h, u64 nblk, u64 stored,
     d.inflated_total = c->kafka_lz4_last.inflated_total + h.inflated;
     d.bad_blocks = (u64)h.zero_blocks + h.decoder_bad;
     d.decoder = !nblk ? 0 : decoder == YSB_LZ4_DECODER_AUTO ? 3 : decoder;
-    if (ev) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) d.measure_ms = ms;
-        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) d.plan_ms = ms;
-        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) d.decode_ms = ms;
-    }
+    add_span(ev, 0, 1, &d.measure_ms);
+    add_span(ev, 1, 2, &d.plan_ms);
+    add_span(ev, 2, 3, &d.decode_ms);
     c->kafka_lz4_last = d;
 }
 
@@ -223,29 +234,36 @@ extern "C" {
 
 // ---- a Kafka batch through a slot (ysb_raw.cpp submit_kafka) ----------------------------------
 
-int kafka_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
-                uint64_t nb, const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample) {
-    u64 nrec = 0, control = 0;
-    int rc = index_args(c, bytes, nbytes, batches, nb, &nrec, &control);
-    if (rc) return rc;
+// the slot's line capacity as a Kafka batch's (the gather writes one offset more than the records)
+static int lines_fit(ysb_ctx* c, u64 nrec) {
     if (nrec + 1 > c->raw_lines_cap)
         return fail(c, YSB_ERR_CAPACITY, "Kafka batch of %llu records, more than the %llu lines its slot holds "
                     "(max(max_batch_events, max_batch_bytes / 32))", (unsigned long long)nrec,
                     (unsigned long long)(c->raw_lines_cap - 1));
+    return YSB_OK;
+}
+
+// What both stage functions do once the batch's arguments and capacity rules are checked.  The
+// slot's buffers: the wire buffer and the pinned heads at their first use, d_kafka[slot] grown
+// to dev_total bytes and h_kafka[slot] to `pinned` (outside steady state: more batches, blocks
+// or records than any call before).  Then the batch placed: a fresh head and the index at the
+// front of the pinned buffer (both layouts'), the wire bytes and the pinned buffer's first
+// `copied` bytes as the slot's copies, the RawBatch's fields.
+static int place(ysb_ctx* c, int slot, const u8* bytes, u64 nbytes, const u8* dsrc, const ysb_kafka_batch* batches, u64 nb,
+                 u64 nrec, u64 control, u64 dev_total, u64 pinned, u64 copied, RawBatch* batch, SlotCopy v[2]) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_lz4[slot]) HIPCHK(c, c->d_lz4[slot].alloc(c->cfg.max_batch_bytes + 64));
+    if (int rc = ensure_wire(c, slot)) return rc;
     if (!c->h_kafka_head) {
         HIPCHK(c, c->h_kafka_head.alloc(2 * sizeof(KafkaHead)));
         std::memset(c->h_kafka_head.get(), 0, 2 * sizeof(KafkaHead));
     }
-    const KafkaLayout l = kafka_layout(nb, nrec);
-    if (l.total > c->kafka_cap[slot]) {   // (outside steady state: more batches or records than any call before)
-        const u64 cap = std::max<u64>(l.total + l.total / 2, 256u << 10);
-        if ((rc = grow_device(c, c->d_kafka[slot], cap + 64, 0))) return rc;
+    if (dev_total > c->kafka_cap[slot]) {
+        const u64 cap = std::max<u64>(dev_total + dev_total / 2, 256u << 10);
+        if (int rc = grow_device(c, c->d_kafka[slot], cap + 64, 0)) return rc;
         c->kafka_cap[slot] = cap;
     }
-    if (l.meta > c->kafka_hcap[slot]) {
-        const u64 cap = std::max<u64>(l.meta + l.meta / 2, 64u << 10);
+    if (pinned > c->kafka_hcap[slot]) {
+        const u64 cap = std::max<u64>(pinned + pinned / 2, 64u << 10);
         c->kafka_hcap[slot] = 0;
         HIPCHK(c, c->h_kafka[slot].alloc(cap + 64));
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hd_kafka[slot]), c->h_kafka[slot], 0));
@@ -254,30 +272,44 @@ int kafka_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, con
     KafkaHead head{};
     head.first_bad = KAFKA_NONE;
     std::memcpy(c->h_kafka[slot], &head, sizeof head);
-    if (nb) std::memcpy(c->h_kafka[slot] + l.batches, batches, nb * sizeof(ysb_kafka_batch));
-    if (!dsrc && nbytes && bytes != c->h_bytes[slot]) std::memcpy(c->h_bytes[slot], bytes, nbytes);
-    v[0] = {c->d_lz4[slot], dsrc ? dsrc : c->hd_bytes[slot], dsrc ? bytes : c->h_bytes[slot].get(), nbytes};
-    v[1] = {c->d_kafka[slot], c->hd_kafka[slot], c->h_kafka[slot], l.batches + nb * sizeof(ysb_kafka_batch)};
+    if (nb) std::memcpy(c->h_kafka[slot] + sizeof head, batches, nb * sizeof(ysb_kafka_batch));
+    v[0] = stage_wire(c, slot, bytes, nbytes, dsrc);
+    v[1] = {c->d_kafka[slot], c->hd_kafka[slot], c->h_kafka[slot], copied};
     batch->nbytes = nbytes;
     batch->off = c->d_roff[slot];
     batch->n_off = nrec;
     batch->kafka = KafkaStaged{nb, nrec, nbytes, control};
-    // the layout sample: the first batch's first values as the host model's reader finds them,
-    // a line each (nothing from a record the reader refuses -- the device decides that for the batch)
-    sample->clear();
-    if (nb) {
-        const ysb_kafka_batch& b = batches[0];
-        KafkaHostIn in{bytes + b.records_off};
-        u32 pos = 0;
-        for (u32 i = 0; i < b.n_records && i < SAMPLE_LINES && pos < b.records_bytes; ++i) {
-            u32 body = 0, end = 0;
-            KafkaRec r{};
-            if (kafka_read_len(in, pos, b.records_bytes, &body, &end) || kafka_read_body(in, body, end, &r)) break;
-            sample->insert(sample->end(), in.p + r.val_pos, in.p + r.val_pos + r.val_len);
-            if (sample->empty() || sample->back() != '\n') sample->push_back('\n');
-            pos = end;
-        }
+    return YSB_OK;
+}
+
+// The layout sample: the first SAMPLE_LINES values of a run of n records (`limit` bytes at p) as
+// the host model's reader finds them, a line each (nothing from a record the reader refuses --
+// the device decides that for the batch).
+static void sample_values(const u8* p, u64 limit, u32 n, std::vector<u8>* sample) {
+    KafkaHostIn in{p};
+    u32 pos = 0;
+    for (u32 i = 0; i < n && i < SAMPLE_LINES && pos < limit; ++i) {
+        u32 body = 0, end = 0;
+        KafkaRec r{};
+        if (kafka_read_len(in, pos, (u32)limit, &body, &end) || kafka_read_body(in, body, end, &r)) break;
+        sample->insert(sample->end(), in.p + r.val_pos, in.p + r.val_pos + r.val_len);
+        if (sample->empty() || sample->back() != '\n') sample->push_back('\n');
+        pos = end;
     }
+}
+
+int kafka_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                uint64_t nb, const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample) {
+    u64 nrec = 0, control = 0;
+    int rc = index_args(c, bytes, nbytes, batches, nb, &nrec, &control);
+    if (!rc) rc = lines_fit(c, nrec);
+    if (rc) return rc;
+    const KafkaLayout l = kafka_layout(nb, nrec);
+    if ((rc = place(c, slot, bytes, nbytes, dsrc, batches, nb, nrec, control, l.total, l.meta,
+                    l.batches + nb * sizeof(ysb_kafka_batch), batch, v)))
+        return rc;
+    sample->clear();
+    if (nb) sample_values(bytes + batches[0].records_off, batches[0].records_bytes, batches[0].n_records, sample);
     return YSB_OK;
 }
 
@@ -292,116 +324,66 @@ int kafka_lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes,
     KafkaError err;
     int rc = kafka_lz4_entries(batches, frames, nb, blocks, nblk, nbytes, &nrec, &control, &compressed, &stored, &err);
     if (rc) return fail(c, rc, "%s", err.msg);
-    if (nrec + 1 > c->raw_lines_cap)
-        return fail(c, YSB_ERR_CAPACITY, "Kafka batch of %llu records, more than the %llu lines its slot holds "
-                    "(max(max_batch_events, max_batch_bytes / 32))", (unsigned long long)nrec,
-                    (unsigned long long)(c->raw_lines_cap - 1));
+    if ((rc = lines_fit(c, nrec))) return rc;
     // the host cannot know the raw sizes: the guaranteed bound, 64 KiB per block
     if (nblk * (u64)LZ4_MAX_RAW > c->cfg.max_batch_bytes)
         return fail(c, YSB_ERR_CAPACITY, "compressed Kafka batch of %llu blocks: %llu x 65536 B may not fit max_batch_bytes "
                     "(%llu); submit fewer Kafka batches per call", (unsigned long long)nblk, (unsigned long long)nblk,
                     (unsigned long long)c->cfg.max_batch_bytes);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_lz4[slot]) HIPCHK(c, c->d_lz4[slot].alloc(c->cfg.max_batch_bytes + 64));
+    const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec);
+    if ((rc = place(c, slot, bytes, nbytes, dsrc, batches, nb, nrec, control, l.total, l.copied, l.copied, batch, v))) return rc;
+    // a compressed batch's own: the inflated records and the plan's pinned head at their first
+    // use, the frames and the blocks behind the index, what its settling reports
     if (!c->d_kafka_infl[slot]) HIPCHK(c, c->d_kafka_infl[slot].alloc(c->cfg.max_batch_bytes + 64));
-    if (!c->h_kafka_head) {
-        HIPCHK(c, c->h_kafka_head.alloc(2 * sizeof(KafkaHead)));
-        std::memset(c->h_kafka_head.get(), 0, 2 * sizeof(KafkaHead));
-    }
     if (!c->h_kafka_plan) {
         HIPCHK(c, c->h_kafka_plan.alloc(2 * sizeof(KafkaPlanHead)));
         std::memset(c->h_kafka_plan.get(), 0, 2 * sizeof(KafkaPlanHead));
     }
-    const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec);
-    if (l.total > c->kafka_cap[slot]) {
-        const u64 cap = std::max<u64>(l.total + l.total / 2, 256u << 10);
-        if ((rc = grow_device(c, c->d_kafka[slot], cap + 64, 0))) return rc;
-        c->kafka_cap[slot] = cap;
-    }
-    if (l.copied > c->kafka_hcap[slot]) {
-        const u64 cap = std::max<u64>(l.copied + l.copied / 2, 64u << 10);
-        c->kafka_hcap[slot] = 0;
-        HIPCHK(c, c->h_kafka[slot].alloc(cap + 64));
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hd_kafka[slot]), c->h_kafka[slot], 0));
-        c->kafka_hcap[slot] = cap;
-    }
-    KafkaHead head{};
-    head.first_bad = KAFKA_NONE;
-    u8* hp = c->h_kafka[slot];
-    std::memcpy(hp, &head, sizeof head);
-    if (nb) std::memcpy(hp + l.batches, batches, nb * sizeof(ysb_kafka_batch));
-    if (nb) std::memcpy(hp + l.frames, frames, nb * sizeof(ysb_kafka_frame));
-    if (nblk) std::memcpy(hp + l.blocks, blocks, nblk * sizeof(ysb_lz4_frame_block));
-    if (!dsrc && nbytes && bytes != c->h_bytes[slot]) std::memcpy(c->h_bytes[slot], bytes, nbytes);
-    v[0] = {c->d_lz4[slot], dsrc ? dsrc : c->hd_bytes[slot], dsrc ? bytes : c->h_bytes[slot].get(), nbytes};
-    v[1] = {c->d_kafka[slot], c->hd_kafka[slot], c->h_kafka[slot], l.copied};
-    batch->nbytes = nbytes;
-    batch->off = c->d_roff[slot];
-    batch->n_off = nrec;
-    KafkaStaged st{nb, nrec, nbytes, control};
+    if (nb) std::memcpy(c->h_kafka[slot] + l.frames, frames, nb * sizeof(ysb_kafka_frame));
+    if (nblk) std::memcpy(c->h_kafka[slot] + l.blocks, blocks, nblk * sizeof(ysb_lz4_frame_block));
+    KafkaStaged& st = *batch->kafka;
     st.lz4 = true;
     st.n_blocks = nblk;
     st.stored_blocks = stored;
     st.compressed_batches = compressed;
     st.decoder = c->lz4_decoder;
-    batch->kafka = st;
     // the layout sample: the first batch inflated and read by the host model
     sample->clear();
     if (nb) {
         std::vector<u8> infl((u64)frames[0].n_blocks * LZ4_MAX_RAW + 1);
         u64 total = 0;
-        if (kafka_inflate_batch(bytes, frames[0], blocks, infl.data(), &total) == KAFKA_NONE) {
-            KafkaHostIn in{infl.data()};
-            u32 pos = 0;
-            for (u32 i = 0; i < batches[0].n_records && i < SAMPLE_LINES && pos < total; ++i) {
-                u32 body = 0, end = 0;
-                KafkaRec r{};
-                if (kafka_read_len(in, pos, (u32)total, &body, &end) || kafka_read_body(in, body, end, &r)) break;
-                sample->insert(sample->end(), in.p + r.val_pos, in.p + r.val_pos + r.val_len);
-                if (sample->empty() || sample->back() != '\n') sample->push_back('\n');
-                pos = end;
-            }
-        }
+        if (kafka_inflate_batch(bytes, frames[0], blocks, infl.data(), &total) == KAFKA_NONE)
+            sample_values(infl.data(), total, batches[0].n_records, sample);
     }
     return YSB_OK;
 }
 
 int kafka_enqueue(ysb_ctx* c, int slot, const KafkaStaged& b, hipStream_t s) {
-    if (b.lz4) {
-        const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
-        const KafkaLz4Layout l = kafka_lz4_layout(b.n_batches, b.n_blocks, b.n_records);
-        const KafkaHead* head = nullptr;
-        const KafkaPlanHead* plan = nullptr;
-        if (int rc = launch_inflate_unframe(c, c->d_kafka[slot], l, c->d_lz4[slot], c->d_kafka_infl[slot], b.n_batches, b.n_blocks,
-                                            b.n_records, b.decoder, c->d_bytes[slot], c->cfg.max_batch_bytes, c->d_roff[slot], s,
-                                            timed ? c->ev_kafka_lz4[slot] : nullptr, timed ? c->ev_kafka[slot] : nullptr, &head,
-                                            &plan))
-            return rc;
-        HIPCHK(c, hipMemcpyAsync(c->h_kafka_head + slot, head, sizeof(KafkaHead), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(c->h_kafka_plan + slot, plan, sizeof(KafkaPlanHead), hipMemcpyDeviceToHost, s));
-        return YSB_OK;
-    }
-    const KafkaLayout l = kafka_layout(b.n_batches, b.n_records);
-    const KafkaParams p = kafka_params(c->d_kafka[slot], l, c->d_lz4[slot], b.n_batches, b.n_records, c->d_bytes[slot],
-                                       c->cfg.max_batch_bytes, c->d_roff[slot]);
-    if (int rc = launch_unframe(c, p, s, (c->cfg.flags & YSB_F_TIMING) ? c->ev_kafka[slot] : nullptr)) return rc;
+    const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
+    const KafkaHead* head = nullptr;
+    const KafkaPlanHead* plan = nullptr;
+    if (int rc = launch_call(c, c->d_kafka[slot], c->d_wire[slot], b.lz4 ? c->d_kafka_infl[slot].get() : nullptr, b.n_batches,
+                             b.n_blocks, b.n_records, b.decoder, c->d_bytes[slot], c->cfg.max_batch_bytes, c->d_roff[slot], s,
+                             timed ? c->ev_kafka_lz4[slot] : nullptr, timed ? c->ev_kafka[slot] : nullptr, &head, &plan))
+        return rc;
     // the verdict comes back through pinned memory with the line count: no host wait here
-    HIPCHK(c, hipMemcpyAsync(c->h_kafka_head + slot, p.head, sizeof(KafkaHead), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_kafka_head + slot, head, sizeof(KafkaHead), hipMemcpyDeviceToHost, s));
+    if (plan) HIPCHK(c, hipMemcpyAsync(c->h_kafka_plan + slot, plan, sizeof(KafkaPlanHead), hipMemcpyDeviceToHost, s));
     return YSB_OK;
 }
 
-int kafka_settle(ysb_ctx* c, int slot, const KafkaStaged& b) {
+int kafka_settle(ysb_ctx* c, int slot, const KafkaStaged& b, u64* nbytes) {
+    const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
     if (b.lz4)
         settle_lz4(c, c->h_kafka_plan[slot], b.n_blocks, b.stored_blocks, b.compressed_batches, b.framed_bytes, b.decoder,
-                   (c->cfg.flags & YSB_F_TIMING) ? c->ev_kafka_lz4[slot] : nullptr);
+                   timed ? c->ev_kafka_lz4[slot] : nullptr);
+    *nbytes = c->h_kafka_head[slot].out_bytes;
     char what[48];
     std::snprintf(what, sizeof what, "Kafka batch (slot %d)", slot);
     return settle(c, c->h_kafka_head[slot], b.n_batches, b.framed_bytes, b.control_skipped,
                   reinterpret_cast<const ysb_kafka_batch*>(c->h_kafka[slot] + sizeof(KafkaHead)),
-                  (c->cfg.flags & YSB_F_TIMING) ? c->ev_kafka[slot] : nullptr, what);
+                  timed ? c->ev_kafka[slot] : nullptr, what);
 }
-
-u64 kafka_out_bytes(const ysb_ctx* c, int slot) { return c->h_kafka_head[slot].out_bytes; }
 
 // ---- the unframing alone ----------------------------------------------------------------------
 
@@ -464,11 +446,8 @@ int ysb_kafka_unframe_lz4_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nb
     if ((rc = grow_device(c, c->d_kafka_lz4_sync, l.total + 64, 256u << 10))) return rc;
     if ((rc = grow_device(c, c->d_kafka_infl_sync, nblk * (u64)LZ4_MAX_RAW + 64, 1u << 20))) return rc;
     u8* d = c->d_kafka_lz4_sync;
-    struct SyncOnExit {
-        hipStream_t s;
-        ~SyncOnExit() { (void)hipStreamSynchronize(s); }
-    } const settled{c->s_comp};
     hipStream_t s = c->s_comp;
+    const SyncOnExit settled{s};
     if (nb) HIPCHK(c, hipMemcpyAsync(d + l.batches, batches, nb * sizeof(ysb_kafka_batch), hipMemcpyHostToDevice, s));
     if (nb) HIPCHK(c, hipMemcpyAsync(d + l.frames, frames, nb * sizeof(ysb_kafka_frame), hipMemcpyHostToDevice, s));
     if (nblk) HIPCHK(c, hipMemcpyAsync(d + l.blocks, blocks, nblk * sizeof(ysb_lz4_frame_block), hipMemcpyHostToDevice, s));
@@ -476,8 +455,8 @@ int ysb_kafka_unframe_lz4_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nb
     Event ev[4], kev[4];
     const KafkaHead* dh = nullptr;
     const KafkaPlanHead* dp = nullptr;
-    if ((rc = launch_inflate_unframe(c, d, l, d_bytes, c->d_kafka_infl_sync, nb, nblk, nrec, c->lz4_decoder, d_out,
-                                     d_out ? out_cap : 0, d_line_off, s, timed ? ev : nullptr, timed ? kev : nullptr, &dh, &dp)))
+    if ((rc = launch_call(c, d, d_bytes, c->d_kafka_infl_sync, nb, nblk, nrec, c->lz4_decoder, d_out, d_out ? out_cap : 0,
+                          d_line_off, s, timed ? ev : nullptr, timed ? kev : nullptr, &dh, &dp)))
         return rc;
     KafkaHead h{};
     KafkaPlanHead ph{};

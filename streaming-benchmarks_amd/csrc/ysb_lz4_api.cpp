@@ -59,71 +59,16 @@ extern "C" {
 
 // One decode launch on s: the n_blocks blocks of d_comp, by the descriptors behind the
 // LZ4_DESC_HEAD bytes of {first bad, bad blocks} in d_descs, into d_out; that pair's read-back
-// to h_bad queued behind it.  ev: YSB_F_TIMING's event pair around the kernel (created on
-// demand), or NULL.
+// to h_bad queued behind it.  ev: YSB_F_TIMING's marks around the kernel, or NULL.
 static int launch_decode(ysb_ctx* c, const u8* d_comp, u8* d_descs, u32 n_blocks, u32 max_raw, u8* d_out, hipStream_t s,
                          Event* ev, u32* h_bad) {
-    if (ev) {
-        for (int k = 0; k < 2; ++k)
-            if (!ev[k]) HIPCHK(c, ev[k].create(hipEventDefault));
-        HIPCHK(c, hipEventRecord(ev[0], s));
-    }
+    HIPCHK(c, mark(ev, 0, s));
     u32* bad = reinterpret_cast<u32*>(d_descs);
     const Lz4Params lp{d_comp, reinterpret_cast<const Lz4Desc*>(d_descs + LZ4_DESC_HEAD), n_blocks, max_raw, d_out, bad, c->lz4_decoder};
     HIPCHK(c, launch_lz4_decode(lp, s));
-    if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, mark(ev, 1, s));
     HIPCHK(c, hipMemcpyAsync(h_bad, bad, 8, hipMemcpyDeviceToHost, s));
     return YSB_OK;
-}
-
-int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
-              uint32_t n_blocks, const uint8_t* dsrc, RawBatch* batch, std::vector<u8>* sample) {
-    u64 raw_total = 0;
-    int rc = dir_args(c, bytes, comp_bytes, dir, n_blocks, &raw_total);
-    if (rc) return rc;
-    if (comp_bytes > c->cfg.max_batch_bytes || raw_total > c->cfg.max_batch_bytes)
-        return fail(c, YSB_ERR_CAPACITY, "LZ4 batch of %llu B (%llu B decoded) exceeds max_batch_bytes",
-                    (unsigned long long)comp_bytes, (unsigned long long)raw_total);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_lz4[slot]) HIPCHK(c, c->d_lz4[slot].alloc(c->cfg.max_batch_bytes + 64));
-    if (!c->h_lz4bad) {
-        HIPCHK(c, c->h_lz4bad.alloc(16));
-        std::memset(c->h_lz4bad, 0, 16);
-    }
-    const u64 need = LZ4_DESC_HEAD + (u64)n_blocks * sizeof(Lz4Desc);
-    if (need > c->lz4desc_cap[slot]) {   // (outside steady state: a batch with more blocks than any before)
-        const u64 cap = std::max<u64>(need + need / 2, 64u << 10);
-        if ((rc = grow_device(c, c->d_lz4desc[slot], cap + 64, 0))) return rc;
-        HIPCHK(c, c->h_lz4desc[slot].alloc(cap + 64));
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->hd_lz4desc[slot]), c->h_lz4desc[slot], 0));
-        c->lz4desc_cap[slot] = cap;
-    }
-    // the bytes: into the slot's pinned buffer, or read where they lie (a registered range)
-    if (!dsrc && bytes != c->h_bytes[slot] && comp_bytes) std::memcpy(c->h_bytes[slot], bytes, comp_bytes);
-    batch->nbytes = raw_total;
-    Lz4Staged* out = &batch->lz4.emplace();
-    out->hsrc = dsrc ? bytes : c->h_bytes[slot].get();
-    out->dsrc = dsrc ? dsrc : c->hd_bytes[slot];
-    fill_descs(dir, n_blocks, c->h_lz4desc[slot], &out->info, &out->max_raw);
-    // the layout sample: block 0 as the host model decodes it (nothing if it is bad -- the
-    // device decides that for the batch)
-    sample->clear();
-    if (n_blocks) {
-        sample->resize(dir[0].raw_bytes);
-        if (!lz4_decode_block(out->hsrc, dir[0], sample->data())) sample->clear();
-    }
-    return YSB_OK;
-}
-
-void lz4_copies(ysb_ctx* c, int slot, const Lz4Staged& b, SlotCopy v[2]) {
-    if (b.frame) {
-        v[0] = {c->d_lz4[slot], b.dsrc, b.hsrc, b.span};
-        v[1] = {c->d_lz4desc[slot], c->hd_lz4desc[slot], c->h_lz4desc[slot], LZ4F_HEAD + b.info.blocks * sizeof(Lz4FrameBlock)};
-        return;
-    }
-    v[0] = {c->d_lz4[slot], b.dsrc, b.hsrc, b.info.comp_bytes};
-    v[1] = {c->d_lz4desc[slot], c->hd_lz4desc[slot], c->h_lz4desc[slot],
-            b.info.blocks ? LZ4_DESC_HEAD + b.info.blocks * sizeof(Lz4Desc) : 0};
 }
 
 // The descriptors' pinned / device buffers of a slot grown to `need` bytes (outside steady
@@ -138,26 +83,67 @@ static int grow_descs(ysb_ctx* c, int slot, u64 need) {
     return YSB_OK;
 }
 
+int lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
+              uint32_t n_blocks, const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample) {
+    u64 raw_total = 0;
+    int rc = dir_args(c, bytes, comp_bytes, dir, n_blocks, &raw_total);
+    if (rc) return rc;
+    if (comp_bytes > c->cfg.max_batch_bytes || raw_total > c->cfg.max_batch_bytes)
+        return fail(c, YSB_ERR_CAPACITY, "LZ4 batch of %llu B (%llu B decoded) exceeds max_batch_bytes",
+                    (unsigned long long)comp_bytes, (unsigned long long)raw_total);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensure_wire(c, slot))) return rc;
+    if (!c->h_lz4bad) {
+        HIPCHK(c, c->h_lz4bad.alloc(16));
+        std::memset(c->h_lz4bad, 0, 16);
+    }
+    const u64 desc_bytes = LZ4_DESC_HEAD + (u64)n_blocks * sizeof(Lz4Desc);
+    if ((rc = grow_descs(c, slot, desc_bytes))) return rc;
+    batch->nbytes = raw_total;
+    Lz4Staged* out = &batch->lz4.emplace();
+    fill_descs(dir, n_blocks, c->h_lz4desc[slot], &out->info, &out->max_raw);
+    v[0] = stage_wire(c, slot, bytes, comp_bytes, dsrc);
+    v[1] = {c->d_lz4desc[slot], c->hd_lz4desc[slot], c->h_lz4desc[slot], n_blocks ? desc_bytes : 0};
+    // the layout sample: block 0 as the host model decodes it (nothing if it is bad -- the
+    // device decides that for the batch)
+    sample->clear();
+    if (n_blocks) {
+        sample->resize(dir[0].raw_bytes);
+        if (!lz4_decode_block(static_cast<const u8*>(v[0].hsrc), dir[0], sample->data())) sample->clear();
+    }
+    return YSB_OK;
+}
+
 // ---- frame batches through the slots (ysb_submit_lz4_blocks) ----------------------------------
 // d_lz4desc[slot]: the batch's Lz4FrameHead, then its index entries (offsets from the span's
 // start); d_lz4f[slot]: the descriptors, then the measured sizes.
 
+// The index entries of a call as argument errors: every block's size rule and, for a slot batch
+// (in_order: a run of consecutive index entries), that each lies behind the one before; how
+// many are stored and their compressed bytes into *stored and *comp_bytes.
+static int frame_blocks(ysb_ctx* c, const ysb_lz4_frame_block* blocks, u32 n, bool in_order, u64* stored, u64* comp_bytes) {
+    *stored = *comp_bytes = 0;
+    for (u32 i = 0; i < n; ++i) {
+        const u32 comp = blocks[i].comp_bytes & ~LZ4_STORED;
+        if (comp < 1 || comp > LZ4F_BLOCK_MAX)
+            return fail(c, YSB_ERR_ARG, "frame block %u: %u bytes, not in 1..%u", i, comp, LZ4F_BLOCK_MAX);
+        if (in_order && i && blocks[i].offset < blocks[i - 1].offset + (blocks[i - 1].comp_bytes & ~LZ4_STORED) + 4)
+            return fail(c, YSB_ERR_ARG, "frame block %u does not lie behind block %u: a batch is a run of consecutive index entries", i, i - 1);
+        *stored += (blocks[i].comp_bytes & LZ4_STORED) ? 1 : 0;
+        *comp_bytes += comp;
+    }
+    return YSB_OK;
+}
+
 int lz4f_stage(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_block* blocks, uint32_t n, uint32_t flags,
-               const uint8_t* dsrc, RawBatch* batch, std::vector<u8>* sample) {
+               const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample) {
     if (n && (!base || !blocks)) return fail(c, YSB_ERR_ARG, "NULL frame buffers");
     if (flags & ~YSB_LZ4F_MORE) return fail(c, YSB_ERR_ARG, "unknown flags %#x", flags);
     ysb_lz4_desc info{};
     info.blocks = n;
     info.first_bad = LZ4_NO_BAD;
-    for (u32 i = 0; i < n; ++i) {
-        const u32 comp = blocks[i].comp_bytes & ~LZ4_STORED;
-        if (comp < 1 || comp > LZ4F_BLOCK_MAX)
-            return fail(c, YSB_ERR_ARG, "frame block %u: %u bytes, not in 1..%u", i, comp, LZ4F_BLOCK_MAX);
-        if (i && blocks[i].offset < blocks[i - 1].offset + (blocks[i - 1].comp_bytes & ~LZ4_STORED) + 4)
-            return fail(c, YSB_ERR_ARG, "frame block %u does not lie behind block %u: a batch is a run of consecutive index entries", i, i - 1);
-        info.stored_blocks += (blocks[i].comp_bytes & LZ4_STORED) ? 1 : 0;
-        info.comp_bytes += comp;
-    }
+    int rc = frame_blocks(c, blocks, n, true, &info.stored_blocks, &info.comp_bytes);
+    if (rc) return rc;
     const u64 first = n ? blocks[0].offset : 0;
     const u64 span = n ? blocks[n - 1].offset + (blocks[n - 1].comp_bytes & ~LZ4_STORED) - first : 0;
     const u64 bound = ((u64)n + 1) * LZ4_MAX_RAW;
@@ -165,7 +151,7 @@ int lz4f_stage(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_bl
         return fail(c, YSB_ERR_CAPACITY, "frame batch of %u blocks (%llu B; up to %llu B decoded with the carry) exceeds max_batch_bytes",
                     n, (unsigned long long)span, (unsigned long long)bound);
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_lz4[slot]) HIPCHK(c, c->d_lz4[slot].alloc(c->cfg.max_batch_bytes + 64));
+    if ((rc = ensure_wire(c, slot))) return rc;
     if (!c->h_lz4f) {
         HIPCHK(c, c->h_lz4f.alloc(2 * LZ4F_HEAD));
         std::memset(c->h_lz4f.get(), 0, 2 * LZ4F_HEAD);
@@ -174,11 +160,13 @@ int lz4f_stage(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_bl
         HIPCHK(c, c->d_carry.alloc(LZ4_CARRY_HEAD + LZ4_CARRY_MAX));
         HIPCHK(c, hipMemset(c->d_carry, 0, LZ4_CARRY_HEAD));
     }
-    int rc = grow_descs(c, slot, LZ4F_HEAD + (u64)n * sizeof(Lz4FrameBlock));
+    const u64 index_bytes = LZ4F_HEAD + (u64)n * sizeof(Lz4FrameBlock);
+    rc = grow_descs(c, slot, index_bytes);
     if (!rc) rc = grow_device(c, c->d_lz4f[slot], (u64)n * (sizeof(Lz4Desc) + 4) + 64, 64u << 10);
     if (rc) return rc;
-    const u8* src = n ? base + first : nullptr;
-    if (!dsrc && span && src != c->h_bytes[slot]) std::memcpy(c->h_bytes[slot], src, span);
+    v[0] = stage_wire(c, slot, n ? base + first : nullptr, span, dsrc);
+    v[1] = {c->d_lz4desc[slot], c->hd_lz4desc[slot], c->h_lz4desc[slot], index_bytes};
+    const u8* hsrc = static_cast<const u8*>(v[0].hsrc);
     Lz4FrameHead head{};
     head.bad[0] = LZ4_NO_BAD;
     std::memcpy(c->h_lz4desc[slot], &head, LZ4F_HEAD);
@@ -188,21 +176,18 @@ int lz4f_stage(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_bl
     }
     batch->nbytes = bound;
     Lz4Staged* out = &batch->lz4.emplace();
-    out->hsrc = dsrc ? src : c->h_bytes[slot].get();
-    out->dsrc = dsrc ? dsrc : c->hd_bytes[slot];
     out->info = info;
     out->max_raw = LZ4_MAX_RAW;
     out->frame = true;
     out->decoder = lz4_pick_decoder(LZ4_MAX_RAW, c->lz4_decoder);
-    out->span = span;
     out->more = (flags & YSB_LZ4F_MORE) != 0;
     // the layout sample: block 0 as the host model measures and decodes it, from behind its
     // first terminator when the batch before left a carry (its head is the tail of a line)
     sample->clear();
     if (n) {
-        const u32 raw = lz4_measure_block(out->hsrc, blocks[0].comp_bytes);
+        const u32 raw = lz4_measure_block(hsrc, blocks[0].comp_bytes);
         sample->resize(raw);
-        if (raw && !lz4_decode_block(out->hsrc, ysb_lz4_block{blocks[0].comp_bytes, raw}, sample->data())) sample->clear();
+        if (raw && !lz4_decode_block(hsrc, ysb_lz4_block{blocks[0].comp_bytes, raw}, sample->data())) sample->clear();
         if (c->lz4f_more && !sample->empty()) {
             size_t k = 0;
             while (k < sample->size() && (*sample)[k] != '\n' && (*sample)[k] != '\r') ++k;
@@ -212,42 +197,41 @@ int lz4f_stage(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4_frame_bl
     return YSB_OK;
 }
 
-const u64* lz4f_nbytes(ysb_ctx* c, int slot) {
-    return &reinterpret_cast<const Lz4FrameHead*>(c->d_lz4desc[slot].get())->nbytes;
-}
-
 int lz4f_readback(ysb_ctx* c, int slot, hipStream_t s) {
     HIPCHK(c, hipMemcpyAsync(c->h_lz4f + slot, c->d_lz4desc[slot], LZ4F_HEAD, hipMemcpyDeviceToHost, s));
     return YSB_OK;
 }
 
-// measure, descriptors, decode behind the carry's length, carry in and out: on s behind the slot's copies
-static int lz4f_enqueue(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s) {
+// YSB_F_TIMING's marks of the slot's LZ4 batch (ev_lz4[slot]; NULL: not timed): a directory batch's
+// decode lies between marks 0 and 1, a frame batch's measure + descriptors there and its decode
+// between marks 1 and 2
+static Event* lz4_marks(ysb_ctx* c, int slot) { return (c->cfg.flags & YSB_F_TIMING) ? c->ev_lz4[slot] : nullptr; }
+
+// measure, descriptors, decode behind the carry's length, carry in and out: on s behind the slot's
+// copies; *d_nbytes: the batch's byte count in its head on the device
+static int lz4f_enqueue(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s, const u64** d_nbytes) {
     const u32 n = (u32)b.info.blocks;
     Lz4FrameHead* head = reinterpret_cast<Lz4FrameHead*>(c->d_lz4desc[slot].get());
     const Lz4FrameBlock* blocks = reinterpret_cast<const Lz4FrameBlock*>(c->d_lz4desc[slot] + LZ4F_HEAD);
     Lz4Desc* desc = reinterpret_cast<Lz4Desc*>(c->d_lz4f[slot].get());
     u32* raw = reinterpret_cast<u32*>(c->d_lz4f[slot] + (u64)n * sizeof(Lz4Desc));
-    Event* ev = (c->cfg.flags & YSB_F_TIMING) ? c->ev_lz4[slot] : nullptr;
-    if (ev) {   // three events: measure + descriptors between the first two, the decode between the last two
-        if (!c->ev_lz4m[slot]) HIPCHK(c, c->ev_lz4m[slot].create(hipEventDefault));
-        for (int k = 0; k < 2; ++k)
-            if (!ev[k]) HIPCHK(c, ev[k].create(hipEventDefault));
-        HIPCHK(c, hipEventRecord(c->ev_lz4m[slot], s));
-    }
-    HIPCHK(c, launch_lz4_measure(c->d_lz4[slot], blocks, n, raw, s));
+    Event* ev = lz4_marks(c, slot);
+    HIPCHK(c, mark(ev, 0, s));
+    HIPCHK(c, launch_lz4_measure(c->d_wire[slot], blocks, n, raw, s));
     HIPCHK(c, launch_lz4_frame_descs(blocks, raw, n, 0, desc, &head->raw_total, s, reinterpret_cast<const u64*>(c->d_carry.get())));
-    if (ev) HIPCHK(c, hipEventRecord(ev[0], s));
-    const Lz4Params lp{c->d_lz4[slot], desc, n, LZ4_MAX_RAW, c->d_bytes[slot], head->bad, b.decoder};
+    HIPCHK(c, mark(ev, 1, s));
+    const Lz4Params lp{c->d_wire[slot], desc, n, LZ4_MAX_RAW, c->d_bytes[slot], head->bad, b.decoder};
     HIPCHK(c, launch_lz4_decode(lp, s));
-    if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, mark(ev, 2, s));
     HIPCHK(c, launch_lz4_frame_carry(c->d_bytes[slot], c->d_carry, head, b.more ? 1u : 0u, s));
+    *d_nbytes = &head->nbytes;
     return YSB_OK;
 }
 
 // at a frame batch's launch: lz4f_last <- its figures; a bad block or a carry above 64 KiB drops it
-static int lz4f_settle(ysb_ctx* c, int slot, const Lz4Staged& b) {
+static int lz4f_settle(ysb_ctx* c, int slot, const Lz4Staged& b, u64* nbytes) {
     const Lz4FrameHead h = c->h_lz4f[slot];
+    *nbytes = h.nbytes;
     ysb_lz4_frame_desc d{};
     d.blocks = b.info.blocks;
     d.stored_blocks = b.info.stored_blocks;
@@ -259,11 +243,8 @@ static int lz4f_settle(ysb_ctx* c, int slot, const Lz4Staged& b) {
     d.carry_in = h.carry_in;
     d.carry_out = h.carry_out;
     d.batches = c->lz4f_last.batches + 1;
-    float ms = 0;
-    if (c->cfg.flags & YSB_F_TIMING) {
-        if (hipEventElapsedTime(&ms, c->ev_lz4m[slot], c->ev_lz4[slot][0]) == hipSuccess) d.measure_ms = ms;
-        if (hipEventElapsedTime(&ms, c->ev_lz4[slot][0], c->ev_lz4[slot][1]) == hipSuccess) d.decode_ms = ms;
-    }
+    add_span(lz4_marks(c, slot), 0, 1, &d.measure_ms);
+    add_span(lz4_marks(c, slot), 1, 2, &d.decode_ms);
     c->lz4f_last = d;
     if (h.bad[1])
         return fail(c, YSB_ERR_FORMAT, "frame batch (slot %d): block %u of %llu breaks the block format (%u bad in all); "
@@ -274,26 +255,24 @@ static int lz4f_settle(ysb_ctx* c, int slot, const Lz4Staged& b) {
     return YSB_OK;
 }
 
-int lz4_enqueue_decode(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s) {
-    if (b.frame) return lz4f_enqueue(c, slot, b, s);
+int lz4_enqueue_decode(ysb_ctx* c, int slot, const Lz4Staged& b, hipStream_t s, const u64** d_nbytes) {
+    if (b.frame) return lz4f_enqueue(c, slot, b, s, d_nbytes);
     c->h_lz4bad[2 * slot] = LZ4_NO_BAD;
     c->h_lz4bad[2 * slot + 1] = 0;
     if (!b.info.blocks) return YSB_OK;
     // the bad-block pair comes back through pinned memory with the line count: no host wait here
-    return launch_decode(c, c->d_lz4[slot], c->d_lz4desc[slot], (u32)b.info.blocks, b.max_raw, c->d_bytes[slot], s,
-                         (c->cfg.flags & YSB_F_TIMING) ? c->ev_lz4[slot] : nullptr, c->h_lz4bad + 2 * slot);
+    return launch_decode(c, c->d_wire[slot], c->d_lz4desc[slot], (u32)b.info.blocks, b.max_raw, c->d_bytes[slot], s,
+                         lz4_marks(c, slot), c->h_lz4bad + 2 * slot);
 }
 
-int lz4_settle(ysb_ctx* c, int slot, const Lz4Staged& b) {
-    if (b.frame) return lz4f_settle(c, slot, b);
+int lz4_settle(ysb_ctx* c, int slot, const Lz4Staged& b, u64* nbytes) {
+    if (b.frame) return lz4f_settle(c, slot, b, nbytes);
     ysb_lz4_desc d = b.info;
+    *nbytes = d.raw_bytes;
     d.batches = c->lz4_last.batches + 1;
     d.first_bad = c->h_lz4bad[2 * slot];
     d.bad_blocks = c->h_lz4bad[2 * slot + 1];
-    if (d.blocks && (c->cfg.flags & YSB_F_TIMING)) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_lz4[slot][0], c->ev_lz4[slot][1]) == hipSuccess) d.decode_ms = ms;
-    }
+    if (d.blocks) add_span(lz4_marks(c, slot), 0, 1, &d.decode_ms);   // (no blocks: no decode ran, the marks are an earlier batch's)
     c->lz4_last = d;
     if (d.bad_blocks)
         return fail(c, YSB_ERR_FORMAT, "LZ4 batch (slot %d): block %llu of %llu breaks the block format (%llu bad in all); "
@@ -325,13 +304,11 @@ int ysb_lz4_decode_device(ysb_ctx* c, const uint8_t* d_comp, uint64_t comp_bytes
     if (n_blocks) {
         if ((rc = grow_device(c, c->d_lz4desc_sync, descs.size(), 64u << 10))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->d_lz4desc_sync, descs.data(), descs.size(), hipMemcpyHostToDevice, c->s_comp));
-        const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
-        Event ev[2];
-        if ((rc = launch_decode(c, d_comp, c->d_lz4desc_sync, n_blocks, max_raw, d_out, c->s_comp, timed ? ev : nullptr, bad)))
-            return rc;
+        Event marks[2];
+        Event* ev = (c->cfg.flags & YSB_F_TIMING) ? marks : nullptr;
+        if ((rc = launch_decode(c, d_comp, c->d_lz4desc_sync, n_blocks, max_raw, d_out, c->s_comp, ev, bad))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->s_comp));
-        float ms = 0;
-        if (timed && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) info.decode_ms = ms;
+        add_span(ev, 0, 1, &info.decode_ms);
     }
     info.first_bad = bad[0];
     info.bad_blocks = bad[1];
@@ -496,12 +473,6 @@ struct FrameScratch {
     Lz4Desc* desc;
     u32* raw;
 };
-// The synchronous calls copy to and from the caller's pageable memory and their own stack: no
-// return, an error's included, leaves such a copy pending.
-struct SyncOnExit {
-    hipStream_t s;
-    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
-};
 
 static int frame_scratch(ysb_ctx* c, const ysb_lz4_frame_block* blocks, u32 n, FrameScratch* fs) {
     const u64 need = 16 + (u64)n * (sizeof(Lz4FrameBlock) + sizeof(Lz4Desc) + 4);
@@ -524,25 +495,15 @@ static int frame_args(ysb_ctx* c, const uint8_t* d_base, const ysb_lz4_frame_blo
     *info = ysb_lz4_frame_desc{};
     info->blocks = n;
     info->first_bad = LZ4_NO_BAD;
-    for (u32 i = 0; i < n; ++i) {
-        const u32 comp = blocks[i].comp_bytes & ~LZ4_STORED;
-        if (comp < 1 || comp > LZ4F_BLOCK_MAX)
-            return fail(c, YSB_ERR_ARG, "frame block %u: %u bytes, not in 1..%u", i, comp, LZ4F_BLOCK_MAX);
-        info->stored_blocks += (blocks[i].comp_bytes & LZ4_STORED) ? 1 : 0;
-        info->comp_bytes += comp;
-    }
-    return YSB_OK;
+    return frame_blocks(c, blocks, n, false, &info->stored_blocks, &info->comp_bytes);
 }
 
-// measure + descriptors on s_comp, timed under YSB_F_TIMING
+// measure + descriptors on s_comp between marks 0 and 1 of ev (YSB_F_TIMING; NULL: not timed)
 static int frame_measure(ysb_ctx* c, const uint8_t* d_base, u32 n, const FrameScratch& fs, Event* ev) {
-    if (ev) {
-        for (int k = 0; k < 2; ++k) HIPCHK(c, ev[k].create(hipEventDefault));
-        HIPCHK(c, hipEventRecord(ev[0], c->s_comp));
-    }
+    HIPCHK(c, mark(ev, 0, c->s_comp));
     HIPCHK(c, launch_lz4_measure(d_base, fs.blocks, n, fs.raw, c->s_comp));
     HIPCHK(c, launch_lz4_frame_descs(fs.blocks, fs.raw, n, 0, fs.desc, fs.total, c->s_comp));
-    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->s_comp));
+    HIPCHK(c, mark(ev, 1, c->s_comp));
     return YSB_OK;
 }
 
@@ -560,14 +521,13 @@ int ysb_lz4_measure_device(ysb_ctx* c, const uint8_t* d_base, const ysb_lz4_fram
         FrameScratch fs;
         const SyncOnExit settled{c->s_comp};
         if ((rc = frame_scratch(c, blocks, n_blocks, &fs))) return rc;
-        const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
-        Event ev[2];
-        if ((rc = frame_measure(c, d_base, n_blocks, fs, timed ? ev : nullptr))) return rc;
+        Event marks[2];
+        Event* ev = (c->cfg.flags & YSB_F_TIMING) ? marks : nullptr;
+        if ((rc = frame_measure(c, d_base, n_blocks, fs, ev))) return rc;
         HIPCHK(c, hipMemcpyAsync(raw_out, fs.raw, (u64)n_blocks * 4, hipMemcpyDeviceToHost, c->s_comp));
         HIPCHK(c, hipMemcpyAsync(&info.raw_bytes, fs.total, 8, hipMemcpyDeviceToHost, c->s_comp));
         HIPCHK(c, hipStreamSynchronize(c->s_comp));
-        float ms = 0;
-        if (timed && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) info.measure_ms = ms;
+        add_span(ev, 0, 1, &info.measure_ms);
         for (u32 i = 0; i < n_blocks; ++i)
             if (!raw_out[i]) {
                 if (!info.bad_blocks) info.first_bad = i;
@@ -596,9 +556,9 @@ int ysb_lz4_decode_blocks_device(ysb_ctx* c, const uint8_t* d_base, const ysb_lz
         FrameScratch fs;
         const SyncOnExit settled{c->s_comp};
         if ((rc = frame_scratch(c, blocks, n_blocks, &fs))) return rc;
-        const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
-        Event evm[2], evd[2];
-        if ((rc = frame_measure(c, d_base, n_blocks, fs, timed ? evm : nullptr))) return rc;
+        Event marks[4];   // the measure pass between marks 0 and 1, the decode (behind a host wait) between 2 and 3
+        Event* ev = (c->cfg.flags & YSB_F_TIMING) ? marks : nullptr;
+        if ((rc = frame_measure(c, d_base, n_blocks, fs, ev))) return rc;
         // the measured total decides the capacity before a byte is decoded (this call is synchronous)
         HIPCHK(c, hipMemcpyAsync(&info.raw_bytes, fs.total, 8, hipMemcpyDeviceToHost, c->s_comp));
         HIPCHK(c, hipStreamSynchronize(c->s_comp));
@@ -607,20 +567,16 @@ int ysb_lz4_decode_blocks_device(ysb_ctx* c, const uint8_t* d_base, const ysb_lz
             return fail(c, YSB_ERR_CAPACITY, "%llu B decoded, cap %llu", (unsigned long long)info.raw_bytes,
                         (unsigned long long)out_cap);
         if (info.raw_bytes && !d_out) return fail(c, YSB_ERR_ARG, "NULL output buffer");
-        if (timed) {
-            for (int k = 0; k < 2; ++k) HIPCHK(c, evd[k].create(hipEventDefault));
-            HIPCHK(c, hipEventRecord(evd[0], c->s_comp));
-        }
+        HIPCHK(c, mark(ev, 2, c->s_comp));
         // (a block measured bad has raw 0: the decode kernel records it in the bad pair)
         const Lz4Params lp{d_base, fs.desc, n_blocks, LZ4_MAX_RAW, d_out, fs.bad, c->lz4_decoder};
         HIPCHK(c, launch_lz4_decode(lp, c->s_comp));
-        if (timed) HIPCHK(c, hipEventRecord(evd[1], c->s_comp));
+        HIPCHK(c, mark(ev, 3, c->s_comp));
         u32 bad[2] = {LZ4_NO_BAD, 0};
         HIPCHK(c, hipMemcpyAsync(bad, fs.bad, 8, hipMemcpyDeviceToHost, c->s_comp));
         HIPCHK(c, hipStreamSynchronize(c->s_comp));
-        float ms = 0;
-        if (timed && hipEventElapsedTime(&ms, evm[0], evm[1]) == hipSuccess) info.measure_ms = ms;
-        if (timed && hipEventElapsedTime(&ms, evd[0], evd[1]) == hipSuccess) info.decode_ms = ms;
+        add_span(ev, 0, 1, &info.measure_ms);
+        add_span(ev, 2, 3, &info.decode_ms);
         info.first_bad = bad[0];
         info.bad_blocks = bad[1];
         info.decoder = lz4_pick_decoder(LZ4_MAX_RAW, c->lz4_decoder);

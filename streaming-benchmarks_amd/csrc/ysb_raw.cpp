@@ -46,13 +46,16 @@ int launch_pending_raw(ysb_ctx* c) {
     if (c->raw_pend < 0) return YSB_OK;
     const int slot = c->raw_pend;
     const RawBatch& b = c->raw[slot];
+    // the decoded bytes: a plain batch's as submitted; counted on the device for a frame or a
+    // Kafka batch, whose settle step reads them from the pinned head that came back with the split's count
+    u64 nbytes = b.nbytes;
     int rc = YSB_OK;
     if (hipSetDevice(c->device) != hipSuccess || hipEventSynchronize(c->ev_raw[slot]) != hipSuccess ||
         hipStreamWaitEvent(c->s_comp, c->ev_raw[slot], 0) != hipSuccess) {
         rc = fail(c, YSB_ERR_HIP, "raw batch (slot %d): waiting for its line split failed", slot);
-    } else if (b.lz4 && (rc = lz4_settle(c, slot, *b.lz4))) {
+    } else if (b.lz4 && (rc = lz4_settle(c, slot, *b.lz4, &nbytes))) {
         // a compressed batch with a bad block: dropped whole (YSB_ERR_FORMAT, the message lz4_settle's)
-    } else if (b.kafka && (rc = kafka_settle(c, slot, *b.kafka))) {
+    } else if (b.kafka && (rc = kafka_settle(c, slot, *b.kafka, &nbytes))) {
         // a Kafka batch with a bad record: dropped whole (YSB_ERR_FORMAT, the message kafka_settle's)
     } else if (b.rebase && c->h_rawn[slot] > c->rebase_n - b.rebase->first_line) {
         rc = fail(c, YSB_ERR_ARG, "raw batch (slot %d): %llu lines, more than the rebase table holds from line %llu",
@@ -62,9 +65,6 @@ int launch_pending_raw(ysb_ctx* c) {
                   "(max(max_batch_events, max_batch_bytes / 32))", slot, (unsigned long long)c->h_rawn[slot],
                   (unsigned long long)c->raw_lines_cap);
     } else {
-        // (a frame batch's bytes were measured on the device: its count came back with the split's)
-        // (a Kafka batch's value bytes were counted there too: they came back with its verdict)
-        const u64 nbytes = b.lz4 && b.lz4->frame ? c->h_lz4f[slot].nbytes : b.kafka ? kafka_out_bytes(c, slot) : b.nbytes;
         const ysb_segment sg{c->d_bytes[slot], nbytes, b.off ? b.off : c->d_roff[slot].get(), c->h_rawn[slot]};
         rc = enqueue_scan(c, &sg, 1, b.lay);
     }
@@ -132,7 +132,8 @@ static int enqueue_deferred(ysb_ctx* c, int slot, RawBatch b, const SlotCopy* v,
     if ((rc = copy_slot_ranges(c, slot, v, nv))) return rc;
     hipStream_t s = c->s_split;
     HIPCHK(c, hipStreamWaitEvent(s, c->ev_h2d[slot], 0));
-    if (b.lz4 && (rc = lz4_enqueue_decode(c, slot, *b.lz4, s))) return rc;
+    const u64* d_nbytes = nullptr;   // a frame batch: its byte count is measured on the device, where the split reads it
+    if (b.lz4 && (rc = lz4_enqueue_decode(c, slot, *b.lz4, s, &d_nbytes))) return rc;
     // a Kafka batch's kernels leave the values in the slot's device buffer and their offsets in
     // d_roff[slot], which is b.off: no split
     if (b.kafka && (rc = kafka_enqueue(c, slot, *b.kafka, s))) return rc;
@@ -140,8 +141,8 @@ static int enqueue_deferred(ysb_ctx* c, int slot, RawBatch b, const SlotCopy* v,
     // empty batch) or the split's
     if (b.off || !b.nbytes) c->h_rawn[slot] = b.n_off;
     else HIPCHK(c, launch_split_lines(c->d_bytes[slot], b.nbytes, c->d_split_chunk, c->d_roff[slot], c->raw_lines_cap,
-                                      c->h_rawn + slot, s, b.lz4 && b.lz4->frame ? lz4f_nbytes(c, slot) : nullptr));
-    if (b.lz4 && b.lz4->frame && (rc = lz4f_readback(c, slot, s))) return rc;
+                                      c->h_rawn + slot, s, d_nbytes));
+    if (d_nbytes && (rc = lz4f_readback(c, slot, s))) return rc;
     if (b.rebase && (b.off || b.nbytes) && (rc = rebase_lines(c, slot, b.nbytes, b.off, b.n_off, *b.rebase, s))) return rc;
     HIPCHK(c, hipEventRecord(c->ev_raw[slot], s));
     c->raw[slot] = b;
@@ -174,27 +175,38 @@ int ysb_submit_raw(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes) 
     return enqueue_plain(c, slot, c->h_bytes[slot], c->hd_bytes[slot], nbytes, nullptr);
 }
 
-// ---- LZ4-compressed raw batches (ysb_lz4_api.cpp, ysb_lz4.hip) --------------------------------
+// ---- batches staged in front of the split: LZ4, standard frames, Kafka ------------------------
 
-// What both compressed submits do once their own arguments are checked: the slot claimed, the
-// batch staged (dsrc: lz4_stage) -- the compressed bytes (from the slot's pinned buffer or in
-// place from a registered range) and the block descriptors are what crosses PCIe --, enqueued.
-static int submit_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, u64 comp_bytes, const ysb_lz4_block* dir, u32 n_blocks,
-                      const u8* dsrc, const u32* d_line_off, u64 n, const ysb_rebase* rb) {
+// What every such submit does once its own arguments are checked: the slot claimed, the batch
+// staged by the entry's own step -- stage(batch, v, sample) fills the RawBatch, the slot's two
+// copies (the wire bytes, from the slot's pinned buffer or in place from a registered range,
+// and the descriptors or index: what crosses PCIe) and the layout sample --, enqueued.
+extern "C++" template <class Stage>
+static int submit_staged(ysb_ctx* c, int slot, Stage stage) {
     int rc = claim_slot(c, slot);
     if (rc) return rc;
-    // the slot's previous H2D must be done before its pinned buffers are rewritten (in place:
-    // the descriptors'; so at most two copies are in flight)
+    // the slot's previous H2D must be done before its pinned buffers are rewritten (a batch read
+    // in place: the descriptors' or the index's; so at most two copies are in flight)
     HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
     RawBatch b;
-    std::vector<u8> sample;
-    if ((rc = lz4_stage(c, slot, bytes, comp_bytes, dir, n_blocks, dsrc, &b, &sample))) return rc;
-    b.off = d_line_off;
-    b.n_off = n;
-    if (rb) b.rebase = *rb;
     SlotCopy v[2];
-    lz4_copies(c, slot, *b.lz4, v);
+    std::vector<u8> sample;
+    if ((rc = stage(&b, v, &sample))) return rc;
     return enqueue_deferred(c, slot, b, v, 2, sample.data(), sample.size());
+}
+
+// ---- LZ4-compressed raw batches (ysb_lz4_api.cpp lz4_stage; ysb_lz4.hip) ----------------------
+
+// both compressed submits once their own arguments are checked (dsrc: lz4_stage)
+static int submit_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, u64 comp_bytes, const ysb_lz4_block* dir, u32 n_blocks,
+                      const u8* dsrc, const u32* d_line_off, u64 n, const ysb_rebase* rb) {
+    return submit_staged(c, slot, [&](RawBatch* b, SlotCopy* v, std::vector<u8>* sample) -> int {
+        if (int rc = lz4_stage(c, slot, bytes, comp_bytes, dir, n_blocks, dsrc, b, v, sample)) return rc;
+        b->off = d_line_off;
+        b->n_off = n;
+        if (rb) b->rebase = *rb;
+        return YSB_OK;
+    });
 }
 
 int ysb_submit_raw_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
@@ -223,16 +235,15 @@ static int submit_frame(ysb_ctx* c, int slot, const uint8_t* base, const ysb_lz4
         if (last < first) return fail(c, YSB_ERR_ARG, "the frame blocks are not in order");
         if (int rc = mapped_src(c, base + first, last - first, &dsrc)) return rc;
     }
-    int rc = claim_slot(c, slot);
-    if (rc) return rc;
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));   // the slot's pinned buffers are rewritten
-    RawBatch b;
-    std::vector<u8> sample;
-    if ((rc = lz4f_stage(c, slot, base, blocks, n_blocks, flags, dsrc, &b, &sample))) return rc;
-    SlotCopy v[2];
-    lz4_copies(c, slot, *b.lz4, v);
-    rc = enqueue_deferred(c, slot, b, v, 2, sample.data(), sample.size());
-    if (c->raw_pend == slot) c->lz4f_more = (flags & YSB_LZ4F_MORE) != 0;   // only once the batch is on the device's queue
+    bool staged = false;
+    const int rc = submit_staged(c, slot, [&](RawBatch* b, SlotCopy* v, std::vector<u8>* sample) {
+        const int rs = lz4f_stage(c, slot, base, blocks, n_blocks, flags, dsrc, b, v, sample);
+        staged = !rs;
+        return rs;
+    });
+    // only once the batch is on the device's queue (the slot was claimed, so it is this batch
+    // that is pending there)
+    if (staged && c->raw_pend == slot) c->lz4f_more = (flags & YSB_LZ4F_MORE) != 0;
     return rc;
 }
 
@@ -248,23 +259,23 @@ int ysb_submit_lz4_blocks_mapped(ysb_ctx* c, int slot, const uint8_t* base, cons
 
 // ---- Kafka record batches (ysb_kafka_api.cpp kafka_stage; ysb_kafka.h) ------------------------
 
-// Both Kafka submits: the slot claimed, the batch staged -- the framed bytes (through the slot's
-// pinned buffer or in place from a registered range) and the index are what crosses PCIe --,
-// enqueued like every deferred batch.
+// What the four Kafka submits check in front: a raw batch's arguments, then (mapped) that the
+// bytes lie in a registered range -- *dsrc their device alias there, else NULL.
+static int kafka_args(ysb_ctx* c, int slot, const uint8_t* bytes, u64 nbytes, bool mapped, const u8** dsrc) {
+    *dsrc = nullptr;
+    const int rc = raw_args(c, slot, bytes, nbytes);
+    return !rc && mapped ? mapped_src(c, bytes, nbytes, dsrc) : rc;
+}
+
+// Both Kafka submits: the framed bytes and the index are what crosses PCIe.
 static int submit_kafka(ysb_ctx* c, int slot, const uint8_t* bytes, u64 nbytes, const ysb_kafka_batch* batches, u64 n_batches,
                         bool mapped) {
     if (!c) return YSB_ERR_ARG;
-    int rc = raw_args(c, slot, bytes, nbytes);
     const u8* dsrc = nullptr;
-    if (!rc && mapped) rc = mapped_src(c, bytes, nbytes, &dsrc);
-    if (!rc) rc = claim_slot(c, slot);
-    if (rc) return rc;
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));   // the slot's pinned buffers are rewritten
-    RawBatch b;
-    SlotCopy v[2];
-    std::vector<u8> sample;
-    if ((rc = kafka_stage(c, slot, bytes, nbytes, batches, n_batches, dsrc, &b, v, &sample))) return rc;
-    return enqueue_deferred(c, slot, b, v, 2, sample.data(), sample.size());
+    if (int rc = kafka_args(c, slot, bytes, nbytes, mapped, &dsrc)) return rc;
+    return submit_staged(c, slot, [&](RawBatch* b, SlotCopy* v, std::vector<u8>* sample) {
+        return kafka_stage(c, slot, bytes, nbytes, batches, n_batches, dsrc, b, v, sample);
+    });
 }
 
 int ysb_submit_kafka(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
@@ -284,17 +295,11 @@ static int submit_kafka_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, u64 nbyt
                             const ysb_kafka_frame* frames, u64 n_batches, const ysb_lz4_frame_block* blocks, u64 n_blocks,
                             bool mapped) {
     if (!c) return YSB_ERR_ARG;
-    int rc = raw_args(c, slot, bytes, nbytes);
     const u8* dsrc = nullptr;
-    if (!rc && mapped) rc = mapped_src(c, bytes, nbytes, &dsrc);
-    if (!rc) rc = claim_slot(c, slot);
-    if (rc) return rc;
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));   // the slot's pinned buffers are rewritten
-    RawBatch b;
-    SlotCopy v[2];
-    std::vector<u8> sample;
-    if ((rc = kafka_lz4_stage(c, slot, bytes, nbytes, batches, frames, n_batches, blocks, n_blocks, dsrc, &b, v, &sample))) return rc;
-    return enqueue_deferred(c, slot, b, v, 2, sample.data(), sample.size());
+    if (int rc = kafka_args(c, slot, bytes, nbytes, mapped, &dsrc)) return rc;
+    return submit_staged(c, slot, [&](RawBatch* b, SlotCopy* v, std::vector<u8>* sample) {
+        return kafka_lz4_stage(c, slot, bytes, nbytes, batches, frames, n_batches, blocks, n_blocks, dsrc, b, v, sample);
+    });
 }
 
 int ysb_submit_kafka_lz4(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
@@ -409,7 +414,7 @@ int ysb_submit_raw_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t n
 
 // A compressed batch read in place from a registered range: the union of
 // ysb_submit_raw_lz4's rules and the mapped calls'.  The copy kernel (the DMA engine with
-// YSB_F_H2D_SDMA) reads the blocks where they lie into d_lz4[slot]; the slot's pinned byte
+// YSB_F_H2D_SDMA) reads the blocks where they lie into d_wire[slot]; the slot's pinned byte
 // buffer is not used and the host makes no pass over the bytes (block 0 apart: the layout
 // sample).  d_line_off NULL: the GPU line split; otherwise n device offsets into the decoded batch.
 int ysb_submit_lz4_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t comp_bytes, const ysb_lz4_block* dir,
