@@ -68,34 +68,26 @@ int arrow_params(ysb_ctx* c, const ysb_arrow_cols& A, ArrowCountParams* p) {
 // kernel, the out-of-ring map's fill level for the host.
 int enqueue_arrowcount(ysb_ctx* c, ArrowCountParams& p) {
     if (p.n_rows == 0) { c->batches++; return YSB_OK; }
-    int rc = drain_side_if_due(c);
+    // the batch's device counters, zero (in front of everything the bracket queues)
+    int rc = first_use(c, c->d_arrow_info, 4 * sizeof(unsigned long long));
     if (rc) return rc;
-    if ((rc = first_use(c, c->d_arrow_info, 4 * sizeof(unsigned long long)))) return rc;
-    context_params(c, &p.sp);
-    p.sp.used_out = c->used_pending ? nullptr : c->h_used;
     p.info = c->d_arrow_info;
     HIPCHK(c, hipMemsetAsync(c->d_arrow_info, 0, 4 * sizeof(unsigned long long), c->s_comp));
-    poll_ring(c);
-    if (!c->ring_known) {
+    Launch L;
+    if ((rc = launch_begin(c, &L))) return rc;
+    context_params(c, &p.sp);
+    p.sp.used_out = L.used_out;
+    if (L.base_ring) {
         launch_arrowcount_autobase(p, c->s_comp);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_ring, c->d_ring, 16, hipMemcpyDeviceToHost, c->s_comp));
-        HIPCHK(c, hipEventRecord(c->ev_ring, c->s_comp));
-        c->ring_query_pending = true;
+        if ((rc = launch_ring_based(c))) return rc;
     }
-    Event* te = nullptr;   // YSB_F_TIMING: {before the count, after it, after the launch's last kernel}
-    if (c->cfg.flags & YSB_F_TIMING) {
-        HIPCHK(c, c->tev.acquire(&te));
-        HIPCHK(c, hipEventRecord(te[0], c->s_comp));
-    }
+    if ((rc = launch_mark(c, &L, 0))) return rc;
     ParkParams park;
     launch_arrowcount(p, c->cus, c->s_comp, park_params(c, &park) ? &park : nullptr);
     HIPCHK(c, hipGetLastError());
-    if (te) HIPCHK(c, hipEventRecord(te[1], c->s_comp));
-    launch_arrowcount_level(p, c->s_comp);   // the map's fill level into h_used (sp.used_out)
+    if ((rc = launch_mark(c, &L, 1))) return rc;
+    launch_used_level(p.sp, c->s_comp);   // the map's fill level into h_used (sp.used_out)
     HIPCHK(c, hipGetLastError());
-    if (te) HIPCHK(c, hipEventRecord(te[2], c->s_comp));
-    c->pend_u64 = true;   // this launch counts into the u64 ring
     ysb_arrow_desc& d = c->last_arrow;
     d = ysb_arrow_desc{};
     d.rows = p.n_rows;
@@ -108,12 +100,7 @@ int enqueue_arrowcount(ysb_ctx* c, ArrowCountParams& p) {
     d.lds_counters = p.sp.lds_wl ? 1u : 0u;
     d.hbm_table = p.sp.probe_serial ? 1u : 0u;
     c->arrow_launched = true;
-    if (p.sp.used_out) {   // the map's fill level is on its way into h_used
-        HIPCHK(c, hipEventRecord(c->ev_used, c->s_comp));
-        c->used_pending = true;
-    }
-    c->batches++;
-    return YSB_OK;
+    return launch_end(c, &L, true, 1);
 }
 
 }  // namespace
@@ -219,23 +206,17 @@ int ysb_submit_arrow(ysb_ctx* c, int slot, const ysb_arrow_binding* binding, con
     if (rc) return fail(c, rc, "%s", err.c_str());
     if (plan.total > c->cfg.max_batch_bytes)
         return fail(c, YSB_ERR_CAPACITY, "Arrow batch of %llu B (the rows' bytes) exceeds max_batch_bytes", (unsigned long long)plan.total);
-    if ((rc = launch_pending_raw(c)) || (rc = ensure_slots(c))) return rc;
+    if ((rc = slot_begin(c, slot))) return rc;
     ArrowCountParams p{};   // (checked before anything is copied)
     if ((rc = arrow_params(c, arrow_plan_cols(plan, c->h_bytes[slot]), &p))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    // the slot's previous H2D must be done before its pinned buffer is rewritten
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
     for (const ArrowRange& q : plan.r) std::memcpy(c->h_bytes[slot] + q.dst, q.src, q.bytes);
     // one copy: the ranges are packed back to back (16-byte boundaries)
     SlotCopy v{c->d_bytes[slot], c->hd_bytes[slot], c->h_bytes[slot], plan.total};
-    // ... and the slot's previous kernel before its device buffer is
-    if ((rc = copy_slot_ranges(c, slot, &v, 1))) return rc;
-    HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_h2d[slot], 0));
-    p = ArrowCountParams{};
-    if ((rc = arrow_params(c, arrow_plan_cols(plan, c->d_bytes[slot]), &p))) return rc;
-    if ((rc = enqueue_arrowcount(c, p))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_kdone[slot], c->s_comp));
-    return YSB_OK;
+    return slot_launch(c, slot, &v, 1, [&] {
+        p = ArrowCountParams{};
+        const int re = arrow_params(c, arrow_plan_cols(plan, c->d_bytes[slot]), &p);
+        return re ? re : enqueue_arrowcount(c, p);
+    });
 }
 
 int ysb_arrow_launch_info(ysb_ctx* c, ysb_arrow_desc* out) {

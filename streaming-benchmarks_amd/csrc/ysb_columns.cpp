@@ -127,50 +127,36 @@ static int colcount_args(ysb_ctx* c, const uint8_t* cols, u64 batch_rows, u64 n_
 // count kernel, the out-of-ring map's fill level for the host.
 static int enqueue_colcount(ysb_ctx* c, const u8* d_cols, const ysb_columns_layout& lay, u64 n_rows, u32 flags) {
     if (n_rows == 0) { c->batches++; return YSB_OK; }
-    int rc = drain_side_if_due(c);
+    Launch L;
+    int rc = launch_begin(c, &L);
     if (rc) return rc;
     ColCountParams p{};
     context_params(c, &p.sp);
-    p.sp.used_out = c->used_pending ? nullptr : c->h_used;
+    p.sp.used_out = L.used_out;
     p.cols = d_cols;
     for (int j = 0; j < 8; ++j) p.start[j] = lay.start[j];
     p.n_rows = n_rows;
     p.n_tiles = (n_rows + TILE_LINES - 1) / TILE_LINES;
     p.java_order = (flags & YSB_COL_JAVA_ORDER) ? 1u : 0u;
     p.validity = (flags & YSB_COL_VALIDITY) ? 1u : 0u;
-    poll_ring(c);
-    if (!c->ring_known) {
+    if (L.base_ring) {
         launch_colcount_autobase(p, c->s_comp);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_ring, c->d_ring, 16, hipMemcpyDeviceToHost, c->s_comp));
-        HIPCHK(c, hipEventRecord(c->ev_ring, c->s_comp));
-        c->ring_query_pending = true;
+        if ((rc = launch_ring_based(c))) return rc;
     }
-    Event* te = nullptr;   // YSB_F_TIMING: {before the count, after it, after the launch's last kernel}
-    if (c->cfg.flags & YSB_F_TIMING) {
-        HIPCHK(c, c->tev.acquire(&te));
-        HIPCHK(c, hipEventRecord(te[0], c->s_comp));
-    }
+    if ((rc = launch_mark(c, &L, 0))) return rc;
     ParkParams park;
     launch_colcount(p, c->cus, c->s_comp, park_params(c, &park) ? &park : nullptr);
     HIPCHK(c, hipGetLastError());
-    if (te) HIPCHK(c, hipEventRecord(te[1], c->s_comp));
-    launch_colcount_level(p, c->s_comp);   // the map's fill level into h_used (sp.used_out)
+    if ((rc = launch_mark(c, &L, 1))) return rc;
+    launch_used_level(p.sp, c->s_comp);   // the map's fill level into h_used (sp.used_out)
     HIPCHK(c, hipGetLastError());
-    if (te) HIPCHK(c, hipEventRecord(te[2], c->s_comp));
-    c->pend_u64 = true;   // this launch counts into the u64 ring
     c->last_col.rows = n_rows;
     c->last_col.lds_counters = p.sp.lds_wl ? 1u : 0u;
     c->last_col.hbm_table = p.sp.probe_serial ? 1u : 0u;
     c->last_col.java_order = p.java_order;
     c->last_col.validity = p.validity;
     c->col_launched = true;
-    if (p.sp.used_out) {   // the map's fill level is on its way into h_used
-        HIPCHK(c, hipEventRecord(c->ev_used, c->s_comp));
-        c->used_pending = true;
-    }
-    c->batches++;
-    return YSB_OK;
+    return launch_end(c, &L, true, 1);
 }
 
 int ysb_submit_columns_device(ysb_ctx* c, const uint8_t* d_cols, uint64_t batch_rows, uint64_t n_rows, uint32_t flags) {
@@ -197,10 +183,7 @@ int ysb_submit_columns(ysb_ctx* c, int slot, const uint8_t* image, uint64_t batc
     if (rc) return rc;
     if (total > c->cfg.max_batch_bytes)
         return fail(c, YSB_ERR_CAPACITY, "column batch of %llu B exceeds max_batch_bytes", (unsigned long long)total);
-    if ((rc = launch_pending_raw(c)) || (rc = ensure_slots(c))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    // the slot's previous H2D must be done before its pinned buffer is rewritten
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
+    if ((rc = slot_begin(c, slot))) return rc;
     u64 off[4], len[4];
     u32 nr = 0;
     if ((rc = ysb_columns_read_ranges(batch_rows, n_rows, flags, off, len, &nr))) return fail(c, rc, "bad column ranges");
@@ -209,12 +192,7 @@ int ysb_submit_columns(ysb_ctx* c, int slot, const uint8_t* image, uint64_t batc
         if (image != c->h_bytes[slot] && len[i]) std::memcpy(c->h_bytes[slot] + off[i], image + off[i], len[i]);
         v[i] = {c->d_bytes[slot] + off[i], c->hd_bytes[slot] + off[i], c->h_bytes[slot] + off[i], len[i]};
     }
-    // ... and the slot's previous kernel before its device buffer is
-    if ((rc = copy_slot_ranges(c, slot, v, (int)nr))) return rc;
-    HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_h2d[slot], 0));
-    if ((rc = enqueue_colcount(c, c->d_bytes[slot], lay, n_rows, flags))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_kdone[slot], c->s_comp));
-    return YSB_OK;
+    return slot_launch(c, slot, v, (int)nr, [&] { return enqueue_colcount(c, c->d_bytes[slot], lay, n_rows, flags); });
 }
 
 int ysb_columns_launch_info(ysb_ctx* c, ysb_colcount_desc* out) {

@@ -3,7 +3,7 @@
 // Part of the scan kernel's translation unit: included at the end of ysb_scan.hip, behind
 // ysb_count_columns.h, whose probe (cc_probe_issue / cc_probe_finish) it shares together with
 // the scan's own span_is_view, span_key, parse_digits, parse_digits_regs, load_span, probe,
-// key_hash_dev, count_miss, park_append, global_add, flush_window, flush_tally and div_trunc.
+// key_hash_dev, count_miss, the count tail (cc_count_view), the LDS window, flush_tally and div_trunc.
 //
 // Shape, after colcount_kernel: one-wave workgroups, tiles of 64 rows, lane i takes row i.
 // Rows are not at a fixed stride, so a tile is loaded in two dependent steps, both ahead of its
@@ -311,21 +311,14 @@ void arrowcount_kernel(const ArrowCountParams C, const ParkParams K) {
     const ScanParams& P = C.sp;
     __shared__ __attribute__((aligned(16))) u32 stage[AC_STAGE_DW];
     __shared__ u32 lcnt[LCNT_CAP];
-    __shared__ i64 req64[2];   // rebase requests of the LDS window, double-buffered by tile parity
+    __shared__ i64 req64[2];   // the LDS window's move requests
     const int tid = threadIdx.x;
     u64 t = blockIdx.x;
     if (t >= C.n_tiles) return;
 
-    const i64 ring_lo = P.ring[0];
-    const bool ring_set = P.ring[1] != 0;
-    const u32 WL = P.lds_wl;
-    const u32 ncells = WL ? P.n_campaigns * WL : 0u;
-    for (u32 i = tid; i < ncells; i += SCAN_TPB) lcnt[i] = 0;
-    if (tid < 2) req64[tid] = INT64_MIN;
+    LdsWindow win(P, lcnt, req64);
+    win.init();
     Tally tl{0, 0, 0, 0, 0, 0, 0, 0};
-    i64 lbase = 0;       // the LDS window's base, identical in every lane
-    bool lset = false;
-    u32 tseq = 0;
     u32 inv_null = 0, inv_offs = 0, inv_dict = 0, lane_tiles = 0;
     ArBufs B;
     ar_bufs(C, B);
@@ -342,18 +335,9 @@ void arrowcount_kernel(const ArrowCountParams C, const ParkParams K) {
             if (!C.type_dict) { const uint4 v[1] = {cur.y}; ar_stage<1>(stage, AC_TY_DW, v, cur.yt, cur.ndy, tid); }
             if (!C.time_i64) { const uint4 v[1] = {cur.m}; ar_stage<1>(stage, AC_TM_DW, v, cur.mt, cur.ndm, tid); }
         }
-        // the previous tile asked to move the LDS window: flush it and re-centre (the scan's rule)
-        const int par = (int)(tseq++ & 1);
-        if (WL) {
-            const i64 req = req64[par ^ 1];
-            if (req != INT64_MIN) {
-                if (lset) flush_window(P, lcnt, ncells, WL, lbase, ring_lo, ring_set, tl);
-                lbase = req - (i64)(WL / 2) + 1;
-                lset = true;
-            }
-        }
+        const int par = win.before_barrier(P, tl);
         __syncthreads();
-        if (tid == 0) req64[par ^ 1] = INT64_MIN;   // every lane has read it
+        win.after_barrier(par);
         // ---- rules 2 and 3, the key, the time -------------------------------------------------
         const bool active = (u32)tid < count;
         ArRow r;
@@ -428,35 +412,7 @@ void arrowcount_kernel(const ArrowCountParams C, const ParkParams K) {
                 const int c = probe(P.table, P.table_mask, r.kw, r.klen);
                 if (c >= 0) ci = (u32)c;
             }
-            if (PARK && ci == EMPTY_SLOT &&
-                park_wanted(r.keyed, r.keyed ? key_hash_dev(r.kw, r.klen) : 0u, P.shard_rank, P.shard_n)) {
-                pl.want = true;
-                pl.tok = r.tok;
-#pragma unroll
-                for (int k = 0; k < (int)KEY_WORDS; ++k) pl.kw[k] = r.kw[k];
-                pl.klen = r.klen;
-                pl.tv = r.tv;
-            } else if (ci == EMPTY_SLOT) {
-                count_miss(P, r.kw, r.klen, r.keyed, tl);   // a join miss, or a key of another shard
-            } else {
-                tl.join++;
-                if (!r.tok) {
-                    tl.terr++;   // CampaignProcessorCommon :58: the time is parsed after the join
-                } else {
-                    const i64 bucket = div_trunc(r.tv, P.div);
-                    if (WL) {
-                        const i64 rel = bucket - lbase;
-                        if (lset && rel >= 0 && rel < (i64)WL) {
-                            atomicAdd(&lcnt[(ci << P.lds_wl_log2) + (u32)rel], 1u);
-                        } else {
-                            global_add(P, ring_lo, ring_set, ci, bucket, 1u, tl);
-                            if (!lset || rel >= (i64)WL) atomicMax(reinterpret_cast<long long*>(&req64[par]), (long long)bucket);
-                        }
-                    } else {
-                        global_add(P, ring_lo, ring_set, ci, bucket, 1u, tl);
-                    }
-                }
-            }
+            cc_count_view<PARK>(P, win, par, ci, r.keyed, r.kw, r.klen, r.tok, r.tv, tl, pl);
         }
         if constexpr (PARK) park_append(K, pl, tl);
         __syncthreads();   // the tile's spans are read and its counts are in before the next one
@@ -478,7 +434,7 @@ void arrowcount_kernel(const ArrowCountParams C, const ParkParams K) {
             tile_step(tk, ta[k], tb[k]);
         }
     }
-    if (WL && lset) flush_window(P, lcnt, ncells, WL, lbase, ring_lo, ring_set, tl);
+    win.finish(P, tl);
     flush_tally(P, tl, tid);
     const u32 sums[3] = {wave_sum(inv_null), wave_sum(inv_offs), wave_sum(inv_dict)};
     if (tid == 0) {
@@ -494,7 +450,6 @@ void arrowcount_kernel(const ArrowCountParams C, const ParkParams K) {
 template <bool SERIAL>
 __global__ __launch_bounds__(AUX_TPB) void arrowcount_autobase_kernel(const ArrowCountParams C, i64* ring) {
     const ScanParams& P = C.sp;
-    __shared__ i64 scratch[AUX_TPB / 64];
     if (ring[1] != 0) return;
     const int tid = threadIdx.x;
     const u32 cnt = C.n_rows < (u64)AUX_TPB ? (u32)C.n_rows : (u32)AUX_TPB;
@@ -520,43 +475,18 @@ __global__ __launch_bounds__(AUX_TPB) void arrowcount_autobase_kernel(const Arro
         }
         if (ci != EMPTY_SLOT) b = div_trunc(r.tv, P.div);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const i64 x = __shfl_xor(b, o, 64);
-        b = x < b ? x : b;
-    }
-    if ((tid & 63) == 0) scratch[tid >> 6] = b;
-    __syncthreads();
-    if (tid == 0) {
-        i64 m = scratch[0];
-        for (int w = 1; w < AUX_TPB / 64; ++w) m = scratch[w] < m ? scratch[w] : m;
-        if (m != INT64_MAX) {
-            ring[0] = m - (i64)(P.ring_w / 8);
-            ring[1] = 1;
-        }
-    }
+    commit_ring_base(b, ring, P.ring_w);
 }
 
 u32 arrowcount_resident_grid(int cus) { return (u32)(cus > 0 ? cus : 1) * (u32)AC_WG_PER_CU; }
 
 void launch_arrowcount(const ArrowCountParams& p, int cus, hipStream_t s, const ParkParams* park) {
     if (p.n_rows == 0) return;
-    // whole rounds of resident workgroups over the tiles (each walks tiles blockIdx.x + k * grid)
-    const u64 resident = arrowcount_resident_grid(cus);
-    const dim3 g((u32)(p.n_tiles < resident ? p.n_tiles : resident)), b(SCAN_TPB);
-    if (park) {
-        if (p.sp.probe_serial) hipLaunchKernelGGL((arrowcount_kernel<true, true>), g, b, 0, s, p, *park);
-        else hipLaunchKernelGGL((arrowcount_kernel<false, true>), g, b, 0, s, p, *park);
-    } else {
-        if (p.sp.probe_serial) hipLaunchKernelGGL((arrowcount_kernel<true, false>), g, b, 0, s, p, ParkParams{});
-        else hipLaunchKernelGGL((arrowcount_kernel<false, false>), g, b, 0, s, p, ParkParams{});
-    }
-}
-
-// the out-of-ring map's fill level for the host (what defer_kernel stores after a scan)
-void launch_arrowcount_level(const ArrowCountParams& p, hipStream_t s) {
-    if (p.n_rows == 0 || !p.sp.used_out) return;
-    hipLaunchKernelGGL(colcount_used_kernel, dim3(1), dim3(1), 0, s, p.sp.side_used, p.sp.used_out);
+    const dim3 g = count_grid(p.n_tiles, arrowcount_resident_grid(cus));
+    launch_serial_park(p.sp.probe_serial, park, [&](auto serial, auto parked) {
+        hipLaunchKernelGGL((arrowcount_kernel<decltype(serial)::value, decltype(parked)::value>), g, dim3(SCAN_TPB), 0, s, p,
+                           park ? *park : ParkParams{});
+    });
 }
 
 void launch_arrowcount_autobase(const ArrowCountParams& p, hipStream_t s) {

@@ -5,7 +5,7 @@
 // window-count chain (:115-119) on column contents: no parser, no deferred lines.
 // Part of the scan kernel's translation unit: included at the end of ysb_scan.hip, whose
 // code it shares rather than repeats -- cuckoo_slots36, bucket_find, probe, key_hash_dev,
-// count_miss, global_add, flush_window, flush_tally and div_trunc.
+// count_miss, park_append, the LDS window (LdsWindow, ysb_ring_add.h), flush_tally and div_trunc.
 //
 // It reads three of the seven columns: ad_id (36 B), event_type (4 B), event_time (8 B),
 // 48 B per row, and with YSB_COL_VALIDITY one bitmap word per 64 rows.  The layout cuts
@@ -157,30 +157,59 @@ __device__ __forceinline__ i64 cc_time(u32 t0, u32 t1, u32 java_order) {
     return (i64)(((u64)t1 << 32) | (u64)t0);
 }
 
-// PARK (parking enabled, ysb_parked.h): a view whose ad is in no table is appended to the log K
-// at the tile's park site -- the key and the time are in registers -- instead of being counted
-// as a join miss.
+// A view's join result, counted -- the columnar and the Arrow count's common tail.  The lane
+// brings its campaign ci (EMPTY_SLOT: in no table), its key (keyed false: no possible map key)
+// and Long.parseLong(event_time)'s outcome (tok, tv).  PARK (parking enabled, ysb_parked.h): a
+// view whose ad is in no table is handed to the tile's park site in pl -- the key and the time
+// are in registers -- instead of being counted as a join miss; the kernel calls park_append
+// behind this with every lane of the wave (a view's lane or not).
+template <bool PARK>
+__device__ __forceinline__ void cc_count_view(const ScanParams& P, LdsWindow& win, int par, u32 ci, bool keyed,
+                                              const u32 (&kw)[KEY_WORDS], u32 klen, bool tok, i64 tv, Tally& tl, ParkLane& pl) {
+    if (PARK && ci == EMPTY_SLOT && park_wanted(keyed, keyed ? key_hash_dev(kw, klen) : 0u, P.shard_rank, P.shard_n)) {
+        pl.want = true;
+        pl.tok = tok;
+#pragma unroll
+        for (int k = 0; k < (int)KEY_WORDS; ++k) pl.kw[k] = kw[k];
+        pl.klen = klen;
+        pl.tv = tv;
+    } else if (ci == EMPTY_SLOT) {
+        count_miss(P, kw, klen, keyed, tl);   // a join miss, or a key of another shard
+    } else {
+        tl.join++;
+        if (!tok) tl.terr++;   // CampaignProcessorCommon :58: the time is parsed after the join
+        else win.count(P, par, ci, div_trunc(tv, P.div), tl);
+    }
+}
+
+// One launch of kernel<SERIAL, PARK>: launch(std::bool_constant<SERIAL>, std::bool_constant<PARK>).
+template <class Launch>
+static void launch_serial_park(bool serial, bool park, Launch&& launch) {
+    if (park) {
+        if (serial) launch(std::true_type{}, std::true_type{});
+        else launch(std::false_type{}, std::true_type{});
+    } else {
+        if (serial) launch(std::true_type{}, std::false_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
+}
+// whole rounds of resident workgroups over the tiles (each walks tiles blockIdx.x + k * grid)
+static dim3 count_grid(u64 n_tiles, u64 resident) { return dim3((u32)(n_tiles < resident ? n_tiles : resident)); }
+
 template <bool SERIAL, bool PARK>
 __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu(CC_WG_PER_CU / 4)))
 void colcount_kernel(const ColCountParams C, const ParkParams K) {
     const ScanParams& P = C.sp;
     __shared__ __attribute__((aligned(16))) u32 keys[CC_KEY_DW];
     __shared__ u32 lcnt[LCNT_CAP];
-    __shared__ i64 req64[2];   // rebase requests of the LDS window, double-buffered by tile parity
+    __shared__ i64 req64[2];   // the LDS window's move requests
     const int tid = threadIdx.x;
     u64 t = blockIdx.x;
     if (t >= C.n_tiles) return;
 
-    const i64 ring_lo = P.ring[0];
-    const bool ring_set = P.ring[1] != 0;
-    const u32 WL = P.lds_wl;
-    const u32 ncells = WL ? P.n_campaigns * WL : 0u;
-    for (u32 i = tid; i < ncells; i += SCAN_TPB) lcnt[i] = 0;
-    if (tid < 2) req64[tid] = INT64_MIN;
+    LdsWindow win(P, lcnt, req64);
+    win.init();
     Tally tl{0, 0, 0, 0, 0, 0, 0, 0};
-    i64 lbase = 0;       // the LDS window's base, identical in every lane
-    bool lset = false;
-    u32 tseq = 0;
 
     // One tile: its blocks arrive in pre (issued CC_PF tiles ago); the tile CC_PF ahead is issued
     // into the same registers once these are in LDS.
@@ -195,18 +224,9 @@ void colcount_kernel(const ColCountParams C, const ParkParams K) {
         if ((u32)tid < pre.count * 9u - whole_dw) keys[whole_dw + tid] = pre.ktail;   // (after the zero chunk above)
         const u32 count = pre.count, et = pre.et, t0 = pre.t0, t1 = pre.t1;
         const unsigned long long vw = pre.vw;
-        // the previous tile asked to move the LDS window: flush it and re-centre (the scan's rule)
-        const int par = (int)(tseq++ & 1);
-        if (WL) {
-            const i64 req = req64[par ^ 1];
-            if (req != INT64_MIN) {
-                if (lset) flush_window(P, lcnt, ncells, WL, lbase, ring_lo, ring_set, tl);
-                lbase = req - (i64)(WL / 2) + 1;
-                lset = true;
-            }
-        }
+        const int par = win.before_barrier(P, tl);
         __syncthreads();
-        if (tid == 0) req64[par ^ 1] = INT64_MIN;   // every lane has read it
+        win.after_barrier(par);
         // ---- filter (EventFilterBolt on the cut value), the key, its probe -----------------
         const bool active = (u32)tid < count;
         const bool valid = active && ((vw >> tid) & 1ull);
@@ -236,29 +256,8 @@ void colcount_kernel(const ColCountParams C, const ParkParams K) {
         pl.want = false;
         if (view) {
             const u32 ci = cc_probe_finish<SERIAL>(P, kw, pr);
-            if (PARK && ci == EMPTY_SLOT && park_wanted(true, key_hash_dev(kw, 36u), P.shard_rank, P.shard_n)) {
-                pl.want = pl.tok = true;   // (a column time is an int64 already: no parse to fail)
-#pragma unroll
-                for (int k = 0; k < (int)KEY_WORDS; ++k) pl.kw[k] = kw[k];
-                pl.klen = 36u;
-                pl.tv = cc_time(t0, t1, C.java_order);
-            } else if (ci == EMPTY_SLOT) {
-                count_miss(P, kw, 36u, true, tl);   // a join miss, or a key of another shard
-            } else {
-                tl.join++;
-                const i64 bucket = div_trunc(cc_time(t0, t1, C.java_order), P.div);
-                if (WL) {
-                    const i64 rel = bucket - lbase;
-                    if (lset && rel >= 0 && rel < (i64)WL) {
-                        atomicAdd(&lcnt[(ci << P.lds_wl_log2) + (u32)rel], 1u);
-                    } else {
-                        global_add(P, ring_lo, ring_set, ci, bucket, 1u, tl);
-                        if (!lset || rel >= (i64)WL) atomicMax(reinterpret_cast<long long*>(&req64[par]), (long long)bucket);
-                    }
-                } else {
-                    global_add(P, ring_lo, ring_set, ci, bucket, 1u, tl);
-                }
-            }
+            // (a column time is an int64 already: no parse to fail)
+            cc_count_view<PARK>(P, win, par, ci, true, kw, 36u, true, cc_time(t0, t1, C.java_order), tl, pl);
         }
         if constexpr (PARK) park_append(K, pl, tl);
         __syncthreads();   // the tile's keys are read and its counts are in before the next one
@@ -274,7 +273,7 @@ void colcount_kernel(const ColCountParams C, const ParkParams K) {
             tile_step(tk, pre[k]);
         }
     }
-    if (WL && lset) flush_window(P, lcnt, ncells, WL, lbase, ring_lo, ring_set, tl);
+    win.finish(P, tl);
     flush_tally(P, tl, tid);
 }
 
@@ -283,7 +282,6 @@ void colcount_kernel(const ColCountParams C, const ParkParams K) {
 template <bool SERIAL>
 __global__ __launch_bounds__(AUX_TPB) void colcount_autobase_kernel(const ColCountParams C, i64* ring) {
     const ScanParams& P = C.sp;
-    __shared__ i64 scratch[AUX_TPB / 64];
     if (ring[1] != 0) return;
     const int tid = threadIdx.x;
     i64 b = INT64_MAX;
@@ -306,21 +304,7 @@ __global__ __launch_bounds__(AUX_TPB) void colcount_autobase_kernel(const ColCou
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const i64 x = __shfl_xor(b, o, 64);
-        b = x < b ? x : b;
-    }
-    if ((tid & 63) == 0) scratch[tid >> 6] = b;
-    __syncthreads();
-    if (tid == 0) {
-        i64 r = scratch[0];
-        for (int w = 1; w < AUX_TPB / 64; ++w) r = scratch[w] < r ? scratch[w] : r;
-        if (r != INT64_MAX) {
-            ring[0] = r - (i64)(P.ring_w / 8);
-            ring[1] = 1;
-        }
-    }
+    commit_ring_base(b, ring, P.ring_w);
 }
 
 // The out-of-ring map's fill level after the launch, for the host (what defer_kernel stores
@@ -329,21 +313,16 @@ __global__ void colcount_used_kernel(const u32* side_used, u32* used_out) { *use
 
 void launch_colcount(const ColCountParams& p, int cus, hipStream_t s, const ParkParams* park) {
     if (p.n_rows == 0) return;
-    // whole rounds of resident workgroups over the tiles (each walks tiles blockIdx.x + k * grid)
-    const u64 resident = (u64)(cus > 0 ? cus : 1) * (u64)CC_WG_PER_CU;
-    const dim3 g((u32)(p.n_tiles < resident ? p.n_tiles : resident)), b(SCAN_TPB);
-    if (park) {
-        if (p.sp.probe_serial) hipLaunchKernelGGL((colcount_kernel<true, true>), g, b, 0, s, p, *park);
-        else hipLaunchKernelGGL((colcount_kernel<false, true>), g, b, 0, s, p, *park);
-    } else {
-        if (p.sp.probe_serial) hipLaunchKernelGGL((colcount_kernel<true, false>), g, b, 0, s, p, ParkParams{});
-        else hipLaunchKernelGGL((colcount_kernel<false, false>), g, b, 0, s, p, ParkParams{});
-    }
+    const dim3 g = count_grid(p.n_tiles, (u64)(cus > 0 ? cus : 1) * (u64)CC_WG_PER_CU);
+    launch_serial_park(p.sp.probe_serial, park, [&](auto serial, auto parked) {
+        hipLaunchKernelGGL((colcount_kernel<decltype(serial)::value, decltype(parked)::value>), g, dim3(SCAN_TPB), 0, s, p,
+                           park ? *park : ParkParams{});
+    });
 }
 
-void launch_colcount_level(const ColCountParams& p, hipStream_t s) {
-    if (p.n_rows == 0 || !p.sp.used_out) return;
-    hipLaunchKernelGGL(colcount_used_kernel, dim3(1), dim3(1), 0, s, p.sp.side_used, p.sp.used_out);
+void launch_used_level(const ScanParams& sp, hipStream_t s) {
+    if (!sp.used_out) return;
+    hipLaunchKernelGGL(colcount_used_kernel, dim3(1), dim3(1), 0, s, sp.side_used, sp.used_out);
 }
 
 void launch_colcount_autobase(const ColCountParams& p, hipStream_t s) {

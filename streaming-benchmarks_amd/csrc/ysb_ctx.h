@@ -552,6 +552,38 @@ YSB_INTERNAL int copy_slot_ranges(ysb_ctx* c, int slot, const SlotCopy* v, int n
 YSB_INTERNAL int drain_side_if_due(ysb_ctx* c);
 // the context's join tables, ring, out-of-ring map and stats as a launch's parameters (no batch)
 YSB_INTERNAL void context_params(ysb_ctx* c, ScanParams* out);
+// The bracket of one counting launch on the compute stream, whatever its front end (enqueue_scan,
+// the columnar count, the Arrow count), in this order:
+//   launch_begin      the out-of-ring map emptied if it is due; L->used_out for the parameters'
+//                     used_out; whether the ring still needs its base (L->base_ring)
+//   launch_ring_based if so, behind the caller's auto-base kernel: the base on its way to the host
+//   launch_mark 0     YSB_F_TIMING's {before the main kernel, after it, after the launch's last kernel}
+//   the caller's main kernel, launch_mark 1, its level / deferred-line / record kernels
+//   launch_end        mark 2, the fill level's event, the launch accounted
+struct Launch {
+    u32* used_out = nullptr;   // where the launch's last kernel stores the map's fill level; NULL: an earlier one is unread
+    bool base_ring = false;
+    Event* te = nullptr;
+};
+YSB_INTERNAL int launch_begin(ysb_ctx* c, Launch* L);
+YSB_INTERNAL int launch_ring_based(ysb_ctx* c);
+YSB_INTERNAL int launch_mark(ysb_ctx* c, Launch* L, int k);
+// u64_ring: the launch counts into the u64 ring; batches: the batches it carried
+YSB_INTERNAL int launch_end(ysb_ctx* c, Launch* L, bool u64_ring, u64 batches);
+// A slot submit's two shared pieces.  slot_begin: the pending batch launches first (batches launch
+// in submission order), the slots exist, the device is current, and the slot's previous H2D is
+// done -- its pinned buffers may be rewritten.  slot_launch: the slot's copies, the compute stream
+// behind them, the caller's enqueue, and the event that frees the slot's device buffers.
+YSB_INTERNAL int slot_begin(ysb_ctx* c, int slot);
+extern "C++" template <class Enqueue>
+int slot_launch(ysb_ctx* c, int slot, const SlotCopy* v, int n, Enqueue enqueue) {
+    int rc = copy_slot_ranges(c, slot, v, n);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_h2d[slot], 0));
+    if ((rc = enqueue())) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_kdone[slot], c->s_comp));
+    return YSB_OK;
+}
 // ysb_raw.cpp
 YSB_INTERNAL int launch_pending_raw(ysb_ctx* c); // the raw batch awaiting its launch
 // ysb_parked_api.cpp

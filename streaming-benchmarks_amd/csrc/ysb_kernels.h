@@ -289,8 +289,9 @@ struct ColCountParams {
     u32 validity;               // 1: rows with a zero validity bit are parse errors (YSB_COL_VALIDITY)
 };
 void launch_colcount(const ColCountParams& p, int cus, hipStream_t s, const ParkParams* park = nullptr);   // park: as launch_defer's
-// Right behind it: *sp.used_out <- the out-of-ring map's fill level (nothing if used_out is null).
-void launch_colcount_level(const ColCountParams& p, hipStream_t s);
+// Right behind it or launch_arrowcount: *sp.used_out <- the out-of-ring map's fill level (nothing
+// if used_out is null).
+void launch_used_level(const ScanParams& sp, hipStream_t s);
 // Sets ring[0..1] from the batch's first 256 rows if ring[1] == 0 (launch_ring_autobase's rule).
 void launch_colcount_autobase(const ColCountParams& p, hipStream_t s);
 
@@ -340,8 +341,6 @@ struct ArrowCountParams {
     unsigned long long* info;
 };
 void launch_arrowcount(const ArrowCountParams& p, int cus, hipStream_t s, const ParkParams* park = nullptr);
-// Right behind it: *sp.used_out <- the out-of-ring map's fill level (nothing if used_out is null).
-void launch_arrowcount_level(const ArrowCountParams& p, hipStream_t s);
 // Sets ring[0..1] from the batch's first 256 rows if ring[1] == 0 (launch_ring_autobase's rule).
 void launch_arrowcount_autobase(const ArrowCountParams& p, hipStream_t s);
 // the largest grid launch_arrowcount takes on a device of `cus` compute units

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ysb_common.h"
+#include "ysb_window.h"
 
 namespace ysb {
 
@@ -84,8 +85,8 @@ YSB_HD u32 park_resolve_class(bool found, bool time_ok) {
     return !found ? (u32)PARK_R_MISS : time_ok ? (u32)PARK_R_COUNT : (u32)PARK_R_TIME_ERR;
 }
 // The ring base a resolve fixes when no batch has fixed one: the smallest bucket among the
-// records it counts, minus W / 8 (ring_autobase_kernel's rule).
-YSB_HD i64 park_ring_base(i64 min_bucket, u32 ring_w) { return min_bucket - (i64)(ring_w / 8); }
+// records it counts, under the auto-base kernels' rule (ysb_window.h).
+YSB_HD i64 park_ring_base(i64 min_bucket, u32 ring_w) { return ring_base_for(min_bucket, ring_w); }
 
 // ---- host model --------------------------------------------------------------------------
 // The cycle on plain host data: miss() is the park site, distinct() the distinct kernel,

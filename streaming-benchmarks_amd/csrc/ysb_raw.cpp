@@ -44,8 +44,12 @@ static int ensure_raw(ysb_ctx* c) {
 int launch_pending_raw(ysb_ctx* c) {
     if (c->raw_fail) return fail(c, c->raw_fail, "%s", c->raw_fail_msg.c_str());
     if (c->raw_pend < 0) return YSB_OK;
+    // the batch is taken before anything is done with it: nothing called below finds it pending
+    // again (enqueue_scan empties a due out-of-ring map through sync_streams, which comes here)
     const int slot = c->raw_pend;
-    const RawBatch& b = c->raw[slot];
+    const RawBatch b = std::move(c->raw[slot]);
+    c->raw_pend = -1;
+    c->raw[slot] = RawBatch{};
     // the decoded bytes: a plain batch's as submitted; counted on the device for a frame or a
     // Kafka batch, whose settle step reads them from the pinned head that came back with the split's count
     u64 nbytes = b.nbytes;
@@ -71,8 +75,6 @@ int launch_pending_raw(ysb_ctx* c) {
     // the slot's device buffers are free again once this launch (or nothing) has run
     if (hipEventRecord(c->ev_kdone[slot], c->s_comp) != hipSuccess && !rc)
         rc = fail(c, YSB_ERR_HIP, "hipEventRecord failed");
-    c->raw_pend = -1;
-    c->raw[slot] = RawBatch{};
     if (rc) {
         c->raw_fail = rc;
         c->raw_fail_msg = c->err;
@@ -448,23 +450,18 @@ int ysb_submit_mapped(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbyte
     const u8* dsrc = nullptr;
     if ((rc = mapped_src(c, bytes, nbytes, &dsrc)) || (rc = rebase_args(c, rb, &n))) return rc;
     if (!n) return YSB_OK;
-    rc = launch_pending_raw(c);   // batches launch in submission order
-    if (!rc) rc = ensure_slots(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     // at most two copies in flight: the slot's previous one must be done (its device buffer is
     // then only still read by its scan, which the copy waits for on the device)
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
+    if ((rc = slot_begin(c, slot))) return rc;
     Layout lay;
     sampled_layout(c, bytes, nbytes, &lay);
     const SlotCopy v{c->d_bytes[slot], dsrc, bytes, nbytes};
-    if ((rc = copy_slot_ranges(c, slot, &v, 1))) return rc;
-    HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_h2d[slot], 0));
-    if (rb && (rc = rebase_lines(c, slot, nbytes, d_line_off, n, *rb, c->s_comp))) return rc;
-    const ysb_segment sg{c->d_bytes[slot], nbytes, d_line_off, n};
-    if ((rc = enqueue_scan(c, &sg, 1, lay))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_kdone[slot], c->s_comp));
-    return YSB_OK;
+    return slot_launch(c, slot, &v, 1, [&] {
+        if (rb)
+            if (const int rr = rebase_lines(c, slot, nbytes, d_line_off, n, *rb, c->s_comp)) return rr;
+        const ysb_segment sg{c->d_bytes[slot], nbytes, d_line_off, n};
+        return enqueue_scan(c, &sg, 1, lay);
+    });
 }
 
 int ysb_split_lines_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, uint32_t* d_off, uint64_t cap,

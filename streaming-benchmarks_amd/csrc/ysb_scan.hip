@@ -48,9 +48,7 @@
 #ifndef YSB_DIAG_NO_REC
 #define YSB_DIAG_NO_REC 0      // record mode: views parsed, never staged
 #endif
-#ifndef YSB_DIAG_NO_FLUSH
-#define YSB_DIAG_NO_FLUSH 0    // LDS window counters never flushed to the ring
-#endif
+// (YSB_DIAG_NO_FLUSH, LDS window counters never flushed to the ring: ysb_ring_add.h)
 #ifndef YSB_DIAG_FLAT_IDX
 #define YSB_DIAG_FLAT_IDX 0    // layout 2: the structural index's classification only (round 6)
 #endif
@@ -59,7 +57,7 @@ namespace ysb {
 
 constexpr bool DIAG_A_ONLY = YSB_DIAG_A_ONLY, DIAG_NO_PROBE = YSB_DIAG_NO_PROBE,
                DIAG_NO_PROBE2 = YSB_DIAG_NO_PROBE2, DIAG_NO_COUNT = YSB_DIAG_NO_COUNT,
-               DIAG_NO_REC = YSB_DIAG_NO_REC, DIAG_NO_FLUSH = YSB_DIAG_NO_FLUSH,
+               DIAG_NO_REC = YSB_DIAG_NO_REC,
                DIAG_FLAT_IDX = YSB_DIAG_FLAT_IDX;
 
 // Key ids (bit masks) of the fields DeserializeBolt reads.
@@ -538,19 +536,6 @@ __device__ __forceinline__ void defer_append(const ScanParams& P, bool dfr, u64 
     }
 }
 
-// LDS window counters: flush every non-zero cell of the window at lbase to the ring.
-__device__ __forceinline__ void flush_window(const ScanParams& P, u32* lcnt, u32 ncells, u32 WL, i64 lbase,
-                                             i64 ring_lo, bool ring_set, Tally& tl) {
-    for (u32 i = threadIdx.x; i < ncells; i += SCAN_TPB) {
-        const u32 v = lcnt[i];
-        if (v) {
-            lcnt[i] = 0;
-            if constexpr (!DIAG_NO_FLUSH)
-                global_add(P, ring_lo, ring_set, i >> P.lds_wl_log2, lbase + (i64)(i & (WL - 1)), v, tl);
-        }
-    }
-}
-
 #ifdef YSB_STAMPS
 // Diagnostic build only: wave-level s_memtime phase accounting (cdna_hip_programming.md
 // section 7, "In-kernel stamps").  The values go to P.dbg, never into results.
@@ -611,7 +596,7 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu((Geom<
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     u32* tile32 = reinterpret_cast<u32*>(smem + G::OFF_TILE);
     u32* lcnt = reinterpret_cast<u32*>(smem + G::OFF_LCNT);
-    i64* misc64 = reinterpret_cast<i64*>(smem + G::OFF_MISC);   // [0] lbase, [1] lset, [2..5] scratch
+    i64* misc64 = reinterpret_cast<i64*>(smem + G::OFF_MISC);   // [0..1] the window's move requests (REC: rcur)
     u32* tb = reinterpret_cast<u32*>(smem + G::OFF_TB);
     // the flat tier's key table past the geometry's LDS (layouts 2-4 launch with KEYTAB_BYTES more)
     u32* keytab = reinterpret_cast<u32*>(smem + G::LDS);
@@ -640,7 +625,7 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu((Geom<
     u32* rcur = reinterpret_cast<u32*>(misc64);
     u32 gcur = 0;
     if (REC && tid < REC_BINS_MAX) rcur[tid] = 0;
-    // rebase requests of the LDS window (double-buffered by tile parity): the largest
+    // move requests of the LDS window (double-buffered by tile parity): the largest
     // bucket that fell ahead of the window, INT64_MIN = none
     if (!REC && tid < 2) misc64[tid] = INT64_MIN;
 
@@ -695,7 +680,7 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu((Geom<
             const i64 req = misc64[par ^ 1];
             if (req != INT64_MIN) {
                 if (lset) flush_window(P, lcnt, ncells, WL, lbase, ring_lo, ring_set, tl);
-                lbase = req - (i64)(WL / 2) + 1;
+                lbase = window_base_for(req, WL);
                 lset = true;
             }
         }
@@ -922,11 +907,11 @@ __global__ __launch_bounds__(SCAN_TPB) __attribute__((amdgpu_waves_per_eu((Geom<
         if (WL) {
             if (valid) {
                 const i64 rel = bucket - lbase;
-                if (lset && rel >= 0 && rel < (i64)WL) {
+                if (window_holds(lset, rel, WL)) {
                     atomicAdd(&lcnt[(campaign << P.lds_wl_log2) + (u32)rel], 1u);
                 } else {
                     global_add(P, ring_lo, ring_set, campaign, bucket, 1u, tl);
-                    if (!lset || rel >= (i64)WL) atomicMax(reinterpret_cast<long long*>(&misc64[par]), (long long)bucket);
+                    if (window_asks_move(lset, rel, WL)) atomicMax(reinterpret_cast<long long*>(&misc64[par]), (long long)bucket);
                 }
             }
         } else if (valid && !DIAG_NO_COUNT) {
@@ -1231,7 +1216,6 @@ __global__ __launch_bounds__(DEFER_TPB) void defer_kernel(const ScanParams P0, c
 // fixes the ring at min bucket - W/8 (room for out-of-order / late events).  TBL: .tbl rows.
 template <bool TBL>
 __global__ __launch_bounds__(AUX_TPB) void ring_autobase_kernel(ScanParams P, i64* ring) {
-    __shared__ i64 scratch[AUX_TPB / 64];
     if (ring[1] != 0) return;
     const int tid = threadIdx.x;
     i64 b = INT64_MAX;
@@ -1245,21 +1229,7 @@ __global__ __launch_bounds__(AUX_TPB) void ring_autobase_kernel(ScanParams P, i6
                             : process_line(gsrc, 0, (int)(le - ls), P, tl, c, bk);
         if (ok) b = bk;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const i64 x = __shfl_xor(b, o, 64);
-        b = x < b ? x : b;
-    }
-    if ((tid & 63) == 0) scratch[tid >> 6] = b;
-    __syncthreads();
-    if (tid == 0) {
-        i64 r = scratch[0];
-        for (int w = 1; w < AUX_TPB / 64; ++w) r = scratch[w] < r ? scratch[w] : r;
-        if (r != INT64_MAX) {
-            ring[0] = r - (i64)(P.ring_w / 8);
-            ring[1] = 1;
-        }
-    }
+    commit_ring_base(b, ring, P.ring_w);
 }
 
 // One scan launch: the instantiation of the probe / record mode for the batch's format and

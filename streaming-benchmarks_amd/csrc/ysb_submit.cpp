@@ -189,6 +189,43 @@ void context_params(ysb_ctx* c, ScanParams* out) {
     *out = make_params(c, &none, 1, Layout{});
 }
 
+// ---- the bracket of a counting launch (ysb_ctx.h) ----------------------------------------------
+
+int launch_begin(ysb_ctx* c, Launch* L) {
+    const int rc = drain_side_if_due(c);
+    if (rc) return rc;
+    L->used_out = c->used_pending ? nullptr : c->h_used.get();
+    poll_ring(c);
+    L->base_ring = !c->ring_known;
+    return YSB_OK;
+}
+
+int launch_ring_based(ysb_ctx* c) {
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->h_ring, c->d_ring, 16, hipMemcpyDeviceToHost, c->s_comp));
+    HIPCHK(c, hipEventRecord(c->ev_ring, c->s_comp));
+    c->ring_query_pending = true;
+    return YSB_OK;
+}
+
+int launch_mark(ysb_ctx* c, Launch* L, int k) {
+    if (!(c->cfg.flags & YSB_F_TIMING)) return YSB_OK;
+    if (k == 0) HIPCHK(c, c->tev.acquire(&L->te));
+    HIPCHK(c, hipEventRecord(L->te[k], c->s_comp));
+    return YSB_OK;
+}
+
+int launch_end(ysb_ctx* c, Launch* L, bool u64_ring, u64 batches) {
+    if (const int rc = launch_mark(c, L, 2)) return rc;
+    if (u64_ring) c->pend_u64 = true;
+    if (L->used_out) {   // the launch's last kernel wrote the map's fill level into h_used
+        HIPCHK(c, hipEventRecord(c->ev_used, c->s_comp));
+        c->used_pending = true;
+    }
+    c->batches += batches;
+    return YSB_OK;
+}
+
 int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout& lay) {
     if (!c->table_loaded) return fail(c, YSB_ERR_STATE, "ysb_load_ad_map has not been called");
     ysb_segment segs[MAX_SEGS];
@@ -205,9 +242,10 @@ int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout& lay) 
         HIPCHK(c, c->d_defer_ctr.alloc(16 + 4 * MAX_SEGS));
         HIPCHK(c, hipMemset(c->d_defer_ctr, 0, 16 + 4 * MAX_SEGS));
     }
-    if ((rc = drain_side_if_due(c))) return rc;
+    Launch L;
+    if ((rc = launch_begin(c, &L))) return rc;
     ScanParams p = make_params(c, segs, nseg, lay);
-    p.used_out = c->used_pending ? nullptr : c->h_used;
+    p.used_out = L.used_out;
     p.defer = c->d_defer;
     p.defer_count = c->d_defer_ctr;
     p.defer_done = c->d_defer_ctr + 1;
@@ -222,32 +260,23 @@ int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout& lay) 
     }
     p.dbg = c->d_dbg;
 #endif
-    poll_ring(c);
-    if (!c->ring_known) {
+    if (L.base_ring) {
         launch_ring_autobase(p, c->s_comp);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_ring, c->d_ring, 16, hipMemcpyDeviceToHost, c->s_comp));
-        HIPCHK(c, hipEventRecord(c->ev_ring, c->s_comp));
-        c->ring_query_pending = true;
+        if ((rc = launch_ring_based(c))) return rc;
     }
     // dynamic claims (off by default) count from zero in every launch
     if (p.dyn_chunk) HIPCHK(c, hipMemsetAsync(p.dyn_ctr, 0, 4 * MAX_SEGS, c->s_comp));
     RecParams rp{};
     if ((rc = plan_records(c, p, n, rp))) return rc;
-    Event* te = nullptr;   // YSB_F_TIMING: {before the scan, after it, after the launch's last kernel}
-    if (c->cfg.flags & YSB_F_TIMING) {
-        HIPCHK(c, c->tev.acquire(&te));
-        HIPCHK(c, hipEventRecord(te[0], c->s_comp));
-    }
+    if ((rc = launch_mark(c, &L, 0))) return rc;
     launch_scan(p, c->s_comp);
     HIPCHK(c, hipGetLastError());
-    if (!p.rec_on) c->pend_u64 = true;   // this launch counts into the u64 ring
     // (launch_scan: the layout instantiations exist for every JSON table layout)
     c->last_launch.layout = p.tbl ? 0u : p.layout;
     c->last_launch.record_mode = p.rec_on ? 1u : 0u;
     c->last_launch.hbm_table = p.probe_serial ? 1u : 0u;
     c->last_launch.tbl = p.tbl ? 1u : 0u;
-    if (te) HIPCHK(c, hipEventRecord(te[1], c->s_comp));
+    if ((rc = launch_mark(c, &L, 1))) return rc;
     ParkParams park;
     launch_defer(p, c->cus, c->s_comp, park_params(c, &park) ? &park : nullptr);
     HIPCHK(c, hipGetLastError());
@@ -258,13 +287,8 @@ int enqueue_scan(ysb_ctx* c, const ysb_segment* in, u32 nin, const Layout& lay) 
         HIPCHK(c, hipGetLastError());
         c->rec_launches++;
     }
-    if (te) HIPCHK(c, hipEventRecord(te[2], c->s_comp));
-    if (p.used_out) {   // defer_kernel wrote the map's fill level into h_used
-        HIPCHK(c, hipEventRecord(c->ev_used, c->s_comp));
-        c->used_pending = true;
-    }
-    c->batches += nin;   // each segment counts as the batch it is
-    return YSB_OK;
+    // (record mode counts into the delta ring; each segment counts as the batch it is)
+    return launch_end(c, &L, !p.rec_on, nin);
 }
 
 // Whether batches pick the scan instantiation from their first line (the default): not
@@ -416,6 +440,15 @@ int copy_slot_ranges(ysb_ctx* c, int slot, const SlotCopy* v, int n) {
     return YSB_OK;
 }
 
+int slot_begin(ysb_ctx* c, int slot) {
+    int rc = launch_pending_raw(c);
+    if (!rc) rc = ensure_slots(c);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
+    return YSB_OK;
+}
+
 int ysb_slot_buffers(ysb_ctx* c, int slot, uint8_t** bytes, uint32_t** line_off) {
     if (!c) return YSB_ERR_ARG;
     int rc = slot_arg(c, slot);
@@ -435,19 +468,11 @@ int ysb_submit(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, cons
                     (unsigned long long)nbytes, (unsigned long long)n);
     if ((nbytes && !bytes) || (n && !line_off)) return fail(c, YSB_ERR_ARG, "NULL batch buffers");
     if (int g = carry_guard(c)) return g;
-    int rc = launch_pending_raw(c);   // batches launch in submission order
-    if (!rc) rc = ensure_slots(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    // the slot's previous H2D must be done before its pinned buffers are rewritten
-    HIPCHK(c, hipEventSynchronize(c->ev_h2d[slot]));
+    if (int rc = slot_begin(c, slot)) return rc;
     if (bytes != c->h_bytes[slot] && nbytes) std::memcpy(c->h_bytes[slot], bytes, nbytes);
     if (line_off != c->h_off[slot] && n) std::memcpy(c->h_off[slot], line_off, n * 4);
-    // ... and the slot's previous kernel must be done before its device buffers are
     const SlotCopy v[2] = {{c->d_bytes[slot], c->hd_bytes[slot], c->h_bytes[slot], nbytes},
                            {c->d_off[slot], c->hd_off[slot], c->h_off[slot], n * 4}};
-    if ((rc = copy_slot_ranges(c, slot, v, 2))) return rc;
-    HIPCHK(c, hipStreamWaitEvent(c->s_comp, c->ev_h2d[slot], 0));
     const ysb_segment sg{c->d_bytes[slot], nbytes, c->d_off[slot], n};
     // the scan instantiation named by the batch's first line, which the host holds in the
     // pinned slot (counts are the same whichever runs)
@@ -455,9 +480,7 @@ int ysb_submit(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, cons
     if (layout_sampling(c) && n)
         lay.layout = hinted_layout(flat_first(c), sniff_layout(require_mask(c), c->h_bytes[slot], nbytes,
                                                                c->h_off[slot], n, &lay.learn));
-    if ((rc = enqueue_scan(c, &sg, 1, lay))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_kdone[slot], c->s_comp));
-    return YSB_OK;
+    return slot_launch(c, slot, v, 2, [&] { return enqueue_scan(c, &sg, 1, lay); });
 }
 
 int ysb_wait(ysb_ctx* c, int slot) {

@@ -9,7 +9,7 @@ import pytest
 
 import golden_data as gd
 from oracle import dostats, oracle
-from ysb_amd import GEN_COMPACT, GEN_REORDER, GenParams, YsbContext
+from ysb_amd import GEN_COMPACT, GEN_REORDER, GenParams, YsbContext, device_sync
 from test_gpu_parity import check_against, make_ctx
 
 pytestmark = pytest.mark.gpu
@@ -348,3 +348,32 @@ def test_raw_batch_over_its_line_capacity_is_a_sticky_error():
         ctx.reset()
         ctx.submit_raw(raw, slot=1)
         check_against(ctx, *gd.expected("gen_s7"))
+
+
+def test_a_due_out_of_ring_map_does_not_launch_the_pending_batch_twice():
+    """A deferred batch whose launch finds the out-of-ring map a quarter full: the launch empties
+    the map first, which waits for every stream and, on its way, launches "the pending batch" --
+    the very batch being launched, unless it was taken off the context first.  Five raw batches of
+    20 views, every view in a cell of its own outside the ring, in a map of 64 slots (due at more
+    than 16 used): each cell is counted once."""
+    ads, _ = gd.ad_arrays()
+    camp = [i % 200 for i in range(len(ads))]
+    batches = []
+    for s in range(5):
+        lines = [b'{"user_id":"x","page_id":"x","ad_id":"' + ads[(20 * s + r) % len(ads)].encode() +
+                 b'","ad_type":"x","event_type":"view","event_time":"' + str((1000 + 20 * s + r) * 10000 + r).encode() + b'"}\n'
+                 for r in range(20)]
+        batches.append(b"".join(lines))
+    whole = b"".join(batches)
+    want, wst = oracle.run(oracle.AdMap(ads, camp), whole, dostats.split_lines(whole)[1])
+    assert len(want) == 100 and set(want.values()) == {1} and wst["joined"] == 100
+    assert {b for _, b in want} == set(range(1000, 1100))
+    with YsbContext(n_campaigns=200, window_ring=16, ring_base_bucket=0, overflow_capacity=32) as c:
+        c.load_ad_map(ads, camp)
+        for s, raw in enumerate(batches):
+            c.submit_raw(np.frombuffer(raw, dtype=np.uint8), slot=s & 1)
+            device_sync(c.device)   # not ysb_sync: only the submits themselves may empty the map
+        got, st = c.drain_buckets(), c.stats()
+    assert got == want
+    assert st["events"] == st["views"] == st["joined"] == st["out_of_ring"] == 100
+    assert st["batches"] == 5 and st["overflow_dropped"] == 0
