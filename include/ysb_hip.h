@@ -724,7 +724,9 @@ uint64_t    ysb_lz4_frame_desc_size(void);   /* sizeof(ysb_lz4_frame_desc) */
  * message naming the byte offset, the field, its value and the rule, for: a magic other than 2
  * (message formats v0 / v1), a codec other than 0 (compressed batches), batchLength < 49, a
  * negative recordsCount and, with YSB_KAFKA_CHECK_CRC, a CRC-32C mismatch (verified on the host,
- * in software: a pass over the bytes, so off by default).  YSB_ERR_CAPACITY with info complete
+ * in software: a pass over the bytes, so off by default; YSB_KAFKA_CHECK_CRC_CONTROL verifies only
+ * the control batches the index skips -- with ysb_kafka_set_crc's device check of the indexed
+ * batches, every byte a check.crcs=true consumer verifies).  YSB_ERR_CAPACITY with info complete
  * when cap is short (batches may be NULL with cap 0 to count).  No context: the message is the
  * thread's (ysb_last_error(NULL)). */
 typedef struct ysb_kafka_batch {
@@ -744,6 +746,7 @@ typedef struct ysb_kafka_summary {
     uint64_t crc_checked;     /* batches whose CRC-32C was verified             */
 } ysb_kafka_summary;
 #define YSB_KAFKA_CHECK_CRC 1u
+#define YSB_KAFKA_CHECK_CRC_CONTROL 2u
 int         ysb_kafka_index(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, ysb_kafka_batch* batches,
                             uint64_t cap, ysb_kafka_summary* info);
 uint32_t    ysb_kafka_crc32c(const uint8_t* bytes, uint64_t nbytes);   /* "123456789" -> 0xE3069283 */
@@ -753,7 +756,10 @@ uint32_t    ysb_kafka_crc32c(const uint8_t* bytes, uint64_t nbytes);   /* "12345
  * do not end exactly at the record's end (or a negative count / header key length), 7 the walk
  * does not yield exactly recordsCount records ending exactly at the batch's end (record: where
  * it stopped), 8 (compressed batches only, below) a block of the batch's LZ4 frame does not
- * decode (record: the block).  The verdict names the smallest bad batch and its smallest bad record. */
+ * decode (record: the block), 9 (only where the CRC is checked: ysb_kafka_set_crc,
+ * ysb_kafka_verdict_crc_host) the batch's CRC-32C differs from the stored one (record 0; it comes
+ * first: no record of such a batch is looked at).  The verdict names the smallest bad batch and
+ * its smallest bad record. */
 typedef struct ysb_kafka_verdict {
     uint32_t bad_batches;
     uint32_t first_bad;       /* index entry; 0xFFFFFFFF: none */
@@ -865,6 +871,50 @@ uint64_t    ysb_kafka_verdict_size(void);
 uint64_t    ysb_kafka_counters_size(void);
 uint64_t    ysb_kafka_pack_opts_size(void);
 uint64_t    ysb_kafka_desc_size(void);
+/* ---- Kafka record batches: CRC-32C on the GPU (additive within ABI 6) -----------------------
+ * What a consumer with check.crcs=true does before it reads a record, on the device, where the
+ * bytes already are: one launch behind the walk (and the codec verdict) and in front of the scan
+ * of the batches' totals verifies every indexed batch -- the range [records_off - 40, records_off
+ * + records_bytes) against the big-endian word at records_off - 44; on the compressed path the
+ * wire bytes.  A batch whose CRC differs is bad by rule 9, whatever the walk or the decoder made
+ * of its bytes.  Only the 16-byte vectors that hold [records_off - 44, records_off +
+ * records_bytes) are loaded.
+ * ysb_kafka_set_crc: YSB_KAFKA_CRC_OFF (the default: no launch, no memory) or _DEVICE (anything
+ * else: YSB_ERR_ARG).  A context setting, kept across ysb_reset; a slot batch is verified by the
+ * mode in force when it was submitted.  With the mode on, ysb_submit_kafka, _mapped, _lz4,
+ * _lz4_mapped, ysb_kafka_unframe_device and _lz4_device verify, and YSB_ERR_ARG for an index
+ * entry with records_off < 44.  The sticky YSB_ERR_FORMAT of a dropped slot batch names the
+ * Kafka batch, its baseOffset and the stored and the computed value. */
+#define YSB_KAFKA_CRC_OFF 0
+#define YSB_KAFKA_CRC_DEVICE 1
+int         ysb_kafka_set_crc(ysb_ctx* ctx, int mode);
+/* The kernel alone, synchronously, whatever the mode: computed[k] / stored[k] (host arrays of
+ * n_batches; stored may be NULL) for the batches of an index over d_bytes (device, any
+ * alignment).  No verdict: a difference is the caller's to see. */
+int         ysb_kafka_crc_device(ysb_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                 uint64_t n_batches, uint32_t* computed, uint32_t* stored);
+/* The last call that verified (a slot batch: at its launch).  Waits for everything submitted. */
+typedef struct ysb_kafka_crc_desc {
+    uint64_t calls;           /* calls that ran the kernel since ysb_open / ysb_reset         */
+    uint64_t mode;            /* the context's setting                                        */
+    uint64_t batches;         /* the last such call: batches verified ...                     */
+    uint64_t bytes;           /* ... and the bytes their CRCs cover                           */
+    uint64_t bad_batches;     /* batches whose CRC differs                                    */
+    uint64_t first_bad;       /* 0xFFFFFFFF: none                                             */
+    uint32_t stored;          /* of first_bad                                                 */
+    uint32_t computed;
+    uint64_t grid_waves;      /* the waves of the kernel's largest grid, one batch each at a
+                                 time: a call with more batches turns the kernel's loop       */
+    double   crc_ms;          /* YSB_F_TIMING: HIP events around the kernel                   */
+} ysb_kafka_crc_desc;
+int         ysb_kafka_crc_info(ysb_ctx* ctx, ysb_kafka_crc_desc* info);
+uint64_t    ysb_kafka_crc_desc_size(void);
+/* The host models with the same rule: the verdict ysb_kafka_unframe_host / _lz4_host give when
+ * every batch's CRC is checked first (rule 9).  YSB_OK or YSB_ERR_FORMAT (the message naming the
+ * batch and, for rule 9, both values) with *verdict set; YSB_ERR_ARG as those, and for an entry
+ * with records_off < 44. */
+int         ysb_kafka_verdict_crc_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                       uint64_t n_batches, ysb_kafka_verdict* verdict);
 /* ---- LZ4-compressed Kafka record batches (additive within ABI 6) ---------------------------
  * A topic whose producers set compression.type=lz4: in message format v2 the 61-byte batch header
  * stays as it is and the records section is ONE standard LZ4 frame (attributes codec 3).  The
@@ -961,6 +1011,10 @@ typedef struct ysb_kafka_lz4_desc {
     double   decode_ms;
 } ysb_kafka_lz4_desc;
 int         ysb_kafka_lz4_info(ysb_ctx* ctx, ysb_kafka_lz4_desc* info);
+int         ysb_kafka_verdict_crc_lz4_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                           const ysb_kafka_frame* frames, uint64_t n_batches,
+                                           const ysb_lz4_frame_block* blocks, uint64_t n_blocks,
+                                           ysb_kafka_verdict* verdict);   /* ysb_kafka_verdict_crc_host, compressed */
 uint64_t    ysb_kafka_frame_size(void);
 uint64_t    ysb_kafka_lz4_summary_size(void);
 uint64_t    ysb_kafka_lz4_desc_size(void);

@@ -169,6 +169,8 @@ struct KafkaStaged {
     bool lz4 = false;
     u64 n_blocks = 0, stored_blocks = 0, compressed_batches = 0;
     u32 decoder = 0;                     // the decode kernel chosen when it was staged
+    u32 crc = 0;                         // ysb_kafka_set_crc's mode when it was staged; with it on, where in the
+    u64 crc_back = 0;                    //   slot's pinned buffer the batches' {computed, stored} come back
 };
 
 // A slot's batch between its submit and its launch one call later (ysb_raw.cpp).  Every submit
@@ -319,6 +321,14 @@ struct ysb_ctx {
     PinBuf<KafkaPlanHead> h_kafka_plan;
     ysb_kafka_lz4_desc kafka_lz4_last{};
     Event ev_kafka_lz4[2][4];
+    // CRC-32C of Kafka batches on the device (ysb_kafka_crc.h; ysb_kafka_set_crc): the mode, kept
+    // across ysb_reset; the kernel's tables and constants, built on the host and copied at the
+    // first call that verifies; ysb_kafka_crc_device's scratch; the last call that verified.
+    u32 kafka_crc_mode = 0;
+    DevBuf<u32> d_kafka_crc_tab;
+    DevBuf<u8> d_kafka_crc_sync;
+    ysb_kafka_crc_desc kafka_crc_last{};
+    Event ev_kafka_crc[2][2];
     // counts
     u32 c_pad = 0;                        // campaigns padded to the group size
     DevBuf<unsigned long long> d_counts;      // [c_pad][W]

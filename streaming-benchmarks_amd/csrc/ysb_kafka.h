@@ -27,6 +27,7 @@
 
 #include "../../include/ysb_hip.h"
 #include "ysb_common.h"
+#include "ysb_kafka_crc.h"
 
 namespace ysb {
 
@@ -53,8 +54,11 @@ enum : u32 {
     KAFKA_R_HEADERS = 6,   // a negative count or header key length, a header past the record, or the
                            //   headers not ending exactly at the record's end
     KAFKA_R_COUNT = 7,     // the batch ends in front of record recordsCount, or bytes are left behind it
-    KAFKA_R_CODEC = 8      // a block of the batch's LZ4 frame does not decode (`record`: the smallest such block
+    KAFKA_R_CODEC = 8,     // a block of the batch's LZ4 frame does not decode (`record`: the smallest such block
                            //   of the batch; ysb_kafka_lz4.h)
+    KAFKA_R_CRC = 9        // the batch's CRC-32C differs from the stored one (`record` 0; only where the check
+                           //   is asked for: ysb_kafka_set_crc, ysb_kafka_verdict_crc_host).  It comes first: a
+                           //   consumer never reads a record of such a batch
 };
 YSB_HD const char* kafka_rule_name(u32 r) {
     return r == KAFKA_R_VARINT ? "a varint runs past its limit or its extent"
@@ -64,7 +68,8 @@ YSB_HD const char* kafka_rule_name(u32 r) {
          : r == KAFKA_R_VALUE ? "the value runs past the record"
          : r == KAFKA_R_HEADERS ? "the headers do not end at the record's end"
          : r == KAFKA_R_COUNT ? "the records do not end at the batch's end"
-         : r == KAFKA_R_CODEC ? "a block of the batch's LZ4 frame does not decode" : "none";
+         : r == KAFKA_R_CODEC ? "a block of the batch's LZ4 frame does not decode"
+         : r == KAFKA_R_CRC ? "the batch's CRC-32C differs" : "none";
 }
 
 YSB_HD int32_t kafka_unzigzag32(u32 v) { return (int32_t)(v >> 1) ^ -(int32_t)(v & 1); }
@@ -160,23 +165,7 @@ YSB_HD bool kafka_entry_ok(const ysb_kafka_batch& b, u64 nbytes, u64 first_recor
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 
-// ---- CRC-32C (Castagnoli, reflected 0x82F63B78), in software ---------------------------------
-
-inline u32 kafka_crc32c(const u8* p, u64 n, u32 crc = 0) {
-    static const struct Table {
-        u32 t[256];
-        Table() {
-            for (u32 i = 0; i < 256; ++i) {
-                u32 c = i;
-                for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1) ? 0x82F63B78u : 0u);
-                t[i] = c;
-            }
-        }
-    } T;
-    crc = ~crc;
-    for (u64 i = 0; i < n; ++i) crc = T.t[(crc ^ p[i]) & 255] ^ (crc >> 8);
-    return ~crc;
-}
+// ---- CRC-32C: kafka_crc32c, sliced sixteen bytes a round (ysb_kafka_crc.h) --------------------
 
 // ---- big-endian fields ----------------------------------------------------------------------
 
@@ -192,6 +181,39 @@ inline void kafka_put_be(u8* p, int n, u64 v) {
 struct KafkaError {
     char msg[512];
 };
+
+// Which batches the index verifies on the host: all of them (YSB_KAFKA_CHECK_CRC), or only the
+// control batches it skips (YSB_KAFKA_CHECK_CRC_CONTROL) -- what the device, which verifies the
+// indexed batches (ysb_kafka_set_crc), never sees.
+inline bool kafka_index_checks_crc(u32 flags, u32 attributes) {
+    return (flags & YSB_KAFKA_CHECK_CRC) || ((flags & YSB_KAFKA_CHECK_CRC_CONTROL) && (attributes & 0x20u));
+}
+
+// An indexed batch's stored CRC and the one its bytes give: the range is [records_off - 40,
+// records_off + records_bytes), the stored value the big-endian word in front of it.  The
+// entry's records_off is at least KAFKA_CRC_STORED (kafka_crc_entries_ok).
+inline bool kafka_crc_differs(const u8* bytes, const ysb_kafka_batch& b, u32* want, u32* got) {
+    *want = (u32)kafka_be(bytes + b.records_off - KAFKA_CRC_STORED, 4);
+    *got = kafka_crc32c(bytes + b.records_off - KAFKA_CRC_COVERED, (u64)b.records_bytes + KAFKA_CRC_COVERED);
+    return *want != *got;
+}
+// the first entry whose header does not lie in the buffer in front of its records, or n
+inline u64 kafka_crc_entries_ok(const ysb_kafka_batch* batches, u64 n) {
+    for (u64 k = 0; k < n; ++k)
+        if (batches[k].records_off < KAFKA_CRC_STORED) return k;
+    return n;
+}
+// a bad batch as a message (the model's, the device calls'): a CRC names the two values
+inline void kafka_bad_batch_message(char* msg, size_t cap, const char* what, u32 k, long long base_offset, u32 rule, u32 rec,
+                                    u32 want, u32 got, u32 bad_batches, const char* tail) {
+    if (rule == KAFKA_R_CRC)
+        std::snprintf(msg, cap, "%sKafka batch %u (baseOffset %lld): %s: stored %08x, computed %08x: the batch's bytes changed "
+                      "between the producer and here (%u bad batches in all)%s", what, k, base_offset, kafka_rule_name(rule),
+                      want, got, bad_batches, tail);
+    else
+        std::snprintf(msg, cap, "%sKafka batch %u (baseOffset %lld), %s %u: %s (%u bad batches in all)%s", what, k, base_offset,
+                      rule == KAFKA_R_CODEC ? "block" : "record", rec, kafka_rule_name(rule), bad_batches, tail);
+}
 
 // ---- the index: the headers alone -------------------------------------------------------------
 // One 61-byte read per batch.  A last batch that is not whole (fewer than 61 bytes, or fewer than
@@ -222,7 +244,7 @@ inline int kafka_index(const u8* bytes, u64 nbytes, u32 flags, ysb_kafka_batch* 
         if (count < 0) return refuse("recordsCount", count, "negative");
         const u64 span = (u64)KAFKA_LEN_BASE + (u64)batch_len;
         if (nbytes - pos < span) break;   // the tail of a fetch response
-        if (flags & YSB_KAFKA_CHECK_CRC) {
+        if (kafka_index_checks_crc(flags, attributes)) {
             const u32 want = (u32)kafka_be(h + 17, 4), got = kafka_crc32c(h + KAFKA_CRC_FROM, span - KAFKA_CRC_FROM);
             if (want != got) return refuse("crc", (long long)want, "the batch's CRC-32C differs");
             ++s.crc_checked;
@@ -298,10 +320,16 @@ inline u32 kafka_unframe_batch(const u8* bytes, const ysb_kafka_batch& b, u8* ou
 // batch all the same: the kernel's verdict says the same).  out / line_off NULL: sizes only.
 inline int kafka_unframe(const u8* bytes, u64 nbytes, const ysb_kafka_batch* batches, u64 n_batches, u8* out, u64 out_cap,
                          u32* line_off, u64 off_cap, u64* n_lines, u64* out_bytes, ysb_kafka_counters* counters,
-                         ysb_kafka_verdict* verdict, KafkaError* err) {
+                         ysb_kafka_verdict* verdict, KafkaError* err, bool check_crc = false) {
     ysb_kafka_counters ct{};
     ysb_kafka_verdict vd{0, KAFKA_NONE, 0, 0};
     u64 first = 0;
+    u32 bad_want = 0, bad_got = 0;
+    if (check_crc && kafka_crc_entries_ok(batches, n_batches) != n_batches) {
+        std::snprintf(err->msg, sizeof err->msg, "index entry %llu: fewer than 44 bytes in front of its records, where the stored "
+                      "CRC lies", (unsigned long long)kafka_crc_entries_ok(batches, n_batches));
+        return YSB_ERR_ARG;
+    }
     for (u64 k = 0; k < n_batches; ++k) {
         if (!kafka_entry_ok(batches[k], nbytes, first)) {
             std::snprintf(err->msg, sizeof err->msg, "index entry %llu does not lie in the buffer or breaks the running record count",
@@ -321,10 +349,15 @@ inline int kafka_unframe(const u8* bytes, u64 nbytes, const ysb_kafka_batch* bat
         u32 bad_rec = 0;
         ysb_kafka_counters bc{};
         const u64 at0 = at;
-        const u32 rule = kafka_unframe_batch(bytes, batches[k], vd.bad_batches ? nullptr : out, out_cap,
-                                             vd.bad_batches ? nullptr : line_off, &at, &bc, &bad_rec);
+        u32 want = 0, got = 0;
+        const u32 rule = check_crc && kafka_crc_differs(bytes, batches[k], &want, &got)
+                             ? KAFKA_R_CRC
+                             : kafka_unframe_batch(bytes, batches[k], vd.bad_batches ? nullptr : out, out_cap,
+                                                   vd.bad_batches ? nullptr : line_off, &at, &bc, &bad_rec);
         if (rule) {
             if (!vd.bad_batches) {
+                bad_want = want;
+                bad_got = got;
                 vd.first_bad = (u32)k;
                 vd.record = bad_rec;
                 vd.rule = rule;
@@ -343,9 +376,8 @@ inline int kafka_unframe(const u8* bytes, u64 nbytes, const ysb_kafka_batch* bat
     if (verdict) *verdict = vd;
     if (out_bytes) *out_bytes = at;
     if (vd.bad_batches) {
-        std::snprintf(err->msg, sizeof err->msg, "Kafka batch %u (baseOffset %lld), record %u: %s (%u bad batches in all)",
-                      vd.first_bad, (long long)batches[vd.first_bad].base_offset, vd.record, kafka_rule_name(vd.rule),
-                      vd.bad_batches);
+        kafka_bad_batch_message(err->msg, sizeof err->msg, "", vd.first_bad, (long long)batches[vd.first_bad].base_offset, vd.rule,
+                                vd.record, bad_want, bad_got, vd.bad_batches, "");
         return YSB_ERR_FORMAT;
     }
     if (at > 0xFFFFFFFFull || (out && at > out_cap)) {

@@ -394,6 +394,73 @@ __global__ __launch_bounds__(256) void kafka_codec_kernel(const KafkaPlanParams 
     if (j != KAFKA_NONE) bout[k] = KafkaBatchOut{0, j, KAFKA_R_CODEC, 0, 0, 0, 0};
 }
 
+// ---- CRC-32C of the indexed batches (ysb_kafka_crc.h: the arithmetic, the layout, the host model) ----
+// The tables are copied into LDS once per workgroup; each wave then takes batches wave-id,
+// wave-id + waves, ...  (wave w of workgroup g has id w * gridDim + g, so a call of few large
+// batches spreads over the CUs before it doubles up inside one).  Per batch: the walk's own
+// geometry, a window of 1024 bytes as one 16-byte vector per lane, two windows' loads in flight;
+// per window one round of 16 independent LDS lookups; behind the last window one multiplication
+// by the lane's constant, an xor over the wave and the final xor.  Nothing outside the vectors
+// that hold [records_off - 44, records_off + records_bytes) is loaded; the bytes of the first and
+// the last vector that lie outside the range are masked (crc_edge), the stored CRC's four among
+// them, which lane 0 reads by themselves.  Every extent is the host's (kafka_entry_ok, records_off
+// >= 44): no byte decides an address or a trip count.
+static_assert(CRC_WIN == KAFKA_WIN && CRC_LANES == 64, "the walk's window, one vector per lane");
+
+__device__ __forceinline__ CrcVec crc_load(const u8* g0, i64 off, u32 span) {
+    CrcVec v{{0, 0, 0, 0}};
+    if (off >= 0 && off < (i64)span) {
+        const uint4 q = *reinterpret_cast<const uint4*>(g0 + off);
+        v.w[0] = q.x;
+        v.w[1] = q.y;
+        v.w[2] = q.z;
+        v.w[3] = q.w;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(KAFKA_CRC_TPB) void kafka_crc_kernel(const KafkaCrcParams P) {
+    __shared__ __align__(16) u32 tab[CRC_TABLE_WORDS];
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    for (u32 i = tid; i < CRC_TABLE_WORDS / 4; i += KAFKA_CRC_TPB)
+        reinterpret_cast<uint4*>(tab)[i] = reinterpret_cast<const uint4*>(P.tables)[i];
+    __syncthreads();
+    const u32* consts = P.tables + CRC_TABLE_WORDS;
+    const u64 waves = (u64)gridDim.x * (KAFKA_CRC_TPB / 64);
+    for (u64 k = (u64)wave * gridDim.x + blockIdx.x; k < P.n_batches; k += waves) {
+        const ysb_kafka_batch b = P.batches[k];
+        const u8* from = P.bytes + b.records_off - KAFKA_CRC_STORED;   // the stored CRC, then the range
+        const CrcGrid g = crc_grid((u64)reinterpret_cast<uintptr_t>(from), KAFKA_CRC_STORED - KAFKA_CRC_COVERED,
+                                   b.records_bytes + KAFKA_CRC_COVERED);   // (g.first is 0: four bytes lie in front)
+        const u8* g0 = from - (reinterpret_cast<uintptr_t>(from) & 15);
+        i64 off = crc_vec_off(g, 0, lane);
+        CrcVec v0 = crc_load(g0, off, g.span), v1 = crc_load(g0, off + CRC_WIN, g.span);
+        u32 s = 0;
+        for (u32 w = 0; w < g.windows; ++w) {
+            const CrcVec v2 = crc_load(g0, off + 2 * (i64)CRC_WIN, g.span);
+            if (off >= 0 && crc_is_edge(g, (u32)off)) crc_edge(g, (u32)off, &v0);
+            s = crc_step16(tab, s, v0);
+            v0 = v1;
+            v1 = v2;
+            off += CRC_WIN;
+        }
+        u32 t = crc_lane_finish(consts, g, lane, s);
+        for (int d = 32; d; d >>= 1) t ^= (u32)__shfl_xor((int)t, d);
+        if (lane == 0) {
+            const u32 got = ~t, want = (u32)from[0] << 24 | (u32)from[1] << 16 | (u32)from[2] << 8 | (u32)from[3];
+            P.crc[k] = make_uint2(got, want);
+            if (P.bout && got != want) P.bout[k] = KafkaBatchOut{0, 0, KAFKA_R_CRC, 0, 0, 0, 0};
+        }
+    }
+}
+
+hipError_t launch_kafka_crc(const KafkaCrcParams& p, u32 cus, hipStream_t s) {
+    const u32 need = (p.n_batches + KAFKA_CRC_TPB / 64 - 1) / (KAFKA_CRC_TPB / 64), cap = cus * KAFKA_CRC_WGS_PER_CU;
+    hipLaunchKernelGGL(kafka_crc_kernel, dim3(need < cap ? need : cap), dim3(KAFKA_CRC_TPB), 0, s, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_kafka_plan(const KafkaPlanParams& p, hipStream_t s) {
     hipLaunchKernelGGL(kafka_inflate_plan_kernel, dim3(1), dim3(KAFKA_PLAN_STEP), 0, s, p);
     return hipGetLastError();

@@ -16,15 +16,18 @@ static_assert(sizeof(KafkaHead) == 64 && sizeof(KafkaBatchOut) == 32 && sizeof(y
 // A call's device buffer: the head and the index entries (what one copy carries), then the
 // kernels' scratch.
 struct KafkaLayout {
-    u64 batches, meta, bout, base, total;
+    u64 batches, meta, bout, base, crc, total;
 };
-static KafkaLayout kafka_layout(u64 nb, u64 nrec) {
+// crc: the call verifies the batches' CRCs -- {computed, stored} per batch behind the rest (a
+// call that does not pays nothing for them)
+static KafkaLayout kafka_layout(u64 nb, u64 nrec, bool crc = false) {
     KafkaLayout l;
     l.batches = sizeof(KafkaHead);
     l.meta = (l.batches + nb * sizeof(ysb_kafka_batch) + 15) & ~15ull;
     l.bout = l.meta + nrec * 16;
     l.base = l.bout + nb * sizeof(KafkaBatchOut);
-    l.total = l.base + nb * 8;
+    l.crc = l.base + nb * 8;
+    l.total = l.crc + (crc ? nb * sizeof(uint2) : 0);
     return l;
 }
 static KafkaParams kafka_params(u8* d, const KafkaLayout& l, const u8* d_bytes, u64 nb, u64 nrec, u8* out, u64 out_cap,
@@ -45,6 +48,30 @@ static KafkaParams kafka_params(u8* d, const KafkaLayout& l, const u8* d_bytes, 
 }
 
 // the index as argument errors (the same for every entry that takes one): *n_records its records
+static int crc_args(ysb_ctx* c, const ysb_kafka_batch* batches, u64 nb) {
+    const u64 k = kafka_crc_entries_ok(batches, nb);
+    if (k != nb)
+        return fail(c, YSB_ERR_ARG, "Kafka index entry %llu: records_off %llu, fewer than 44 bytes in front of its records, where "
+                    "the stored CRC-32C lies (the CRC check is on: ysb_kafka_set_crc)", (unsigned long long)k,
+                    (unsigned long long)batches[k].records_off);
+    return YSB_OK;
+}
+
+// The CRC kernel's tables and constants on the device, at the first call that verifies.
+static int ensure_crc_tables(ysb_ctx* c) {
+    if (c->d_kafka_crc_tab) return YSB_OK;
+    const CrcTables& T = crc_tables();
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->d_kafka_crc_tab.alloc((CRC_TABLE_WORDS + CRC_CONST_WORDS) * sizeof(u32)));
+    hipError_t e = hipMemcpy(c->d_kafka_crc_tab.get(), T.win, sizeof T.win, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->d_kafka_crc_tab.get() + CRC_TABLE_WORDS, T.consts, sizeof T.consts, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        c->d_kafka_crc_tab.reset();
+        return fail(c, YSB_ERR_HIP, "copying the CRC tables: %s", hipGetErrorString(e));
+    }
+    return YSB_OK;
+}
+
 static int index_args(ysb_ctx* c, const uint8_t* bytes, u64 nbytes, const ysb_kafka_batch* batches, u64 nb, u64* n_records,
                       u64* control) {
     if ((nbytes && !bytes) || (nb && !batches)) return fail(c, YSB_ERR_ARG, "NULL Kafka buffers");
@@ -65,7 +92,11 @@ static int index_args(ysb_ctx* c, const uint8_t* bytes, u64 nbytes, const ysb_ka
 
 // walk, base, gather on s (ev: YSB_F_TIMING's four events, created on demand, or NULL; codec: a
 // compressed call's plan, whose bad batches become rule 8 behind the walk, or NULL)
-static int launch_unframe(ysb_ctx* c, const KafkaParams& p, hipStream_t s, Event* ev, const KafkaPlanParams* codec = nullptr) {
+// crc: the call verifies -- one launch behind the walk and the codec verdict, in front of the base
+// kernel, so a batch whose CRC differs is bad by rule 9 whatever they made of its bytes (cev:
+// YSB_F_TIMING's two marks around it, or NULL)
+static int launch_unframe(ysb_ctx* c, const KafkaParams& p, hipStream_t s, Event* ev, const KafkaPlanParams* codec = nullptr,
+                          const KafkaCrcParams* crc = nullptr, Event* cev = nullptr) {
     if (ev)
         for (int k = 0; k < 4; ++k)
             if (!ev[k]) HIPCHK(c, ev[k].create(hipEventDefault));
@@ -73,6 +104,11 @@ static int launch_unframe(ysb_ctx* c, const KafkaParams& p, hipStream_t s, Event
     if (p.n_batches) HIPCHK(c, launch_kafka_walk(p, s));
     if (codec) HIPCHK(c, launch_kafka_codec(*codec, p.bout, s));
     if (ev) HIPCHK(c, hipEventRecord(ev[1], s));
+    if (crc && crc->n_batches) {
+        HIPCHK(c, mark(cev, 0, s));
+        HIPCHK(c, launch_kafka_crc(*crc, (u32)c->cus, s));
+        HIPCHK(c, mark(cev, 1, s));
+    }
     HIPCHK(c, launch_kafka_base(p, s));
     if (ev) HIPCHK(c, hipEventRecord(ev[2], s));
     HIPCHK(c, launch_kafka_gather(p, s));
@@ -81,8 +117,29 @@ static int launch_unframe(ysb_ctx* c, const KafkaParams& p, hipStream_t s, Event
 }
 
 // kafka_last <- a call's figures; the error its verdict asks for
+// kafka_crc_last <- what a call's CRC kernel found: crcs[k] = {computed, stored}
+static void settle_crc(ysb_ctx* c, const uint2* crcs, const ysb_kafka_batch* batches, u64 nb, Event* cev) {
+    ysb_kafka_crc_desc d{};
+    d.calls = c->kafka_crc_last.calls + 1;
+    d.batches = nb;
+    d.first_bad = KAFKA_NONE;
+    for (u64 k = 0; k < nb; ++k) {
+        d.bytes += (u64)batches[k].records_bytes + KAFKA_CRC_COVERED;
+        if (crcs[k].x == crcs[k].y) continue;
+        if (!d.bad_batches++) {
+            d.first_bad = k;
+            d.computed = crcs[k].x;
+            d.stored = crcs[k].y;
+        }
+    }
+    if (nb) add_span(cev, 0, 1, &d.crc_ms);
+    c->kafka_crc_last = d;
+}
+
+// crcs: the call verified (settle_crc), else NULL
 static int settle(ysb_ctx* c, const KafkaHead& h, u64 nb, u64 framed, u64 control, const ysb_kafka_batch* batches,
-                  Event* ev, const char* what) {
+                  Event* ev, const char* what, const uint2* crcs = nullptr, Event* cev = nullptr) {
+    if (crcs) settle_crc(c, crcs, batches, nb, cev);
     ysb_kafka_desc d{};
     d.calls = c->kafka_last.calls + 1;
     d.batches = nb;
@@ -100,13 +157,18 @@ static int settle(ysb_ctx* c, const KafkaHead& h, u64 nb, u64 framed, u64 contro
         if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) d.walk_ms = ms;
         if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) d.base_ms = ms;
         if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) d.gather_ms = ms;
+        if (crcs) d.base_ms = std::max(0.0, d.base_ms - c->kafka_crc_last.crc_ms);   // (the CRC launch lies between those marks)
     }
     c->kafka_last = d;
-    if (h.bad_batches)
-        return fail(c, YSB_ERR_FORMAT, "%s: Kafka batch %u (baseOffset %lld), %s %u: %s (%u bad batches in all); "
-                    "nothing of the call was counted", what, h.first_bad,
-                    h.first_bad < nb ? (long long)batches[h.first_bad].base_offset : -1LL,
-                    h.rule == KAFKA_R_CODEC ? "block" : "record", h.bad_rec, kafka_rule_name(h.rule), h.bad_batches);
+    if (h.bad_batches) {
+        char msg[512], pre[64];
+        std::snprintf(pre, sizeof pre, "%s: ", what);
+        const bool named = crcs && h.first_bad < nb;
+        kafka_bad_batch_message(msg, sizeof msg, pre, h.first_bad, h.first_bad < nb ? (long long)batches[h.first_bad].base_offset : -1LL,
+                                h.rule, h.bad_rec, named ? crcs[h.first_bad].y : 0u, named ? crcs[h.first_bad].x : 0u, h.bad_batches,
+                                "; nothing of the call was counted");
+        return fail(c, YSB_ERR_FORMAT, "%s", msg);
+    }
     if (h.overflow)
         return fail(c, YSB_ERR_CAPACITY, "%s: %llu value bytes do not fit the output", what, (unsigned long long)h.out_bytes);
     return YSB_OK;
@@ -125,7 +187,7 @@ struct KafkaLz4Layout {
     u64 planned, desc, phead, raw, zeros, bbad, cbad, kafka, total;
     KafkaLayout kl;
 };
-static KafkaLz4Layout kafka_lz4_layout(u64 nb, u64 nblk, u64 nrec) {
+static KafkaLz4Layout kafka_lz4_layout(u64 nb, u64 nblk, u64 nrec, bool crc = false) {
     KafkaLz4Layout l;
     l.batches = sizeof(KafkaHead);
     l.frames = l.batches + nb * sizeof(ysb_kafka_batch);
@@ -139,7 +201,7 @@ static KafkaLz4Layout kafka_lz4_layout(u64 nb, u64 nblk, u64 nrec) {
     l.bbad = l.zeros + (nblk + 1) * 4;
     l.cbad = l.bbad + nblk * 4;
     l.kafka = (l.cbad + nb * 4 + 15) & ~15ull;
-    l.kl = kafka_layout(nb, nrec);
+    l.kl = kafka_layout(nb, nrec, crc);
     l.total = l.kafka + l.kl.total;
     return l;
 }
@@ -191,24 +253,39 @@ static int launch_inflate(ysb_ctx* c, const KafkaPlanParams& pp, const u8* d_wir
 // kafka_lz4_layout has them) -- the inflate chain in front, the walk over the inflated bytes by
 // the planned index, the codec verdict behind it.  *head / *plan: where the two heads lie on the
 // device (*plan NULL: not compressed).  zev / kev: YSB_F_TIMING's marks around the inflate chain's
-// and the unframing's kernels, or NULL.
+// and the unframing's kernels, or NULL.  crc: the call verifies its batches' CRCs over the wire
+// bytes by the host's index (*d_crc: where the values lie on the device; cev: its two marks).
 static int launch_call(ysb_ctx* c, u8* d, const u8* d_wire, u8* d_infl, u64 nb, u64 nblk, u64 nrec, u32 decoder, u8* out,
                        u64 out_cap, u32* line_off, hipStream_t s, Event* zev, Event* kev, const KafkaHead** head,
-                       const KafkaPlanHead** plan) {
+                       const KafkaPlanHead** plan, bool crc = false, const uint2** d_crc = nullptr, Event* cev = nullptr) {
     KafkaParams p;
     KafkaPlanParams pp{};
+    KafkaCrcParams cp{};
+    if (crc) {
+        if (int rc = ensure_crc_tables(c)) return rc;
+        cp.bytes = d_wire;
+        cp.n_batches = (u32)nb;
+        cp.tables = c->d_kafka_crc_tab;
+    }
     if (d_infl) {
-        const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec);
+        const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec, crc);
+        cp.batches = reinterpret_cast<const ysb_kafka_batch*>(d + l.batches);
+        cp.crc = reinterpret_cast<uint2*>(d + l.kafka + l.kl.crc);
         pp = kafka_plan_params(d, l, nb, nblk);
         p = kafka_params(d + l.kafka, l.kl, d_infl, nb, nrec, out, out_cap, line_off);
         p.batches = pp.planned;
         if (int rc = launch_inflate(c, pp, d_wire, d_infl, decoder, s, zev)) return rc;
     } else {
-        p = kafka_params(d, kafka_layout(nb, nrec), d_wire, nb, nrec, out, out_cap, line_off);
+        const KafkaLayout l = kafka_layout(nb, nrec, crc);
+        p = kafka_params(d, l, d_wire, nb, nrec, out, out_cap, line_off);
+        cp.batches = p.batches;
+        cp.crc = reinterpret_cast<uint2*>(d + l.crc);
     }
+    cp.bout = p.bout;
     *head = p.head;
     *plan = d_infl ? pp.head : nullptr;
-    return launch_unframe(c, p, s, kev, d_infl ? &pp : nullptr);
+    if (d_crc) *d_crc = cp.crc;
+    return launch_unframe(c, p, s, kev, d_infl ? &pp : nullptr, crc ? &cp : nullptr, cev);
 }
 
 // kafka_lz4_last <- the inflate half of a call's figures
@@ -250,8 +327,10 @@ static int lines_fit(ysb_ctx* c, u64 nrec) {
 // front of the pinned buffer (both layouts'), the wire bytes and the pinned buffer's first
 // `copied` bytes as the slot's copies, the RawBatch's fields.
 static int place(ysb_ctx* c, int slot, const u8* bytes, u64 nbytes, const u8* dsrc, const ysb_kafka_batch* batches, u64 nb,
-                 u64 nrec, u64 control, u64 dev_total, u64 pinned, u64 copied, RawBatch* batch, SlotCopy v[2]) {
+                 u64 nrec, u64 control, u64 dev_total, u64 pinned_index, u64 copied, RawBatch* batch, SlotCopy v[2]) {
     HIPCHK(c, hipSetDevice(c->device));
+    // with the CRC check on the batches' {computed, stored} come back behind the index
+    const u64 pinned = c->kafka_crc_mode ? ((pinned_index + 7) & ~7ull) + nb * sizeof(uint2) : pinned_index;
     if (int rc = ensure_wire(c, slot)) return rc;
     if (!c->h_kafka_head) {
         HIPCHK(c, c->h_kafka_head.alloc(2 * sizeof(KafkaHead)));
@@ -279,6 +358,8 @@ static int place(ysb_ctx* c, int slot, const u8* bytes, u64 nbytes, const u8* ds
     batch->off = c->d_roff[slot];
     batch->n_off = nrec;
     batch->kafka = KafkaStaged{nb, nrec, nbytes, control};
+    batch->kafka->crc = c->kafka_crc_mode;
+    batch->kafka->crc_back = (pinned_index + 7) & ~7ull;
     return YSB_OK;
 }
 
@@ -303,8 +384,9 @@ int kafka_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes, con
     u64 nrec = 0, control = 0;
     int rc = index_args(c, bytes, nbytes, batches, nb, &nrec, &control);
     if (!rc) rc = lines_fit(c, nrec);
+    if (!rc && c->kafka_crc_mode) rc = crc_args(c, batches, nb);
     if (rc) return rc;
-    const KafkaLayout l = kafka_layout(nb, nrec);
+    const KafkaLayout l = kafka_layout(nb, nrec, c->kafka_crc_mode != 0);
     if ((rc = place(c, slot, bytes, nbytes, dsrc, batches, nb, nrec, control, l.total, l.meta,
                     l.batches + nb * sizeof(ysb_kafka_batch), batch, v)))
         return rc;
@@ -325,12 +407,13 @@ int kafka_lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes,
     int rc = kafka_lz4_entries(batches, frames, nb, blocks, nblk, nbytes, &nrec, &control, &compressed, &stored, &err);
     if (rc) return fail(c, rc, "%s", err.msg);
     if ((rc = lines_fit(c, nrec))) return rc;
+    if (c->kafka_crc_mode && (rc = crc_args(c, batches, nb))) return rc;
     // the host cannot know the raw sizes: the guaranteed bound, 64 KiB per block
     if (nblk * (u64)LZ4_MAX_RAW > c->cfg.max_batch_bytes)
         return fail(c, YSB_ERR_CAPACITY, "compressed Kafka batch of %llu blocks: %llu x 65536 B may not fit max_batch_bytes "
                     "(%llu); submit fewer Kafka batches per call", (unsigned long long)nblk, (unsigned long long)nblk,
                     (unsigned long long)c->cfg.max_batch_bytes);
-    const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec);
+    const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec, c->kafka_crc_mode != 0);
     if ((rc = place(c, slot, bytes, nbytes, dsrc, batches, nb, nrec, control, l.total, l.copied, l.copied, batch, v))) return rc;
     // a compressed batch's own: the inflated records and the plan's pinned head at their first
     // use, the frames and the blocks behind the index, what its settling reports
@@ -362,10 +445,14 @@ int kafka_enqueue(ysb_ctx* c, int slot, const KafkaStaged& b, hipStream_t s) {
     const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
     const KafkaHead* head = nullptr;
     const KafkaPlanHead* plan = nullptr;
+    const uint2* d_crc = nullptr;
     if (int rc = launch_call(c, c->d_kafka[slot], c->d_wire[slot], b.lz4 ? c->d_kafka_infl[slot].get() : nullptr, b.n_batches,
                              b.n_blocks, b.n_records, b.decoder, c->d_bytes[slot], c->cfg.max_batch_bytes, c->d_roff[slot], s,
-                             timed ? c->ev_kafka_lz4[slot] : nullptr, timed ? c->ev_kafka[slot] : nullptr, &head, &plan))
+                             timed ? c->ev_kafka_lz4[slot] : nullptr, timed ? c->ev_kafka[slot] : nullptr, &head, &plan,
+                             b.crc != 0, &d_crc, timed ? c->ev_kafka_crc[slot] : nullptr))
         return rc;
+    if (b.crc && b.n_batches)
+        HIPCHK(c, hipMemcpyAsync(c->h_kafka[slot] + b.crc_back, d_crc, b.n_batches * sizeof(uint2), hipMemcpyDeviceToHost, s));
     // the verdict comes back through pinned memory with the line count: no host wait here
     HIPCHK(c, hipMemcpyAsync(c->h_kafka_head + slot, head, sizeof(KafkaHead), hipMemcpyDeviceToHost, s));
     if (plan) HIPCHK(c, hipMemcpyAsync(c->h_kafka_plan + slot, plan, sizeof(KafkaPlanHead), hipMemcpyDeviceToHost, s));
@@ -382,7 +469,9 @@ int kafka_settle(ysb_ctx* c, int slot, const KafkaStaged& b, u64* nbytes) {
     std::snprintf(what, sizeof what, "Kafka batch (slot %d)", slot);
     return settle(c, c->h_kafka_head[slot], b.n_batches, b.framed_bytes, b.control_skipped,
                   reinterpret_cast<const ysb_kafka_batch*>(c->h_kafka[slot] + sizeof(KafkaHead)),
-                  timed ? c->ev_kafka[slot] : nullptr, what);
+                  timed ? c->ev_kafka[slot] : nullptr, what,
+                  b.crc ? reinterpret_cast<const uint2*>(c->h_kafka[slot] + b.crc_back) : nullptr,
+                  timed ? c->ev_kafka_crc[slot] : nullptr);
 }
 
 // ---- the unframing alone ----------------------------------------------------------------------
@@ -393,6 +482,8 @@ int ysb_kafka_unframe_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes
     if (!c) return YSB_ERR_ARG;
     u64 nrec = 0, control = 0;
     int rc = index_args(c, d_bytes, nbytes, batches, nb, &nrec, &control);
+    const bool crc = c->kafka_crc_mode != 0;
+    if (!rc && crc) rc = crc_args(c, batches, nb);
     if (rc) return rc;
     if (n_lines) *n_lines = nrec;
     if (out_bytes) *out_bytes = 0;
@@ -402,23 +493,25 @@ int ysb_kafka_unframe_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes
     if (out_cap && !d_out) return fail(c, YSB_ERR_ARG, "NULL output buffer");
     if ((rc = launch_pending_raw(c))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const KafkaLayout l = kafka_layout(nb, nrec);
+    const KafkaLayout l = kafka_layout(nb, nrec, crc);
     if ((rc = grow_device(c, c->d_kafka_sync, l.total + 64, 256u << 10))) return rc;
+    if (crc && (rc = ensure_crc_tables(c))) return rc;
     const KafkaParams p = kafka_params(c->d_kafka_sync, l, d_bytes, nb, nrec, d_out, d_out ? out_cap : 0, d_line_off);
+    const KafkaCrcParams cp{d_bytes, p.batches, (u32)nb, c->d_kafka_crc_tab, reinterpret_cast<uint2*>(c->d_kafka_sync + l.crc), p.bout};
+    std::vector<uint2> crcs(crc ? nb : 0);
     // (the index is the caller's pageable memory, the head this frame's: nothing is left pending)
-    struct SyncOnExit {
-        hipStream_t s;
-        ~SyncOnExit() { (void)hipStreamSynchronize(s); }
-    } const settled{c->s_comp};
+    const SyncOnExit settled{c->s_comp};
     if (nb) HIPCHK(c, hipMemcpyAsync(c->d_kafka_sync + l.batches, batches, nb * sizeof(ysb_kafka_batch), hipMemcpyHostToDevice, c->s_comp));
     const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
-    Event ev[4];
-    if ((rc = launch_unframe(c, p, c->s_comp, timed ? ev : nullptr))) return rc;
+    Event ev[4], cev[2];
+    if ((rc = launch_unframe(c, p, c->s_comp, timed ? ev : nullptr, nullptr, crc ? &cp : nullptr, timed ? cev : nullptr))) return rc;
     KafkaHead h{};
     HIPCHK(c, hipMemcpyAsync(&h, p.head, sizeof h, hipMemcpyDeviceToHost, c->s_comp));
+    if (crc && nb) HIPCHK(c, hipMemcpyAsync(crcs.data(), cp.crc, nb * sizeof(uint2), hipMemcpyDeviceToHost, c->s_comp));
     HIPCHK(c, hipStreamSynchronize(c->s_comp));
     if (out_bytes) *out_bytes = h.out_bytes;
-    return settle(c, h, nb, nbytes, control, batches, timed ? ev : nullptr, "ysb_kafka_unframe_device");
+    return settle(c, h, nb, nbytes, control, batches, timed ? ev : nullptr, "ysb_kafka_unframe_device", crc ? crcs.data() : nullptr,
+                  timed ? cev : nullptr);
 }
 
 // ---- the inflate and the unframing alone ---------------------------------------------------------
@@ -434,6 +527,8 @@ int ysb_kafka_unframe_lz4_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nb
     KafkaError err;
     int rc = kafka_lz4_entries(batches, frames, nb, blocks, nblk, nbytes, &nrec, &control, &compressed, &stored, &err);
     if (rc) return fail(c, rc, "%s", err.msg);
+    const bool crc = c->kafka_crc_mode != 0;
+    if (crc && (rc = crc_args(c, batches, nb))) return rc;
     if (n_lines) *n_lines = nrec;
     if (out_bytes) *out_bytes = 0;
     if (!d_line_off || nrec + 1 > off_cap)
@@ -442,7 +537,9 @@ int ysb_kafka_unframe_lz4_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nb
     if (out_cap && !d_out) return fail(c, YSB_ERR_ARG, "NULL output buffer");
     if ((rc = launch_pending_raw(c))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec);
+    const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec, crc);
+    std::vector<uint2> crcs(crc ? nb : 0);
+    const uint2* d_crc = nullptr;
     if ((rc = grow_device(c, c->d_kafka_lz4_sync, l.total + 64, 256u << 10))) return rc;
     if ((rc = grow_device(c, c->d_kafka_infl_sync, nblk * (u64)LZ4_MAX_RAW + 64, 1u << 20))) return rc;
     u8* d = c->d_kafka_lz4_sync;
@@ -452,12 +549,13 @@ int ysb_kafka_unframe_lz4_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nb
     if (nb) HIPCHK(c, hipMemcpyAsync(d + l.frames, frames, nb * sizeof(ysb_kafka_frame), hipMemcpyHostToDevice, s));
     if (nblk) HIPCHK(c, hipMemcpyAsync(d + l.blocks, blocks, nblk * sizeof(ysb_lz4_frame_block), hipMemcpyHostToDevice, s));
     const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
-    Event ev[4], kev[4];
+    Event ev[4], kev[4], cev[2];
     const KafkaHead* dh = nullptr;
     const KafkaPlanHead* dp = nullptr;
     if ((rc = launch_call(c, d, d_bytes, c->d_kafka_infl_sync, nb, nblk, nrec, c->lz4_decoder, d_out, d_out ? out_cap : 0,
-                          d_line_off, s, timed ? ev : nullptr, timed ? kev : nullptr, &dh, &dp)))
+                          d_line_off, s, timed ? ev : nullptr, timed ? kev : nullptr, &dh, &dp, crc, &d_crc, timed ? cev : nullptr)))
         return rc;
+    if (crc && nb) HIPCHK(c, hipMemcpyAsync(crcs.data(), d_crc, nb * sizeof(uint2), hipMemcpyDeviceToHost, s));
     KafkaHead h{};
     KafkaPlanHead ph{};
     HIPCHK(c, hipMemcpyAsync(&h, dh, sizeof h, hipMemcpyDeviceToHost, s));
@@ -465,8 +563,88 @@ int ysb_kafka_unframe_lz4_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nb
     HIPCHK(c, hipStreamSynchronize(s));
     if (out_bytes) *out_bytes = h.out_bytes;
     settle_lz4(c, ph, nblk, stored, compressed, nbytes, c->lz4_decoder, timed ? ev : nullptr);
-    return settle(c, h, nb, nbytes, control, batches, timed ? kev : nullptr, "ysb_kafka_unframe_lz4_device");
+    return settle(c, h, nb, nbytes, control, batches, timed ? kev : nullptr, "ysb_kafka_unframe_lz4_device",
+                  crc ? crcs.data() : nullptr, timed ? cev : nullptr);
 }
+
+// ---- CRC-32C on the device: the setting, the kernel alone, the last call's figures ---------------
+
+int ysb_kafka_set_crc(ysb_ctx* c, int mode) {
+    if (!c) return YSB_ERR_ARG;
+    if (mode != YSB_KAFKA_CRC_OFF && mode != YSB_KAFKA_CRC_DEVICE)
+        return fail(c, YSB_ERR_ARG, "ysb_kafka_set_crc: mode %d (0: off, 1: on the device)", mode);
+    c->kafka_crc_mode = (u32)mode;
+    return YSB_OK;
+}
+
+int ysb_kafka_crc_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const ysb_kafka_batch* batches, uint64_t nb,
+                         uint32_t* computed, uint32_t* stored) {
+    if (!c) return YSB_ERR_ARG;
+    if (nb && !computed) return fail(c, YSB_ERR_ARG, "ysb_kafka_crc_device: computed is NULL");
+    u64 nrec = 0;
+    int rc = index_args(c, d_bytes, nbytes, batches, nb, &nrec, nullptr);
+    if (!rc) rc = crc_args(c, batches, nb);
+    if (!rc) rc = launch_pending_raw(c);
+    if (!rc) rc = ensure_crc_tables(c);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const u64 idx_bytes = (nb * sizeof(ysb_kafka_batch) + 15) & ~15ull;
+    if ((rc = grow_device(c, c->d_kafka_crc_sync, idx_bytes + nb * sizeof(uint2) + 64, 64u << 10))) return rc;
+    u8* d = c->d_kafka_crc_sync;
+    const KafkaCrcParams cp{d_bytes, reinterpret_cast<const ysb_kafka_batch*>(d), (u32)nb, c->d_kafka_crc_tab,
+                            reinterpret_cast<uint2*>(d + idx_bytes), nullptr};
+    std::vector<uint2> crcs(nb);
+    hipStream_t s = c->s_comp;
+    const SyncOnExit settled{s};
+    const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
+    Event cev[2];
+    if (nb) {
+        HIPCHK(c, hipMemcpyAsync(d, batches, nb * sizeof(ysb_kafka_batch), hipMemcpyHostToDevice, s));
+        HIPCHK(c, mark(timed ? cev : nullptr, 0, s));
+        HIPCHK(c, launch_kafka_crc(cp, (u32)c->cus, s));
+        HIPCHK(c, mark(timed ? cev : nullptr, 1, s));
+        HIPCHK(c, hipMemcpyAsync(crcs.data(), cp.crc, nb * sizeof(uint2), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (u64 k = 0; k < nb; ++k) {
+        computed[k] = crcs[k].x;
+        if (stored) stored[k] = crcs[k].y;
+    }
+    settle_crc(c, crcs.data(), batches, nb, timed ? cev : nullptr);
+    return YSB_OK;
+}
+
+int ysb_kafka_crc_info(ysb_ctx* c, ysb_kafka_crc_desc* info) {
+    if (!c || !info) return c ? fail(c, YSB_ERR_ARG, "info is NULL") : YSB_ERR_ARG;
+    const int rc = sync_streams(c);   // (a Kafka batch awaiting its launch settles here)
+    *info = c->kafka_crc_last;
+    info->mode = c->kafka_crc_mode;
+    info->grid_waves = kafka_crc_grid_waves((u32)c->cus);
+    if (!info->calls) info->first_bad = KAFKA_NONE;
+    return rc;
+}
+
+int ysb_kafka_verdict_crc_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, uint64_t n_batches,
+                               ysb_kafka_verdict* verdict) {
+    if ((nbytes && !bytes) || (n_batches && !batches)) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_verdict_crc_host: NULL buffers");
+    KafkaError err;
+    const int rc = kafka_unframe(bytes, nbytes, batches, n_batches, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, verdict,
+                                 &err, true);
+    return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
+}
+
+int ysb_kafka_verdict_crc_lz4_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                   const ysb_kafka_frame* frames, uint64_t n_batches, const ysb_lz4_frame_block* blocks,
+                                   uint64_t n_blocks, ysb_kafka_verdict* verdict) {
+    if ((nbytes && !bytes) || (n_batches && (!batches || !frames)) || (n_blocks && !blocks))
+        return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_verdict_crc_lz4_host: NULL buffers");
+    KafkaError err;
+    const int rc = kafka_unframe_lz4(bytes, nbytes, batches, frames, n_batches, blocks, n_blocks, nullptr, 0, nullptr, 0, nullptr,
+                                     nullptr, nullptr, nullptr, verdict, &err, true);
+    return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
+}
+
+uint64_t ysb_kafka_crc_desc_size(void) { return sizeof(ysb_kafka_crc_desc); }
 
 int ysb_kafka_lz4_info(ysb_ctx* c, ysb_kafka_lz4_desc* info) {
     if (!c || !info) return c ? fail(c, YSB_ERR_ARG, "info is NULL") : YSB_ERR_ARG;
@@ -489,7 +667,7 @@ int ysb_kafka_info(ysb_ctx* c, ysb_kafka_desc* info) {
 int ysb_kafka_index(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, ysb_kafka_batch* batches, uint64_t cap,
                     ysb_kafka_summary* info) {
     if (nbytes && !bytes) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index: NULL buffer");
-    if (flags & ~YSB_KAFKA_CHECK_CRC) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index: unknown flags %#x", flags);
+    if (flags & ~(YSB_KAFKA_CHECK_CRC | YSB_KAFKA_CHECK_CRC_CONTROL)) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index: unknown flags %#x", flags);
     KafkaError err;
     const int rc = kafka_index(bytes, nbytes, flags, batches, batches ? cap : 0, info, &err);
     return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
@@ -510,7 +688,7 @@ int ysb_kafka_unframe_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafk
 int ysb_kafka_index_lz4(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, ysb_kafka_batch* batches, ysb_kafka_frame* frames,
                         uint64_t cap, ysb_lz4_frame_block* blocks, uint64_t block_cap, ysb_kafka_lz4_summary* info) {
     if (nbytes && !bytes) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: NULL buffer");
-    if (flags & ~YSB_KAFKA_CHECK_CRC) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: unknown flags %#x", flags);
+    if (flags & ~(YSB_KAFKA_CHECK_CRC | YSB_KAFKA_CHECK_CRC_CONTROL)) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: unknown flags %#x", flags);
     if (!batches != !frames) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: batches and frames go together");
     KafkaError err;
     const int rc = kafka_index_lz4(bytes, nbytes, flags, batches, frames, batches ? cap : 0, blocks, blocks ? block_cap : 0, info, &err);

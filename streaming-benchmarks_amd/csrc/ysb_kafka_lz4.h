@@ -65,7 +65,7 @@ inline int kafka_index_lz4(const u8* bytes, u64 nbytes, u32 flags, ysb_kafka_bat
         if (count < 0) return refuse("recordsCount", count, "negative");
         const u64 span = (u64)KAFKA_LEN_BASE + (u64)batch_len;
         if (nbytes - pos < span) break;   // the tail of a fetch response
-        if (flags & YSB_KAFKA_CHECK_CRC) {
+        if (kafka_index_checks_crc(flags, attributes)) {
             const u32 want = (u32)kafka_be(h + 17, 4), got = kafka_crc32c(h + KAFKA_CRC_FROM, span - KAFKA_CRC_FROM);
             if (want != got) return refuse("crc", (long long)want, "the batch's CRC-32C differs");
             ++s.crc_checked;
@@ -209,10 +209,17 @@ inline u32 kafka_inflate_batch(const u8* bytes, const ysb_kafka_frame& f, const 
 inline int kafka_unframe_lz4(const u8* bytes, u64 nbytes, const ysb_kafka_batch* batches, const ysb_kafka_frame* frames,
                              u64 n_batches, const ysb_lz4_frame_block* blocks, u64 n_blocks, u8* out, u64 out_cap,
                              u32* line_off, u64 off_cap, u64* n_lines, u64* out_bytes, u64* inflated,
-                             ysb_kafka_counters* counters, ysb_kafka_verdict* verdict, KafkaError* err) {
+                             ysb_kafka_counters* counters, ysb_kafka_verdict* verdict, KafkaError* err,
+                             bool check_crc = false) {
     ysb_kafka_counters ct{};
     ysb_kafka_verdict vd{0, KAFKA_NONE, 0, 0};
     u64 first = 0;
+    u32 bad_want = 0, bad_got = 0;
+    if (check_crc && kafka_crc_entries_ok(batches, n_batches) != n_batches) {
+        std::snprintf(err->msg, sizeof err->msg, "index entry %llu: fewer than 44 bytes in front of its records, where the stored "
+                      "CRC lies", (unsigned long long)kafka_crc_entries_ok(batches, n_batches));
+        return YSB_ERR_ARG;
+    }
     if (int rc = kafka_lz4_entries(batches, frames, n_batches, blocks, n_blocks, nbytes, &first, nullptr, nullptr, nullptr, err))
         return rc;
     if (n_lines) *n_lines = first;
@@ -229,9 +236,13 @@ inline int kafka_unframe_lz4(const u8* bytes, u64 nbytes, const ysb_kafka_batch*
         const u64 at0 = at;
         u64 total = 0;
         if (scratch.size() < (u64)frames[k].n_blocks * LZ4_MAX_RAW) scratch.resize((u64)frames[k].n_blocks * LZ4_MAX_RAW);
-        u32 rule = KAFKA_OK;
-        const u32 bad_block = kafka_inflate_batch(bytes, frames[k], blocks, scratch.data(), &total);
-        if (bad_block != KAFKA_NONE) {
+        u32 rule = KAFKA_OK, want = 0, got = 0;
+        // the CRC is over the wire bytes and comes first: a batch that fails it is not inflated
+        const bool crc_bad = check_crc && kafka_crc_differs(bytes, batches[k], &want, &got);
+        const u32 bad_block = crc_bad ? KAFKA_NONE : kafka_inflate_batch(bytes, frames[k], blocks, scratch.data(), &total);
+        if (crc_bad) {
+            rule = KAFKA_R_CRC;
+        } else if (bad_block != KAFKA_NONE) {
             rule = KAFKA_R_CODEC;
             bad_rec = bad_block;
         } else {
@@ -244,6 +255,8 @@ inline int kafka_unframe_lz4(const u8* bytes, u64 nbytes, const ysb_kafka_batch*
         }
         if (rule) {
             if (!vd.bad_batches) {
+                bad_want = want;
+                bad_got = got;
                 vd.first_bad = (u32)k;
                 vd.record = bad_rec;
                 vd.rule = rule;
@@ -263,9 +276,8 @@ inline int kafka_unframe_lz4(const u8* bytes, u64 nbytes, const ysb_kafka_batch*
     if (out_bytes) *out_bytes = at;
     if (inflated) *inflated = infl;
     if (vd.bad_batches) {
-        std::snprintf(err->msg, sizeof err->msg, "Kafka batch %u (baseOffset %lld), %s %u: %s (%u bad batches in all)",
-                      vd.first_bad, (long long)batches[vd.first_bad].base_offset, vd.rule == KAFKA_R_CODEC ? "block" : "record",
-                      vd.record, kafka_rule_name(vd.rule), vd.bad_batches);
+        kafka_bad_batch_message(err->msg, sizeof err->msg, "", vd.first_bad, (long long)batches[vd.first_bad].base_offset, vd.rule,
+                                vd.record, bad_want, bad_got, vd.bad_batches, "");
         return YSB_ERR_FORMAT;
     }
     if (at > 0xFFFFFFFFull || (out && at > out_cap)) {

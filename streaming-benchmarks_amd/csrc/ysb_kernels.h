@@ -515,6 +515,24 @@ hipError_t launch_kafka_base(const KafkaParams& p, hipStream_t s);
 // the total); nothing at all when head says a batch is bad or the values do not fit.
 hipError_t launch_kafka_gather(const KafkaParams& p, hipStream_t s);
 
+// CRC-32C of the indexed batches (ysb_kafka_crc.h), between the walk and the base kernel: one
+// wave per batch at a time, a bounded grid looping over the batches so that the copy of the 16
+// KiB of tables into LDS amortises.
+struct KafkaCrcParams {
+    const u8* bytes;            // the wire bytes, any alignment
+    const ysb_kafka_batch* batches;   // [n_batches] the host's index: records_off >= 44, the host checked
+    u32 n_batches;
+    const u32* tables;          // CRC_TABLE_WORDS (distance CRC_WIN), then CRC_CONST_WORDS
+    uint2* crc;                 // [n_batches] out: {computed, stored}
+    KafkaBatchOut* bout;        // [n_batches] a batch whose CRC differs becomes rule 9; NULL: the values only
+};
+constexpr u32 KAFKA_CRC_TPB = 256;           // four waves: four batches at a time
+constexpr u32 KAFKA_CRC_WGS_PER_CU = 4;      // the grid's bound
+// Only the 16-byte vectors that hold [records_off - 44, records_off + records_bytes) of a batch
+// are read.  Asynchronous on s; n_batches >= 1.
+hipError_t launch_kafka_crc(const KafkaCrcParams& p, u32 cus, hipStream_t s);
+inline u32 kafka_crc_grid_waves(u32 cus) { return cus * KAFKA_CRC_WGS_PER_CU * (KAFKA_CRC_TPB / 64); }
+
 
 // LZ4-compressed Kafka batches (ysb_kafka_lz4.h): between the measure pass and the decode, one
 // launch turns the measured sizes into the decode's descriptors AND the walk's index.

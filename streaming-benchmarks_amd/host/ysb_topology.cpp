@@ -619,6 +619,8 @@ void GpuAdCampaignOperator::submitKafkaLz4(const uint8_t* bytes, uint64_t nbytes
     waitS_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 }
 
+void GpuAdCampaignOperator::setKafkaCrc(int mode) { check(ysb_kafka_set_crc(ctx_, mode), "ysb_kafka_set_crc"); }
+
 ysb_kafka_lz4_desc GpuAdCampaignOperator::kafkaLz4Info() {
     ysb_kafka_lz4_desc d{};
     check(ysb_kafka_lz4_info(ctx_, &d), "ysb_kafka_lz4_info");

@@ -201,6 +201,9 @@ public:
     // `bytes`, first_record running from 0) as one batch: through the slot, or (mapped) read where
     // it lies in the registered mapping.
     void submitKafka(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, uint64_t nBatches, bool mapped);
+    // ysb_kafka_set_crc: the Kafka submits verify every batch's CRC-32C on the GPU (a batch whose
+    // CRC differs drops its slot batch: the sticky error is thrown by the call that meets it)
+    void setKafkaCrc(int mode);
     // The same for batches that may be LZ4-compressed (ysb_kafka_index_lz4's three arrays, offsets
     // relative to `bytes`): inflated on the GPU in front of the unframing (ysb_submit_kafka_lz4).
     void submitKafkaLz4(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, const ysb_kafka_frame* frames,

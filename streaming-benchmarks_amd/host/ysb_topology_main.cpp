@@ -68,6 +68,10 @@ struct Args {
     // --kafka --kafka-codec lz4): inflated on the GPU in front of the unframing (ysb_submit_kafka_lz4).
     // Without it a compressed segment is refused, as before.
     std::string kafka_codec;
+    // --kafka-check-crc device|host|off: every data batch's CRC-32C verified on the GPU in front of
+    // its records (ysb_kafka_set_crc; the control batches the index skips on the host), or all of
+    // them on the host at index time (a pass over the bytes), or not at all (the default)
+    std::string kafka_check_crc = "off";
     // streaming mode (configs[4]): --stream plus its options (ysb_stream.hpp)
     bool stream = false;
     StreamOptions so;
@@ -85,7 +89,8 @@ void usage() {
                  "       [--format json|tbl] [--flush-ms MS] [--batch-mb MB | --batch-bytes B] [--batch-events N]\n"
                  "       [--window-ring W] [--require-ip] [--dry-run] [--print-config] [--replay-rows CSV]\n"
                  "       [--host-split] [--repeat K] [--io-threads T] [--io auto|mapped|mmap|pread]\n"
-                 "       [--h2d-sdma] [--join-redis [--park-capacity N]] [--lz4] [--kafka [--kafka-codec lz4]]\n"
+                 "       [--h2d-sdma] [--join-redis [--park-capacity N]] [--lz4] [--kafka [--kafka-codec lz4]\n"
+                 "       [--kafka-check-crc device|host|off]]\n"
                  "   or: ysb_topology --confPath PATH --columns [--device N] [--format json|tbl] [--require-ip]\n"
                  "       [--batch-mb MB | --batch-bytes B]   (window.size rows per <shared_file>_<k>)\n"
                  "   or: ysb_topology --confPath PATH --from-columns [--device N] [--sink none|csv:FILE|redis[:HOST[:PORT]]]\n"
@@ -134,7 +139,13 @@ Args parse(int argc, char** argv) {
         else if (k == "--park-capacity") a.park_capacity = std::max(1ll, std::atoll(val().c_str()));
         else if (k == "--lz4") a.lz4 = true;
         else if (k == "--kafka") a.kafka = true;
-        else if (k == "--kafka-codec") {
+        else if (k == "--kafka-check-crc") {
+            a.kafka_check_crc = val();
+            if (a.kafka_check_crc != "device" && a.kafka_check_crc != "host" && a.kafka_check_crc != "off") {
+                std::fprintf(stderr, "--kafka-check-crc %s: device, host or off\n", a.kafka_check_crc.c_str());
+                std::exit(2);
+            }
+        } else if (k == "--kafka-codec") {
             a.kafka_codec = val();
             if (a.kafka_codec != "lz4") {
                 std::fprintf(stderr, "--kafka-codec %s: lz4 is the codec that is read (gzip, snappy and zstd are not)\n",
@@ -198,6 +209,10 @@ Args parse(int argc, char** argv) {
     if (a.kafka && (a.stream || a.columns || a.from_columns || a.lz4 || a.host_split)) {
         std::fprintf(stderr, "--kafka reads events_path as a log segment of record batches in batch mode: not with --stream, "
                              "--columns, --from-columns, --lz4 or --host-split\n");
+        std::exit(2);
+    }
+    if (a.kafka_check_crc != "off" && !a.kafka) {
+        std::fprintf(stderr, "--kafka-check-crc verifies a log segment's batches: only with --kafka\n");
         std::exit(2);
     }
     if (!a.kafka_codec.empty() && !a.kafka) {
@@ -480,6 +495,9 @@ int run(const Args& a) {
         }
     }
     uint64_t kafka_compressed = 0, kafka_inflated = 0;
+    const uint32_t kafka_index_flags = a.kafka_check_crc == "host" ? YSB_KAFKA_CHECK_CRC
+                                       : a.kafka_check_crc == "device" ? YSB_KAFKA_CHECK_CRC_CONTROL : 0u;
+    if (a.kafka && a.kafka_check_crc == "device") op.setKafkaCrc(YSB_KAFKA_CRC_DEVICE);
     if (a.kafka && !a.kafka_codec.empty()) {
         // the three arrays of ysb_kafka_index_lz4; runs of whole batches by the slot's bytes and lines
         // and by the guaranteed bound on what they inflate to: 64 KiB per block
@@ -488,12 +506,12 @@ int run(const Args& a) {
         const uint8_t* fb = kafka_mapped ? src.mapping() : reinterpret_cast<const uint8_t*>(file.data());
         const uint64_t fn = kafka_mapped ? src.fileBytes() : file.size();
         ysb_kafka_lz4_summary sum{};
-        int rc = ysb_kafka_index_lz4(fb, fn, 0, nullptr, nullptr, 0, nullptr, 0, &sum);
+        int rc = ysb_kafka_index_lz4(fb, fn, kafka_index_flags, nullptr, nullptr, 0, nullptr, 0, &sum);
         if (rc && rc != YSB_ERR_CAPACITY) throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
         std::vector<ysb_kafka_batch> idx(sum.n_batches);
         std::vector<ysb_kafka_frame> frames(sum.n_batches);
         std::vector<ysb_lz4_frame_block> blocks(sum.blocks);
-        if (sum.n_batches && ysb_kafka_index_lz4(fb, fn, 0, idx.data(), frames.data(), idx.size(), blocks.data(), blocks.size(), &sum))
+        if (sum.n_batches && ysb_kafka_index_lz4(fb, fn, kafka_index_flags, idx.data(), frames.data(), idx.size(), blocks.data(), blocks.size(), &sum))
             throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
         if (sum.consumed != fn)
             std::fprintf(stderr, "note: %llu bytes behind the segment's last whole batch are left alone\n",
@@ -547,10 +565,10 @@ int run(const Args& a) {
         const uint8_t* fb = kafka_mapped ? src.mapping() : reinterpret_cast<const uint8_t*>(file.data());
         const uint64_t fn = kafka_mapped ? src.fileBytes() : file.size();
         ysb_kafka_summary sum{};
-        int rc = ysb_kafka_index(fb, fn, 0, nullptr, 0, &sum);
+        int rc = ysb_kafka_index(fb, fn, kafka_index_flags, nullptr, 0, &sum);
         if (rc && rc != YSB_ERR_CAPACITY) throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
         std::vector<ysb_kafka_batch> idx(sum.n_batches);
-        if (sum.n_batches && ysb_kafka_index(fb, fn, 0, idx.data(), idx.size(), &sum))
+        if (sum.n_batches && ysb_kafka_index(fb, fn, kafka_index_flags, idx.data(), idx.size(), &sum))
             throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
         if (sum.consumed != fn)
             std::fprintf(stderr, "note: %llu bytes behind the segment's last whole batch are left alone\n",

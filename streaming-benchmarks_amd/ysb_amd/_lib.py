@@ -199,6 +199,11 @@ class YsbKafkaDesc(C.Structure):
                 ("verdict", YsbKafkaVerdict), ("walk_ms", C.c_double), ("base_ms", C.c_double), ("gather_ms", C.c_double)]
 
 
+class YsbKafkaCrcDesc(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "mode", "batches", "bytes", "bad_batches", "first_bad")] + [
+                ("stored", C.c_uint32), ("computed", C.c_uint32), ("grid_waves", C.c_uint64), ("crc_ms", C.c_double)]
+
+
 class YsbKafkaFrame(C.Structure):
     _fields_ = [("first_block", C.c_uint64), ("n_blocks", C.c_uint32), ("codec", C.c_uint32)]
 
@@ -312,6 +317,12 @@ SIGNATURES = {
     "ysb_submit_kafka_lz4": (_I, [_P, _I, _PU8, _U64, _P, _P, _U64, _P, _U64]),
     "ysb_submit_kafka_lz4_mapped": (_I, [_P, _I, _PU8, _U64, _P, _P, _U64, _P, _U64]),
     "ysb_kafka_lz4_info": (_I, [_P, C.POINTER(YsbKafkaLz4Desc)]),
+    "ysb_kafka_set_crc": (_I, [_P, _I]),
+    "ysb_kafka_crc_device": (_I, [_P, _PU8, _U64, _P, _U64, _PU32, _PU32]),
+    "ysb_kafka_crc_info": (_I, [_P, C.POINTER(YsbKafkaCrcDesc)]),
+    "ysb_kafka_crc_desc_size": (_U64, []),
+    "ysb_kafka_verdict_crc_host": (_I, [_PU8, _U64, _P, _U64, C.POINTER(YsbKafkaVerdict)]),
+    "ysb_kafka_verdict_crc_lz4_host": (_I, [_PU8, _U64, _P, _P, _U64, _P, _U64, C.POINTER(YsbKafkaVerdict)]),
     "ysb_kafka_frame_size": (_U64, []),
     "ysb_kafka_lz4_summary_size": (_U64, []),
     "ysb_kafka_lz4_desc_size": (_U64, []),
@@ -490,6 +501,7 @@ def lib():
                        (L.ysb_kafka_summary_size, YsbKafkaSummary), (L.ysb_kafka_verdict_size, YsbKafkaVerdict),
                        (L.ysb_kafka_counters_size, YsbKafkaCounters), (L.ysb_kafka_pack_opts_size, YsbKafkaPackOpts),
                        (L.ysb_kafka_desc_size, YsbKafkaDesc), (L.ysb_kafka_frame_size, YsbKafkaFrame),
+                       (L.ysb_kafka_crc_desc_size, YsbKafkaCrcDesc),
                        (L.ysb_kafka_lz4_summary_size, YsbKafkaLz4Summary), (L.ysb_kafka_lz4_desc_size, YsbKafkaLz4Desc)):
             if fn() != C.sizeof(st):
                 raise ImportError("%s is %d bytes in the library, %d in this binding"

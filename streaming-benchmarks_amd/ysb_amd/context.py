@@ -484,6 +484,33 @@ class YsbContext:
                                                    C.c_void_p(d_line_off), off_cap, C.byref(n), C.byref(nb)))
         return n.value, nb.value
 
+    def kafka_set_crc(self, mode):
+        """ysb_kafka_set_crc: 0 off (the default), 1 (ysb_amd.kafka.CRC_DEVICE) every indexed
+        batch's CRC-32C verified on the GPU by the Kafka submits and unframe calls; a batch whose
+        CRC differs is bad by rule 9.  Kept across reset()."""
+        self._c(lib().ysb_kafka_set_crc(self._h, int(mode)))
+
+    def kafka_crc_device(self, d_bytes, nbytes, index):
+        """ysb_kafka_crc_device: the CRC kernel alone over the indexed batches of a device buffer.
+        Returns (computed, stored) as uint32 arrays, one entry per batch."""
+        idx = np.ascontiguousarray(index)
+        got, want = np.zeros(max(idx.size, 1), dtype=np.uint32), np.zeros(max(idx.size, 1), dtype=np.uint32)
+        self._c(lib().ysb_kafka_crc_device(self._h, C.c_void_p(d_bytes), nbytes, _ptr(idx), idx.size, _ptr(got), _ptr(want)))
+        return got[:idx.size], want[:idx.size]
+
+    def kafka_crc_info(self, check=True):
+        """ysb_kafka_crc_info as a dict: the last call that verified CRCs on the device (calls,
+        mode, batches, bytes, bad_batches, first_bad or None, stored, computed, grid_waves, and
+        with timing=True crc_ms)."""
+        d = _lib.YsbKafkaCrcDesc()
+        rc = lib().ysb_kafka_crc_info(self._h, C.byref(d))
+        if check:
+            self._c(rc)
+        out = {n: getattr(d, n) for n, _ in d._fields_}
+        if out["first_bad"] == 0xFFFFFFFF:
+            out["first_bad"] = None
+        return out
+
     def kafka_lz4_info(self, check=True):
         """ysb_kafka_lz4_info as a dict: the inflate half of the last compressed Kafka call settled
         (calls, blocks, stored_blocks, compressed_batches, wire_bytes, inflated_bytes, bad_blocks,

@@ -12,13 +12,15 @@ from . import _lib
 from ._lib import check, lib
 
 CHECK_CRC = 1
+CHECK_CRC_CONTROL = 2   # only the control batches the index skips: the rest is the device's (CRC_DEVICE)
+CRC_OFF, CRC_DEVICE = 0, 1   # YsbContext.kafka_set_crc
 BATCH = np.dtype([("records_off", "<u8"), ("records_bytes", "<u4"), ("n_records", "<u4"), ("first_record", "<u8"),
                   ("base_offset", "<i8"), ("control_before", "<u4"), ("reserved", "<u4")])
 FRAME = np.dtype([("first_block", "<u8"), ("n_blocks", "<u4"), ("codec", "<u4")])
 BLOCK = np.dtype([("offset", "<u8"), ("comp_bytes", "<u4"), ("reserved", "<u4")])   # ysb_lz4_frame_block
 CODEC_LZ4 = 3
 RULES = {0: "none", 1: "varint", 2: "length", 3: "past_batch", 4: "key", 5: "value", 6: "headers", 7: "count",
-         8: "codec"}
+         8: "codec", 9: "crc"}
 DEFAULT_BATCH = 16384   # a producer's default batch.size
 
 
@@ -33,14 +35,19 @@ def crc32c(data):
     return lib().ysb_kafka_crc32c(src.ctypes.data if src.size else None, src.size)
 
 
-def index(data, check_crc=False):
+def _index_flags(check_crc, check_control_crc):
+    return (CHECK_CRC if check_crc else 0) | (CHECK_CRC_CONTROL if check_control_crc else 0)
+
+
+def index(data, check_crc=False, check_control_crc=False):
     """ysb_kafka_index: (index, summary dict) of a buffer of record batches.  index is a BATCH
     array with one entry per data batch; summary["consumed"] stops in front of a last batch that
     is not whole.  Raises YsbError (YSB_ERR_FORMAT) naming the byte offset, the field and the rule
     for a batch the library does not take (magic other than 2, a codec, batchLength < 49, a negative
-    recordsCount, with check_crc a CRC-32C mismatch)."""
+    recordsCount, with check_crc a CRC-32C mismatch; check_control_crc verifies only the control
+    batches the index skips, which the device's check never sees)."""
     src = _u8(data)
-    flags = CHECK_CRC if check_crc else 0
+    flags = _index_flags(check_crc, check_control_crc)
     info = _lib.YsbKafkaSummary()
     p = src.ctypes.data if src.size else None
     rc = lib().ysb_kafka_index(p, src.size, flags, None, 0, C.byref(info))
@@ -52,7 +59,7 @@ def index(data, check_crc=False):
     return idx, {k: getattr(info, k) for k, _ in info._fields_}
 
 
-def index_lz4(data, check_crc=False):
+def index_lz4(data, check_crc=False, check_control_crc=False):
     """ysb_kafka_index_lz4: (batches, frames, blocks, summary dict) of a buffer whose record
     batches are uncompressed (codec 0) or LZ4-compressed (codec 3).  batches is a BATCH array
     (records_off / records_bytes: the wire bytes), frames a FRAME array with one entry per batch,
@@ -60,7 +67,7 @@ def index_lz4(data, check_crc=False):
     what `index` refuses, for gzip, snappy and zstd by name, and for a frame the LZ4 frame index
     refuses (naming the Kafka batch, its byte, and the frame's byte and rule)."""
     src = _u8(data)
-    flags = CHECK_CRC if check_crc else 0
+    flags = _index_flags(check_crc, check_control_crc)
     info = _lib.YsbKafkaLz4Summary()
     p = src.ctypes.data if src.size else None
     rc = lib().ysb_kafka_index_lz4(p, src.size, flags, None, None, 0, None, 0, C.byref(info))
@@ -118,6 +125,43 @@ def _unframe_lz4(data, idx, frames, blocks, sizes_only):
     c = {k: getattr(ct, k) for k, _ in ct._fields_}
     c["inflated_bytes"] = infl.value
     return out, off, c, v, rc
+
+
+def _verdict_dict(vd):
+    v = {k: getattr(vd, k) for k, _ in vd._fields_}
+    if v["first_bad"] == 0xFFFFFFFF:
+        v["first_bad"] = None
+    return v
+
+
+def verdict_crc(data, idx, raises=False):
+    """ysb_kafka_verdict_crc_host: the model's verdict when every batch's CRC-32C is checked in
+    front of its records (rule 9), as a dict.  raises=True: YsbError for a bad batch, its message
+    naming the stored and the computed value."""
+    src = _u8(data)
+    idx = np.ascontiguousarray(idx, dtype=BATCH)
+    vd = _lib.YsbKafkaVerdict()
+    rc = lib().ysb_kafka_verdict_crc_host(src.ctypes.data if src.size else None, src.size,
+                                          idx.ctypes.data if idx.size else None, idx.size, C.byref(vd))
+    if rc != -5 or raises:
+        check(rc)
+    return _verdict_dict(vd)
+
+
+def verdict_crc_lz4(data, idx, frames, blocks, raises=False):
+    """ysb_kafka_verdict_crc_lz4_host: verdict_crc for batches indexed by index_lz4 (the CRC is
+    over the wire bytes and comes in front of the decode: rule 9, not 8)."""
+    src = _u8(data)
+    idx = np.ascontiguousarray(idx, dtype=BATCH)
+    frames = np.ascontiguousarray(frames, dtype=FRAME)
+    blocks = np.ascontiguousarray(blocks, dtype=BLOCK)
+    vd = _lib.YsbKafkaVerdict()
+    rc = lib().ysb_kafka_verdict_crc_lz4_host(src.ctypes.data if src.size else None, src.size,
+                                              idx.ctypes.data if idx.size else None, frames.ctypes.data if frames.size else None,
+                                              idx.size, blocks.ctypes.data if blocks.size else None, blocks.size, C.byref(vd))
+    if rc != -5 or raises:
+        check(rc)
+    return _verdict_dict(vd)
 
 
 def unframe_host(data, idx, sizes_only=False):

@@ -231,10 +231,17 @@ class KafkaLogDataSource:
     reads one 61-byte header per batch).  A tail that is not a whole batch is left alone.
     codecs=("lz4",): the segment's batches may be LZ4-compressed (ysb_gen --kafka --kafka-codec lz4);
     runs are then also cut by the guaranteed bound on what they inflate to, 65536 bytes per block,
-    and submitted with ysb_submit_kafka_lz4_mapped.  Without it a compressed batch is refused."""
+    and submitted with ysb_submit_kafka_lz4_mapped.  Without it a compressed batch is refused.
+    check_crc: True verifies every batch's CRC-32C on the host at index time; "device" leaves the
+    data batches to the GPU (`run` turns ysb_kafka_set_crc on for its submits) and verifies on the
+    host only the control batches the index skips."""
 
-    def __init__(self, path: str, check_crc: bool = False, codecs=()):
+    def __init__(self, path: str, check_crc=False, codecs=()):
         from . import kafka
+        if check_crc not in (False, True, "device"):
+            raise ValueError("check_crc %r: False, True (the host pass) or \"device\"" % (check_crc,))
+        self.crc_device = check_crc == "device"
+        check_control, check_crc = self.crc_device, check_crc is True
         self.path = str(path)
         self.size = os.path.getsize(self.path)
         self._mm = None
@@ -249,9 +256,10 @@ class KafkaLogDataSource:
         self.lz4 = "lz4" in codecs
         self.frames = self.blocks = None
         if self.lz4:
-            self.index, self.frames, self.blocks, self.summary = kafka.index_lz4(self.data, check_crc=check_crc)
+            self.index, self.frames, self.blocks, self.summary = kafka.index_lz4(self.data, check_crc=check_crc,
+                                                                                check_control_crc=check_control)
         else:
-            self.index, self.summary = kafka.index(self.data, check_crc=check_crc)
+            self.index, self.summary = kafka.index(self.data, check_crc=check_crc, check_control_crc=check_control)
         self.framed_bytes = 0
         self.batches = 0
 
@@ -281,10 +289,14 @@ class KafkaLogDataSource:
     def run(self, ctx, cap: int):
         """Every run of the segment through ctx (a YsbContext), in place; returns the framed
         bytes submitted.  At most two batches in flight."""
+        from . import kafka
         max_bytes, max_events = ctx.slot_capacity()
         max_records = max(max_events, max_bytes // 32)
         if self.size:
             ctx.host_register(self.data, self.mapping_bytes)
+        crc_before = ctx.kafka_crc_info()["mode"] if self.crc_device else None
+        if self.crc_device:
+            ctx.kafka_set_crc(kafka.CRC_DEVICE)
         try:
             slot = 0
             for off, nbytes, b, k in self.runs(min(cap, max_bytes), max_records):
@@ -306,6 +318,8 @@ class KafkaLogDataSource:
                 self.batches += 1
             ctx.sync()
         finally:
+            if self.crc_device:
+                ctx.kafka_set_crc(crc_before)      # the context's setting is the caller's again
             if self.size:
                 ctx.host_unregister(self.data)
         return self.framed_bytes

@@ -21,6 +21,14 @@ Per compressed leg also the wire bytes per event, the measured compression ratio
 per slot batch and which stage bounds it; plus the six kernels alone (measure, plan, decode, walk,
 base, gather by HIP events, the median of five after two warm-ups).  Those figures go to
 profiles/kafka_lz4_bench.json.
+
+With --crc every Kafka leg (with --lz4 the compressed ones too) also runs with each batch's CRC-32C verified: on the device
+(ysb_kafka_set_crc: one more launch between the walk and the scan of the totals) and on the host at
+index time (ysb_kafka_index with YSB_KAFKA_CHECK_CRC inside the timed loop, once per submit),
+alternating with the unverified legs in the same process; plus the CRC kernel alone
+(ysb_kafka_crc_device, HIP events).  Per batch size the medians, each verified leg as a ratio to
+the unverified leg of the same run, and whether the device leg's median lies within the spread of
+the unverified leg's repeats.  Those figures go to profiles/kafka_crc_bench.json.
 """
 from __future__ import annotations
 
@@ -58,6 +66,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kafka_bench.json"))
     ap.add_argument("--lz4", action="store_true", help="add the LZ4-compressed legs (profiles/kafka_lz4_bench.json)")
     ap.add_argument("--lz4-out", default=os.path.join(ROOT, "profiles", "kafka_lz4_bench.json"))
+    ap.add_argument("--crc", action="store_true", help="add the CRC-verified legs (profiles/kafka_crc_bench.json)")
+    ap.add_argument("--crc-out", default=os.path.join(ROOT, "profiles", "kafka_crc_bench.json"))
     a = ap.parse_args()
 
     from ysb_amd import GenParams, YsbContext, kafka
@@ -71,6 +81,8 @@ def main():
            "unframe_alone": []}
     zres = {"events_per_raw_batch": per, "slot_MB": a.slot_mb, "repeats": a.repeats, "batch_sizes": sizes,
             "blocks_per_slot_batch_cap": slot_bytes // 65536, "legs": [], "kernels_alone": []}
+    cres = {"events_per_batch": per, "slot_MB": a.slot_mb, "repeats": a.repeats, "batch_sizes": sizes, "legs": [],
+            "kernel_alone": []}
     with YsbContext(device=a.device, n_campaigns=100, window_ring=1024, timing=True, max_batch_bytes=slot_bytes,
                     max_batch_events=per, ring_base_bucket=g.c.t0_ms // 10000 - 8) as ctx:
         ctx.load_ad_map(aids, g.ad_campaign_index())
@@ -86,7 +98,8 @@ def main():
         raw_bytes = sum(r.size for r in raw)
         slot = [view(ctx.slot_buffers(s)[0], slot_bytes) for s in (0, 1)]
 
-        def leg(kind, blobs, idxs, reg, at):
+        def leg(kind, blobs, idxs, reg, at, crc="off"):
+            ctx.kafka_set_crc(1 if crc == "device" else 0)
             for s in (0, 1):   # staged once per leg: the slot's pinned buffer holds what crosses PCIe
                 ctx.wait(s)
                 if kind in ("raw", "kafka"):
@@ -94,6 +107,8 @@ def main():
                     slot[s][:src.size] = src
 
             def submit(s):
+                if crc == "host":   # what a caller without the device check does per fetch response: a pass over the bytes
+                    assert kafka.index(blobs[s], check_crc=True)[1]["crc_checked"] == idxs[s].size
                 if kind == "raw":
                     check(lib().ysb_submit_raw(ctx._h, s, C.c_void_p(slot[s].ctypes.data), raw[s].size), ctx._h)
                 elif kind == "kafka":
@@ -117,6 +132,8 @@ def main():
             cms, copies, cbytes = ctx.copy_time()
             st = ctx.stats()
             info = ctx.kafka_info() if kind != "raw" else None
+            cinfo = ctx.kafka_crc_info() if crc == "device" else None
+            ctx.kafka_set_crc(0)
             for i in range(nsub):
                 ctx.truth_accumulate(g, (i & 1) * per, per)
             mism, truth, counted = ctx.truth_compare()
@@ -131,12 +148,18 @@ def main():
                 out.update(walk_ms_last_batch=round(info["walk_ms"], 4), base_ms_last_batch=round(info["base_ms"], 4),
                            gather_ms_last_batch=round(info["gather_ms"], 4), kafka_batches_last_batch=info["batches"],
                            bad_batches=info["verdict"]["bad_batches"])
+            if crc != "off":
+                out["leg"] = kind + "+crc_" + crc
+            if cinfo:
+                out.update(crc_ms_last_batch=round(cinfo["crc_ms"], 4), crc_batches_last_batch=cinfo["batches"],
+                           crc_bad_batches=cinfo["bad_batches"], crc_calls=cinfo["calls"])
             log(json.dumps(out))
             return out
 
-        def leg_lz4(kind, z, reg, at):
+        def leg_lz4(kind, z, reg, at, crc="off"):
             """A compressed leg: z holds per staged batch the wire bytes, the three index arrays and
             the events of the Kafka batches that fit a slot batch by the capacity rule."""
+            ctx.kafka_set_crc(1 if crc == "device" else 0)
             for s in (0, 1):
                 ctx.wait(s)
                 if kind == "kafka_lz4":
@@ -144,6 +167,8 @@ def main():
 
             def submit(s):
                 b, i, f, k = z["blobs"][s], z["idx"][s], z["frames"][s], z["blocks"][s]
+                if crc == "host":
+                    assert kafka.index_lz4(b, check_crc=True)[3]["crc_checked"] == i.size
                 if kind == "kafka_lz4":
                     check(lib().ysb_submit_kafka_lz4(ctx._h, s, C.c_void_p(slot[s].ctypes.data), b.size, C.c_void_p(i.ctypes.data),
                                                      C.c_void_p(f.ctypes.data), i.size, C.c_void_p(k.ctypes.data), k.size), ctx._h)
@@ -166,6 +191,8 @@ def main():
             cms, copies, cbytes = ctx.copy_time()
             st = ctx.stats()
             info, li = ctx.kafka_info(), ctx.kafka_lz4_info()
+            cinfo = ctx.kafka_crc_info() if crc == "device" else None
+            ctx.kafka_set_crc(0)
             for i in range(nsub):
                 ctx.truth_accumulate(g, (i & 1) * per, ev[i & 1])
             mism, truth, counted = ctx.truth_compare()
@@ -188,6 +215,11 @@ def main():
                    "bad_batches": info["verdict"]["bad_batches"],
                    "check": {"truth_mismatched_cells": mism, "truth_views": truth, "counted_views": counted,
                              "events": st["events"], "parse_errors": st["parse_errors"]}}
+            if crc != "off":
+                out["leg"] = kind + "+crc_" + crc
+            if cinfo:
+                out.update(crc_ms_last_batch=round(cinfo["crc_ms"], 4), crc_batches_last_batch=cinfo["batches"],
+                           crc_bad_batches=cinfo["bad_batches"], crc_calls=cinfo["calls"])
             log(json.dumps(out))
             return out
 
@@ -267,6 +299,17 @@ def main():
                                              walk_GBs_in=round(blobs[0].size / (w * 1e-3) / 1e9, 2),
                                              gather_GBs_out=round(raw[0].size / (gt * 1e-3) / 1e9, 2), output_equal=same))
             log(json.dumps(res["unframe_alone"][-1]))
+            if a.crc:   # the CRC kernel alone over the same bytes
+                cms_ = []
+                for _ in range(7):
+                    got, stored = ctx.kafka_crc_device(d_in, blobs[0].size, idxs[0])
+                    cms_.append(ctx.kafka_crc_info()["crc_ms"])
+                ci = ctx.kafka_crc_info()
+                cm = statistics.median(cms_[2:])
+                cres["kernel_alone"].append({"batch_bytes": size, "kafka_batches": int(idxs[0].size), "verified_bytes": ci["bytes"],
+                                             "crc_ms": round(cm, 4), "GBs": round(ci["bytes"] / (cm * 1e-3) / 1e9, 2) if cm else 0.0,
+                                             "all_equal_stored": bool((got == stored).all()), "grid_waves": ci["grid_waves"]})
+                log(json.dumps(cres["kernel_alone"][-1]))
             ctx.device_free(d_in)
             if a.unframe_only:
                 continue
@@ -297,8 +340,14 @@ def main():
                     res["legs"].append(dict(leg(kind, blobs, idxs, reg, at), batch_bytes=size, round=rep))
                     if z and kind == "raw":
                         zres["legs"].append(dict(res["legs"][-1]))
+                if a.crc:
+                    for kind, crc in (("kafka", "device"), ("kafka", "host"), ("kafka_mapped", "device"), ("kafka_mapped", "host")):
+                        cres["legs"].append(dict(leg(kind, blobs, idxs, reg, at, crc), batch_bytes=size, round=rep))
                 for kind in (("kafka_lz4", "kafka_lz4_mapped") if z else ()):
                     zres["legs"].append(dict(leg_lz4(kind, z, zreg, zat), batch_bytes=size, round=rep))
+                    if a.crc:
+                        for crc in ("device", "host"):
+                            cres["legs"].append(dict(leg_lz4(kind, z, zreg, zat, crc), batch_bytes=size, round=rep))
             ctx.sync()
             ctx.host_unregister(reg)
             if z:
@@ -329,6 +378,29 @@ def main():
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
+    if a.crc:
+        cs = {"kernel_alone": cres["kernel_alone"]}
+        for size in (sizes if not a.unframe_only else []):
+            cs[str(size)] = {}
+            for kind in ("kafka", "kafka_mapped") + (("kafka_lz4", "kafka_lz4_mapped") if a.lz4 else ()):
+                off = [l["events_per_s"] for l in res["legs"] + zres["legs"] if l["leg"] == kind and l["batch_bytes"] == size]
+                row = {"off": {"median": statistics.median(off), "min": min(off), "max": max(off)}}
+                for crc in ("device", "host"):
+                    e = [l["events_per_s"] for l in cres["legs"] if l["leg"] == kind + "+crc_" + crc and l["batch_bytes"] == size]
+                    row[crc] = {"median": statistics.median(e), "min": min(e), "max": max(e),
+                                "over_off_median": round(statistics.median(e) / statistics.median(off), 4)}
+                row["device_median_within_off_spread"] = min(off) <= row["device"]["median"] <= max(off)
+                cms_ = [l["crc_ms_last_batch"] for l in cres["legs"] if l["leg"] == kind + "+crc_device" and l["batch_bytes"] == size]
+                row["crc_ms_last_batch_median"] = statistics.median(cms_)
+                cs[str(size)][kind] = row
+        cs["all_checks_exact"] = all(l["check"]["truth_mismatched_cells"] == 0 and l["check"]["truth_views"] == l["check"]["counted_views"]
+                                     and l["check"]["events"] == l["events"] and l.get("crc_bad_batches", 0) == 0
+                                     for l in cres["legs"])
+        cres["summary"] = cs
+        with open(a.crc_out, "w") as f:
+            json.dump(cres, f, indent=1)
+            f.write("\n")
+        print(json.dumps(cs), flush=True)
     if a.lz4 and not a.unframe_only:
         zs = {"kernels_alone": zres["kernels_alone"], "all_inflated_equal": all(u["output_equal"] for u in zres["kernels_alone"])}
         for size in sizes:
