@@ -804,11 +804,16 @@ typedef struct ysb_kafka_pack_opts {
     uint32_t        n_headers;
     uint32_t        codec;           /* 0: uncompressed; YSB_KAFKA_CODEC_LZ4: each batch's records as one
                                         standard LZ4 frame (64 KiB independent blocks, a block that does not
-                                        shrink stored), attributes = 3, the CRC over the wire bytes; any
-                                        other value: YSB_ERR_ARG                                            */
+                                        shrink stored), attributes = 3, the CRC over the wire bytes;
+                                        YSB_KAFKA_CODEC_SNAPPY: as snappy (snappy_framing below), attributes
+                                        = 2; any other value: YSB_ERR_ARG                                   */
     const char* const*    header_keys;      /* NUL-terminated                  */
     const uint8_t* const* header_vals;
     const int32_t*        header_val_len;   /* -1: a null value                */
+    uint32_t        snappy_framing;  /* codec YSB_KAFKA_CODEC_SNAPPY: YSB_KAFKA_SNAPPY_XERIAL (0, the Java client's
+                                        stream of chunks) or _RAW (one raw block per batch, as librdkafka writes:
+                                        YSB_ERR_ARG where a batch's records pass 64 KiB)                     */
+    uint32_t        snappy_chunk;    /* raw bytes per xerial chunk: 0 takes the client's 32 KiB, at most 65536 */
 } ysb_kafka_pack_opts;
 uint64_t    ysb_kafka_bound(uint64_t nbytes, uint64_t n_lines, const ysb_kafka_pack_opts* opts);
 int         ysb_kafka_pack(const uint8_t* src, uint64_t nbytes, const uint32_t* line_off, uint64_t n_lines,
@@ -932,7 +937,7 @@ int         ysb_kafka_verdict_crc_host(const uint8_t* bytes, uint64_t nbytes, co
  * the frame's byte and rule (with the way out where ysb_lz4_frame_index gives one: linked blocks,
  * a block maximum above 64 KiB) for every frame refusal, truncation inside the records and bytes
  * behind the last frame included; codecs 1, 2 and 4 are refused by name (gzip, snappy, zstd:
- * have the producer write lz4 or none).  cap counts batches and frames, block_cap blocks;
+ * have the producer write lz4 or none; snappy is read with YSB_KAFKA_ACCEPT_SNAPPY, below).  cap counts batches and frames, block_cap blocks;
  * YSB_ERR_CAPACITY with info complete when either is short (NULL arrays with 0 caps count). */
 #define YSB_KAFKA_CODEC_LZ4 3u
 typedef struct ysb_kafka_frame {
@@ -1009,6 +1014,8 @@ typedef struct ysb_kafka_lz4_desc {
     double   measure_ms;         /* YSB_F_TIMING: HIP events around each kernel            */
     double   plan_ms;
     double   decode_ms;
+    uint64_t snappy_blocks;      /* of `blocks`: those tagged YSB_SNAPPY_BLOCK             */
+    double   preamble_ms;        /* YSB_F_TIMING: the snappy preamble kernel               */
 } ysb_kafka_lz4_desc;
 int         ysb_kafka_lz4_info(ysb_ctx* ctx, ysb_kafka_lz4_desc* info);
 int         ysb_kafka_verdict_crc_lz4_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
@@ -1018,6 +1025,62 @@ int         ysb_kafka_verdict_crc_lz4_host(const uint8_t* bytes, uint64_t nbytes
 uint64_t    ysb_kafka_frame_size(void);
 uint64_t    ysb_kafka_lz4_summary_size(void);
 uint64_t    ysb_kafka_lz4_desc_size(void);
+/* ---- snappy-compressed Kafka record batches (additive within ABI 6) -------------------------
+ * A topic whose producers set compression.type=snappy (attributes codec 2).  The 61-byte batch
+ * header stays as it is, the CRC-32C covers the wire bytes, and the records section is either the
+ * Java client's xerial stream -- a 16-byte header (magic 82 'SNAPPY' 00, version, compatible
+ * version 1) and chunks of a big-endian int32 length and one raw snappy block, 32 KiB of raw
+ * bytes by default -- or, without that magic, one raw block (librdkafka, sarama, kafka-python).
+ * A raw block opens with its raw size as a varint, so no measure pass runs over it: a thread per
+ * block reads the preamble (snappy_preamble_kernel), the plan and the rest of the compressed
+ * chain stay as they are, and snappy_decode_kernel decodes a block per wave beside the LZ4
+ * kernels, each skipping the other's blocks: a fetch response of codecs 0, 2 and 3 takes one call.
+ * Opt-in twice.  At the index: ysb_kafka_index_lz4 with YSB_KAFKA_ACCEPT_SNAPPY accepts codec 2
+ * (without the flag it stays refused by name): frames[k].codec = 2 and one block entry per chunk,
+ * or one for a raw block, offset at the preamble, comp_bytes the chunk's length |
+ * YSB_SNAPPY_BLOCK.  Refused, naming the Kafka batch, its byte, the chunk's byte and the rule: a
+ * compatible version other than 1, a chunk length <= 0 or past the records section, trailing
+ * bytes shorter than a length word, a preamble of more than 5 bytes or >= 2^32, and a block of 0
+ * or more than 65536 raw bytes -- larger raw blocks are chains of 64 KiB fragments whose
+ * compressed boundaries nothing records; the way out is the Java client's framing or a producer
+ * batch.size of at most 64 KiB.  At the context: ysb_kafka_set_codecs with YSB_KAFKA_CODECS_SNAPPY
+ * in the mask (the default, YSB_KAFKA_CODECS_DEFAULT, is none and lz4; the only other mask taken
+ * adds snappy; kept across ysb_reset) lets ysb_submit_kafka_lz4, _mapped and
+ * ysb_kafka_unframe_lz4_device take such an index; without it YSB_ERR_ARG, as before.  The host
+ * models (ysb_kafka_unframe_lz4_host, ysb_kafka_verdict_crc_lz4_host) have no context and take
+ * what the index wrote.  Capacity: a slot batch's snappy blocks count their preambles' raw
+ * sizes, every other block 65536, the sum at most max_batch_bytes; the plan kernel also makes
+ * a block bad whose extent would pass the inflated buffer (mapped memory may change under the
+ * host's read).  A block that breaks the format's rules is rule 8, as for LZ4. */
+#define YSB_KAFKA_CODEC_SNAPPY 2u
+#define YSB_KAFKA_ACCEPT_SNAPPY 0x100u     /* ysb_kafka_index_lz4's flags */
+#define YSB_SNAPPY_BLOCK 0x40000000u       /* ysb_lz4_frame_block.comp_bytes bit 30 */
+#define YSB_KAFKA_SNAPPY_XERIAL 0u
+#define YSB_KAFKA_SNAPPY_RAW 1u
+#define YSB_KAFKA_CODECS_DEFAULT 0x9u      /* codec 0 and codec 3 */
+#define YSB_KAFKA_CODECS_SNAPPY 0x4u
+int         ysb_kafka_set_codecs(ysb_ctx* ctx, uint32_t mask);
+/* Test support: the plan kernel refuses (rule 8) a batch whose inflated extent would end past the
+ * inflated buffer -- reachable otherwise only when registered memory changes under the host's
+ * capacity check.  A non-zero `bytes` below the buffer's size takes its place in the kernel's test
+ * for the compressed calls that follow; 0 (the default) and ysb_reset restore it.  Nothing else
+ * changes. */
+int         ysb_kafka_test_inflated_cap(ysb_ctx* ctx, uint64_t bytes);
+/* The capacity rule per Kafka batch, for a caller that cuts an index into slot batches: bounds[k]
+ * <- what batch k's blocks count -- a snappy block its preamble's raw size, every other block
+ * 65536.  A run of batches fits a slot when their sum is at most max_batch_bytes.  Host only; the
+ * entries are checked as ysb_kafka_unframe_lz4_host checks them (YSB_ERR_ARG). */
+int         ysb_kafka_inflate_bounds(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches,
+                                     const ysb_kafka_frame* frames, uint64_t n_batches,
+                                     const ysb_lz4_frame_block* blocks, uint64_t n_blocks, uint64_t* bounds);
+/* One snappy block by the host compressor and the host decoder (csrc/ysb_snappy.h; test inputs
+ * and the model of the kernel, no context).  compress: raw_bytes in 1..65536 into dst, cap at
+ * least 32 + raw_bytes + raw_bytes / 6; *comp_bytes the block's size, preamble included.
+ * decompress: src[0, comp_bytes) into dst (cap at least the preamble's size, 65536 always
+ * suffices); *raw_bytes the decoded size; YSB_ERR_FORMAT for a block that breaks the format's
+ * rules or says 0 or more than 65536 raw bytes. */
+int         ysb_snappy_compress_block(const uint8_t* src, uint32_t raw_bytes, uint8_t* dst, uint32_t cap, uint32_t* comp_bytes);
+int         ysb_snappy_decompress_block(const uint8_t* src, uint32_t comp_bytes, uint8_t* dst, uint32_t cap, uint32_t* raw_bytes);
 /* Device-resident batch (HBM pointers, e.g. from ysb_device_alloc). Asynchronous.  The batch
  * must be complete when submitted, or its producer ordered before the compute stream
  * (hipStreamWaitEvent(ysb_stream(ctx), ...), or produced on that stream).  Unless

@@ -856,6 +856,7 @@ int ysb_reset(ysb_ctx* c) {
     c->lz4f_more = false;
     c->kafka_last = ysb_kafka_desc{};
     c->kafka_lz4_last = ysb_kafka_lz4_desc{};
+    c->kafka_infl_cap_test = 0;   // (test support does not outlive a reset)
     c->kafka_crc_last = ysb_kafka_crc_desc{};   // (the mode stays: a context setting)
     if (c->d_carry) HIPCHK(c, hipMemset(c->d_carry, 0, LZ4_CARRY_HEAD));   // the carry is cleared
     return YSB_OK;

@@ -169,6 +169,8 @@ struct KafkaStaged {
     bool lz4 = false;
     u64 n_blocks = 0, stored_blocks = 0, compressed_batches = 0;
     u32 decoder = 0;                     // the decode kernel chosen when it was staged
+    u64 snappy_blocks = 0;               // of n_blocks: those tagged SNAPPY_BLOCK, and the largest raw size their
+    u32 snappy_max_raw = 0;              //   preambles gave the host (0: none; sizes the decode's LDS)
     u32 crc = 0;                         // ysb_kafka_set_crc's mode when it was staged; with it on, where in the
     u64 crc_back = 0;                    //   slot's pinned buffer the batches' {computed, stored} come back
 };
@@ -320,7 +322,9 @@ struct ysb_ctx {
     DevBuf<u8> d_kafka_infl_sync, d_kafka_lz4_sync;
     PinBuf<KafkaPlanHead> h_kafka_plan;
     ysb_kafka_lz4_desc kafka_lz4_last{};
-    Event ev_kafka_lz4[2][4];
+    Event ev_kafka_lz4[2][6];                   // (4, 5: around the snappy preamble kernel)
+    u32 kafka_codecs = YSB_KAFKA_CODECS_DEFAULT;   // ysb_kafka_set_codecs's mask, kept across ysb_reset
+    u64 kafka_infl_cap_test = 0;                   // ysb_kafka_test_inflated_cap: 0 (and after ysb_reset), or a smaller limit for the plan kernel
     // CRC-32C of Kafka batches on the device (ysb_kafka_crc.h; ysb_kafka_set_crc): the mode, kept
     // across ysb_reset; the kernel's tables and constants, built on the host and copied at the
     // first call that verifies; ysb_kafka_crc_device's scratch; the last call that verified.

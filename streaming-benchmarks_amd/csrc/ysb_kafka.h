@@ -416,6 +416,10 @@ inline u64 kafka_headers_bytes(const ysb_kafka_pack_opts& o) {
 inline u64 kafka_bound(u64 nbytes, u64 n_lines, const ysb_kafka_pack_opts& o) {
     const u64 keys = o.key_off ? o.key_off[n_lines] : 0;
     const u64 plain = nbytes + keys + n_lines * (KAFKA_HEADER + 40 + kafka_headers_bytes(o));
+    if (o.codec == YSB_KAFKA_CODEC_SNAPPY) {   // (ysb_snappy.h snappy_pack_bound, a batch per line at the worst)
+        const u64 chunk = o.snappy_chunk ? o.snappy_chunk : 32768u;
+        return plain + plain / 6 + (plain / chunk + n_lines + 1) * 36 + n_lines * 48;
+    }
     return o.codec ? plain + n_lines * 23 + 4 * (plain / 65536 + 1) : plain;
 }
 

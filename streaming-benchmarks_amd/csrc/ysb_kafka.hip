@@ -35,6 +35,12 @@
 //   kafka_walk_kernel          P.bytes the inflated buffer, P.batches the planned index
 //   kafka_codec_kernel         the batches with a bad block become rule 8 in bout, whatever the
 //                              walk made of their undecoded bytes; then base and gather as above.
+// Snappy-compressed batches (codec 2; ysb_snappy.h, ysb_snappy.hip) take the same chain: their
+// blocks carry YSB_SNAPPY_BLOCK in comp, the LZ4 measure and decode kernels skip those,
+// snappy_preamble_kernel writes their raw sizes in front of the plan and snappy_decode_kernel
+// decodes them behind the LZ4 decode -- a call may hold blocks of both kinds.  The plan also calls
+// a batch bad whose extent would pass the inflated buffer (infl_cap): a snappy block's size is
+// what its bytes say, and mapped bytes may change under the host's capacity check.
 // The inflated extents lie at any byte alignment and the walk loads whole 16-byte vectors around
 // an extent.  That is safe: the inflated buffer is 256-byte aligned with 64 bytes of slack
 // behind the last extent, and the decode is complete before the walk (the same stream).  A batch
@@ -297,8 +303,8 @@ __global__ __launch_bounds__(KAFKA_G_TPB) void kafka_gather_kernel(const KafkaPa
 // 0) inside each wave, the four waves' totals through LDS, two running prefixes carried from
 // step to step.  desc[i].out_off is block i's place in the inflated buffer.  Phase 2, a thread
 // per Kafka batch: its extent is [out_off of its first block, out_off + raw of its last); a
-// batch whose zero count moves is bad -- its smallest such block is the verdict and its blocks'
-// descriptors get raw 0, so the decode writes nothing of it.  Every index read is bounded by
+// batch whose zero count moves, or whose extent would end past P.infl_cap, is bad -- its smallest
+// such block is the verdict and its blocks' descriptors get raw 0, so the decode writes nothing of it.  Every index read is bounded by
 // the host's checks (kafka_lz4_entries); all values leave through ordinary vector stores.
 static_assert(KAFKA_PLAN_STEP == 256, "four waves per step");
 
@@ -358,9 +364,12 @@ __global__ __launch_bounds__(KAFKA_PLAN_STEP) void kafka_inflate_plan_kernel(con
             const u64 first = f.first_block, last = first + f.n_blocks - 1;
             off = P.desc[first].out_off;
             bytes = (u32)(P.desc[last].out_off + P.raw[last] - off);
-            if (P.zeros[last + 1] != P.zeros[first]) {
+            // (a block past the inflated buffer: the host sized it by what it read, and mapped
+            // bytes may have changed since; an LZ4 call's 64 KiB per block never gets here)
+            const bool over = P.desc[last].out_off + P.raw[last] > P.infl_cap;
+            if (over || P.zeros[last + 1] != P.zeros[first]) {
                 for (u32 j = 0; j < f.n_blocks; ++j)
-                    if (P.raw[first + j] == 0u) {
+                    if (P.raw[first + j] == 0u || P.desc[first + j].out_off + P.raw[first + j] > P.infl_cap) {
                         bad = j;
                         break;
                     }

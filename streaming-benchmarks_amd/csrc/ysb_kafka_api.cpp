@@ -205,7 +205,7 @@ static KafkaLz4Layout kafka_lz4_layout(u64 nb, u64 nblk, u64 nrec, bool crc = fa
     l.total = l.kafka + l.kl.total;
     return l;
 }
-static KafkaPlanParams kafka_plan_params(u8* d, const KafkaLz4Layout& l, u64 nb, u64 nblk) {
+static KafkaPlanParams kafka_plan_params(u8* d, const KafkaLz4Layout& l, u64 nb, u64 nblk, u64 infl_cap) {
     KafkaPlanParams p{};
     p.blocks = reinterpret_cast<const Lz4FrameBlock*>(d + l.blocks);
     p.raw = reinterpret_cast<const u32*>(d + l.raw);
@@ -219,15 +219,24 @@ static KafkaPlanParams kafka_plan_params(u8* d, const KafkaLz4Layout& l, u64 nb,
     p.planned = reinterpret_cast<ysb_kafka_batch*>(d + l.planned);
     p.codec_bad = reinterpret_cast<u32*>(d + l.cbad);
     p.head = reinterpret_cast<KafkaPlanHead*>(d + l.phead);
+    p.infl_cap = infl_cap;
     return p;
 }
 
 // The inflate chain on s: measure, plan, decode of the wire bytes into d_infl by pp's arrays (ev:
-// YSB_F_TIMING's four marks, or NULL).
+// YSB_F_TIMING's marks, or NULL).  snappy_max_raw set: the call holds blocks tagged SNAPPY_BLOCK --
+// their preambles are read in front of the chain (marks 4 and 5) and their decode follows the LZ4
+// kernels', each kernel skipping the other codec's blocks; its LDS is sized by that many raw bytes.
 static int launch_inflate(ysb_ctx* c, const KafkaPlanParams& pp, const u8* d_wire, u8* d_infl, u32 decoder, hipStream_t s,
-                          Event* ev) {
+                          Event* ev, u32 snappy_max_raw) {
+    const u32 tag = snappy_max_raw ? SNAPPY_BLOCK : 0u;
+    if (tag) {
+        HIPCHK(c, mark(ev, 4, s));
+        HIPCHK(c, launch_snappy_preamble(d_wire, pp.blocks, pp.n_blocks, const_cast<u32*>(pp.raw), s));
+        HIPCHK(c, mark(ev, 5, s));
+    }
     HIPCHK(c, mark(ev, 0, s));
-    HIPCHK(c, launch_lz4_measure(d_wire, pp.blocks, pp.n_blocks, const_cast<u32*>(pp.raw), s));
+    HIPCHK(c, launch_lz4_measure(d_wire, pp.blocks, pp.n_blocks, const_cast<u32*>(pp.raw), s, tag));
     HIPCHK(c, mark(ev, 1, s));
     HIPCHK(c, launch_kafka_plan(pp, s));
     HIPCHK(c, mark(ev, 2, s));
@@ -235,14 +244,18 @@ static int launch_inflate(ysb_ctx* c, const KafkaPlanParams& pp, const u8* d_wir
         // only the device knows the sizes: each kernel takes its size class (lz4_pick_decoder's
         // threshold), the one-wave kernel with the small window that keeps many waves per CU
         const Lz4Params small{d_wire, pp.desc, pp.n_blocks, LZ4_WIDE_ABOVE, d_infl, pp.head->bad, YSB_LZ4_DECODER_NARROW,
-                              pp.block_bad, LZ4_WIDE_ABOVE, 0};
+                              pp.block_bad, LZ4_WIDE_ABOVE, 0, tag};
         const Lz4Params large{d_wire, pp.desc, pp.n_blocks, LZ4_MAX_RAW, d_infl, pp.head->bad, YSB_LZ4_DECODER_WIDE,
-                              pp.block_bad, 0, LZ4_WIDE_ABOVE};
+                              pp.block_bad, 0, LZ4_WIDE_ABOVE, tag};
         HIPCHK(c, launch_lz4_decode(small, s));
         HIPCHK(c, launch_lz4_decode(large, s));
     } else {
-        const Lz4Params lp{d_wire, pp.desc, pp.n_blocks, LZ4_MAX_RAW, d_infl, pp.head->bad, decoder, pp.block_bad, 0, 0};
+        const Lz4Params lp{d_wire, pp.desc, pp.n_blocks, LZ4_MAX_RAW, d_infl, pp.head->bad, decoder, pp.block_bad, 0, 0, tag};
         HIPCHK(c, launch_lz4_decode(lp, s));
+    }
+    if (tag) {
+        const Lz4Params sp{d_wire, pp.desc, pp.n_blocks, snappy_max_raw, d_infl, pp.head->bad, 0, pp.block_bad, 0, 0, tag};
+        HIPCHK(c, launch_snappy_decode(sp, s));
     }
     HIPCHK(c, mark(ev, 3, s));
     return YSB_OK;
@@ -257,7 +270,8 @@ static int launch_inflate(ysb_ctx* c, const KafkaPlanParams& pp, const u8* d_wir
 // bytes by the host's index (*d_crc: where the values lie on the device; cev: its two marks).
 static int launch_call(ysb_ctx* c, u8* d, const u8* d_wire, u8* d_infl, u64 nb, u64 nblk, u64 nrec, u32 decoder, u8* out,
                        u64 out_cap, u32* line_off, hipStream_t s, Event* zev, Event* kev, const KafkaHead** head,
-                       const KafkaPlanHead** plan, bool crc = false, const uint2** d_crc = nullptr, Event* cev = nullptr) {
+                       const KafkaPlanHead** plan, bool crc = false, const uint2** d_crc = nullptr, Event* cev = nullptr,
+                       u64 infl_cap = 0, u32 snappy_max_raw = 0) {
     KafkaParams p;
     KafkaPlanParams pp{};
     KafkaCrcParams cp{};
@@ -268,13 +282,14 @@ static int launch_call(ysb_ctx* c, u8* d, const u8* d_wire, u8* d_infl, u64 nb, 
         cp.tables = c->d_kafka_crc_tab;
     }
     if (d_infl) {
+        if (c->kafka_infl_cap_test && c->kafka_infl_cap_test < infl_cap) infl_cap = c->kafka_infl_cap_test;
         const KafkaLz4Layout l = kafka_lz4_layout(nb, nblk, nrec, crc);
         cp.batches = reinterpret_cast<const ysb_kafka_batch*>(d + l.batches);
         cp.crc = reinterpret_cast<uint2*>(d + l.kafka + l.kl.crc);
-        pp = kafka_plan_params(d, l, nb, nblk);
+        pp = kafka_plan_params(d, l, nb, nblk, infl_cap);
         p = kafka_params(d + l.kafka, l.kl, d_infl, nb, nrec, out, out_cap, line_off);
         p.batches = pp.planned;
-        if (int rc = launch_inflate(c, pp, d_wire, d_infl, decoder, s, zev)) return rc;
+        if (int rc = launch_inflate(c, pp, d_wire, d_infl, decoder, s, zev, snappy_max_raw)) return rc;
     } else {
         const KafkaLayout l = kafka_layout(nb, nrec, crc);
         p = kafka_params(d, l, d_wire, nb, nrec, out, out_cap, line_off);
@@ -290,7 +305,7 @@ static int launch_call(ysb_ctx* c, u8* d, const u8* d_wire, u8* d_infl, u64 nb, 
 
 // kafka_lz4_last <- the inflate half of a call's figures
 static void settle_lz4(ysb_ctx* c, const KafkaPlanHead& h, u64 nblk, u64 stored, u64 compressed, u64 wire, u32 decoder,
-                       Event* ev) {
+                       Event* ev, u64 snappy = 0) {
     ysb_kafka_lz4_desc d{};
     d.calls = c->kafka_lz4_last.calls + 1;
     d.blocks = nblk;
@@ -300,7 +315,9 @@ static void settle_lz4(ysb_ctx* c, const KafkaPlanHead& h, u64 nblk, u64 stored,
     d.inflated_bytes = h.inflated;
     d.inflated_total = c->kafka_lz4_last.inflated_total + h.inflated;
     d.bad_blocks = (u64)h.zero_blocks + h.decoder_bad;
-    d.decoder = !nblk ? 0 : decoder == YSB_LZ4_DECODER_AUTO ? 3 : decoder;
+    d.decoder = nblk == snappy ? 0 : decoder == YSB_LZ4_DECODER_AUTO ? 3 : decoder;
+    d.snappy_blocks = snappy;
+    if (snappy) add_span(ev, 4, 5, &d.preamble_ms);
     add_span(ev, 0, 1, &d.measure_ms);
     add_span(ev, 1, 2, &d.plan_ms);
     add_span(ev, 2, 3, &d.decode_ms);
@@ -402,14 +419,27 @@ int kafka_lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes,
                     const uint8_t* dsrc, RawBatch* batch, SlotCopy v[2], std::vector<u8>* sample) {
     if ((nbytes && !bytes) || (nb && (!batches || !frames)) || (nblk && !blocks)) return fail(c, YSB_ERR_ARG, "NULL Kafka buffers");
     if (nb > 0x7FFFFFFFull || nblk > 0x7FFFFFFFull) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 Kafka batches and blocks per call");
-    u64 nrec = 0, control = 0, compressed = 0, stored = 0;
+    u64 nrec = 0, control = 0, compressed = 0, stored = 0, snappy = 0;
     KafkaError err;
-    int rc = kafka_lz4_entries(batches, frames, nb, blocks, nblk, nbytes, &nrec, &control, &compressed, &stored, &err);
+    int rc = kafka_lz4_entries(batches, frames, nb, blocks, nblk, nbytes, &nrec, &control, &compressed, &stored, &err,
+                               c->kafka_codecs, &snappy);
     if (rc) return fail(c, rc, "%s", err.msg);
     if ((rc = lines_fit(c, nrec))) return rc;
     if (c->kafka_crc_mode && (rc = crc_args(c, batches, nb))) return rc;
-    // the host cannot know the raw sizes: the guaranteed bound, 64 KiB per block
-    if (nblk * (u64)LZ4_MAX_RAW > c->cfg.max_batch_bytes)
+    // the host cannot know an LZ4 block's raw size: the guaranteed bound, 64 KiB per block; a
+    // snappy block says its own (a preamble the index would refuse counts nothing: the device
+    // makes that block bad)
+    u64 bound = 0;
+    u32 snappy_max = 0;
+    if (snappy)
+        for (u64 k = 0; k < nb; ++k) bound += kafka_inflate_bound(bytes, frames[k], blocks, &snappy_max);
+    const u64 snappy_raw = snappy ? bound - (nblk - snappy) * (u64)LZ4_MAX_RAW : 0;
+    if (snappy && bound > c->cfg.max_batch_bytes)
+        return fail(c, YSB_ERR_CAPACITY, "compressed Kafka batch: %llu snappy blocks of %llu raw bytes by their preambles and "
+                    "%llu other blocks x 65536 B may not fit max_batch_bytes (%llu); submit fewer Kafka batches per call",
+                    (unsigned long long)snappy, (unsigned long long)snappy_raw, (unsigned long long)(nblk - snappy),
+                    (unsigned long long)c->cfg.max_batch_bytes);
+    if (!snappy && nblk * (u64)LZ4_MAX_RAW > c->cfg.max_batch_bytes)
         return fail(c, YSB_ERR_CAPACITY, "compressed Kafka batch of %llu blocks: %llu x 65536 B may not fit max_batch_bytes "
                     "(%llu); submit fewer Kafka batches per call", (unsigned long long)nblk, (unsigned long long)nblk,
                     (unsigned long long)c->cfg.max_batch_bytes);
@@ -430,6 +460,8 @@ int kafka_lz4_stage(ysb_ctx* c, int slot, const uint8_t* bytes, uint64_t nbytes,
     st.stored_blocks = stored;
     st.compressed_batches = compressed;
     st.decoder = c->lz4_decoder;
+    st.snappy_blocks = snappy;
+    st.snappy_max_raw = snappy ? std::max(snappy_max, 1u) : 0u;
     // the layout sample: the first batch inflated and read by the host model
     sample->clear();
     if (nb) {
@@ -449,7 +481,7 @@ int kafka_enqueue(ysb_ctx* c, int slot, const KafkaStaged& b, hipStream_t s) {
     if (int rc = launch_call(c, c->d_kafka[slot], c->d_wire[slot], b.lz4 ? c->d_kafka_infl[slot].get() : nullptr, b.n_batches,
                              b.n_blocks, b.n_records, b.decoder, c->d_bytes[slot], c->cfg.max_batch_bytes, c->d_roff[slot], s,
                              timed ? c->ev_kafka_lz4[slot] : nullptr, timed ? c->ev_kafka[slot] : nullptr, &head, &plan,
-                             b.crc != 0, &d_crc, timed ? c->ev_kafka_crc[slot] : nullptr))
+                             b.crc != 0, &d_crc, timed ? c->ev_kafka_crc[slot] : nullptr, c->cfg.max_batch_bytes, b.snappy_max_raw))
         return rc;
     if (b.crc && b.n_batches)
         HIPCHK(c, hipMemcpyAsync(c->h_kafka[slot] + b.crc_back, d_crc, b.n_batches * sizeof(uint2), hipMemcpyDeviceToHost, s));
@@ -463,7 +495,7 @@ int kafka_settle(ysb_ctx* c, int slot, const KafkaStaged& b, u64* nbytes) {
     const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
     if (b.lz4)
         settle_lz4(c, c->h_kafka_plan[slot], b.n_blocks, b.stored_blocks, b.compressed_batches, b.framed_bytes, b.decoder,
-                   timed ? c->ev_kafka_lz4[slot] : nullptr);
+                   timed ? c->ev_kafka_lz4[slot] : nullptr, b.snappy_blocks);
     *nbytes = c->h_kafka_head[slot].out_bytes;
     char what[48];
     std::snprintf(what, sizeof what, "Kafka batch (slot %d)", slot);
@@ -523,9 +555,10 @@ int ysb_kafka_unframe_lz4_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nb
     if (!c) return YSB_ERR_ARG;
     if ((nbytes && !d_bytes) || (nb && (!batches || !frames)) || (nblk && !blocks)) return fail(c, YSB_ERR_ARG, "NULL Kafka buffers");
     if (nb > 0x7FFFFFFFull || nblk > 0x7FFFFFFFull) return fail(c, YSB_ERR_CAPACITY, "at most 2^31-1 Kafka batches and blocks per call");
-    u64 nrec = 0, control = 0, compressed = 0, stored = 0;
+    u64 nrec = 0, control = 0, compressed = 0, stored = 0, snappy = 0;
     KafkaError err;
-    int rc = kafka_lz4_entries(batches, frames, nb, blocks, nblk, nbytes, &nrec, &control, &compressed, &stored, &err);
+    int rc = kafka_lz4_entries(batches, frames, nb, blocks, nblk, nbytes, &nrec, &control, &compressed, &stored, &err,
+                               c->kafka_codecs, &snappy);
     if (rc) return fail(c, rc, "%s", err.msg);
     const bool crc = c->kafka_crc_mode != 0;
     if (crc && (rc = crc_args(c, batches, nb))) return rc;
@@ -549,11 +582,12 @@ int ysb_kafka_unframe_lz4_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nb
     if (nb) HIPCHK(c, hipMemcpyAsync(d + l.frames, frames, nb * sizeof(ysb_kafka_frame), hipMemcpyHostToDevice, s));
     if (nblk) HIPCHK(c, hipMemcpyAsync(d + l.blocks, blocks, nblk * sizeof(ysb_lz4_frame_block), hipMemcpyHostToDevice, s));
     const bool timed = (c->cfg.flags & YSB_F_TIMING) != 0u;
-    Event ev[4], kev[4], cev[2];
+    Event ev[6], kev[4], cev[2];
     const KafkaHead* dh = nullptr;
     const KafkaPlanHead* dp = nullptr;
     if ((rc = launch_call(c, d, d_bytes, c->d_kafka_infl_sync, nb, nblk, nrec, c->lz4_decoder, d_out, d_out ? out_cap : 0,
-                          d_line_off, s, timed ? ev : nullptr, timed ? kev : nullptr, &dh, &dp, crc, &d_crc, timed ? cev : nullptr)))
+                          d_line_off, s, timed ? ev : nullptr, timed ? kev : nullptr, &dh, &dp, crc, &d_crc, timed ? cev : nullptr,
+                          nblk * (u64)LZ4_MAX_RAW, snappy ? SNAPPY_MAX_RAW : 0u)))
         return rc;
     if (crc && nb) HIPCHK(c, hipMemcpyAsync(crcs.data(), d_crc, nb * sizeof(uint2), hipMemcpyDeviceToHost, s));
     KafkaHead h{};
@@ -562,7 +596,7 @@ int ysb_kafka_unframe_lz4_device(ysb_ctx* c, const uint8_t* d_bytes, uint64_t nb
     HIPCHK(c, hipMemcpyAsync(&ph, dp, sizeof ph, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (out_bytes) *out_bytes = h.out_bytes;
-    settle_lz4(c, ph, nblk, stored, compressed, nbytes, c->lz4_decoder, timed ? ev : nullptr);
+    settle_lz4(c, ph, nblk, stored, compressed, nbytes, c->lz4_decoder, timed ? ev : nullptr, snappy);
     return settle(c, h, nb, nbytes, control, batches, timed ? kev : nullptr, "ysb_kafka_unframe_lz4_device",
                   crc ? crcs.data() : nullptr, timed ? cev : nullptr);
 }
@@ -574,6 +608,20 @@ int ysb_kafka_set_crc(ysb_ctx* c, int mode) {
     if (mode != YSB_KAFKA_CRC_OFF && mode != YSB_KAFKA_CRC_DEVICE)
         return fail(c, YSB_ERR_ARG, "ysb_kafka_set_crc: mode %d (0: off, 1: on the device)", mode);
     c->kafka_crc_mode = (u32)mode;
+    return YSB_OK;
+}
+
+int ysb_kafka_set_codecs(ysb_ctx* c, uint32_t mask) {
+    if (!c) return YSB_ERR_ARG;
+    if (mask != YSB_KAFKA_CODECS_DEFAULT && mask != (YSB_KAFKA_CODECS_DEFAULT | YSB_KAFKA_CODECS_SNAPPY))
+        return fail(c, YSB_ERR_ARG, "ysb_kafka_set_codecs: mask %#x (0x9: none and lz4; 0xd: snappy too)", mask);
+    c->kafka_codecs = mask;
+    return YSB_OK;
+}
+
+int ysb_kafka_test_inflated_cap(ysb_ctx* c, uint64_t bytes) {
+    if (!c) return YSB_ERR_ARG;
+    c->kafka_infl_cap_test = bytes;
     return YSB_OK;
 }
 
@@ -640,7 +688,7 @@ int ysb_kafka_verdict_crc_lz4_host(const uint8_t* bytes, uint64_t nbytes, const 
         return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_verdict_crc_lz4_host: NULL buffers");
     KafkaError err;
     const int rc = kafka_unframe_lz4(bytes, nbytes, batches, frames, n_batches, blocks, n_blocks, nullptr, 0, nullptr, 0, nullptr,
-                                     nullptr, nullptr, nullptr, verdict, &err, true);
+                                     nullptr, nullptr, nullptr, verdict, &err, true, KAFKA_CODECS_ALL);
     return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
 }
 
@@ -688,7 +736,8 @@ int ysb_kafka_unframe_host(const uint8_t* bytes, uint64_t nbytes, const ysb_kafk
 int ysb_kafka_index_lz4(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, ysb_kafka_batch* batches, ysb_kafka_frame* frames,
                         uint64_t cap, ysb_lz4_frame_block* blocks, uint64_t block_cap, ysb_kafka_lz4_summary* info) {
     if (nbytes && !bytes) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: NULL buffer");
-    if (flags & ~(YSB_KAFKA_CHECK_CRC | YSB_KAFKA_CHECK_CRC_CONTROL)) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: unknown flags %#x", flags);
+    if (flags & ~(YSB_KAFKA_CHECK_CRC | YSB_KAFKA_CHECK_CRC_CONTROL | YSB_KAFKA_ACCEPT_SNAPPY))
+        return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: unknown flags %#x", flags);
     if (!batches != !frames) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_index_lz4: batches and frames go together");
     KafkaError err;
     const int rc = kafka_index_lz4(bytes, nbytes, flags, batches, frames, batches ? cap : 0, blocks, blocks ? block_cap : 0, info, &err);
@@ -703,7 +752,7 @@ int ysb_kafka_unframe_lz4_host(const uint8_t* bytes, uint64_t nbytes, const ysb_
         return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_unframe_lz4_host: NULL buffers");
     KafkaError err;
     const int rc = kafka_unframe_lz4(bytes, nbytes, batches, frames, n_batches, blocks, n_blocks, out, out_cap, line_off, off_cap,
-                                     n_lines, out_bytes, inflated, counters, verdict, &err);
+                                     n_lines, out_bytes, inflated, counters, verdict, &err, false, KAFKA_CODECS_ALL);
     return rc ? fail(nullptr, rc, "%s", err.msg) : YSB_OK;
 }
 
@@ -721,9 +770,18 @@ static int pack_args(const uint8_t* src, uint64_t nbytes, const uint32_t* line_o
     if (o.key_off && !o.keys && o.key_off[n_lines]) return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: key offsets without keys");
     if (o.n_headers && (!o.header_keys || !o.header_vals || !o.header_val_len))
         return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: headers without their arrays");
-    if (o.codec != 0 && o.codec != YSB_KAFKA_CODEC_LZ4)
-        return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: codec %u: 0 (none) and 3 (lz4) are written", o.codec);
+    if (o.codec != 0 && o.codec != YSB_KAFKA_CODEC_LZ4 && o.codec != YSB_KAFKA_CODEC_SNAPPY)
+        return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: codec %u: 0 (none), 2 (snappy) and 3 (lz4) are written", o.codec);
+    if (o.codec == YSB_KAFKA_CODEC_SNAPPY && (o.snappy_framing > YSB_KAFKA_SNAPPY_RAW || o.snappy_chunk > SNAPPY_MAX_RAW))
+        return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: snappy_framing %u (0: xerial, 1: raw), snappy_chunk %u (at most 65536)",
+                    o.snappy_framing, o.snappy_chunk);
     return YSB_OK;
+}
+
+static int raw_over(uint64_t* dst_bytes) {
+    if (dst_bytes) *dst_bytes = 0;
+    return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_pack: snappy_framing raw: a batch's records are not 1..65536 bytes, which one raw "
+                "block holds (a batch_bytes of at most 65536, or the xerial framing)");
 }
 
 int ysb_kafka_pack(const uint8_t* src, uint64_t nbytes, const uint32_t* line_off, uint64_t n_lines,
@@ -738,6 +796,7 @@ int ysb_kafka_pack(const uint8_t* src, uint64_t nbytes, const uint32_t* line_off
     *dst_bytes = o.codec ? kafka_pack_lz4(src, nbytes, line_off, n_lines, o, dst, &nb)
                          : kafka_pack(src, nbytes, line_off, n_lines, o, dst, &nb);
     if (n_batches) *n_batches = nb;
+    if (*dst_bytes == KAFKA_PACK_RAW_OVER) return raw_over(dst_bytes);
     return YSB_OK;
 }
 
@@ -750,11 +809,43 @@ int ysb_kafka_write_file(const char* path, const uint8_t* src, uint64_t nbytes, 
     u64 nb = 0;
     const u64 n = o.codec ? kafka_pack_lz4(src, nbytes, line_off, n_lines, o, blob.data(), &nb)
                           : kafka_pack(src, nbytes, line_off, n_lines, o, blob.data(), &nb);
+    if (n == KAFKA_PACK_RAW_OVER) return raw_over(nullptr);
     FILE* f = std::fopen(path, "wb");
     if (!f) return fail(nullptr, YSB_ERR_ARG, "cannot write %s", path);
     bool ok = !n || std::fwrite(blob.data(), 1, n, f) == n;
     ok = (std::fclose(f) == 0) && ok;
     return ok ? YSB_OK : fail(nullptr, YSB_ERR_ARG, "short write to %s", path);
+}
+
+int ysb_kafka_inflate_bounds(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, const ysb_kafka_frame* frames,
+                             uint64_t n_batches, const ysb_lz4_frame_block* blocks, uint64_t n_blocks, uint64_t* bounds) {
+    if ((nbytes && !bytes) || (n_batches && (!batches || !frames || !bounds)) || (n_blocks && !blocks))
+        return fail(nullptr, YSB_ERR_ARG, "ysb_kafka_inflate_bounds: NULL buffers");
+    KafkaError err;
+    if (int rc = kafka_lz4_entries(batches, frames, n_batches, blocks, n_blocks, nbytes, nullptr, nullptr, nullptr, nullptr, &err,
+                                   KAFKA_CODECS_ALL))
+        return fail(nullptr, rc, "%s", err.msg);
+    for (u64 k = 0; k < n_batches; ++k) bounds[k] = kafka_inflate_bound(bytes, frames[k], blocks);
+    return YSB_OK;
+}
+
+int ysb_snappy_compress_block(const uint8_t* src, uint32_t raw_bytes, uint8_t* dst, uint32_t cap, uint32_t* comp_bytes) {
+    if (!src || !dst || !comp_bytes || raw_bytes < 1 || raw_bytes > SNAPPY_MAX_RAW)
+        return fail(nullptr, YSB_ERR_ARG, "ysb_snappy_compress_block: NULL buffers or raw_bytes not in 1..65536");
+    if (cap < snappy_bound(raw_bytes)) return fail(nullptr, YSB_ERR_CAPACITY, "ysb_snappy_compress_block: needs %u bytes", snappy_bound(raw_bytes));
+    *comp_bytes = snappy_compress_block(src, raw_bytes, dst);
+    return YSB_OK;
+}
+
+int ysb_snappy_decompress_block(const uint8_t* src, uint32_t comp_bytes, uint8_t* dst, uint32_t cap, uint32_t* raw_bytes) {
+    if (!src || !dst || !raw_bytes) return fail(nullptr, YSB_ERR_ARG, "ysb_snappy_decompress_block: NULL argument");
+    const u32 raw = snappy_raw_of(src, comp_bytes);
+    if (raw > cap) return fail(nullptr, YSB_ERR_CAPACITY, "ysb_snappy_decompress_block: the preamble says %u bytes, room for %u", raw, cap);
+    *raw_bytes = raw ? snappy_decode_block(src, comp_bytes, dst) : 0;
+    if (!*raw_bytes)
+        return fail(nullptr, YSB_ERR_FORMAT, "ysb_snappy_decompress_block: a block of %u bytes that breaks the format's rules, or "
+                    "whose preamble is not 1..65536", comp_bytes);
+    return YSB_OK;
 }
 
 uint64_t ysb_kafka_batch_size(void) { return sizeof(ysb_kafka_batch); }

@@ -16,11 +16,14 @@
 
 #include "ysb_kafka.h"
 #include "ysb_lz4_frame.h"
+#include "ysb_snappy.h"
 
 namespace ysb {
 
 // a batch's blocks: the bound that keeps its inflated bytes below 2^31 (records_bytes is u32)
 constexpr u32 KAFKA_LZ4_MAX_BLOCKS = 32767;
+// every codec the compressed path reads (the host models, which have no context's mask)
+constexpr u32 KAFKA_CODECS_ALL = YSB_KAFKA_CODECS_DEFAULT | YSB_KAFKA_CODECS_SNAPPY;
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 
@@ -35,7 +38,10 @@ inline const char* kafka_codec_name(u32 codec) {
 // 3 the frame), frames[k] the blocks of entry k, blocks[] every block's place in the buffer.  A
 // codec-3 batch's records go through lz4f_index and any refusal of it becomes a refusal of the
 // Kafka batch; a codec-0 batch's records become stored blocks of at most 64 KiB, so a mixed
-// fetch response takes one path on the device.  Codecs 1, 2 and 4 are refused by name.
+// fetch response takes one path on the device.  Codecs 1, 2 and 4 are refused by name -- unless
+// flags holds YSB_KAFKA_ACCEPT_SNAPPY: then a codec-2 batch's records go through snappy_index
+// (ysb_snappy.h: one block entry per xerial chunk, or one for a raw block, each tagged
+// SNAPPY_BLOCK), and any refusal of it becomes a refusal of the Kafka batch.
 inline int kafka_index_lz4(const u8* bytes, u64 nbytes, u32 flags, ysb_kafka_batch* out, ysb_kafka_frame* frames, u64 cap,
                            ysb_lz4_frame_block* blocks, u64 block_cap, ysb_kafka_lz4_summary* info, KafkaError* err) {
     ysb_kafka_lz4_summary s{};
@@ -55,7 +61,8 @@ inline int kafka_index_lz4(const u8* bytes, u64 nbytes, u32 flags, ysb_kafka_bat
         if (batch_len < (int32_t)(KAFKA_HEADER - KAFKA_LEN_BASE))
             return refuse("batchLength", batch_len, "below 49, the header's own bytes behind the field");
         const u32 attributes = (u32)kafka_be(h + 21, 2), codec = attributes & 7u;
-        if (codec != 0 && codec != YSB_KAFKA_CODEC_LZ4) {
+        const bool snappy = codec == YSB_KAFKA_CODEC_SNAPPY && (flags & YSB_KAFKA_ACCEPT_SNAPPY);
+        if (codec != 0 && codec != YSB_KAFKA_CODEC_LZ4 && !snappy) {
             char rule[96];
             std::snprintf(rule, sizeof rule, "%s-compressed record batches are not read (codec 0, none, and 3, lz4, only)",
                           kafka_codec_name(codec));
@@ -94,6 +101,22 @@ inline int kafka_index_lz4(const u8* bytes, u64 nbytes, u32 flags, ysb_kafka_bat
                     for (u64 j = 0; j < nblk && first_block + j < block_cap; ++j) blocks[first_block + j].offset += roff;
                 s.stored_blocks += fs.stored_blocks;
                 s.comp_bytes += fs.comp_bytes;
+                ++s.compressed_batches;
+            } else if (snappy) {
+                const bool room = blocks && first_block < block_cap;
+                SnappyError se;
+                const int rc = snappy_index(bytes + roff, rbytes, room ? blocks + first_block : nullptr,
+                                            room ? block_cap - first_block : 0, &nblk, &se);
+                if (rc == YSB_ERR_FORMAT) {
+                    char rule[400];
+                    std::snprintf(rule, sizeof rule, "its records, %llu bytes at byte %llu, are not snappy that is read: %s",
+                                  (unsigned long long)rbytes, (unsigned long long)roff, se.msg);
+                    return refuse("attributes.codec", codec, rule);
+                }
+                if (nblk > KAFKA_LZ4_MAX_BLOCKS) return refuse("blocks", (long long)nblk, "more than 32767 blocks in one batch");
+                if (room)
+                    for (u64 j = 0; j < nblk && first_block + j < block_cap; ++j) blocks[first_block + j].offset += roff;
+                s.comp_bytes += snappy_is_xerial(bytes + roff, rbytes) ? rbytes - XERIAL_HEADER - 4 * nblk : rbytes;
                 ++s.compressed_batches;
             } else {
                 nblk = (rbytes + LZ4F_BLOCK_MAX - 1) / LZ4F_BLOCK_MAX;
@@ -138,10 +161,14 @@ inline int kafka_index_lz4(const u8* bytes, u64 nbytes, u32 flags, ysb_kafka_bat
 // A batch entry as kafka_entry_ok has it; a frame entry's first_block the running sum, its codec
 // 0 or 3, at most KAFKA_LZ4_MAX_BLOCKS blocks; each block of 1..65536 bytes inside its batch's
 // wire bytes; the frames' blocks n_blocks in all.  0, or the message in err.
+// codecs (ysb_kafka_set_codecs's mask) with YSB_KAFKA_CODECS_SNAPPY: a frame entry of codec 2 is
+// taken too, each of its blocks tagged SNAPPY_BLOCK and of 1..SNAPPY_MAX_COMP bytes; a tagged
+// block anywhere else is refused.  *snappy (may be NULL): the tagged blocks.
 inline int kafka_lz4_entries(const ysb_kafka_batch* batches, const ysb_kafka_frame* frames, u64 nb,
                              const ysb_lz4_frame_block* blocks, u64 n_blocks, u64 nbytes, u64* n_records, u64* control,
-                             u64* compressed, u64* stored, KafkaError* err) {
-    u64 first = 0, blk = 0, ctl = 0, comp = 0, st = 0;
+                             u64* compressed, u64* stored, KafkaError* err, u32 codecs = YSB_KAFKA_CODECS_DEFAULT,
+                             u64* snappy = nullptr) {
+    u64 first = 0, blk = 0, ctl = 0, comp = 0, st = 0, sn = 0;
     for (u64 k = 0; k < nb; ++k) {
         const ysb_kafka_batch& b = batches[k];
         const ysb_kafka_frame& f = frames[k];
@@ -152,7 +179,8 @@ inline int kafka_lz4_entries(const ysb_kafka_batch* batches, const ysb_kafka_fra
             return YSB_ERR_ARG;
         }
         if (f.first_block != blk || f.n_blocks > KAFKA_LZ4_MAX_BLOCKS || f.n_blocks > n_blocks - blk ||
-            (f.codec != 0 && f.codec != YSB_KAFKA_CODEC_LZ4)) {
+            (f.codec != 0 && f.codec != YSB_KAFKA_CODEC_LZ4 &&
+             !(f.codec == YSB_KAFKA_CODEC_SNAPPY && (codecs & YSB_KAFKA_CODECS_SNAPPY)))) {
             std::snprintf(err->msg, sizeof err->msg, "Kafka frame entry %llu: first_block %llu (expected %llu), %u blocks of "
                           "%llu, codec %u", (unsigned long long)k, (unsigned long long)f.first_block, (unsigned long long)blk,
                           f.n_blocks, (unsigned long long)n_blocks, f.codec);
@@ -160,14 +188,18 @@ inline int kafka_lz4_entries(const ysb_kafka_batch* batches, const ysb_kafka_fra
         }
         for (u64 j = 0; j < f.n_blocks; ++j) {
             const ysb_lz4_frame_block& e = blocks[blk + j];
-            const u32 len = e.comp_bytes & ~LZ4_STORED;
-            if (len < 1 || len > LZ4F_BLOCK_MAX || e.offset < b.records_off || e.offset - b.records_off > b.records_bytes ||
+            const bool tagged = f.codec == YSB_KAFKA_CODEC_SNAPPY;
+            const u32 len = tagged ? e.comp_bytes & SNAPPY_LEN_MASK : e.comp_bytes & ~LZ4_STORED;
+            const bool kind_ok = tagged ? (e.comp_bytes & ~SNAPPY_LEN_MASK) == SNAPPY_BLOCK : !(e.comp_bytes & SNAPPY_BLOCK);
+            if (!kind_ok || len < 1 || len > (tagged ? SNAPPY_MAX_COMP : LZ4F_BLOCK_MAX) || e.offset < b.records_off || e.offset - b.records_off > b.records_bytes ||
                 len > b.records_bytes - (e.offset - b.records_off)) {
-                std::snprintf(err->msg, sizeof err->msg, "block %llu of Kafka batch %llu is not 1..65536 bytes inside the "
-                              "batch's records", (unsigned long long)j, (unsigned long long)k);
+                std::snprintf(err->msg, sizeof err->msg, "block %llu of Kafka batch %llu is not 1..%u bytes inside the "
+                              "batch's records%s", (unsigned long long)j, (unsigned long long)k, tagged ? SNAPPY_MAX_COMP : 65536u,
+                              tagged ? ", tagged as a snappy block" : "");
                 return YSB_ERR_ARG;
             }
-            st += (e.comp_bytes & LZ4_STORED) ? 1 : 0;
+            st += (!tagged && (e.comp_bytes & LZ4_STORED)) ? 1 : 0;
+            sn += tagged ? 1 : 0;
         }
         comp += f.codec ? 1 : 0;
         blk += f.n_blocks;
@@ -183,7 +215,27 @@ inline int kafka_lz4_entries(const ysb_kafka_batch* batches, const ysb_kafka_fra
     if (control) *control = ctl;
     if (compressed) *compressed = comp;
     if (stored) *stored = st;
+    if (snappy) *snappy = sn;
     return YSB_OK;
+}
+
+// ---- the capacity rule ------------------------------------------------------------------------
+// What a batch's blocks may inflate to, as the slot submits count it: a snappy block what its
+// preamble says (0 for a preamble the index would refuse: the device makes that block bad), every
+// other block LZ4_MAX_RAW, the host having no way to know.  *snappy_max (may be NULL) is raised to
+// the largest preamble seen.  The entries have passed kafka_lz4_entries.
+inline u64 kafka_inflate_bound(const u8* bytes, const ysb_kafka_frame& f, const ysb_lz4_frame_block* blocks, u32* snappy_max = nullptr) {
+    u64 sum = 0;
+    for (u32 j = 0; j < f.n_blocks; ++j) {
+        const ysb_lz4_frame_block& e = blocks[f.first_block + j];
+        u32 raw = LZ4_MAX_RAW;
+        if (e.comp_bytes & SNAPPY_BLOCK) {
+            raw = snappy_raw_of(bytes + e.offset, e.comp_bytes & SNAPPY_LEN_MASK);
+            if (snappy_max && raw > *snappy_max) *snappy_max = raw;
+        }
+        sum += raw;
+    }
+    return sum;
 }
 
 // ---- the host model ---------------------------------------------------------------------------
@@ -194,8 +246,14 @@ inline u32 kafka_inflate_batch(const u8* bytes, const ysb_kafka_frame& f, const 
     u64 at = 0;
     for (u32 j = 0; j < f.n_blocks; ++j) {
         const ysb_lz4_frame_block& e = blocks[f.first_block + j];
-        const u32 raw = lz4_measure_block(bytes + e.offset, e.comp_bytes);
-        if (!raw || !lz4_decode_block(bytes + e.offset, ysb_lz4_block{e.comp_bytes, raw}, scratch + at)) return j;
+        u32 raw = 0;
+        if (e.comp_bytes & SNAPPY_BLOCK) {
+            raw = snappy_decode_block(bytes + e.offset, e.comp_bytes & SNAPPY_LEN_MASK, scratch + at);
+            if (!raw) return j;
+        } else {
+            raw = lz4_measure_block(bytes + e.offset, e.comp_bytes);
+            if (!raw || !lz4_decode_block(bytes + e.offset, ysb_lz4_block{e.comp_bytes, raw}, scratch + at)) return j;
+        }
         at += raw;
     }
     *total = at;
@@ -210,7 +268,7 @@ inline int kafka_unframe_lz4(const u8* bytes, u64 nbytes, const ysb_kafka_batch*
                              u64 n_batches, const ysb_lz4_frame_block* blocks, u64 n_blocks, u8* out, u64 out_cap,
                              u32* line_off, u64 off_cap, u64* n_lines, u64* out_bytes, u64* inflated,
                              ysb_kafka_counters* counters, ysb_kafka_verdict* verdict, KafkaError* err,
-                             bool check_crc = false) {
+                             bool check_crc = false, u32 codecs = YSB_KAFKA_CODECS_DEFAULT) {
     ysb_kafka_counters ct{};
     ysb_kafka_verdict vd{0, KAFKA_NONE, 0, 0};
     u64 first = 0;
@@ -220,7 +278,8 @@ inline int kafka_unframe_lz4(const u8* bytes, u64 nbytes, const ysb_kafka_batch*
                       "CRC lies", (unsigned long long)kafka_crc_entries_ok(batches, n_batches));
         return YSB_ERR_ARG;
     }
-    if (int rc = kafka_lz4_entries(batches, frames, n_batches, blocks, n_blocks, nbytes, &first, nullptr, nullptr, nullptr, err))
+    if (int rc = kafka_lz4_entries(batches, frames, n_batches, blocks, n_blocks, nbytes, &first, nullptr, nullptr, nullptr, err,
+                                   codecs))
         return rc;
     if (n_lines) *n_lines = first;
     if (line_off && first + 1 > off_cap) {
@@ -294,6 +353,10 @@ inline int kafka_unframe_lz4(const u8* bytes, u64 nbytes, const ysb_kafka_batch*
 // them), each one's records rewritten as one standard frame: 64 KiB blocks from the library's
 // greedy compressor, a block that does not shrink stored; attributes = 3, batchLength and the
 // CRC over what is on the wire.  dst holds kafka_bound bytes (o.codec == 3).
+// o.codec == 2: the records as snappy instead (ysb_snappy.h snappy_pack: a xerial stream of chunks
+// of o.snappy_chunk raw bytes, or with o.snappy_framing RAW one raw block -- KAFKA_PACK_RAW_OVER
+// is returned where a batch's records are not 1..65536 bytes, which one block cannot hold).
+constexpr u64 KAFKA_PACK_RAW_OVER = ~0ull;
 inline u64 kafka_pack_lz4(const u8* src, u64 nbytes, const u32* line_off, u64 n_lines, const ysb_kafka_pack_opts& o, u8* dst,
                           u64* n_batches) {
     ysb_kafka_pack_opts plain = o;
@@ -307,10 +370,14 @@ inline u64 kafka_pack_lz4(const u8* src, u64 nbytes, const u32* line_off, u64 n_
         const u64 span = KAFKA_LEN_BASE + kafka_be(h + 8, 4);
         u8* d = dst + at;
         std::memcpy(d, h, KAFKA_HEADER);
-        const u64 fb = lz4f_pack(h + KAFKA_HEADER, span - KAFKA_HEADER, LZ4F_BLOCK_MAX, 1, d + KAFKA_HEADER);
+        const u64 rb = span - KAFKA_HEADER;
+        const bool snappy = o.codec == YSB_KAFKA_CODEC_SNAPPY, xerial = o.snappy_framing != YSB_KAFKA_SNAPPY_RAW;
+        if (snappy && !xerial && (rb < 1 || rb > SNAPPY_MAX_RAW)) return KAFKA_PACK_RAW_OVER;
+        const u64 fb = snappy ? snappy_pack(h + KAFKA_HEADER, rb, o.snappy_chunk, xerial, d + KAFKA_HEADER)
+                              : lz4f_pack(h + KAFKA_HEADER, rb, LZ4F_BLOCK_MAX, 1, d + KAFKA_HEADER);
         const u64 p = KAFKA_HEADER + fb;
         kafka_put_be(d + 8, 4, p - KAFKA_LEN_BASE);
-        kafka_put_be(d + 21, 2, YSB_KAFKA_CODEC_LZ4);
+        kafka_put_be(d + 21, 2, o.codec);
         kafka_put_be(d + 17, 4, kafka_crc32c(d + KAFKA_CRC_FROM, p - KAFKA_CRC_FROM));
         at += p;
         pos += span;

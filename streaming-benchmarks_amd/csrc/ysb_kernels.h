@@ -438,6 +438,9 @@ struct Lz4Params {
     // several-wave kernel blocks of skip_upto or fewer.  A compressed Kafka call, whose sizes only
     // the device knows, launches both (ysb_kafka_api.cpp).
     u32 skip_above, skip_upto;
+    // 0, or bits of desc[i].comp that mark a block as another codec's (YSB_SNAPPY_BLOCK in a
+    // compressed Kafka call): the LZ4 kernels leave it alone, snappy_decode_kernel takes only those
+    u32 skip_tag;
 };
 // Every block decoded (a bad block writes nothing and is recorded in bad[]).  Asynchronous on s.
 // One wave per block (lz4_decode_kernel) or four (lz4_decode_wide_kernel), by p.decoder.
@@ -451,7 +454,18 @@ struct Lz4FrameBlock {
 };
 // raw[i] <- block i's raw size by a walk of its tokens alone (no copies), 0 for a bad block.
 // One wave per block, four blocks per workgroup.  Asynchronous on s.
-hipError_t launch_lz4_measure(const u8* base, const Lz4FrameBlock* blocks, u32 n_blocks, u32* raw, hipStream_t s);
+// (skip_tag: bits of blocks[i].comp that mark another codec's block, whose raw[i] is left alone)
+hipError_t launch_lz4_measure(const u8* base, const Lz4FrameBlock* blocks, u32 n_blocks, u32* raw, hipStream_t s,
+                              u32 skip_tag = 0);
+
+// snappy blocks (ysb_snappy.hip; the format's rules: ysb_snappy.h), for the blocks tagged
+// YSB_SNAPPY_BLOCK alone.  raw[i] <- block i's preamble when it is in 1..65536, else 0: a thread
+// per block.  Asynchronous on s.
+hipError_t launch_snappy_preamble(const u8* base, const Lz4FrameBlock* blocks, u32 n_blocks, u32* raw, hipStream_t s);
+// Every tagged block of p.desc decoded (comp: the tag and the length; raw: the planned size, which
+// the kernel asks the preamble to repeat); a bad block writes nothing and is recorded in bad[] and
+// block_bad[].  One wave per block, LDS sized by p.max_raw.  Asynchronous on s.
+hipError_t launch_snappy_decode(const Lz4Params& p, hipStream_t s);
 // desc[i] <- {blocks[i].offset, carry + the raw sizes before it, blocks[i].comp, raw[i]};
 // *total <- the sum of the raw sizes.  One workgroup.  Asynchronous on s.
 // (d_carry: the carry length in device memory, or NULL: `carry`)
@@ -555,6 +569,7 @@ struct KafkaPlanParams {
     ysb_kafka_batch* planned;        // [n_batches] out: records_off / records_bytes in the inflated buffer, the rest copied
     u32* codec_bad;                  // [n_batches] out: the smallest block measured 0, or KAFKA_NONE
     KafkaPlanHead* head;
+    u64 infl_cap;                    // the inflated buffer's bytes: a batch whose extent would pass them is bad
 };
 // One workgroup: a pass over the blocks with two running prefixes (raw bytes, blocks measured
 // 0), KAFKA_PLAN_STEP blocks per step, then one thread per Kafka batch.  Asynchronous on s.

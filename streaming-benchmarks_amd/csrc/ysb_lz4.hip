@@ -36,10 +36,9 @@
 #include "ysb_kernels.h"
 #include "ysb_lz4.h"
 #include "ysb_lz4_frame.h"
+#include "ysb_lz4_device.h"
 
 namespace ysb {
-
-constexpr u32 LZ4_TPB = 64;   // one wave
 
 // The reader's input: the compressed bytes in LDS at lds[base + pos], 64 at a time in one
 // register per lane.  byte() is wave-uniform: pos is, and readlane broadcasts one lane's byte.
@@ -57,31 +56,6 @@ struct Lz4WaveIn {
     }
 };
 
-// n bytes between global memory and the LDS window, lds_at congruent to g mod 16: vectors
-// between the 16-byte boundaries inside [g, g + n), bytes at the edges.
-// (NT threads take part; `lane` is the thread's index among them)
-template <bool TO_LDS, u32 NT = LZ4_TPB>
-__device__ __forceinline__ void lz4_move(u8* lds, u32 lds_at, u8* g, u32 n, u32 lane) {
-    const u32 mis = (u32)(reinterpret_cast<uintptr_t>(g) & 15);
-    u32 head = (16 - mis) & 15;
-    if (head > n) head = n;
-    const u32 nvec = (n - head) / 16, tail = head + nvec * 16;
-    for (u32 j = lane; j < head; j += NT) {
-        if (TO_LDS) lds[lds_at + j] = g[j];
-        else g[j] = lds[lds_at + j];
-    }
-    for (u32 v = lane; v < nvec; v += NT) {
-        uint4* l = reinterpret_cast<uint4*>(lds + lds_at + head + v * 16);
-        uint4* m = reinterpret_cast<uint4*>(g + head + v * 16);
-        if (TO_LDS) *l = *m;
-        else *m = *l;
-    }
-    for (u32 j = tail + lane; j < n; j += NT) {
-        if (TO_LDS) lds[lds_at + j] = g[j];
-        else g[j] = lds[lds_at + j];
-    }
-}
-
 __global__ __launch_bounds__(LZ4_TPB) void lz4_decode_kernel(const Lz4Params P) {
     extern __shared__ __align__(16) u8 lz4_lds[];
     u8* lds = lz4_lds;
@@ -92,6 +66,7 @@ __global__ __launch_bounds__(LZ4_TPB) void lz4_decode_kernel(const Lz4Params P) 
     const u8* gin = P.in + d.in_off;
     u8* gout = P.out + d.out_off;
     if (P.skip_above && raw > P.skip_above) return;   // (the whole workgroup: the other launch's block)
+    if (d.comp & P.skip_tag) return;                  // (... or another codec's: ysb_snappy.hip)
     // (the host has checked every entry: lz4_check_dir; a launch sized for max_raw must not
     // meet a larger block all the same)
     bool bad = !lz4_entry_ok(e) || raw > P.max_raw;
@@ -190,53 +165,6 @@ __global__ __launch_bounds__(LZ4_TPB) void lz4_decode_kernel(const Lz4Params P) 
 // below raw, by the reader's checks; a bad block leaves the loop before anything is stored.
 constexpr u32 LZ4W_TPB = 256;
 
-// The reader's input straight from global memory: 256 bytes at a time, one aligned dword per
-// lane, and the next 256 already in flight (a refill waits for a load issued a window ago, not
-// for a fresh one).  Only dwords that hold at least one of the block's bytes are loaded -- an
-// aligned dword never crosses a page, so nothing is touched that the block's own bytes do not
-// make accessible.  byte() is wave-uniform, positions only grow.
-struct Lz4GlobalIn {
-    const u32* base4;
-    u32 mis, ndw, lane;
-    u32 win_pos, cur, nxt;
-    __device__ __forceinline__ u32 load(u32 wp) const {
-        const u32 i = wp / 4 + lane;
-        return base4[i < ndw ? i : ndw - 1];
-    }
-    __device__ __forceinline__ void init(const u8* g, u32 comp, u32 lane_) {   // comp >= 1
-        mis = (u32)(reinterpret_cast<uintptr_t>(g) & 3);
-        base4 = reinterpret_cast<const u32*>(g - mis);
-        ndw = (mis + comp + 3) / 4;
-        lane = lane_;
-        win_pos = 0;
-        cur = load(0);
-        nxt = load(256);
-    }
-    __device__ __forceinline__ u32 byte(u32 pos) {
-        u32 rel = pos + mis - win_pos;
-        if (rel >= 256u) {
-            if (rel < 512u) {
-                cur = nxt;
-                win_pos += 256;
-            } else {   // a long run of literals was stepped over
-                win_pos = (pos + mis) & ~3u;
-                cur = load(win_pos);
-            }
-            nxt = load(win_pos + 256);
-            rel = pos + mis - win_pos;
-        }
-        const u32 w = (u32)__builtin_amdgcn_readlane((int)cur, (int)(rel >> 2));
-        return (w >> ((rel & 3) * 8)) & 0xFFu;
-    }
-};
-
-// between an LDS write of this wave and a read of it by another lane of the same wave
-__device__ __forceinline__ void lz4_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 __global__ __launch_bounds__(LZ4W_TPB) void lz4_decode_wide_kernel(const Lz4Params P) {
     extern __shared__ __align__(16) u8 lz4_lds[];
     u8* lds = lz4_lds;
@@ -248,6 +176,7 @@ __global__ __launch_bounds__(LZ4W_TPB) void lz4_decode_wide_kernel(const Lz4Para
     const u8* gin = P.in + d.in_off;
     u8* gout = P.out + d.out_off;
     if (P.skip_upto && raw <= P.skip_upto) return;   // (the whole workgroup: the other launch's block)
+    if (d.comp & P.skip_tag) return;                 // (... or another codec's: ysb_snappy.hip)
     bool bad = !lz4_entry_ok(e) || raw > P.max_raw;
     if (!bad && (d.comp & LZ4_STORED)) {
         bad = !lz4_stored_ok(e);
@@ -394,11 +323,12 @@ hipError_t launch_lz4_decode(const Lz4Params& p, hipStream_t s) {
 constexpr u32 LZ4M_TPB = 256;   // four waves, four blocks
 
 __global__ __launch_bounds__(LZ4M_TPB) void lz4_measure_kernel(const u8* base, const Lz4FrameBlock* blocks, u32 n_blocks,
-                                                               u32* raw_out) {
+                                                               u32* raw_out, u32 skip_tag) {
     const u32 lane = threadIdx.x & 63;
     const u32 blk = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (LZ4M_TPB / 64) + (threadIdx.x >> 6)));
     if (blk >= n_blocks) return;
     const Lz4FrameBlock e = blocks[blk];
+    if (e.comp & skip_tag) return;   // another codec's block: its raw size is not this kernel's to write
     const u32 comp = e.comp & ~LZ4_STORED;
     u32 raw = 0;
     if (e.comp & LZ4_STORED) {
@@ -411,10 +341,10 @@ __global__ __launch_bounds__(LZ4M_TPB) void lz4_measure_kernel(const u8* base, c
     if (lane == 0) raw_out[blk] = raw;
 }
 
-hipError_t launch_lz4_measure(const u8* base, const Lz4FrameBlock* blocks, u32 n_blocks, u32* raw, hipStream_t s) {
+hipError_t launch_lz4_measure(const u8* base, const Lz4FrameBlock* blocks, u32 n_blocks, u32* raw, hipStream_t s, u32 skip_tag) {
     if (!n_blocks) return hipSuccess;
     const u32 per = LZ4M_TPB / 64;
-    hipLaunchKernelGGL(lz4_measure_kernel, dim3((n_blocks + per - 1) / per), dim3(LZ4M_TPB), 0, s, base, blocks, n_blocks, raw);
+    hipLaunchKernelGGL(lz4_measure_kernel, dim3((n_blocks + per - 1) / per), dim3(LZ4M_TPB), 0, s, base, blocks, n_blocks, raw, skip_tag);
     return hipGetLastError();
 }
 

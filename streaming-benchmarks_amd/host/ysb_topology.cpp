@@ -620,6 +620,7 @@ void GpuAdCampaignOperator::submitKafkaLz4(const uint8_t* bytes, uint64_t nbytes
 }
 
 void GpuAdCampaignOperator::setKafkaCrc(int mode) { check(ysb_kafka_set_crc(ctx_, mode), "ysb_kafka_set_crc"); }
+void GpuAdCampaignOperator::setKafkaCodecs(uint32_t mask) { check(ysb_kafka_set_codecs(ctx_, mask), "ysb_kafka_set_codecs"); }
 
 ysb_kafka_lz4_desc GpuAdCampaignOperator::kafkaLz4Info() {
     ysb_kafka_lz4_desc d{};

@@ -204,6 +204,8 @@ public:
     // ysb_kafka_set_crc: the Kafka submits verify every batch's CRC-32C on the GPU (a batch whose
     // CRC differs drops its slot batch: the sticky error is thrown by the call that meets it)
     void setKafkaCrc(int mode);
+    // ysb_kafka_set_codecs: which codecs the compressed Kafka submits take (YSB_KAFKA_CODECS_*)
+    void setKafkaCodecs(uint32_t mask);
     // The same for batches that may be LZ4-compressed (ysb_kafka_index_lz4's three arrays, offsets
     // relative to `bytes`): inflated on the GPU in front of the unframing (ysb_submit_kafka_lz4).
     void submitKafkaLz4(const uint8_t* bytes, uint64_t nbytes, const ysb_kafka_batch* batches, const ysb_kafka_frame* frames,

@@ -66,6 +66,8 @@ struct Args {
     bool kafka = false;
     // --kafka-codec lz4: the segment's batches may be LZ4-compressed (attributes codec 3; ysb_gen
     // --kafka --kafka-codec lz4): inflated on the GPU in front of the unframing (ysb_submit_kafka_lz4).
+    // --kafka-codec snappy: they may be snappy too (codec 2; ysb_gen --kafka --kafka-codec snappy), in
+    // either framing: ysb_kafka_index_lz4 with YSB_KAFKA_ACCEPT_SNAPPY and ysb_kafka_set_codecs.
     // Without it a compressed segment is refused, as before.
     std::string kafka_codec;
     // --kafka-check-crc device|host|off: every data batch's CRC-32C verified on the GPU in front of
@@ -89,7 +91,7 @@ void usage() {
                  "       [--format json|tbl] [--flush-ms MS] [--batch-mb MB | --batch-bytes B] [--batch-events N]\n"
                  "       [--window-ring W] [--require-ip] [--dry-run] [--print-config] [--replay-rows CSV]\n"
                  "       [--host-split] [--repeat K] [--io-threads T] [--io auto|mapped|mmap|pread]\n"
-                 "       [--h2d-sdma] [--join-redis [--park-capacity N]] [--lz4] [--kafka [--kafka-codec lz4]\n"
+                 "       [--h2d-sdma] [--join-redis [--park-capacity N]] [--lz4] [--kafka [--kafka-codec lz4|snappy]\n"
                  "       [--kafka-check-crc device|host|off]]\n"
                  "   or: ysb_topology --confPath PATH --columns [--device N] [--format json|tbl] [--require-ip]\n"
                  "       [--batch-mb MB | --batch-bytes B]   (window.size rows per <shared_file>_<k>)\n"
@@ -147,8 +149,8 @@ Args parse(int argc, char** argv) {
             }
         } else if (k == "--kafka-codec") {
             a.kafka_codec = val();
-            if (a.kafka_codec != "lz4") {
-                std::fprintf(stderr, "--kafka-codec %s: lz4 is the codec that is read (gzip, snappy and zstd are not)\n",
+            if (a.kafka_codec != "lz4" && a.kafka_codec != "snappy") {
+                std::fprintf(stderr, "--kafka-codec %s: lz4 and snappy are the codecs that are read (gzip and zstd are not)\n",
                              a.kafka_codec.c_str());
                 std::exit(2);
             }
@@ -495,12 +497,16 @@ int run(const Args& a) {
         }
     }
     uint64_t kafka_compressed = 0, kafka_inflated = 0;
-    const uint32_t kafka_index_flags = a.kafka_check_crc == "host" ? YSB_KAFKA_CHECK_CRC
-                                       : a.kafka_check_crc == "device" ? YSB_KAFKA_CHECK_CRC_CONTROL : 0u;
+    const bool kafka_snappy = a.kafka_codec == "snappy";
+    const uint32_t kafka_index_flags = (a.kafka_check_crc == "host" ? YSB_KAFKA_CHECK_CRC
+                                        : a.kafka_check_crc == "device" ? YSB_KAFKA_CHECK_CRC_CONTROL : 0u) |
+                                       (kafka_snappy ? YSB_KAFKA_ACCEPT_SNAPPY : 0u);
+    if (a.kafka && kafka_snappy) op.setKafkaCodecs(YSB_KAFKA_CODECS_DEFAULT | YSB_KAFKA_CODECS_SNAPPY);
     if (a.kafka && a.kafka_check_crc == "device") op.setKafkaCrc(YSB_KAFKA_CRC_DEVICE);
     if (a.kafka && !a.kafka_codec.empty()) {
         // the three arrays of ysb_kafka_index_lz4; runs of whole batches by the slot's bytes and lines
-        // and by the guaranteed bound on what they inflate to: 64 KiB per block
+        // and by the bound on what they inflate to (ysb_kafka_inflate_bounds: 64 KiB per block, a
+        // snappy block what its preamble says)
         std::string file;
         if (!kafka_mapped) file = readFile(events);
         const uint8_t* fb = kafka_mapped ? src.mapping() : reinterpret_cast<const uint8_t*>(file.data());
@@ -517,17 +523,21 @@ int run(const Args& a) {
             std::fprintf(stderr, "note: %llu bytes behind the segment's last whole batch are left alone\n",
                          (unsigned long long)(fn - sum.consumed));
         const uint64_t max_lines = std::max<uint64_t>(o.batchEvents, o.batchBytes / 32);
+        std::vector<uint64_t> inflates_to(idx.size());
+        if (!idx.empty() && ysb_kafka_inflate_bounds(fb, fn, idx.data(), frames.data(), idx.size(), blocks.data(), blocks.size(), inflates_to.data()))
+            throw std::runtime_error(events + ": " + ysb_last_error(nullptr));
         std::vector<ysb_kafka_batch> rel;
         std::vector<ysb_kafka_frame> relf;
         std::vector<ysb_lz4_frame_block> relb;
         for (long long rep = 0; rep < a.repeat; ++rep) {
             for (uint64_t b = 0; b < idx.size();) {
                 const uint64_t start = idx[b].records_off - 61;
-                uint64_t e = b, recs = 0, nblk = 0;
+                uint64_t e = b, recs = 0, nblk = 0, infl = 0;
                 while (e < idx.size() && idx[e].records_off + idx[e].records_bytes - start <= o.batchBytes &&
-                       recs + idx[e].n_records <= max_lines && (nblk + frames[e].n_blocks) * 65536ull <= o.batchBytes) {
+                       recs + idx[e].n_records <= max_lines && infl + inflates_to[e] <= o.batchBytes) {
                     recs += idx[e].n_records;
                     nblk += frames[e].n_blocks;
+                    infl += inflates_to[e];
                     ++e;
                 }
                 if (e == b) throw std::runtime_error(events + ": batch " + std::to_string(b) + " exceeds the slot (--batch-mb; "

@@ -3,7 +3,7 @@
 //
 //   ysb_gen -d DIR [-n EVENTS] [--seed S] [--campaigns C] [--ads-per-campaign A]
 //           [--rate EVENTS_PER_SEC] [--t0 MS] [--with-skew] [--users K]
-//           [--shards K] [--tbl] [--lz4 [--lz4-block N] | --lz4-frame] [--kafka [--kafka-batch BYTES] [--kafka-codec lz4]]
+//           [--shards K] [--tbl] [--lz4 [--lz4-block N] | --lz4-frame] [--kafka [--kafka-batch BYTES] [--kafka-codec lz4|snappy [--kafka-snappy-framing xerial|raw]]]
 //
 // Writes campaign-ids.txt, ad-ids.txt, ad-to-campaign-ids.txt (JSON map lines),
 // ad-to-campaign.csv (the fork's CSV map) and kafka-json.txt into DIR; with --shards K
@@ -18,7 +18,10 @@
 // each event one record's value without its line terminator, as write-to-kafka (core.clj:61-98)
 // sends it -- for ysb_topology --kafka.  With --kafka-codec lz4 each batch's records are one
 // standard LZ4 frame (attributes codec 3, what compression.type=lz4 puts on the wire), for
-// ysb_topology --kafka --kafka-codec lz4.
+// ysb_topology --kafka --kafka-codec lz4.  With --kafka-codec snappy they are snappy (attributes
+// codec 2): the Java client's xerial stream of 32 KiB chunks, or with --kafka-snappy-framing raw
+// one raw block per batch as librdkafka writes it (--kafka-batch at most 65536) -- for
+// ysb_topology --kafka --kafka-codec snappy.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,7 +41,9 @@ int main(int argc, char** argv) {
     unsigned lz4_block = 8192;
     bool kafka = false;
     unsigned kafka_batch = 16384;
-    unsigned kafka_codec = 0;     // --kafka-codec lz4: each batch's records as one LZ4 frame (attributes codec 3)
+    unsigned kafka_codec = 0;     // --kafka-codec lz4: each batch's records as one LZ4 frame (attributes codec 3);
+                                  //   snappy: as a xerial stream or one raw block (codec 2)
+    unsigned kafka_snappy_framing = YSB_KAFKA_SNAPPY_XERIAL;
     for (int i = 1; i < argc; ++i) {
         auto val = [&]() -> const char* {
             if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", argv[i]); std::exit(2); }
@@ -62,8 +67,16 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--kafka-batch")) kafka_batch = (unsigned)std::strtoul(val(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--kafka-codec")) {
             const char* v = val();
-            if (std::strcmp(v, "lz4")) { std::fprintf(stderr, "ysb_gen: --kafka-codec %s: lz4 is the codec that is written\n", v); return 2; }
-            kafka_codec = YSB_KAFKA_CODEC_LZ4;
+            if (std::strcmp(v, "lz4") && std::strcmp(v, "snappy")) {
+                std::fprintf(stderr, "ysb_gen: --kafka-codec %s: lz4 and snappy are the codecs that are written\n", v);
+                return 2;
+            }
+            kafka_codec = std::strcmp(v, "lz4") ? YSB_KAFKA_CODEC_SNAPPY : YSB_KAFKA_CODEC_LZ4;
+        }
+        else if (!std::strcmp(argv[i], "--kafka-snappy-framing")) {
+            const char* v = val();
+            if (std::strcmp(v, "xerial") && std::strcmp(v, "raw")) { std::fprintf(stderr, "ysb_gen: --kafka-snappy-framing %s: xerial or raw\n", v); return 2; }
+            kafka_snappy_framing = std::strcmp(v, "raw") ? YSB_KAFKA_SNAPPY_XERIAL : YSB_KAFKA_SNAPPY_RAW;
         }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
@@ -117,6 +130,7 @@ int main(int argc, char** argv) {
         ysb_kafka_pack_opts o{};
         o.batch_bytes = kafka_batch;
         o.codec = kafka_codec;
+        o.snappy_framing = kafka_snappy_framing;
         o.base_timestamp = p.t0_ms;
         rc = ysb_kafka_write_file((std::string(dir) + "/kafka-json.log").c_str(), data.data(), data.size(), off.data(), off.size(), &o);
         if (rc) { std::fprintf(stderr, "ysb_gen: %s\n", ysb_last_error(nullptr)); return 1; }

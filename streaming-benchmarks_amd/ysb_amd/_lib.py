@@ -190,7 +190,8 @@ class YsbKafkaPackOpts(C.Structure):
     _fields_ = [("batch_bytes", C.c_uint32), ("batch_records", C.c_uint32), ("base_offset", C.c_int64),
                 ("base_timestamp", C.c_int64), ("key_off", C.c_void_p), ("keys", C.c_void_p), ("ts_delta", C.c_void_p),
                 ("n_headers", C.c_uint32), ("codec", C.c_uint32), ("header_keys", C.POINTER(C.c_char_p)),
-                ("header_vals", C.POINTER(C.c_char_p)), ("header_val_len", C.POINTER(C.c_int32))]
+                ("header_vals", C.POINTER(C.c_char_p)), ("header_val_len", C.POINTER(C.c_int32)),
+                ("snappy_framing", C.c_uint32), ("snappy_chunk", C.c_uint32)]
 
 
 class YsbKafkaDesc(C.Structure):
@@ -217,7 +218,8 @@ class YsbKafkaLz4Desc(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("calls", "blocks", "stored_blocks", "compressed_batches", "wire_bytes",
                                           "inflated_bytes", "bad_blocks", "decoder", "inflated_buffer_bytes",
                                           "inflated_total")] + [
-                ("measure_ms", C.c_double), ("plan_ms", C.c_double), ("decode_ms", C.c_double)]
+                ("measure_ms", C.c_double), ("plan_ms", C.c_double), ("decode_ms", C.c_double),
+                ("snappy_blocks", C.c_uint64), ("preamble_ms", C.c_double)]
 
 
 class YsbGenParams(C.Structure):
@@ -318,6 +320,11 @@ SIGNATURES = {
     "ysb_submit_kafka_lz4_mapped": (_I, [_P, _I, _PU8, _U64, _P, _P, _U64, _P, _U64]),
     "ysb_kafka_lz4_info": (_I, [_P, C.POINTER(YsbKafkaLz4Desc)]),
     "ysb_kafka_set_crc": (_I, [_P, _I]),
+    "ysb_kafka_set_codecs": (_I, [_P, _U32]),
+    "ysb_kafka_test_inflated_cap": (_I, [_P, _U64]),
+    "ysb_kafka_inflate_bounds": (_I, [_PU8, _U64, _P, _P, _U64, _P, _U64, _P]),
+    "ysb_snappy_compress_block": (_I, [_PU8, _U32, _PU8, _U32, C.POINTER(_U32)]),
+    "ysb_snappy_decompress_block": (_I, [_PU8, _U32, _PU8, _U32, C.POINTER(_U32)]),
     "ysb_kafka_crc_device": (_I, [_P, _PU8, _U64, _P, _U64, _PU32, _PU32]),
     "ysb_kafka_crc_info": (_I, [_P, C.POINTER(YsbKafkaCrcDesc)]),
     "ysb_kafka_crc_desc_size": (_U64, []),

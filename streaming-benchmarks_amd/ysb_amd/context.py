@@ -490,6 +490,25 @@ class YsbContext:
         CRC differs is bad by rule 9.  Kept across reset()."""
         self._c(lib().ysb_kafka_set_crc(self._h, int(mode)))
 
+    def kafka_set_codecs(self, codecs=("lz4",)):
+        """ysb_kafka_set_codecs: which codecs the compressed Kafka entries take -- names
+        ("lz4", "snappy"; none and lz4 are always in) or the mask itself.  Kept across reset."""
+        from . import kafka
+        if isinstance(codecs, int):
+            mask = codecs
+        else:
+            if any(n not in kafka.CODECS for n in codecs):
+                raise ValueError("codecs %r: of %s" % (codecs, sorted(kafka.CODECS)))
+            mask = kafka.CODECS["none"] | kafka.CODECS["lz4"]
+            for n in codecs:
+                mask |= kafka.CODECS[n]
+        self._c(lib().ysb_kafka_set_codecs(self._h, mask))
+
+    def kafka_test_inflated_cap(self, nbytes):
+        """ysb_kafka_test_inflated_cap (test support): a smaller limit in the plan kernel's test of a
+        batch's inflated extent; 0 restores the buffer's size."""
+        self._c(lib().ysb_kafka_test_inflated_cap(self._h, int(nbytes)))
+
     def kafka_crc_device(self, d_bytes, nbytes, index):
         """ysb_kafka_crc_device: the CRC kernel alone over the indexed batches of a device buffer.
         Returns (computed, stored) as uint32 arrays, one entry per batch."""

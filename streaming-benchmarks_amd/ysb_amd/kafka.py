@@ -19,6 +19,10 @@ BATCH = np.dtype([("records_off", "<u8"), ("records_bytes", "<u4"), ("n_records"
 FRAME = np.dtype([("first_block", "<u8"), ("n_blocks", "<u4"), ("codec", "<u4")])
 BLOCK = np.dtype([("offset", "<u8"), ("comp_bytes", "<u4"), ("reserved", "<u4")])   # ysb_lz4_frame_block
 CODEC_LZ4 = 3
+CODEC_SNAPPY = 2
+ACCEPT_SNAPPY = 0x100        # index_lz4(accept_snappy=True)
+SNAPPY_BLOCK = 0x40000000    # BLOCK.comp_bytes bit 30: a snappy block
+CODECS = {"none": 1, "snappy": 4, "lz4": 8}   # YsbContext.kafka_set_codecs
 RULES = {0: "none", 1: "varint", 2: "length", 3: "past_batch", 4: "key", 5: "value", 6: "headers", 7: "count",
          8: "codec", 9: "crc"}
 DEFAULT_BATCH = 16384   # a producer's default batch.size
@@ -59,15 +63,18 @@ def index(data, check_crc=False, check_control_crc=False):
     return idx, {k: getattr(info, k) for k, _ in info._fields_}
 
 
-def index_lz4(data, check_crc=False, check_control_crc=False):
+def index_lz4(data, check_crc=False, check_control_crc=False, accept_snappy=False):
     """ysb_kafka_index_lz4: (batches, frames, blocks, summary dict) of a buffer whose record
     batches are uncompressed (codec 0) or LZ4-compressed (codec 3).  batches is a BATCH array
     (records_off / records_bytes: the wire bytes), frames a FRAME array with one entry per batch,
     blocks a BLOCK array with every block's place in `data`.  Raises YsbError (YSB_ERR_FORMAT) for
     what `index` refuses, for gzip, snappy and zstd by name, and for a frame the LZ4 frame index
-    refuses (naming the Kafka batch, its byte, and the frame's byte and rule)."""
+    refuses (naming the Kafka batch, its byte, and the frame's byte and rule).
+    accept_snappy=True: snappy batches (codec 2) are indexed too, a block per xerial chunk or one
+    for a raw block, each tagged SNAPPY_BLOCK in comp_bytes; a context takes such an index after
+    kafka_set_codecs(("lz4", "snappy"))."""
     src = _u8(data)
-    flags = _index_flags(check_crc, check_control_crc)
+    flags = _index_flags(check_crc, check_control_crc) | (ACCEPT_SNAPPY if accept_snappy else 0)
     info = _lib.YsbKafkaLz4Summary()
     p = src.ctypes.data if src.size else None
     rc = lib().ysb_kafka_index_lz4(p, src.size, flags, None, None, 0, None, 0, C.byref(info))
@@ -202,15 +209,53 @@ def _unframe(data, idx, sizes_only):
     return out, off, {k: getattr(ct, k) for k, _ in ct._fields_}, v, rc
 
 
+def inflate_bounds(data, idx, frames, blocks):
+    """ysb_kafka_inflate_bounds: per batch what the capacity rule of the compressed submits counts
+    (a snappy block its preamble's raw size, every other block 65536), an int64 array."""
+    src = _u8(data)
+    idx = np.ascontiguousarray(idx, dtype=BATCH)
+    frames = np.ascontiguousarray(frames, dtype=FRAME)
+    blocks = np.ascontiguousarray(blocks, dtype=BLOCK)
+    out = np.zeros(idx.size, dtype=np.uint64)
+    check(lib().ysb_kafka_inflate_bounds(src.ctypes.data if src.size else None, src.size, idx.ctypes.data if idx.size else None,
+                                         frames.ctypes.data if frames.size else None, idx.size,
+                                         blocks.ctypes.data if blocks.size else None, blocks.size,
+                                         out.ctypes.data if out.size else None))
+    return out.astype(np.int64)
+
+
+def snappy_compress_block(data):
+    """ysb_snappy_compress_block: 1..65536 bytes as one raw snappy block (preamble included) by the
+    host compressor; a uint8 array."""
+    src = _u8(data)
+    dst = np.empty(32 + src.size + src.size // 6, dtype=np.uint8)
+    n = C.c_uint32()
+    check(lib().ysb_snappy_compress_block(src.ctypes.data if src.size else None, src.size, dst.ctypes.data, dst.size, C.byref(n)))
+    return dst[:n.value]
+
+
+def snappy_decompress_block(data):
+    """ysb_snappy_decompress_block, the model of the GPU's decoder: the block's raw bytes as a
+    uint8 array; YsbError (YSB_ERR_FORMAT) for a block that breaks the format's rules."""
+    src = _u8(data)
+    dst = np.empty(65536, dtype=np.uint8)
+    n = C.c_uint32()
+    check(lib().ysb_snappy_decompress_block(src.ctypes.data if src.size else None, src.size, dst.ctypes.data, dst.size, C.byref(n)))
+    return dst[:n.value]
+
+
 class _Opts:
     """ysb_kafka_pack_opts with the arrays it points to kept alive."""
 
     def __init__(self, n_lines, batch_bytes, batch_records, base_offset, base_timestamp, keys, ts_delta, headers,
-                 codec=None):
+                 codec=None, snappy_framing="xerial", snappy_chunk=0):
         o = self.o = _lib.YsbKafkaPackOpts()
-        if codec not in (None, "none", "lz4"):
-            raise ValueError("codec %r: None or \"lz4\"" % (codec,))
-        o.codec = CODEC_LZ4 if codec == "lz4" else 0
+        if codec not in (None, "none", "lz4", "snappy"):
+            raise ValueError("codec %r: None, \"lz4\" or \"snappy\"" % (codec,))
+        if snappy_framing not in ("xerial", "raw"):
+            raise ValueError("snappy_framing %r: \"xerial\" or \"raw\"" % (snappy_framing,))
+        o.codec = CODEC_LZ4 if codec == "lz4" else CODEC_SNAPPY if codec == "snappy" else 0
+        o.snappy_framing, o.snappy_chunk = int(snappy_framing == "raw"), int(snappy_chunk or 0)
         o.batch_bytes, o.batch_records = int(batch_bytes or 0), int(batch_records or 0)
         o.base_offset, o.base_timestamp = int(base_offset), int(base_timestamp)
         self.keep = []
@@ -242,14 +287,17 @@ def _lines(data, offsets):
 
 
 def pack(data, offsets, batch_bytes=DEFAULT_BATCH, batch_records=0, base_offset=0, base_timestamp=0, keys=None,
-         ts_delta=None, headers=None, codec=None):
+         ts_delta=None, headers=None, codec=None, snappy_framing="xerial", snappy_chunk=0):
     """ysb_kafka_pack: the lines data[offsets[i]:offsets[i + 1]] (the last one ends at len(data))
     as record batches of at most batch_bytes bytes (uncompressed) or batch_records records; a
     uint8 array.  codec="lz4": each batch's records as one standard LZ4 frame (attributes 3).
+    codec="snappy" (attributes 2): as the Java client's xerial stream of chunks of snappy_chunk raw
+    bytes (0: its 32 KiB), or with snappy_framing="raw" as one raw block (batch_bytes at most 64 KiB).
     keys: None (null keys) or one bytes per line; ts_delta: None or one int per line; headers: a
     list of (key bytes, value bytes or None) put on every record."""
     src, off = _lines(data, offsets)
-    o = _Opts(off.size, batch_bytes, batch_records, base_offset, base_timestamp, keys, ts_delta, headers, codec)
+    o = _Opts(off.size, batch_bytes, batch_records, base_offset, base_timestamp, keys, ts_delta, headers, codec,
+              snappy_framing, snappy_chunk)
     dst = np.empty(max(lib().ysb_kafka_bound(src.size, off.size, C.byref(o.o)), 1), dtype=np.uint8)
     n, nb = C.c_uint64(), C.c_uint64()
     check(lib().ysb_kafka_pack(src.ctypes.data if src.size else None, src.size, off.ctypes.data if off.size else None,
@@ -263,7 +311,7 @@ def write_file(path, data, offsets, **kw):
     src, off = _lines(data, offsets)
     o = _Opts(off.size, kw.pop("batch_bytes", DEFAULT_BATCH), kw.pop("batch_records", 0), kw.pop("base_offset", 0),
               kw.pop("base_timestamp", 0), kw.pop("keys", None), kw.pop("ts_delta", None), kw.pop("headers", None),
-              kw.pop("codec", None))
+              kw.pop("codec", None), kw.pop("snappy_framing", "xerial"), kw.pop("snappy_chunk", 0))
     if kw:
         raise TypeError("unknown options %s" % sorted(kw))
     check(lib().ysb_kafka_write_file(str(path).encode(), src.ctypes.data if src.size else None, src.size,

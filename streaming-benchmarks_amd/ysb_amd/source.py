@@ -232,6 +232,9 @@ class KafkaLogDataSource:
     codecs=("lz4",): the segment's batches may be LZ4-compressed (ysb_gen --kafka --kafka-codec lz4);
     runs are then also cut by the guaranteed bound on what they inflate to, 65536 bytes per block,
     and submitted with ysb_submit_kafka_lz4_mapped.  Without it a compressed batch is refused.
+    codecs=("lz4", "snappy"): snappy batches (ysb_gen --kafka --kafka-codec snappy, either framing)
+    are read too; a snappy block counts what its preamble says, and `run` tells the context
+    (ysb_kafka_set_codecs; the setting stays).
     check_crc: True verifies every batch's CRC-32C on the host at index time; "device" leaves the
     data batches to the GPU (`run` turns ysb_kafka_set_crc on for its submits) and verifies on the
     host only the control batches the index skips."""
@@ -251,13 +254,14 @@ class KafkaLogDataSource:
                 self._mm = mmap.mmap(f.fileno(), 0, flags=mmap.MAP_SHARED, prot=mmap.PROT_READ)
             self.data = np.frombuffer(self._mm, dtype=np.uint8)
         codecs = tuple(codecs or ())
-        if any(c != "lz4" for c in codecs):
-            raise ValueError("codecs %r: \"lz4\" is the codec that is read" % (codecs,))
-        self.lz4 = "lz4" in codecs
+        if any(c not in ("lz4", "snappy") for c in codecs):
+            raise ValueError("codecs %r: \"lz4\" and \"snappy\" are the codecs that are read" % (codecs,))
+        self.lz4 = bool(codecs)          # the compressed path (ysb_submit_kafka_lz4_mapped)
+        self.snappy = "snappy" in codecs
         self.frames = self.blocks = None
         if self.lz4:
-            self.index, self.frames, self.blocks, self.summary = kafka.index_lz4(self.data, check_crc=check_crc,
-                                                                                check_control_crc=check_control)
+            self.index, self.frames, self.blocks, self.summary = kafka.index_lz4(
+                self.data, check_crc=check_crc, check_control_crc=check_control, accept_snappy=self.snappy)
         else:
             self.index, self.summary = kafka.index(self.data, check_crc=check_crc, check_control_crc=check_control)
         self.framed_bytes = 0
@@ -273,13 +277,14 @@ class KafkaLogDataSource:
         n, b = self.index.size, 0
         start = self.index["records_off"].astype(np.int64) - 61
         end = self.index["records_off"].astype(np.int64) + self.index["records_bytes"].astype(np.int64)
-        nblk = self.frames["n_blocks"].astype(np.int64) if self.lz4 else np.zeros(n, dtype=np.int64)
+        from . import kafka
+        infl = kafka.inflate_bounds(self.data, self.index, self.frames, self.blocks) if self.lz4 else np.zeros(n, dtype=np.int64)
         while b < n:
-            e, recs, blocks = b, 0, 0
+            e, recs, raw = b, 0, 0
             while e < n and int(end[e]) - int(start[b]) <= cap and recs + int(self.index[e]["n_records"]) <= max_records \
-                    and (blocks + int(nblk[e])) * 65536 <= cap:
+                    and raw + int(infl[e]) <= cap:
                 recs += int(self.index[e]["n_records"])
-                blocks += int(nblk[e])
+                raw += int(infl[e])
                 e += 1
             if e == b:
                 raise ValueError("%s: batch %d exceeds the slot" % (self.path, b))
@@ -290,6 +295,8 @@ class KafkaLogDataSource:
         """Every run of the segment through ctx (a YsbContext), in place; returns the framed
         bytes submitted.  At most two batches in flight."""
         from . import kafka
+        if self.snappy:
+            ctx.kafka_set_codecs(("lz4", "snappy"))
         max_bytes, max_events = ctx.slot_capacity()
         max_records = max(max_events, max_bytes // 32)
         if self.size:

@@ -22,6 +22,14 @@ per slot batch and which stage bounds it; plus the six kernels alone (measure, p
 base, gather by HIP events, the median of five after two warm-ups).  Those figures go to
 profiles/kafka_lz4_bench.json.
 
+With --snappy (which turns --lz4 on, for the comparison) the same batches also go snappy-compressed
+(attributes codec 2 as the Java client's xerial stream of 32 KiB chunks; ysb_kafka_set_codecs, then
+the same two submits), alternating with all the legs above in the same process.  A snappy block
+counts what its preamble says in the capacity rule, so a slot batch holds every Kafka batch of the
+staged one.  Per leg the figures of the LZ4 legs, each also as a ratio to the LZ4 leg of the same
+run; plus the chain's kernels alone with the preamble kernel in the measure pass's place.  Those
+figures go to profiles/kafka_snappy_bench.json.
+
 With --crc every Kafka leg (with --lz4 the compressed ones too) also runs with each batch's CRC-32C verified: on the device
 (ysb_kafka_set_crc: one more launch between the walk and the scan of the totals) and on the host at
 index time (ysb_kafka_index with YSB_KAFKA_CHECK_CRC inside the timed loop, once per submit),
@@ -66,9 +74,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kafka_bench.json"))
     ap.add_argument("--lz4", action="store_true", help="add the LZ4-compressed legs (profiles/kafka_lz4_bench.json)")
     ap.add_argument("--lz4-out", default=os.path.join(ROOT, "profiles", "kafka_lz4_bench.json"))
+    ap.add_argument("--snappy", action="store_true", help="add the snappy legs beside the LZ4 ones (profiles/kafka_snappy_bench.json)")
+    ap.add_argument("--snappy-out", default=os.path.join(ROOT, "profiles", "kafka_snappy_bench.json"))
     ap.add_argument("--crc", action="store_true", help="add the CRC-verified legs (profiles/kafka_crc_bench.json)")
     ap.add_argument("--crc-out", default=os.path.join(ROOT, "profiles", "kafka_crc_bench.json"))
     a = ap.parse_args()
+    a.lz4 = a.lz4 or a.snappy
 
     from ysb_amd import GenParams, YsbContext, kafka
     from ysb_amd._lib import check, lib
@@ -81,11 +92,15 @@ def main():
            "unframe_alone": []}
     zres = {"events_per_raw_batch": per, "slot_MB": a.slot_mb, "repeats": a.repeats, "batch_sizes": sizes,
             "blocks_per_slot_batch_cap": slot_bytes // 65536, "legs": [], "kernels_alone": []}
+    sres = {"events_per_raw_batch": per, "slot_MB": a.slot_mb, "repeats": a.repeats, "batch_sizes": sizes,
+            "framing": "xerial, 32 KiB chunks", "legs": [], "kernels_alone": []}
     cres = {"events_per_batch": per, "slot_MB": a.slot_mb, "repeats": a.repeats, "batch_sizes": sizes, "legs": [],
             "kernel_alone": []}
     with YsbContext(device=a.device, n_campaigns=100, window_ring=1024, timing=True, max_batch_bytes=slot_bytes,
                     max_batch_events=per, ring_base_bucket=g.c.t0_ms // 10000 - 8) as ctx:
         ctx.load_ad_map(aids, g.ad_campaign_index())
+        if a.snappy:
+            ctx.kafka_set_codecs(("lz4", "snappy"))
         raw, offs = [], []
         for s in (0, 1):   # two distinct batches, generated on the device, kept on the host
             cap = per * g.max_line_bytes()
@@ -162,14 +177,14 @@ def main():
             ctx.kafka_set_crc(1 if crc == "device" else 0)
             for s in (0, 1):
                 ctx.wait(s)
-                if kind == "kafka_lz4":
+                if kind in ("kafka_lz4", "kafka_snappy"):
                     slot[s][:z["blobs"][s].size] = z["blobs"][s]
 
             def submit(s):
                 b, i, f, k = z["blobs"][s], z["idx"][s], z["frames"][s], z["blocks"][s]
                 if crc == "host":
-                    assert kafka.index_lz4(b, check_crc=True)[3]["crc_checked"] == i.size
-                if kind == "kafka_lz4":
+                    assert kafka.index_lz4(b, check_crc=True, accept_snappy=a.snappy)[3]["crc_checked"] == i.size
+                if kind in ("kafka_lz4", "kafka_snappy"):
                     check(lib().ysb_submit_kafka_lz4(ctx._h, s, C.c_void_p(slot[s].ctypes.data), b.size, C.c_void_p(i.ctypes.data),
                                                      C.c_void_p(f.ctypes.data), i.size, C.c_void_p(k.ctypes.data), k.size), ctx._h)
                 else:
@@ -199,6 +214,8 @@ def main():
             n = sum(ev[i & 1] for i in range(nsub))
             stages = {k: round(v, 4) for k, v in (("measure", li["measure_ms"]), ("plan", li["plan_ms"]), ("decode", li["decode_ms"]),
                                                    ("walk", info["walk_ms"]), ("base", info["base_ms"]), ("gather", info["gather_ms"]))}
+            if li["snappy_blocks"]:
+                stages["preamble"] = round(li["preamble_ms"], 4)
             chain_ms = sum(stages.values())
             busy = cms * 1e-3 / el
             chain_share = chain_ms * 1e-3 * nsub / el     # (the last batch's kernels, taken for every batch)
@@ -223,14 +240,15 @@ def main():
             log(json.dumps(out))
             return out
 
-        def lz4_staging(size):
+        def lz4_staging(size, codec="lz4"):
             """The staged batches compressed, cut to the Kafka batches a slot batch may hold."""
             z = {"blobs": [], "idx": [], "frames": [], "blocks": [], "events": [], "batch_bytes": size}
             t0 = time.perf_counter()
             for r, o in zip(raw, offs):
-                blob = kafka.pack(r, o, batch_bytes=size, codec="lz4")
-                idx, fr, bl, _ = kafka.index_lz4(blob)
-                keep = int(np.searchsorted(np.cumsum(fr["n_blocks"]), slot_bytes // 65536, side="right"))
+                blob = kafka.pack(r, o, batch_bytes=size, codec=codec)
+                idx, fr, bl, _ = kafka.index_lz4(blob, accept_snappy=codec == "snappy")
+                ends = np.cumsum(kafka.inflate_bounds(blob, idx, fr, bl))   # the capacity rule: 65536 per block, a snappy block its preamble
+                keep = int(np.searchsorted(ends, slot_bytes, side="right"))
                 keep = min(keep, idx.size)
                 nblk = int(fr["n_blocks"][:keep].sum())
                 end = int(idx[keep - 1]["records_off"]) + int(idx[keep - 1]["records_bytes"])
@@ -253,15 +271,20 @@ def main():
                 got = ctx.kafka_unframe_lz4_device(d_in, b.size, i, f, k, d_out, raw[0].size, d_off, per + 1)
                 assert got == (n, nval), (got, n, nval)
                 ki, li = ctx.kafka_info(), ctx.kafka_lz4_info()
-                rows.append((li["measure_ms"], li["plan_ms"], li["decode_ms"], ki["walk_ms"], ki["base_ms"], ki["gather_ms"]))
+                rows.append((li["measure_ms"], li["plan_ms"], li["decode_ms"], ki["walk_ms"], ki["base_ms"], ki["gather_ms"],
+                             li["preamble_ms"]))
             same = bool((ctx.d2h(np.empty(nval, dtype=np.uint8), d_out) == raw[0][:nval]).all()) and \
                 bool((ctx.d2h(np.empty(n, dtype=np.uint32), d_off) == offs[0][:n]).all())
             med = [statistics.median(r[c] for r in rows[2:]) for c in range(6)]
+            pre_ms = statistics.median(r[6] for r in rows[2:])
             out = {"batch_bytes": z["batch_bytes"], "kafka_batches": int(i.size), "blocks": int(k.size), "events": n,
                    "wire_bytes": int(b.size), "inflated_bytes": li["inflated_bytes"], "value_bytes": nval,
                    "compression_ratio": round(li["inflated_bytes"] / b.size, 4), "decoder": li["decoder"],
                    "output_equal": same}
             out.update({nm + "_ms": round(v, 4) for nm, v in zip(("measure", "plan", "decode", "walk", "base", "gather"), med)})
+            if li["snappy_blocks"]:
+                out.update(snappy_blocks=li["snappy_blocks"], preamble_ms=round(pre_ms, 4))
+                med = med + [pre_ms]
             out["decode_GBs_out"] = round(li["inflated_bytes"] / (med[2] * 1e-3) / 1e9, 2) if med[2] else 0.0
             out["chain_GBs_out"] = round(li["inflated_bytes"] / (sum(med) * 1e-3) / 1e9, 2) if sum(med) else 0.0
             ctx.device_free(d_in)
@@ -322,7 +345,19 @@ def main():
             for o, p in zip(at, blobs):
                 reg[o:o + p.size] = p
             ctx.host_register(reg)
-            z = zreg = zat = None
+            z = zreg = zat = y = yreg = yat = None
+            if a.snappy:   # the snappy staging, its kernels alone, its registered copy
+                y = lz4_staging(size, "snappy")
+                sres["kernels_alone"].append(lz4_kernels_alone(y))
+                yat, ypos = [], 0
+                for p in y["blobs"]:
+                    yat.append(ypos)
+                    ypos += (p.size + 63) // 64 * 64 + 64 + 1
+                yreg = np.empty(ypos + 8192, dtype=np.uint8)
+                yreg = yreg[(-yreg.ctypes.data) % 4096:][:(ypos + 4095) // 4096 * 4096]
+                for o, p in zip(yat, y["blobs"]):
+                    yreg[o:o + p.size] = p
+                ctx.host_register(yreg)
             if a.lz4:   # the compressed staging, its kernels alone, its registered copy (the second batch at an odd address)
                 z = lz4_staging(size)
                 zres["kernels_alone"].append(lz4_kernels_alone(z))
@@ -340,18 +375,26 @@ def main():
                     res["legs"].append(dict(leg(kind, blobs, idxs, reg, at), batch_bytes=size, round=rep))
                     if z and kind == "raw":
                         zres["legs"].append(dict(res["legs"][-1]))
+                    if y and kind == "raw":
+                        sres["legs"].append(dict(res["legs"][-1]))
                 if a.crc:
                     for kind, crc in (("kafka", "device"), ("kafka", "host"), ("kafka_mapped", "device"), ("kafka_mapped", "host")):
                         cres["legs"].append(dict(leg(kind, blobs, idxs, reg, at, crc), batch_bytes=size, round=rep))
                 for kind in (("kafka_lz4", "kafka_lz4_mapped") if z else ()):
                     zres["legs"].append(dict(leg_lz4(kind, z, zreg, zat), batch_bytes=size, round=rep))
+                    if y:
+                        sres["legs"].append(dict(zres["legs"][-1]))
                     if a.crc:
                         for crc in ("device", "host"):
                             cres["legs"].append(dict(leg_lz4(kind, z, zreg, zat, crc), batch_bytes=size, round=rep))
+                for kind in (("kafka_snappy", "kafka_snappy_mapped") if y else ()):
+                    sres["legs"].append(dict(leg_lz4(kind, y, yreg, yat), batch_bytes=size, round=rep))
             ctx.sync()
             ctx.host_unregister(reg)
             if z:
                 ctx.host_unregister(zreg)
+            if y:
+                ctx.host_unregister(yreg)
         ctx.device_free(d_out)
         ctx.device_free(d_off)
 
@@ -427,6 +470,36 @@ def main():
             json.dump(zres, f, indent=1)
             f.write("\n")
         print(json.dumps(zs), flush=True)
+    if a.snappy and not a.unframe_only:
+        ss = {"kernels_alone": sres["kernels_alone"], "all_inflated_equal": all(u["output_equal"] for u in sres["kernels_alone"])}
+        for size in sizes:
+            def sof(kind):
+                return [l for l in sres["legs"] if l["leg"] == kind and l["batch_bytes"] == size]
+            rawm = statistics.median(l["events_per_s"] for l in sof("raw"))
+            ss[str(size)] = {"raw_median_events_per_s": rawm}
+            for kind, other in (("kafka_snappy", "kafka_lz4"), ("kafka_snappy_mapped", "kafka_lz4_mapped")):
+                v = sof(kind)
+                e = [l["events_per_s"] for l in v]
+                lz = statistics.median(l["events_per_s"] for l in sof(other))
+                ss[str(size)][kind] = {
+                    "M_events_per_s": {"min": round(min(e) / 1e6, 2), "median": round(statistics.median(e) / 1e6, 2),
+                                       "max": round(max(e) / 1e6, 2)},
+                    "over_raw_median": round(statistics.median(e) / rawm, 4),
+                    "over_" + other + "_median": round(statistics.median(e) / lz, 4),
+                    other + "_M_events_per_s_median": round(lz / 1e6, 2),
+                    "wire_bytes_per_event": statistics.median(l["wire_bytes_per_event"] for l in v),
+                    other + "_wire_bytes_per_event": statistics.median(l["wire_bytes_per_event"] for l in sof(other)),
+                    "compression_ratio": statistics.median(l["compression_ratio"] for l in v),
+                    "copy_busy_frac": statistics.median(l["copy_busy_frac"] for l in v),
+                    "kafka_batches_per_slot_batch": v[0]["kafka_batches_per_slot_batch"],
+                    "events_per_slot_batch": v[0]["events"] // v[0]["batches"], "bound": v[-1]["bound"]}
+        ss["all_checks_exact"] = all(l["check"]["truth_mismatched_cells"] == 0 and l["check"]["truth_views"] == l["check"]["counted_views"]
+                                     and l["check"]["events"] == l["events"] and l.get("bad_batches", 0) == 0 for l in sres["legs"])
+        sres["summary"] = ss
+        with open(a.snappy_out, "w") as f:
+            json.dump(sres, f, indent=1)
+            f.write("\n")
+        print(json.dumps(ss), flush=True)
     print(json.dumps(res["summary"]), flush=True)
 
 
